@@ -2,7 +2,7 @@
 """Headline benchmark: CD-1 training steps of the Gaussian-Bernoulli RBM 4096 -> 1024 at
 batch 512 per GPU (BASELINE.json configs[1]; configs[2] with N > 1 ranks).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no torchrun environment this process starts the N ranks itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...` as a CHILD process, before
@@ -11,13 +11,21 @@ anything here has touched the GPU) and relays rank 0's JSON line; under torchrun
 One "step" = one call of the compiled step function of reference src/rbm.py:258-376 as
 src/dbn.py:302-312 builds it: minibatch gather, positive phase, one gibbs_hvh, the
 statistics GEMM, (all-reduce over ranks,) parameter update and monitoring cost -- nothing
-skipped.  Inputs are synthetic N(0,1) rows already resident in HBM.  Timing: W warm-up steps,
-then windows of exactly K steps, each bracketed by barrier + synchronize on both sides (max
-over ranks); `ms_per_step` is the MEDIAN window (>= 5 windows, more for short ones, so that the
-driver's small K gives the same number as a long run); all windows are listed in `windows_ms`.
-Rank 0 prints ONE JSON line with `roofline` (per-kernel HIP-event times against the matrix pipe
-each kernel issues on) and `cpu_baseline` (the numpy float32 oracle on the host cores: Theano is
-not installable offline, so kind "port").
+skipped.  Inputs are synthetic N(0,1) rows already resident in HBM, generated from fixed seeds.
+
+A plain run sets up, lets the GPU settle for 1 s on a throwaway model (`settle`), runs W warm-up
+steps, times ONE window of exactly K steps (the product's default setting; --windows M: M windows,
+`ms_per_step` is their median), bracketed by barrier + synchronize on both sides (max over ranks),
+and prints ONE JSON line on rank 0.
+--dump-outputs DIR: what the last timed step left to its caller -- the monitoring cost and the
+updated parameters and speeds -- as DIR/<name>.npy (float32; the cost float64), about 32 MB.
+--full adds everything else, as before: >= 5 windows and >= 6 s of timed steps on one GPU (more
+windows for short ones, so that a small K gives the same number as a long run); `roofline`
+(per-kernel HIP-event times against the matrix pipe each kernel issues on); the exact-f32 MFMA,
+bf16-input and host-resident-table variants; the free-energy check against the float64 oracle;
+`cpu_baseline` (the numpy float32 oracle on the host cores: Theano is not installable offline,
+so kind "port"); with N > 1 the data-parallel sweep (whose fastest point becomes `value`), the
+all-reduce alone and the exposed-communication probe.
 """
 import argparse
 import glob
@@ -46,7 +54,13 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=0, help="timed windows of --steps steps (0 = auto, >= 5)")
+    ap.add_argument("--windows", type=int, default=0,
+                    help="timed windows of --steps steps (0 = auto: one in a plain run, >= 5 with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the cost, parameters and speeds after the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the other precisions and configurations, the oracle check, the CPU baseline "
+                         "and (N > 1) the data-parallel sweep; the headline then takes >= 5 windows")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--default-only", action="store_true",
                     help="only the default (product) path: no exact-f32 / bf16-input re-runs, no CPU baseline (profiling runs)")
@@ -75,6 +89,10 @@ def launch_ranks(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--windows", str(args.windows)]
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", args.dump_outputs]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if args.default_only:
@@ -418,6 +436,25 @@ def main():
                            next_indexes=perm[nb * B_global:(nb + 1) * B_global])
         return cost
 
+    def settle(seconds):
+        """Back-to-back steps of a throwaway model, on a context of its own, until `seconds` have passed.  The first tens of
+        milliseconds of steps after start run slower (one GPU: the first 200-step window after 20 warm-up steps read 0.144
+        ms per step, every later window 0.135), so a short plain run would time that ramp; the timed model's own steps stay
+        a fixed number whatever the clock says."""
+        eng_t = mdbn_amd.HipEngine()
+        rbm_t = mdbn_amd.GRBM(n_visible=V, n_hidden=H, numpy_rng=np.random.RandomState(123), engine=eng_t)
+        _, up = rbm_t.get_cost_updates(lr=LR, k=K_GIBBS, lambda_1=LAMBDA_1, lambda_2=LAMBDA_2, batch_size=B_PER_GPU)
+        fn = mdbn_amd.function(up, train_set_x, data_parallel=None)
+        t0, it = time.perf_counter(), 0
+        while time.perf_counter() - t0 < seconds:
+            for _ in range(50):
+                mb, nb = it % n_mb, (it + 1) % n_mb
+                fn(indexes=perm[mb * B_global:mb * B_global + B_PER_GPU], momentum=0.0,
+                   next_indexes=perm[nb * B_global:nb * B_global + B_PER_GPU])
+                it += 1
+            torch.cuda.synchronize(dev)
+        del fn, up, rbm_t, eng_t
+
     def barrier():
         if world > 1:
             td.barrier()
@@ -435,10 +472,10 @@ def main():
             dt = float(t.item())
         return dt, cost
 
-    def measure(first, min_total=1.0):
+    def measure(first, min_total=1.0, n_win=None):
         """Median of >= 5 windows of exactly --steps steps; short windows are repeated until >= min_total s of steps has been
-        timed (at most 20000 windows), so that a sampler beside the run sees the GPU busy."""
-        n_win = args.windows
+        timed (at most 20000 windows), so that a sampler beside the run sees the GPU busy.  n_win > 0: exactly that many."""
+        n_win = args.windows if n_win is None else n_win
         wins, cost = [], None
         while True:
             dt, cost = timed_window(first)
@@ -465,6 +502,20 @@ def main():
             raise SystemExit("kernel timing buffer overflowed: %d launches recorded, %d returned" % (n_recorded, len(detail)))
         return detail, n, first + n
 
+    def measure_headline(first, min_total):
+        """The timed steps behind `value`: one window of --steps steps in a plain run (--windows M: M windows), the >= 5
+        windows of `measure` under --full."""
+        return measure(first, min_total) if args.full else measure(first, n_win=args.windows or 1)
+
+    def outputs_of(cost):
+        """Host copies of what the last step left to its caller (--dump-outputs)."""
+        if not args.dump_outputs:
+            return None
+        out = {"cost": np.array([float(cost)], dtype=np.float64)}
+        for name in ("W", "hbias", "vbias", "W_speed", "hbias_speed", "vbias_speed"):
+            out[name] = getattr(rbm, name).get_value().astype(np.float32)
+        return out
+
     def agree(flag):
         """All ranks take rank 0's decision (one small broadcast through the default communicator)."""
         if world == 1:
@@ -479,12 +530,8 @@ def main():
                                          and fn.group.native is not False) else "torch",
                 "update_inside_statistics_gemm": int(getattr(fn, "fuse_deferred", 0)), "rccl_max_ctas": None}
 
-    def line_for(wins, cost, detail, n_timed_steps, dist_block, extras=None):
-        """The complete JSON line of one measured setting."""
-        elapsed = float(np.median(wins))
-        steps_per_s = args.steps / elapsed
-        # algorithmic FLOPs (SURVEY 8d): 2*B*V*H per product, 2k+3 products per CD-k step
-        flop_per_step = 2.0 * B_PER_GPU * V * H * (2 * K_GIBBS + 3)
+    def roofline_of(detail, n_timed_steps):
+        """The `roofline` block: the GEMM launches of `n_timed_steps` steps timed with HIP events (time_kernels)."""
         rows = kernel_breakdown(detail)
         n_launch = len(detail)
         t_all = sum(d[0] for d in detail) * 1e-3
@@ -496,6 +543,36 @@ def main():
         traffic_file, traffic, traffic_kernels, traffic_note = pmc_traffic(rows)
         algorithmic_bytes = 4.0 * B_PER_GPU * V + 16.0 * V * H       # v0 read once, W and W_speed read + written
         worst = min(rows.items(), key=lambda kv: kv[1]["frac_of_pipe"])[0] if rows else None
+        # achieved = FLOPs ISSUED on the matrix pipe the GEMM kernels execute on (six / three bf16 products per
+        # algorithmic f32 product), summed over the step's GEMM launches, / their summed HIP-event durations;
+        # peak = that pipe's dense peak.  `kernels` has the same per GEMM; the f32-equivalent (algorithmic)
+        # rate is a separate, informational field.
+        return {"bound": "mfma",
+                "kernel": "GEMM launches of the step (%s)" % ("bf16 matrix pipe, split f32 operands" if on_bf16
+                                                              else "mixed / f32 matrix pipe"),
+                "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                "frac": (achieved / peak) if achieved else None,
+                # HBM bytes per CD STEP over ALL kernels of the step (PMC, profiled run of the default path) beside
+                # the algorithmic bytes of SURVEY 8d; their ratio is the re-read / double-storage overhead
+                "traffic": traffic, "traffic_unit": "bytes per CD step, all kernels", "traffic_source": traffic_file,
+                "traffic_note": traffic_note,
+                "traffic_by_kernel": traffic_kernels,
+                "algorithmic_bytes": algorithmic_bytes,
+                "traffic_over_algorithmic": (traffic / algorithmic_bytes) if traffic else None,
+                "launches_timed": n_launch, "launches_per_step": n_launch / float(n_timed_steps),
+                "avg_launch_us": 1e6 * t_all / max(n_launch, 1),
+                "issued_flop_per_step": issued / float(n_timed_steps),
+                "algorithmic_flop_per_step": alg / float(n_timed_steps),
+                "algorithmic_f32_tflops": alg / t_all / 1e12 if n_launch else None,
+                "furthest_below_roof": worst,
+                "kernels": rows}
+
+    def line_for(wins, cost, detail, n_timed_steps, dist_block, extras=None):
+        """The complete JSON line of one measured setting (`roofline` when its kernels were timed: --full)."""
+        elapsed = float(np.median(wins))
+        steps_per_s = args.steps / elapsed
+        # algorithmic FLOPs (SURVEY 8d): 2*B*V*H per product, 2k+3 products per CD-k step
+        flop_per_step = 2.0 * B_PER_GPU * V * H * (2 * K_GIBBS + 3)
         out = {
             "metric": "CD-k Gibbs steps/sec (samples/sec), GRBM 4096->1024 CD-1",
             "value": steps_per_s * B_global * K_GIBBS,
@@ -521,40 +598,23 @@ def main():
             "step_algorithmic_f32_tflops_over_f32_mfma_peak": flop_per_step * steps_per_s / 1e12 / MFMA_F32_PEAK_TFLOPS,
             "final_cost": float(cost),
             "distributed": dist_block,
-            # achieved = FLOPs ISSUED on the matrix pipe the GEMM kernels execute on (six / three bf16 products per
-            # algorithmic f32 product), summed over the step's GEMM launches, / their summed HIP-event durations;
-            # peak = that pipe's dense peak.  `kernels` has the same per GEMM; the f32-equivalent (algorithmic)
-            # rate is a separate, informational field.
-            "roofline": {"bound": "mfma",
-                         "kernel": "GEMM launches of the step (%s)" % ("bf16 matrix pipe, split f32 operands" if on_bf16
-                                                                       else "mixed / f32 matrix pipe"),
-                         "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": (achieved / peak) if achieved else None,
-                         # HBM bytes per CD STEP over ALL kernels of the step (PMC, profiled run of the default path) beside
-                         # the algorithmic bytes of SURVEY 8d; their ratio is the re-read / double-storage overhead
-                         "traffic": traffic, "traffic_unit": "bytes per CD step, all kernels", "traffic_source": traffic_file,
-                         "traffic_note": traffic_note,
-                         "traffic_by_kernel": traffic_kernels,
-                         "algorithmic_bytes": algorithmic_bytes,
-                         "traffic_over_algorithmic": (traffic / algorithmic_bytes) if traffic else None,
-                         "launches_timed": n_launch, "launches_per_step": n_launch / float(n_timed_steps),
-                         "avg_launch_us": 1e6 * t_all / max(n_launch, 1),
-                         "issued_flop_per_step": issued / float(n_timed_steps),
-                         "algorithmic_flop_per_step": alg / float(n_timed_steps),
-                         "algorithmic_f32_tflops": alg / t_all / 1e12 if n_launch else None,
-                         "furthest_below_roof": worst,
-                         "kernels": rows},
         }
+        if detail is not None:
+            out["roofline"] = roofline_of(detail, n_timed_steps)
         if extras:
             out.update(extras)
         return out
 
+    settle(1.0)
     run(args.warmup, 0)
     # ------------------------------------------------------------------ the DEFAULT setting, always first
-    # (one GPU: 6 s of back-to-back steps -- a 5-second utilisation sampler beside the run then has a busy sample; the
-    #  r04 driver log showed none for 1 s of steps)
-    wins, cost, nxt = measure(args.warmup, min_total=6.0 if world == 1 else 1.5)
-    detail, n_timed_steps, nxt = time_kernels(nxt)
+    # (--full on one GPU: 6 s of back-to-back steps -- a 5-second utilisation sampler beside the run then has a busy sample;
+    #  the r04 driver log showed none for 1 s of steps)
+    wins, cost, nxt = measure_headline(args.warmup, min_total=6.0 if world == 1 else 1.5)
+    outputs = outputs_of(cost)
+    detail, n_timed_steps = None, 0
+    if args.full:
+        detail, n_timed_steps, nxt = time_kernels(nxt)
 
     dog = None
     dist_block = {"ranks": world, "backend": backend_name, "rccl_ranks": world if backend_name == "nccl" else 0,
@@ -576,17 +636,18 @@ def main():
         allr = [torch.zeros_like(mine) for _ in range(world)]
         td.all_gather(allr, mine)
         dist_block["per_rank_ms_per_step"] = [float(x.item()) for x in allr]
-        buf = torch.zeros(V * H + H + V + 4, dtype=torch.float32, device=dev)
-        for _ in range(5):
-            td.all_reduce(buf)
-        barrier()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            td.all_reduce(buf)
-        e1.record()
-        torch.cuda.synchronize(dev)
-        dist_block["allreduce_alone_us"] = 1e3 * e0.elapsed_time(e1) / 20
+        if args.full:
+            buf = torch.zeros(V * H + H + V + 4, dtype=torch.float32, device=dev)
+            for _ in range(5):
+                td.all_reduce(buf)
+            barrier()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(20):
+                td.all_reduce(buf)
+            e1.record()
+            torch.cuda.synchronize(dev)
+            dist_block["allreduce_alone_us"] = 1e3 * e0.elapsed_time(e1) / 20
         dist_block["rccl"] = rccl_summary(rccl_log) if rank == 0 else None
         dog.park(line_for(wins, cost, detail, n_timed_steps, dict(dist_block, note="default setting; the sweep did not finish")))
 
@@ -594,9 +655,10 @@ def main():
     # How many CUs to leave to the collective (and which collective) cannot be known from one GPU -- measure it here: short
     # windows at every setting, all reported in `distributed.sweep`; the fastest is installed and timed like the default
     # (it is `value`).  Rank 0's clock decides what still fits the budget; points that do not are reported as skipped.
+    # --full only: a plain run times the default setting.
     sweep, groups, best = None, {}, None
     budget = float(args.sweep_budget)
-    if world > 1 and not args.no_sweep and budget > 0 and getattr(step_fn, "overlap", False):
+    if world > 1 and args.full and not args.no_sweep and budget > 0 and getattr(step_fn, "overlap", False):
         sweep = []
         default = setting_of(step_fn)
         t_sweep0 = time.time()
@@ -694,6 +756,7 @@ def main():
             install({k: best[k] for k in default}, groups[best.get("rccl_max_ctas")])
             run(args.warmup, nxt0)
             wins, cost, nxt0 = measure(nxt0)
+            outputs = outputs_of(cost)
             detail, n_timed_steps, nxt0 = time_kernels(nxt0)
         else:
             install(default, default_pg)
@@ -719,6 +782,7 @@ def main():
         dist_block["allreduce_alone_us_by_rccl_max_ctas"] = allreduce_by_cap
     if world > 1:
         dist_block["sweep"] = sweep
+    if world > 1 and args.full:
         dog.park(line_for(wins, cost, detail, n_timed_steps, dict(dist_block, note="the reporting tail did not finish")))
         dog.arm(float(os.environ.get("MDBN_BENCH_TAIL_BUDGET_S", "180")), "exposed-communication probe")
         # What the collective costs the step: the SAME setting with both all-reduce calls stubbed out (Group.stub_collective:
@@ -782,7 +846,7 @@ def main():
     # DESIGN.md section 3); both numbers are reported
     exact_ms = None
     exact_rows = None
-    if world == 1 and not args.default_only:
+    if world == 1 and args.full and not args.default_only:
         eng.set_option("gemm_bf16x6", 0)
         eng.set_option("gemm_planes", 0)
         run(args.warmup, 0)
@@ -800,7 +864,7 @@ def main():
     # GEMM instead of six, f32 accumulation) is a REPORTING figure only -- probabilities are then off by ~4e-3, so it
     # is never the parity path and never `value`
     bf16_in = None
-    if world == 1 and not args.default_only:
+    if world == 1 and args.full and not args.default_only:
         eng.set_option("bf16_inputs", 1)
         run(args.warmup, 0)
         bwins, _, _ = measure(args.warmup, min_total=0.25)
@@ -816,7 +880,7 @@ def main():
     # minibatch's rows gathered over PCIe into a double buffer one step ahead of the step that uses them).  Its rate is
     # reported beside `value`, never as `value` (the metric is defined with inputs resident in HBM).
     pcie = None
-    if world == 1 and not args.default_only:
+    if world == 1 and args.full and not args.default_only:
         try:
             host_x = mdbn_amd.shared(data.cpu().numpy(), engine=eng, resident="host")
             rbm_h = mdbn_amd.GRBM(n_visible=V, n_hidden=H, numpy_rng=np.random.RandomState(123), engine=eng)
@@ -853,7 +917,7 @@ def main():
 
     # free-energy parity of the trained model vs the float64 oracle (north star: <= 1e-4 rel)
     fe_rel = fe_rel_elem = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import rbm_np
         st = rbm_np.RBMState(V, H, W=rbm.W.get_value(), hbias=rbm.hbias.get_value(),
                              vbias=rbm.vbias.get_value(), gauss=True)
@@ -870,16 +934,21 @@ def main():
             dog.finish(None)
         return
     dist_block["wall_s_since_start"] = time.time() - t_job0
-    out = line_for(wins, cost, detail, n_timed_steps, dist_block, {
+    extras = {
         "exact_f32_mfma_ms_per_step": exact_ms,
         "exact_f32_mfma_value": (B_global * K_GIBBS * 1e3 / exact_ms) if exact_ms else None,
         "exact_f32_mfma_kernels": exact_rows,
         "bf16_input_mode": bf16_in,
         "pcie_inclusive_host_resident_table": pcie,
         "free_energy_max_rel_err_vs_f64_oracle": fe_rel,
-        "free_energy_max_elementwise_rel_err": fe_rel_elem})
-    if world == 1 and not args.no_cpu_baseline and not args.default_only:
+        "free_energy_max_elementwise_rel_err": fe_rel_elem}
+    out = line_for(wins, cost, detail, n_timed_steps, dist_block, extras if args.full else None)
+    if world == 1 and args.full and not args.no_cpu_baseline and not args.default_only:
         out["cpu_baseline"] = cpu_baseline()
+    if outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     if dog is not None:
         dog.finish(out)
     else:
