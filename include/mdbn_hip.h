@@ -165,7 +165,8 @@ int  mdbn_ctx_destroy(mdbn_ctx *ctx);
  * "x6_min_jobs" (default 48): problems with fewer 128x128-tile jobs keep the exact-f32 kernel.
  * "x6_producer_waves" (default 4): producer waves per operand of the bf16x6 kernel (2 | 4).
  * "gemm_bk": GEMM slice depth, 0 = auto, 32 or 64.  "gemm_cw": MFMA waves per SIMD of the tiled
- *   GEMM, 0 = auto (2 for <= 512 rows), 1 or 2.
+ *   GEMM, 0 = auto (2 for <= 512 rows), 1 or 2.  "gemm_min_splitk" (default 128, >= 32): smallest reduction
+ *   length one split-K job of the tiled GEMM takes.
  * "epilogue_cw": columns per thread of the activation epilogue, 0 = auto, 1, 2 or 4.
  * "fused_epilogue" (default 1): GEMMs that need no split-K apply bias + activation + sampling to
  *   their own output tile instead of writing slabs for a second kernel (bitwise the same result).
@@ -183,7 +184,9 @@ int  mdbn_ctx_destroy(mdbn_ctx *ctx);
  *   register-streaming kernel on the bf16 matrix pipe (f32 operands split in registers into their three exact bf16
  *   pieces; six piece products, three when the row operand holds 0/1 samples) with the activation / update epilogue on
  *   the tile: one launch per pass instead of split-K GEMM + slabs + epilogue launch.  2: the small-layer passes of
- *   "skinny_gemm" above 64 rows too; 1: only the passes the LDS-tiled kernels served; 0: off.  "stream_mi": 0 = auto, 1 | 2 = 32-row blocks per tile.
+ *   "skinny_gemm" above 64 rows too; 1: only the passes the LDS-tiled kernels served; 0: off.  "stream_mi": 0 = auto, 1 | 2 = 32-row blocks per tile;
+ *   "stream_ni": 0 = auto, 1 | 2 = 32-column strips per tile.  stream_ni = 2 (set, or chosen by auto) implies 64-row
+ *   tiles whatever "stream_mi" says: the kernel's tiles are 32 x 32, 64 x 32 and 64 x 64.
  * "gemm_planes" (default 1): use the bf16 plane path of mdbn_cd_args when its buffers are given and the
  *   shape qualifies.  "planes_mfma" (default 16): its MFMA shape, 16 = v_mfma_f32_16x16x32_bf16, 32 =
  *   v_mfma_f32_32x32x16_bf16 (bit-identical to the f32-operand path). 
@@ -196,6 +199,8 @@ int  mdbn_ctx_destroy(mdbn_ctx *ctx);
  * "narrow_tiles" (default 1): a forward pass of the plane path whose 128 x 128 plan would split K exactly two ways
  *   (propdown at the c2 shape) runs unsplit on 128 x 64 tiles with the activation fused into the GEMM instead: no slabs,
  *   no epilogue launch; another fp32 summation grouping (one K-long chain instead of two halves).
+ * "feed_copy_streams" (default 1): a host-resident row feeder created afterwards moves each minibatch as 1 or 2 copies
+ *   on as many streams.
  * "gather_ahead" (default 1): honour mdbn_cd_args.next_indexes (the next minibatch gathered inside the statistics
  *   kernel); 0 = every step launches its own gather.
  * "comm_cus" (default 0): CUs left to a collective that runs beside the step when mdbn_cd_args.comm_cus is 0 (see

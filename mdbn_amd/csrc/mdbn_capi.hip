@@ -8,6 +8,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cstdint>
 #include <deque>
 #include <map>
 #include <mutex>
@@ -353,7 +354,8 @@ bool try_bf16x6(Plan& p, int64_t M, int64_t N, int64_t K, bool unsplit = false)
 // launch per pass.  2: the small-layer passes prefer_skinny() sends to the exact-f32 streaming kernel use it as well
 // (256 -> 200 at B = 512: CD-1 37.9 -> 30.1 us, CD-5 100.1 -> 71.6: profiles/r05za_configs_ab.log); 1: only the passes
 // the LDS-tiled kernels served.
-// "stream_max_macs": largest M * N * K served; "stream_mi": 0 = auto, 1 | 2 = 32-row blocks per tile.
+// "stream_max_macs": largest M * N * K served; "stream_mi": 0 = auto, 1 | 2 = 32-row blocks per tile; "stream_ni": 0 = auto,
+// 1 | 2 = 32-column strips per tile.  ni = 2 implies mi = 2, whatever "stream_mi" says: the tiles are 32 x 32, 64 x 32 or 64 x 64.
 #define g_opt_stream_x6 (t_opt->stream_x6)
 #define g_opt_stream_max_macs (t_opt->stream_max_macs)
 #define g_opt_stream_mi (t_opt->stream_mi)
@@ -375,6 +377,7 @@ Plan plan_stream(int64_t M, int64_t K, int64_t ldo)
     p.ni = tiles32 >= 4 * kStreamMinTiles ? 2 : 1;
     if (g_opt_stream_mi) p.mi = g_opt_stream_mi;
     if (g_opt_stream_ni) p.ni = g_opt_stream_ni;
+    if (p.ni == 2) p.mi = 2;        // two strips only on 64-row tiles (launch_stream_gemm has no 32 x 64 instance)
     p.tiles_m = (int)((M + 32 * p.mi - 1) / (32 * p.mi));
     p.x6 = 1;
     return p;
@@ -1141,10 +1144,12 @@ int mdbn_set_option(mdbn_ctx* ctx, const char* name, int64_t value)
         return MDBN_OK;
     }
     if (strcmp(name, "skinny_fused_max_k") == 0) {
-        ctx->opt.skinny_fused_max_k = value;
+        REQUIRE(value >= 0 && value <= INT32_MAX, "skinny_fused_max_k must be in [0, 2^31)");
+        ctx->opt.skinny_fused_max_k = (int)value;
         return MDBN_OK;
     }
     if (strcmp(name, "x6_min_jobs") == 0) {
+        REQUIRE(value >= 0 && value <= INT32_MAX, "x6_min_jobs must be in [0, 2^31)");
         ctx->opt.x6_min_jobs = (int)value;
         return MDBN_OK;
     }
@@ -1154,7 +1159,7 @@ int mdbn_set_option(mdbn_ctx* ctx, const char* name, int64_t value)
         return MDBN_OK;
     }
     if (strcmp(name, "gemm_min_splitk") == 0) {
-        if (value < 32) return fail(MDBN_EINVAL, "gemm_min_splitk must be >= 32");
+        if (value < 32 || value > INT32_MAX) return fail(MDBN_EINVAL, "gemm_min_splitk must be in [32, 2^31)");
         ctx->opt.min_splitk = (int)value;
         return MDBN_OK;
     }
@@ -1164,10 +1169,12 @@ int mdbn_set_option(mdbn_ctx* ctx, const char* name, int64_t value)
         return MDBN_OK;
     }
     if (strcmp(name, "stream_x6") == 0) {
+        REQUIRE(value == 0 || value == 1 || value == 2, "stream_x6 must be 0, 1 or 2");
         ctx->opt.stream_x6 = (int)value;
         return MDBN_OK;
     }
     if (strcmp(name, "stream_max_macs") == 0) {
+        REQUIRE(value >= 0, "stream_max_macs must be >= 0");
         ctx->opt.stream_max_macs = value;
         return MDBN_OK;
     }
@@ -1182,11 +1189,13 @@ int mdbn_set_option(mdbn_ctx* ctx, const char* name, int64_t value)
         return MDBN_OK;
     }
     if (strcmp(name, "skinny_max_macs") == 0) {
+        REQUIRE(value >= 0 && value < ((int64_t)1 << 61), "skinny_max_macs must be in [0, 2^61)");   // (3x it must fit)
         ctx->opt.skinny_max_macs = value;
         return MDBN_OK;
     }
     if (strcmp(name, "gemm_bf16x6") == 0) {
-        ctx->opt.gemm_bf16x6 = (int)value & 3;
+        REQUIRE(value >= 0 && value <= 3, "gemm_bf16x6 must be in 0..3 (bit 0 statistics, bit 1 forward passes)");
+        ctx->opt.gemm_bf16x6 = (int)value;
         return MDBN_OK;
     }
     if (strcmp(name, "planes_min_work") == 0) {
