@@ -403,6 +403,34 @@ int  mdbn_free_energy(mdbn_ctx *ctx, void *stream, const float *x, int64_t N, in
                       const float *vbias, int gauss, float *out,
                       void *workspace, int64_t workspace_bytes);
 
+/* Annealed importance sampling (Salakhutdinov & Murray 2008) of a trained layer: M independent chains annealed from the
+ * base-rate model (W = 0, hbias = 0, visible bias base_vbias; log Z_A = H log 2 + sum_i softplus(base_vbias_i) for Bernoulli,
+ * H log 2 + V/2 log 2 pi for unit-variance Gaussian visibles, rbm.py:631-699) to the trained one through the inverse temperatures
+ * betas[0] = 0 < ... < betas[K] = 1 (device array, n_betas = K + 1 values).  With a(v) = v W + hbias and
+ * b_beta = (1 - beta) base_vbias + beta vbias:
+ *   log p*_beta(v) = sum_j softplus(beta a_j(v)) + { v . b_beta  |  -|v - b_beta|^2 / 2 }
+ *   v_1 ~ p_0;  k = 1 .. K:  logw += log p*_{beta_k}(v_k) - log p*_{beta_{k-1}}(v_k);
+ *               k < K:  h ~ Bernoulli(sigmoid(beta_k a(v_k))),  v_{k+1} ~ Bernoulli(sigmoid(b_beta_k + beta_k h W^T))  |
+ *                                                                        b_beta_k + beta_k h W^T + N(0, 1)
+ * and log Z ~ log Z_A + logsumexp(logw) - log M (left to the caller: float64 on the host).  Products, softplus and row sums
+ * are float32, the per-chain logw a double.  Random draws: v_1 uses step rng->step, the hidden draw of temperature k step
+ * rng->step + 2k - 1, its visible draw rng->step + 2k, all with draw index 0 (normals: the Box-Muller pair of
+ * mdbn_rng_normal); the caller advances its step counter by 2K - 1.
+ * path: 0 = by shape, 1 = the one-launch path (LDS-resident layers: the shapes of "small_fused"; W staged once, a workgroup
+ * runs the whole schedule for four chains, cut into launches of at most 4096 temperatures with the state carried in
+ * v_state / logw) or MDBN_EINVAL if the shape does not fit, 2 = the general path (per temperature: the propup GEMM, a fused
+ * weight-update + hidden-draw kernel, the propdown GEMM, a visible-draw kernel).  The paths meet the same uniforms and
+ * differ by fp32 summation order only.  v_state (nullable): the final visible state [M, ldv].  trace_h [K-1][M][ldh] /
+ * trace_v [K][M][ldv] (nullable): the hidden / visible sample of every temperature.  Bad arguments (M < 1, n_betas < 2,
+ * path 1 on a shape that does not fit, a workspace shorter than mdbn_ais_workspace_bytes -- which answers for leading
+ * dimensions up to mdbn_padded_ld) return MDBN_EINVAL without a launch. */
+int  mdbn_ais_workspace_bytes(mdbn_ctx *ctx, int64_t M, int64_t V, int64_t H, int64_t n_betas, int path, int64_t *bytes);
+int  mdbn_ais_run(mdbn_ctx *ctx, void *stream, const float *W, int64_t V, int64_t H, int64_t ldh,
+                  const float *hbias, const float *vbias, const float *base_vbias, int gauss,
+                  const float *betas, int64_t n_betas, int64_t M, int64_t ldv, float *v_state,
+                  double *logw, float *trace_h, float *trace_v, int path, const mdbn_rng *rng,
+                  void *workspace, int64_t workspace_bytes);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)). */

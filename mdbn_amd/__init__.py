@@ -11,10 +11,10 @@ from .rng import RandomStreams
 from .shared import HostTable, SharedArray, shared
 from .utils import get_minibatches_idx
 from .mlp import HiddenLayer
-from .rbm import RBM, GRBM, Scalar, function
+from .rbm import RBM, GRBM, Scalar, ais_estimate, function
 from .dbn import DBN
 from . import MDBN, checkpoint, dist, utils
 
 __all__ = ["MdbnError", "HipEngine", "RngAddr", "get_engine", "set_engine", "RandomStreams",
            "SharedArray", "HostTable", "shared", "get_minibatches_idx", "HiddenLayer", "RBM", "GRBM",
-           "Scalar", "function", "DBN", "MDBN", "dist", "checkpoint", "utils"]
+           "Scalar", "function", "ais_estimate", "DBN", "MDBN", "dist", "checkpoint", "utils"]

@@ -1,0 +1,52 @@
+// Annealed importance sampling of a trained RBM / GRBM (mdbn_ais.hip): arguments and launchers.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "mdbn_kernels.h"
+#include "mdbn_small.h"
+
+namespace mdbn {
+
+constexpr int AIS_CUT = 4096;               // temperatures one launch of the one-launch path runs at most: a launch stays short
+                                            // (~3 us per temperature) and the Philox addressing makes the cut invisible
+constexpr int AIS_NT = 256;                 // threads of the general path's per-temperature kernels: one wave per chain
+
+// One-launch path (LDS-resident layers, small_shape_ok): temperatures k0 + 1 .. k1 of chains 0 .. M - 1.
+struct AisSmallArgs {
+    int M, V, H, gauss;
+    int64_t ldv, ldh;                                // leading dimensions of v_state / the traces; W is [V][ldh]
+    const float* W; const float* hbias; const float* vbias; const float* base_vbias;
+    const float* betas;                              // [K + 1] device
+    int K, k0, k1;                                   // the whole schedule's length; this launch's temperatures (k0, k1]
+    PhiloxKey rng;                                   // .step = the run's first step; .draw unused (always 0)
+    SmallLayout L;                                   // LDS layout (small_layout; filled in by launch_ais_small)
+    float* v_state;                                  // [M][ldv]: k0 > 0: v_{k0 + 1} on entry; v_{min(k1 + 1, K)} on return
+    double* logw;                                    // [M]: k0 > 0: log w after temperature k0 on entry; after k1 on return
+    float* trace_h; float* trace_v;                  // [K - 1][M][ldh], [K][M][ldv] or NULL
+};
+
+// General path, per temperature k: pre_h = v_k W + c is in `pre` (the propup GEMM), then
+//   hidden : logw += sum_j softplus(b1 pre) - softplus(b0 pre) + bias term (from s1 / d2); h ~ Bernoulli(sigmoid(b1 pre))
+//   visible: v_{k+1} from m = h W^T (the propdown GEMM, no bias), s1 = sum_i (v_{k+1} - [gauss] b_A) (b - b_A)
+struct AisStepArgs {
+    int M, V, H, gauss, k, K;
+    int64_t ldv, ldh;
+    const float* betas;
+    const float* vbias; const float* base_vbias;
+    PhiloxKey rng;                                   // .step = the run's first step
+    float* pre;                                      // [M][ldh] propup output / [M][ldv] propdown output (m)
+    float* h;                                        // [M][ldh] hidden sample
+    float* v;                                        // [M][ldv] visible state
+    float* s1;                                       // [M]
+    const float* d2;                                 // [1]: sum_i (b - b_A)^2 (Gaussian)
+    double* logw;                                    // [M]
+    float* trace;                                    // this temperature's trace slot or NULL
+};
+
+bool ais_small_ok(int64_t M, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh);
+hipError_t launch_ais_small(const AisSmallArgs& a, hipStream_t s);
+hipError_t launch_ais_d2(const float* vbias, const float* base_vbias, int V, float* d2, hipStream_t s);
+hipError_t launch_ais_hidden(const AisStepArgs& a, hipStream_t s);
+hipError_t launch_ais_visible(const AisStepArgs& a, hipStream_t s);      // a.k = 0: draws v_1 from the base model (pre unused)
+
+}  // namespace mdbn

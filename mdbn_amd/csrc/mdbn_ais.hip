@@ -1,0 +1,408 @@
+// Annealed importance sampling (Salakhutdinov & Murray 2008) of a trained RBM / GRBM on gfx950 / MI355X: M independent
+// chains annealed from a base-rate model (W = 0, c = 0, visible bias b_A) to the trained model through the inverse
+// temperatures 0 = beta_0 < ... < beta_K = 1; log Z ~ log Z_A + log mean exp(log w).
+//
+//   a(v) = v W + c,  b_beta = b_A + beta (b - b_A)
+//   temperature k = 1 .. K:  log w += sum_j softplus(beta_k a_j(v_k)) - softplus(beta_{k-1} a_j(v_k))
+//                                     + (beta_k - beta_{k-1}) s1(v_k)  [- (beta_k^2 - beta_{k-1}^2) / 2 * sum_i (b - b_A)_i^2, Gaussian]
+//                            s1(v) = sum_i (v_i - [Gaussian] b_A,i) (b - b_A)_i        (the bias term of log p*_beta, regrouped:
+//                                     v . b_beta for Bernoulli, -|v - b_beta|^2 / 2 for Gaussian visibles, as a difference)
+//                            k < K:  h ~ Bernoulli(sigmoid(beta_k a(v_k))),  m = h W^T,
+//                                    v_{k+1} ~ Bernoulli(sigmoid(b_beta_k + beta_k m))  |  b_beta_k + beta_k m + N(0, 1)
+// Products, softplus and row sums are float32; the per-chain log w is a double (one scalar add per chain and temperature).
+// Random draws: rng.step = s: v_1 uses step s, the hidden draw of temperature k step s + 2 k - 1, its visible draw s + 2 k,
+// draw index 0, the usual (column, global row >> 2) addressing -- so a run cut into several launches, the one-launch path and
+// the general path all meet the same uniforms.
+//
+// ais_small_kernel (LDS-resident layers): the shape of small_cd_kernel -- W staged once into one CU's LDS, a workgroup owns
+// four-chain slabs (one Philox block) and runs the whole loop over the temperatures on the exact-f32 4x4x1 MFMA passes of
+// mdbn_small_passes.h.  No workgroup ever waits for, or exchanges anything with, another.
+// ais_hidden_kernel / ais_visible_kernel (any shape): the per-temperature epilogues around the library's propup / propdown
+// GEMMs; a workgroup owns a four-chain group and reduces its rows in a fixed order.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "mdbn_kernels.h"
+#include "mdbn_device.h"
+#include "mdbn_small.h"
+#include "mdbn_small_passes.h"
+#include "mdbn_ais.h"
+
+namespace mdbn {
+
+namespace {
+
+constexpr float AIS_TWO_PI = 6.28318530717958647692f;
+
+// v_{k+1} | h_k for one (4-chain group, column): pre = b_A + beta (b - b_A) + beta m, then the draw.  `s` receives the
+// column's share of s1.  The one statement of this arithmetic: both paths call it.
+template <bool GAUSS>
+__device__ __forceinline__ void ais_draw_v(const PhiloxKey& key, uint64_t grow0, int col, float beta, float bA, float db,
+                                           const float (&m)[4], const bool (&ok)[4], float (&v)[4], float (&s)[4])
+{
+    uint32_t wa[4], wb[4] = {0u, 0u, 0u, 0u};
+    philox_rows4(key, 0u, grow0, (uint32_t)col, wa);
+    if (GAUSS) philox_rows4(key, MDBN_NORMAL_BIT, grow0, (uint32_t)col, wb);
+    const float bb = fmaf(beta, db, bA);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float pre = fmaf(beta, m[e], bb);
+        if (GAUSS) {
+            const float z = sqrtf(-2.0f * logf(philox_u01(wa[e]))) * cosf(AIS_TWO_PI * philox_u01(wb[e]));
+            v[e] = ok[e] ? pre + z : 0.f;
+            s[e] = ok[e] ? (v[e] - bA) * db : 0.f;
+        } else {
+            v[e] = ok[e] && philox_u01(wa[e]) < sigmoidf_(pre) ? 1.0f : 0.0f;
+            s[e] = v[e] * db;
+        }
+    }
+}
+
+// h_k | v_k and the hidden share of the weight update for one (4-chain group, column); a = pre-activation (c included)
+__device__ __forceinline__ void ais_draw_h(const PhiloxKey& key, uint64_t grow0, int col, float b1, float b0, bool draw,
+                                           const float (&a)[4], const bool (&ok)[4], float (&h)[4], float (&d)[4])
+{
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (draw) philox_rows4(key, 0u, grow0, (uint32_t)col, w);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        d[e] = ok[e] ? softplusf_(b1 * a[e]) - softplusf_(b0 * a[e]) : 0.f;
+        h[e] = draw && ok[e] && philox_u01(w[e]) < sigmoidf_(b1 * a[e]) ? 1.0f : 0.0f;
+    }
+}
+
+// log w after one temperature (double: the increments are O(1 / K) of a total of hundreds of nats)
+__device__ __forceinline__ double ais_logw_add(double lw, float hsum, float s1, float d2, float b1, float b0, bool gauss)
+{
+    const double B1 = (double)b1, B0 = (double)b0;
+    lw += (double)hsum + (B1 - B0) * (double)s1;
+    if (gauss) lw -= 0.5 * (B1 * B1 - B0 * B0) * (double)d2;
+    return lw;
+}
+
+__device__ __forceinline__ float wave_sum(float x)       // every lane of the wave active; the same tree in every call
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+}  // namespace
+
+template <bool GAUSS, bool TRACE>
+__global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const SmallLayout& L = a.L;
+    lds_f* const lds = (lds_f*)sm;
+    // small_layout's buffers under the roles they have here
+    lds_f* const Wl = lds + L.oW;
+    lds_f* const X = lds + L.oXa;           // [4][ldx] visible state v_k
+    lds_f* const Hs = lds + L.oHs;          // [4][ldhs] hidden sample h_k
+    lds_f* const part = lds + L.oPart;
+    lds_f* const hbl = lds + L.oHb;         // c
+    lds_f* const bAl = lds + L.oVb;         // b_A
+    lds_f* const dbl = lds + L.oCsV;        // b - b_A
+    lds_f* const redH = lds + L.oM0;        // [4][8] per-wave row partials of the hidden share (one per 64-column tile)
+    lds_f* const redV = redH + 32;          // [4][8] ... of s1
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int V = a.V, H = a.H, M = a.M, K = a.K;
+    const int64_t ldv = a.ldv, ldh = a.ldh;
+    const int nslabs = (M + SM_ROWS - 1) / SM_ROWS;
+
+    // ---- W image [Vp][ldw] (rows >= V and columns >= ldh zero, + the slack behind the last row), biases, zeroed row buffers
+    {
+        const int q4w = L.ldw >> 2, q4 = (int)(ldh >> 2);
+        const int total = L.Vp * q4w + 4;
+        for (int e = tid; e < total; e += SM_NT) {
+            const int r = e / q4w, c4 = e - r * q4w;
+            sf32x4 w = {0.f, 0.f, 0.f, 0.f};
+            if (r < V && c4 < q4) w = *reinterpret_cast<const sf32x4*>(a.W + (int64_t)r * ldh + 4 * c4);
+            *(lds_f4*)(Wl + 4 * e) = w;
+        }
+    }
+    if (tid < L.H64) hbl[tid] = tid < H ? a.hbias[tid] : 0.f;
+    if (tid < L.V64) {
+        const float bA = tid < V ? a.base_vbias[tid] : 0.f, b = tid < V ? a.vbias[tid] : 0.f;
+        bAl[tid] = bA; dbl[tid] = b - bA;
+    }
+    for (int i = tid; i < SM_ROWS * L.ldx; i += SM_NT) X[i] = 0.f;
+    for (int i = tid; i < SM_ROWS * L.ldhs; i += SM_NT) Hs[i] = 0.f;
+    SM_SYNC();
+    float d2 = 0.f;                          // sum_i (b - b_A)_i^2: every thread sums it in the same order
+    if (GAUSS) {
+        for (int i = lane; i < L.V64; i += 64) d2 += dbl[i] * dbl[i];
+        d2 = wave_sum(d2);
+    }
+
+    for (int slab = blockIdx.x; slab < nslabs; slab += gridDim.x) {
+        const int row0 = slab * SM_ROWS;
+        const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
+        bool ok[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ok[e] = row0 + e < M;
+        if (slab != (int)blockIdx.x) SM_SYNC();                        // (the previous slab's last readers are done)
+
+        // a visible state goes into X; its share of s1 into redV (whole waves: V64 is a multiple of 64)
+        auto put_v = [&](const float (&v)[4], const float (&s)[4], int col, float* trace) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) X[e * L.ldx + col] = v[e];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float t = wave_sum(s[e]);
+                if (lane == 0) redV[e * 8 + (col >> 6)] = t;
+            }
+            if (TRACE && trace && col < (int)ldv) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (ok[e]) trace[(int64_t)(row0 + e) * ldv + col] = v[e];
+            }
+        };
+        // ---- the chain's start: v_1 ~ p_0 (step s), or the state an earlier launch left
+        double lw = 0.0;
+        if (tid < L.V64) {
+            const int col = tid;
+            const bool live = col < V;
+            const float bA = bAl[col], db = dbl[col];
+            const bool okc[4] = {ok[0] && live, ok[1] && live, ok[2] && live, ok[3] && live};
+            float v[4], s[4];
+            if (a.k0 == 0) {
+                const float m0[4] = {0.f, 0.f, 0.f, 0.f};
+                ais_draw_v<GAUSS>(a.rng, grow0, col, 0.0f, bA, db, m0, okc, v, s);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = okc[e] ? a.v_state[(int64_t)(row0 + e) * ldv + col] : 0.f;
+                    s[e] = okc[e] ? (GAUSS ? (v[e] - bA) * db : v[e] * db) : 0.f;
+                }
+            }
+            put_v(v, s, col, a.k0 == 0 ? a.trace_v : nullptr);
+        }
+        if (a.k0 > 0 && tid < SM_ROWS && row0 + tid < M) lw = a.logw[row0 + tid];
+        SM_SYNC();
+        float s1 = 0.f;
+        if (tid < SM_ROWS)
+            for (int t = 0; t < L.tiles_dn; ++t) s1 += redV[tid * 8 + t];
+
+        // ---- the temperatures of this launch (beta_{k+1} is requested one temperature ahead of its use)
+        float b0 = a.betas[a.k0], b1 = a.betas[a.k0 + 1];
+        for (int k = a.k0 + 1; k <= a.k1; ++k) {
+            const float b_next = a.betas[min(k + 1, K)];
+            const bool draw = k < K;
+            PhiloxKey kh = a.rng, kv = a.rng;
+            kh.step = a.rng.step + (uint32_t)(2 * k - 1);
+            kv.step = a.rng.step + (uint32_t)(2 * k);
+            sm_up(X, Wl, L, part, wave, lane, [] {},
+                  [&](const sf32x4& x, int col) {
+                      const bool live = col < H;
+                      const float bias = hbl[col];
+                      const bool okc[4] = {ok[0] && live, ok[1] && live, ok[2] && live, ok[3] && live};
+                      const float pre[4] = {x[0] + bias, x[1] + bias, x[2] + bias, x[3] + bias};
+                      float h[4], d[4];
+                      ais_draw_h(kh, grow0, col, b1, b0, draw, pre, okc, h, d);
+#pragma unroll
+                      for (int e = 0; e < 4; ++e) Hs[e * L.ldhs + col] = h[e];
+#pragma unroll
+                      for (int e = 0; e < 4; ++e) {
+                          const float t = wave_sum(d[e]);
+                          if (lane == 0) redH[e * 8 + (col >> 6)] = t;
+                      }
+                      if (TRACE && a.trace_h && draw && col < (int)ldh) {
+#pragma unroll
+                          for (int e = 0; e < 4; ++e)
+                              if (ok[e]) a.trace_h[((int64_t)(k - 1) * M + row0 + e) * ldh + col] = h[e];
+                      }
+                  });
+            if (tid < SM_ROWS) {
+                float hsum = 0.f;
+                for (int t = 0; t < L.tiles_up; ++t) hsum += redH[tid * 8 + t];
+                lw = ais_logw_add(lw, hsum, s1, d2, b1, b0, GAUSS);
+            }
+            if (draw) {
+                sm_down(Hs, Wl, L, wave, lane,
+                        [&](const sf32x4& x, int col) {
+                            const bool live = col < V;
+                            const float bA = bAl[col], db = dbl[col];
+                            const bool okc[4] = {ok[0] && live, ok[1] && live, ok[2] && live, ok[3] && live};
+                            const float m[4] = {x[0], x[1], x[2], x[3]};
+                            float v[4], s[4];
+                            ais_draw_v<GAUSS>(kv, grow0, col, b1, bA, db, m, okc, v, s);
+                            put_v(v, s, col, TRACE && a.trace_v ? a.trace_v + (int64_t)k * M * ldv : nullptr);
+                        });
+                if (tid < SM_ROWS) {
+                    s1 = 0.f;
+                    for (int t = 0; t < L.tiles_dn; ++t) s1 += redV[tid * 8 + t];
+                }
+            }
+            b0 = b1; b1 = b_next;
+        }
+
+        // ---- what the next launch (or the caller) reads: the visible state and log w
+        if (a.v_state) {
+            for (int i = tid; i < SM_ROWS * (int)ldv; i += SM_NT) {
+                const int e = i / (int)ldv, col = i - e * (int)ldv;
+                if (row0 + e < M) a.v_state[(int64_t)(row0 + e) * ldv + col] = X[e * L.ldx + col];
+            }
+        }
+        if (tid < SM_ROWS && row0 + tid < M) a.logw[row0 + tid] = lw;
+    }
+}
+
+bool ais_small_ok(int64_t M, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh)
+{
+    return small_shape_ok(M, V, H, gauss) && small_ld_ok(V, H, ldv, ldh);
+}
+
+hipError_t launch_ais_small(const AisSmallArgs& a, hipStream_t s)
+{
+    if (!ais_small_ok(a.M, a.V, a.H, a.gauss, a.ldv, a.ldh) || a.k0 < 0 || a.k1 <= a.k0 || a.k1 > a.K) return hipErrorInvalidValue;
+    const SmallLayout L = small_layout(a.V, a.H, a.gauss != 0);
+    const bool trace = a.trace_h || a.trace_v;
+    const int variant = (a.gauss ? 2 : 0) | (trace ? 1 : 0);
+    static bool attr_set[4] = {false, false, false, false};
+    const void* kerns[4] = {reinterpret_cast<const void*>(ais_small_kernel<false, false>), reinterpret_cast<const void*>(ais_small_kernel<false, true>),
+                            reinterpret_cast<const void*>(ais_small_kernel<true, false>), reinterpret_cast<const void*>(ais_small_kernel<true, true>)};
+    if (!attr_set[variant]) {
+        hipError_t e = hipFuncSetAttribute(kerns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, SM_MAX_LDS);
+        if (e != hipSuccess) return e;
+        attr_set[variant] = true;
+    }
+    // one workgroup per slab up to one per CU of the chip (no partials to sum here: the cap only bounds the W stagings)
+    const int nslabs = (a.M + SM_ROWS - 1) / SM_ROWS;
+    const dim3 grid(nslabs < 256 ? nslabs : 256), block(SM_NT);
+    AisSmallArgs k = a;
+    k.L = L;
+    switch (variant) {
+        case 0: hipLaunchKernelGGL((ais_small_kernel<false, false>), grid, block, L.bytes, s, k); break;
+        case 1: hipLaunchKernelGGL((ais_small_kernel<false, true>), grid, block, L.bytes, s, k); break;
+        case 2: hipLaunchKernelGGL((ais_small_kernel<true, false>), grid, block, L.bytes, s, k); break;
+        default: hipLaunchKernelGGL((ais_small_kernel<true, true>), grid, block, L.bytes, s, k); break;
+    }
+    return hipGetLastError();
+}
+
+// ----------------------------------------------------------------------------------
+// General path: a workgroup of AIS_NT threads owns one four-chain group; a thread walks the columns tid, tid + AIS_NT, ...
+// and the four row sums are combined wave by wave in a fixed order.
+// ----------------------------------------------------------------------------------
+namespace {
+
+__device__ __forceinline__ void ais_rows_sum(float (&acc)[4], float* red /* [4][AIS_NT / 64] */)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float t = wave_sum(acc[e]);
+        if (lane == 0) red[e * (AIS_NT / 64) + wave] = t;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float t = 0.f;
+        for (int w = 0; w < AIS_NT / 64; ++w) t += red[e * (AIS_NT / 64) + w];
+        acc[e] = t;
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(64) void ais_d2_kernel(const float* vbias, const float* base_vbias, int V, float* d2)
+{
+    float t = 0.f;
+    for (int i = threadIdx.x; i < V; i += 64) { const float d = vbias[i] - base_vbias[i]; t += d * d; }
+    t = wave_sum(t);
+    if (threadIdx.x == 0) d2[0] = t;
+}
+
+__global__ __launch_bounds__(AIS_NT) void ais_hidden_kernel(AisStepArgs a)
+{
+    __shared__ float red[4 * (AIS_NT / 64)];
+    const int row0 = (int)blockIdx.x * 4, tid = threadIdx.x;
+    const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
+    const float b1 = a.betas[a.k], b0 = a.betas[a.k - 1];
+    const bool draw = a.k < a.K;
+    PhiloxKey key = a.rng;
+    key.step = a.rng.step + (uint32_t)(2 * a.k - 1);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int col = tid; col < (int)a.ldh; col += AIS_NT) {
+        const bool live = col < a.H;
+        bool ok[4];
+        float pre[4], h[4], d[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            ok[e] = live && row0 + e < a.M;
+            pre[e] = ok[e] ? a.pre[(int64_t)(row0 + e) * a.ldh + col] : 0.f;
+        }
+        ais_draw_h(key, grow0, col, b1, b0, draw, pre, ok, h, d);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[e] += d[e];
+            if (row0 + e < a.M) {
+                a.h[(int64_t)(row0 + e) * a.ldh + col] = h[e];          // (pad columns: zeros)
+                if (a.trace && draw) a.trace[(int64_t)(row0 + e) * a.ldh + col] = h[e];
+            }
+        }
+    }
+    ais_rows_sum(acc, red);
+    if (tid < 4 && row0 + tid < a.M) {
+        const float hsum = tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3];
+        const double lw = a.k == 1 ? 0.0 : a.logw[row0 + tid];
+        a.logw[row0 + tid] = ais_logw_add(lw, hsum, a.s1[row0 + tid], a.gauss ? a.d2[0] : 0.f, b1, b0, a.gauss != 0);
+    }
+}
+
+template <bool GAUSS>
+__global__ __launch_bounds__(AIS_NT) void ais_visible_kernel(AisStepArgs a)
+{
+    __shared__ float red[4 * (AIS_NT / 64)];
+    const int row0 = (int)blockIdx.x * 4, tid = threadIdx.x;
+    const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
+    const float beta = a.k == 0 ? 0.0f : a.betas[a.k];
+    PhiloxKey key = a.rng;
+    key.step = a.rng.step + (uint32_t)(2 * a.k);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int col = tid; col < (int)a.ldv; col += AIS_NT) {
+        const bool live = col < a.V;
+        const float bA = live ? a.base_vbias[col] : 0.f, db = live ? a.vbias[col] - bA : 0.f;
+        bool ok[4];
+        float m[4], v[4], s[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            ok[e] = live && row0 + e < a.M;
+            m[e] = ok[e] && a.k > 0 ? a.pre[(int64_t)(row0 + e) * a.ldv + col] : 0.f;
+        }
+        ais_draw_v<GAUSS>(key, grow0, col, beta, bA, db, m, ok, v, s);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[e] += s[e];
+            if (row0 + e < a.M) {
+                a.v[(int64_t)(row0 + e) * a.ldv + col] = v[e];
+                if (a.trace) a.trace[(int64_t)(row0 + e) * a.ldv + col] = v[e];
+            }
+        }
+    }
+    ais_rows_sum(acc, red);
+    if (tid < 4 && row0 + tid < a.M) a.s1[row0 + tid] = tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3];
+}
+
+hipError_t launch_ais_d2(const float* vbias, const float* base_vbias, int V, float* d2, hipStream_t s)
+{
+    hipLaunchKernelGGL(ais_d2_kernel, dim3(1), dim3(64), 0, s, vbias, base_vbias, V, d2);
+    return hipGetLastError();
+}
+
+hipError_t launch_ais_hidden(const AisStepArgs& a, hipStream_t s)
+{
+    if (a.M < 1 || a.k < 1 || a.k > a.K) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ais_hidden_kernel, dim3((a.M + 3) / 4), dim3(AIS_NT), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ais_visible(const AisStepArgs& a, hipStream_t s)
+{
+    if (a.M < 1 || a.k < 0 || a.k >= a.K) return hipErrorInvalidValue;
+    if (a.gauss) hipLaunchKernelGGL((ais_visible_kernel<true>), dim3((a.M + 3) / 4), dim3(AIS_NT), 0, s, a);
+    else hipLaunchKernelGGL((ais_visible_kernel<false>), dim3((a.M + 3) / 4), dim3(AIS_NT), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace mdbn

@@ -24,6 +24,7 @@
 #include "mdbn_small.h"
 #include "mdbn_thin.h"
 #include "mdbn_gchain.h"
+#include "mdbn_ais.h"
 
 using namespace mdbn;
 
@@ -2169,6 +2170,145 @@ int mdbn_free_energy(mdbn_ctx* ctx, void* stream, const float* x, int64_t N, int
         HIP_OK(launch_free_energy(ws.slabs, p.splitk, g.slab_stride, ldh, (int)H, hbias, x + r0 * ldv, ldv,
                                   (int)V, vbias, gauss, R, out + r0, s));
         r0 += R;
+    }
+    return MDBN_OK;
+}
+
+// ---------------------------------------------------------------------------------- annealed importance sampling
+namespace {
+
+// The caller's workspace of mdbn_ais_run.  One-launch path: the visible state carried between launches.  General path: a
+// zero bias (the propdown product is taken without bias), the pre-activations of a pass, the hidden and the visible state,
+// s1 and d2 (mdbn_ais.hip), then the scratch of the propagation GEMMs.
+struct AisWs {
+    int64_t zero, pre, h, v, s1, gemm_bytes;
+    int64_t total_bytes() const { return 4 * (zero + pre + h + v + s1 + 64) + gemm_bytes; }
+};
+
+AisWs ais_ws(int path, int64_t M, int64_t V, int64_t H, int64_t ldv, int64_t ldh)
+{
+    AisWs w{};
+    w.v = ru64(M * ldv);
+    if (path == 2) {
+        w.zero = ru64(std::max(ldv, ldh));
+        w.pre = ru64(M * std::max(ldv, ldh));
+        w.h = ru64(M * ldh);
+        w.s1 = ru64(M);
+        // scratch of the propagation GEMMs (carve: slabs + a fixed cost region).  Any size serves (a pass is chunked until its
+        // split-K slabs fit); what the plans of M rows ask for is not monotone in M (fewer rows: more split-K), so the answer
+        // is the largest over M and the whole 32-row tilings below it -- a buffer sized for M chains serves any fewer
+        int64_t g = ws_sizes(M, V, H).total_bytes();
+        const int64_t step = std::max<int64_t>(32, ((M >> 12) + 31) & ~int64_t(31));
+        for (int64_t m = step; m < M; m += step) g = std::max(g, ws_sizes(m, V, H).total_bytes());
+        w.gemm_bytes = g + 4 * ((int64_t)(1 << 16) + 4096);
+    }
+    return w;
+}
+
+int ais_path(int path, int64_t M, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh)
+{
+    if (path == 0) return ais_small_ok(M, V, H, gauss, ldv, ldh) ? 1 : 2;
+    return path;
+}
+
+}  // namespace
+
+int mdbn_ais_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t V, int64_t H, int64_t n_betas, int path, int64_t* bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(bytes != nullptr, "bytes is NULL");
+    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
+    REQUIRE(n_betas >= 2, "n_betas = %lld: a schedule has at least beta_0 = 0 and beta_K = 1", (long long)n_betas);
+    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
+    const int64_t ldv = padded_ld(V), ldh = padded_ld(H);
+    // (either visible type: the larger of the two answers, so that one buffer serves a layer whatever its type)
+    const bool fits = ais_small_ok(M, V, H, 0, ldv, ldh) || ais_small_ok(M, V, H, 1, ldv, ldh);
+    REQUIRE(path != 1 || fits, "path 1: %lld -> %lld is not LDS-resident", (long long)V, (long long)H);
+    int64_t need = ais_ws(2, M, V, H, ldv, ldh).total_bytes();
+    if (path == 1 || (path == 0 && ais_small_ok(M, V, H, 0, ldv, ldh) && ais_small_ok(M, V, H, 1, ldv, ldh)))
+        need = ais_ws(1, M, V, H, ldv, ldh).total_bytes();
+    *bytes = need;
+    return MDBN_OK;
+}
+
+int mdbn_ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+                 const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t n_betas, int64_t M,
+                 int64_t ldv, float* v_state, double* logw, float* trace_h, float* trace_v, int path, const mdbn_rng* rng,
+                 void* workspace, int64_t workspace_bytes)
+{
+    CtxScope ctx_scope(ctx);
+    // (the argument rules first: they need no device)
+    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
+    REQUIRE(M < (1ll << 31) && n_betas < (1ll << 30), "M / n_betas too large");
+    REQUIRE(n_betas >= 2, "n_betas = %lld: a schedule has at least beta_0 = 0 and beta_K = 1", (long long)n_betas);
+    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
+    REQUIRE(ldv % 4 == 0 && ldv >= V && ldh % 4 == 0 && ldh >= H, "leading dimensions must be multiples of 4, ldv >= V, ldh >= H");
+    REQUIRE(path != 1 || ais_small_ok(M, V, H, gauss, ldv, ldh),
+            "path 1: %lld -> %lld (ldv %lld, ldh %lld) is not LDS-resident", (long long)V, (long long)H, (long long)ldv, (long long)ldh);
+    const int p = ais_path(path, M, V, H, gauss, ldv, ldh);
+    const AisWs w = ais_ws(p, M, V, H, ldv, ldh);
+    REQUIRE(workspace_bytes >= w.total_bytes(), "workspace %lld bytes < %lld needed (mdbn_ais_workspace_bytes)",
+            (long long)workspace_bytes, (long long)w.total_bytes());
+    REQUIRE(ctx != nullptr && rng != nullptr, "ctx / rng is NULL");
+    CHECK(check_mat(W, ldh, H, "W"));
+    REQUIRE(hbias && vbias && base_vbias && betas && logw, "NULL pointer");
+    REQUIRE(workspace != nullptr && aligned16(workspace), "workspace must be a 16-byte aligned device pointer");
+    for (const float* q : {(const float*)v_state, (const float*)trace_h, (const float*)trace_v})
+        REQUIRE(q == nullptr || aligned16(q), "output not 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int K = (int)n_betas - 1;
+    float* wsf = reinterpret_cast<float*>(workspace);
+
+    if (p == 1) {
+        AisSmallArgs a{};
+        a.M = (int)M; a.V = (int)V; a.H = (int)H; a.gauss = gauss != 0;
+        a.ldv = ldv; a.ldh = ldh;
+        a.W = W; a.hbias = hbias; a.vbias = vbias; a.base_vbias = base_vbias; a.betas = betas;
+        a.K = K;
+        a.rng = make_key(*rng, 0u);
+        a.v_state = v_state ? v_state : wsf;
+        a.logw = logw;
+        a.trace_h = trace_h; a.trace_v = trace_v;
+        for (int k0 = 0; k0 < K; k0 += AIS_CUT) {       // a launch stays short; the state travels in v_state / logw
+            a.k0 = k0; a.k1 = std::min(K, k0 + AIS_CUT);
+            HIP_OK(launch_ais_small(a, s));
+        }
+        return MDBN_OK;
+    }
+
+    float* zero = wsf;
+    float* pre = zero + w.zero;
+    float* h = pre + w.pre;
+    float* v = h + w.h;
+    float* s1 = v + w.v;
+    float* d2 = s1 + w.s1;
+    void* gemm_ws = d2 + 64;
+    if (v_state) v = v_state;
+    Workspace ws;
+    CHECK(carve(gemm_ws, w.gemm_bytes, M, V, H, ws, false));
+    HIP_OK(hipMemsetAsync(zero, 0, sizeof(float) * w.zero, s));
+    HIP_OK(launch_ais_d2(vbias, base_vbias, (int)V, d2, s));
+    AisStepArgs st{};
+    st.M = (int)M; st.V = (int)V; st.H = (int)H; st.gauss = gauss != 0; st.K = K;
+    st.ldv = ldv; st.ldh = ldh;
+    st.betas = betas; st.vbias = vbias; st.base_vbias = base_vbias;
+    st.rng = make_key(*rng, 0u);
+    st.pre = pre; st.h = h; st.v = v; st.s1 = s1; st.d2 = d2; st.logw = logw;
+    st.k = 0; st.trace = trace_v;
+    HIP_OK(launch_ais_visible(st, s));
+    for (int k = 1; k <= K; ++k) {
+        st.k = k;
+        Affine up{v, M, ldv, W, V, H, ldh, 0, hbias, pre, nullptr, nullptr, ldh, 1.0f, 0, nullptr, 0, false, nullptr, 0u};
+        up.x_binary = !gauss;
+        CHECK(run_affine(up, ws, s, nullptr));
+        st.trace = trace_h && k < K ? trace_h + (int64_t)(k - 1) * M * ldh : nullptr;
+        HIP_OK(launch_ais_hidden(st, s));
+        if (k == K) break;
+        Affine down{h, M, ldh, W, V, H, ldh, 1, zero, pre, nullptr, nullptr, ldv, 1.0f, 1, nullptr, 0, false, nullptr, 0u};
+        down.x_binary = true;
+        CHECK(run_affine(down, ws, s, nullptr));
+        st.trace = trace_v ? trace_v + (int64_t)k * M * ldv : nullptr;
+        HIP_OK(launch_ais_visible(st, s));
     }
     return MDBN_OK;
 }

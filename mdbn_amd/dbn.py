@@ -147,6 +147,12 @@ class DBN(object):
             return None
         return self.engine.to_numpy(self._forward(input, layer))
 
+    def layer_log_likelihood(self, i, data, **ais):
+        """``(mean log p, std_err)`` of layer ``i``'s RBM on ``data`` seen through the frozen layers below it
+        (``get_output(data, i - 1)``: the view ``training`` uses for the free-energy gap), by ``RBM.log_likelihood``."""
+        below = getattr(data, "tensor", data) if i == 0 else self._forward(data, i - 1)
+        return self.rbm_layers[i].log_likelihood(self.engine.to_numpy(self.engine.as_matrix(below)), **ais)
+
     def _layer_input_fn(self, i, train_set_x):
         """Input matrix of RBM i: the data for i == 0, else the activations of layer i-1
         (dbn.py:146).  Lower layers are frozen while layer i trains (dbn.py:426-458), so

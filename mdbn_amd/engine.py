@@ -456,6 +456,42 @@ class HipEngine(object):
             self._p(ws), ws.numel() * 4), "mdbn_free_energy")
         return out
 
+    def ais(self, W, hbias, vbias, base_vbias, gauss, betas, n_chains, rng, path=0, trace=False):
+        """Annealed importance sampling of the layer (W, hbias, vbias) from the base-rate model ``base_vbias`` through
+        the inverse temperatures ``betas`` (0 = betas[0] < ... < betas[K] = 1) in ONE library call (mdbn_ais_run):
+        the per-chain log importance weights as a float64 numpy vector (one device -> host copy) and, with ``trace``,
+        the hidden [K-1, M, H] and visible [K, M, V] samples of every temperature.  ``path``: 0 = by shape, 1 = the
+        one-launch kernel (LDS-resident layers), 2 = the general path.  Consumes 2K - 1 RNG steps from ``rng.step``."""
+        V, H = W.shape
+        M = int(n_chains)
+        ldh, ldv = W.stride(0), padded_ld(V)
+        betas = numpy.ascontiguousarray(betas, dtype=numpy.float32)
+        if betas.ndim != 1 or betas.size < 2 or betas[0] != 0.0 or betas[-1] != 1.0 or not (numpy.diff(betas) > 0).all():
+            raise ValueError("betas must rise strictly from 0 to 1")
+        K = betas.size - 1
+        d_betas = torch.from_numpy(betas).to(self.device)
+        base = self.to_device(numpy.asarray(base_vbias, dtype=numpy.float32)) if not isinstance(base_vbias, torch.Tensor) \
+            else base_vbias.to(device=self.device, dtype=torch.float32).contiguous()
+        n, need = C.c_int64(), 0
+        for Hq in sorted({H, ldh}):        # (a weight matrix on a padded leading dimension: every buffer is as large as that width's)
+            _lib.check(self.lib.mdbn_ais_workspace_bytes(self.ctx, M, V, Hq, K + 1, int(path) if Hq == H else 2, C.byref(n)),
+                       "mdbn_ais_workspace_bytes")
+            need = max(need, n.value)
+        ws = torch.empty(need // 4 + 64, dtype=torch.float32, device=self.device)
+        logw = torch.zeros(M, dtype=torch.float64, device=self.device)
+        v_state = self.alloc_matrix(M, V, ldv)
+        trace_h = torch.zeros((max(K - 1, 1), M, ldh), dtype=torch.float32, device=self.device) if trace else None
+        trace_v = torch.zeros((K, M, ldv), dtype=torch.float32, device=self.device) if trace else None
+        r = rng.c()
+        _lib.check(self.lib.mdbn_ais_run(
+            self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base), int(bool(gauss)),
+            self._p(d_betas), K + 1, M, ldv, self._p(v_state), self._p(logw), self._p(trace_h), self._p(trace_v),
+            int(path), C.byref(r), self._p(ws), ws.numel() * 4), "mdbn_ais_run")
+        out = logw.cpu().numpy()
+        if trace:
+            return out, trace_h.cpu().numpy()[:K - 1, :, :H], trace_v.cpu().numpy()[:, :, :V]
+        return out
+
     def gather_rows(self, src, indexes):
         src = self.as_matrix(src)
         idx = self.index_tensor(indexes, src.shape[0])

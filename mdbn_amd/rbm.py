@@ -477,6 +477,21 @@ def function(updates, train_set_x=None, input_fn=None, name=None, data_parallel=
                         data_parallel=data_parallel, overlap=overlap)
 
 
+def ais_estimate(logw, base_vbias, n_hidden, gauss):
+    """``(log_Z, std_err)`` from the per-chain log importance weights of an AIS run (float64 on the host):
+    log Z_A + logsumexp(logw) - log M with log Z_A = H log 2 + sum softplus(b_A) (Bernoulli) | H log 2 + V/2 log 2 pi
+    (unit-variance Gaussian visibles), and the delta-method standard error std(w) / (mean(w) sqrt(M))."""
+    logw = numpy.asarray(logw, dtype=numpy.float64)
+    bA = numpy.asarray(base_vbias, dtype=numpy.float64)
+    log_ZA = n_hidden * numpy.log(2.0) + (0.5 * bA.size * numpy.log(2.0 * numpy.pi) if gauss
+                                          else numpy.logaddexp(0.0, bA).sum())
+    top = logw.max()
+    w = numpy.exp(logw - top)
+    log_Z = log_ZA + top + numpy.log(w.mean())
+    err = w.std() / (w.mean() * numpy.sqrt(w.size))
+    return float(log_Z), float(err)
+
+
 class RBM(object):
     """Restricted Boltzmann Machine (RBM) -- Bernoulli visible and hidden units."""
 
@@ -567,6 +582,47 @@ class RBM(object):
     def free_energies(self, train, test):
         """rbm.py:182-185, evaluated: two host vectors (as dbn.py:498-501 consumes them)."""
         return self.free_energy(train).get_value(), self.free_energy(test).get_value()
+
+    # ------------------------------------------------------------------ likelihood (annealed importance sampling)
+    def base_rate_vbias(self, data):
+        """Visible bias of the base-rate model of ``data`` (host matrix): Bernoulli: the logit of the smoothed column
+        means (N mean + 0.05) / (N + 0.1) -- a constant column stays finite --; Gaussian: the column means."""
+        if isinstance(data, torch.Tensor):
+            data = data.detach().cpu().numpy()
+        x = numpy.asarray(getattr(data, "get_value", lambda: data)(), dtype=numpy.float64)
+        mean = x.mean(axis=0)
+        if self.gauss:
+            return mean.astype(numpy.float32)
+        p = (x.shape[0] * mean + 0.05) / (x.shape[0] + 0.1)
+        return (numpy.log(p) - numpy.log1p(-p)).astype(numpy.float32)
+
+    def log_partition(self, n_chains=512, betas=None, n_betas=1000, base_vbias=None, data=None, path=0):
+        """``(log_Z, std_err)`` of the layer by annealed importance sampling (Salakhutdinov & Murray 2008) on the device:
+        ``n_chains`` chains through the inverse temperatures ``betas`` (None: ``linspace(0, 1, n_betas + 1)``) from the
+        base-rate model ``base_vbias`` (None: taken from ``data`` by ``base_rate_vbias``; with neither, the layer's own
+        visible bias).  The logsumexp and the delta-method standard error std(w) / (mean(w) sqrt(M)) are float64 numpy on
+        the host.  Consumes 2K - 1 RNG steps."""
+        if betas is None:
+            betas = numpy.linspace(0.0, 1.0, int(n_betas) + 1)
+        betas = numpy.asarray(betas, dtype=numpy.float32)
+        K = betas.size - 1
+        if base_vbias is None:
+            base_vbias = self.base_rate_vbias(data) if data is not None else self.vbias.get_value()
+        base_vbias = numpy.asarray(base_vbias, dtype=numpy.float32)
+        step = self._rng_step
+        logw = self.engine.ais(self.W.tensor, self.hbias.tensor, self.vbias.tensor, base_vbias, self.gauss, betas,
+                               int(n_chains), RngAddr(self.theano_rng.seed, self.stream_id, step, 0, 0), path=path)
+        self._rng_step = step + 2 * K - 1
+        return ais_estimate(logw, base_vbias, self.n_hidden, self.gauss)
+
+    def log_likelihood(self, data, **ais):
+        """``(mean log p(data), std_err)``: mean(-free_energy(data)) - log_Z with ``log_partition(**ais)``'s estimate (the
+        standard error is that of log_Z; ``data`` also gives the base rate unless ``base_vbias`` / ``data`` is passed)."""
+        if "base_vbias" not in ais and "data" not in ais:
+            ais = dict(ais, data=data)
+        log_Z, err = self.log_partition(**ais)
+        neg_F = -numpy.asarray(self.free_energy(data).get_value(), dtype=numpy.float64)
+        return float(neg_F.mean() - log_Z), err
 
     # ------------------------------------------------------------------ propagation
     def propup(self, vis):
