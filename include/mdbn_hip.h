@@ -431,6 +431,41 @@ int  mdbn_ais_run(mdbn_ctx *ctx, void *stream, const float *W, int64_t V, int64_
                   double *logw, float *trace_h, float *trace_v, int path, const mdbn_rng *rng,
                   void *workspace, int64_t workspace_bytes);
 
+/* Clamped Gibbs sampling: the chain of mdbn_gibbs_chain with part of the visible layer held at observed values, and the
+ * running means of its conditional expectations -- the posterior of the unobserved visibles (a missing modality under the
+ * joint layer of a multimodal DBN, Srivastava & Salakhutdinov 2012) and of the hidden layer given the observed ones.
+ * mask [mask_rows, ldv] holds 0 / 1 (1 = observed: held at obs), mask_rows = B (per element) or 1 (one row for the batch).
+ *   on entry v := mask ? obs : v;  step t = 0 .. n_steps - 1:
+ *     h_mean = sigmoid(v W + hbias),                 h_sample = (U(rng->step + 2t) < h_mean)
+ *     RBM : v_mean = sigmoid(h_sample W^T + vbias),  v_new = (U(rng->step + 2t + 1) < v_mean)
+ *     GRBM: v_mean = h_mean W^T + vbias,             v_new = v_mean [+ N(0, 1) from rng->step + 2t + 1 if add_noise]   (gauss = 1)
+ *           v_mean = h_sample W^T + vbias,           v_new = v_mean + N(0, 1) from rng->step + 2t + 1                  (gauss = 2)
+ *     v_mean := mask ? obs : v_mean;  v := mask ? obs : v_new
+ *     t >= burn_in:  v_acc += v_mean;  h_acc += h_mean             (float32, in step order)
+ * gauss = 1 is the chain of the reference and of mdbn_gibbs_chain (the hidden MEAN goes down: a mean-field iteration, whose
+ * averages are NOT the posterior means of the model); gauss = 2 is the Gibbs sampler of the same model (the hidden SAMPLE
+ * goes down, unit noise always; add_noise is ignored), whose v_avg / h_avg estimate E[v | v_obs], E[h | v_obs].
+ * Draw index 0 and the row addressing of mdbn_gibbs_chain; the caller advances its step counter by 2 * n_steps.  On return
+ * v [B, ldv] is the final state, h_mean / h_sample [B, ldh] and v_mean [B, ldv] the last step's values, v_avg = v_acc /
+ * (n_steps - burn_in) and h_avg likewise (each nullable); trace_v [n_steps][B][ldv] (the state after the clamp) and trace_h
+ * [n_steps][B][ldh] (h_sample) are nullable taps.  With an all-zero mask the state, h_* and v_mean are those of
+ * mdbn_gibbs_chain; with an all-one mask v never moves.
+ * path: 0 = by shape, 1 = the one-launch path (LDS-resident layers: W staged once, a workgroup runs every step for four rows
+ * with their observed values, mask and accumulators in registers; cut into launches of at most steps_per_launch steps, 0 =
+ * the default 2048, the state carried in v and the workspace -- the cut changes no bit of any output) or MDBN_EINVAL if the
+ * shape does not fit, 2 = the general path (per step the two passes of mdbn_gibbs_chain and one element-wise kernel).  The
+ * paths meet the same uniforms and differ by fp32 summation order only.  Bad arguments (n_steps < 1, burn_in outside
+ * [0, n_steps), mask_rows not 1 or B, path 1 on a shape that does not fit, a workspace shorter than
+ * mdbn_gibbs_clamped_workspace_bytes -- which answers for leading dimensions up to mdbn_padded_ld) return MDBN_EINVAL
+ * without a launch. */
+int  mdbn_gibbs_clamped_workspace_bytes(mdbn_ctx *ctx, int64_t B, int64_t V, int64_t H, int path, int64_t *bytes);
+int  mdbn_gibbs_clamped(mdbn_ctx *ctx, void *stream, float *v, const float *obs, const float *mask, int64_t mask_rows,
+                        int64_t B, int64_t ldv, const float *W, int64_t V, int64_t H, int64_t ldh,
+                        const float *hbias, const float *vbias, int gauss, int add_noise, int64_t n_steps,
+                        int64_t burn_in, float *h_mean, float *h_sample, float *v_mean, float *v_avg, float *h_avg,
+                        float *trace_h, float *trace_v, int path, int64_t steps_per_launch, const mdbn_rng *rng,
+                        void *workspace, int64_t workspace_bytes);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)). */

@@ -98,3 +98,46 @@ def train_bottom_layer(train_set, validation_set, batch_size=20, k=1, layers_siz
                rows, held_out, batch_size, graph_output, k=k, pretraining_epochs=pretraining_epochs,
                pretrain_lr=pretrain_lr, lambda_1=lambda_1, lambda_2=lambda_2)
     return net, net.get_output(rows), net.get_output(held_out)
+
+
+def impute_modalities(nets, joint, inputs, n_steps=1000, burn_in=200, n_chains=8):
+    """Answer for rows of which some modality was never measured (the patients data/AML/common_pat_id.sh drops).
+
+    ``nets``: the modality DBNs in the joint layer's column order; ``joint``: the joint DBN (``train_top``);
+    ``inputs[i]``: the data matrix of modality i, or None when it is missing for every row.  A row of NaNs inside a given
+    matrix marks that modality as missing for that row alone, so rows may differ in what they lack (a row that is only partly
+    NaN is refused).  Observed modalities go up
+    (``get_output``), the joint layer's first RBM runs ``RBM.impute`` with the column-block mask -- clamped Gibbs sampling on
+    the device, ``n_chains`` chains per row -- and the result is ``(joint_visible [N, sum of tops], joint_top =
+    joint.get_output(joint_visible), {i: nets[i].down_pass(block_i)})`` for every modality i that is missing somewhere
+    (rows where it was observed reproduce the mean-field reconstruction of their own block)."""
+    import numpy
+    widths = [net.stacked_layers_sizes[-1] for net in nets]
+    if len(inputs) != len(nets):
+        raise ValueError("one input (or None) per modality")
+    rows = [len(x) for x in inputs if x is not None]
+    if not rows or len(set(rows)) != 1:
+        raise ValueError("at least one modality must be given, and all given ones need the same number of rows")
+    N = rows[0]
+    visible = numpy.zeros((N, sum(widths)), dtype=numpy.float32)
+    mask = numpy.zeros((N, sum(widths)), dtype=numpy.float32)
+    missing, lo = [], 0
+    for i, (net, x, w) in enumerate(zip(nets, inputs, widths)):
+        seen = numpy.zeros(N, dtype=bool)
+        if x is not None:
+            x = numpy.asarray(getattr(x, "get_value", lambda: x)(), dtype=numpy.float32)
+            nan = numpy.isnan(x)
+            seen = ~nan.all(axis=1)
+            if (nan.any(axis=1) & seen).any():
+                raise ValueError("modality %d: a row is partly NaN; a missing modality is a row of NaN only" % i)
+            if seen.any():
+                visible[seen, lo:lo + w] = net.get_output(x[seen])
+        mask[seen, lo:lo + w] = 1.0
+        if not seen.all():
+            missing.append((i, lo, w))
+        lo += w
+    if not mask.any(axis=1).all():
+        raise ValueError("a row with no observed modality cannot be imputed")
+    joint_visible, _ = joint.rbm_layers[0].impute(visible, mask, n_steps=n_steps, burn_in=burn_in, n_chains=n_chains)
+    return joint_visible, joint.get_output(joint_visible), {i: nets[i].down_pass(joint_visible[:, lo:lo + w])
+                                                           for i, lo, w in missing}

@@ -25,6 +25,7 @@
 #include "mdbn_thin.h"
 #include "mdbn_gchain.h"
 #include "mdbn_ais.h"
+#include "mdbn_clamp.h"
 
 using namespace mdbn;
 
@@ -2309,6 +2310,138 @@ int mdbn_ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t
         CHECK(run_affine(down, ws, s, nullptr));
         st.trace = trace_v ? trace_v + (int64_t)k * M * ldv : nullptr;
         HIP_OK(launch_ais_visible(st, s));
+    }
+    return MDBN_OK;
+}
+
+// ---------------------------------------------------------------------------------- clamped Gibbs sampling
+namespace {
+
+// The caller's workspace of mdbn_gibbs_clamped: the two accumulators (one-launch path: what a cut run carries from launch to
+// launch), then -- general path -- the scratch of the propagation GEMMs.
+struct ClampWs {
+    int64_t acc_v, acc_h, gemm_bytes;
+    int64_t total_bytes() const { return 4 * (acc_v + acc_h) + gemm_bytes; }
+};
+
+ClampWs clamp_ws(int path, int64_t B, int64_t V, int64_t H, int64_t ldv, int64_t ldh)
+{
+    ClampWs w{};
+    w.acc_v = ru64(B * ldv);
+    w.acc_h = ru64(B * ldh);
+    if (path == 2) w.gemm_bytes = ws_sizes(B, V, H).total_bytes() + 4 * ((int64_t)(1 << 16) + 4096);
+    return w;
+}
+
+}  // namespace
+
+int mdbn_gibbs_clamped_workspace_bytes(mdbn_ctx* ctx, int64_t B, int64_t V, int64_t H, int path, int64_t* bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(bytes != nullptr, "bytes is NULL");
+    REQUIRE(B >= 1 && V >= 1 && H >= 1, "bad shape B=%lld V=%lld H=%lld", (long long)B, (long long)V, (long long)H);
+    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
+    const int64_t ldv = padded_ld(V), ldh = padded_ld(H);
+    // (either visible type: the larger of the two answers, so that one buffer serves a layer whatever its type)
+    const bool any = clamp_small_ok(B, V, H, 0, ldv, ldh) || clamp_small_ok(B, V, H, 1, ldv, ldh);
+    const bool both = clamp_small_ok(B, V, H, 0, ldv, ldh) && clamp_small_ok(B, V, H, 1, ldv, ldh);
+    REQUIRE(path != 1 || any, "path 1: %lld -> %lld is not LDS-resident", (long long)V, (long long)H);
+    *bytes = clamp_ws(path == 1 || (path == 0 && both) ? 1 : 2, B, V, H, ldv, ldh).total_bytes();
+    return MDBN_OK;
+}
+
+int mdbn_gibbs_clamped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, const float* mask, int64_t mask_rows,
+                       int64_t B, int64_t ldv, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+                       const float* vbias, int gauss, int add_noise, int64_t n_steps, int64_t burn_in, float* h_mean,
+                       float* h_sample, float* v_mean, float* v_avg, float* h_avg, float* trace_h, float* trace_v,
+                       int path, int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes)
+{
+    CtxScope ctx_scope(ctx);
+    // (the argument rules first: they need no device)
+    REQUIRE(B >= 1 && V >= 1 && H >= 1, "bad shape B=%lld V=%lld H=%lld", (long long)B, (long long)V, (long long)H);
+    REQUIRE(B < (1ll << 31), "B too large");
+    REQUIRE(n_steps >= 1 && n_steps < (1ll << 30), "n_steps = %lld must be in [1, 2^30)", (long long)n_steps);
+    REQUIRE(burn_in >= 0 && burn_in < n_steps, "burn_in = %lld must be in [0, n_steps = %lld)", (long long)burn_in, (long long)n_steps);
+    REQUIRE(mask_rows == 1 || mask_rows == B, "mask_rows = %lld is neither 1 nor B = %lld", (long long)mask_rows, (long long)B);
+    REQUIRE(gauss >= 0 && gauss <= 2, "gauss = %d is not 0 (Bernoulli), 1 (Gaussian, hidden mean down) or 2 (Gaussian, Gibbs sampler)", gauss);
+    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
+    REQUIRE(steps_per_launch >= 0, "steps_per_launch = %lld is negative (0 = default)", (long long)steps_per_launch);
+    REQUIRE(ldv % 4 == 0 && ldv >= V && ldh % 4 == 0 && ldh >= H, "leading dimensions must be multiples of 4, ldv >= V, ldh >= H");
+    const bool fits = clamp_small_ok(B, V, H, gauss, ldv, ldh);
+    REQUIRE(path != 1 || fits, "path 1: %lld -> %lld (ldv %lld, ldh %lld) is not LDS-resident", (long long)V, (long long)H,
+            (long long)ldv, (long long)ldh);
+    const int p = path == 0 ? (fits ? 1 : 2) : path;
+    const ClampWs w = clamp_ws(p, B, V, H, ldv, ldh);
+    REQUIRE(workspace_bytes >= w.total_bytes(), "workspace %lld bytes < %lld needed (mdbn_gibbs_clamped_workspace_bytes)",
+            (long long)workspace_bytes, (long long)w.total_bytes());
+    REQUIRE(ctx != nullptr && rng != nullptr, "ctx / rng is NULL");
+    CHECK(check_mat(v, ldv, V, "v"));
+    CHECK(check_mat(obs, ldv, V, "obs"));
+    CHECK(check_mat(mask, ldv, V, "mask"));
+    CHECK(check_mat(W, ldh, H, "W"));
+    CHECK(check_mat(h_mean, ldh, H, "h_mean"));
+    CHECK(check_mat(h_sample, ldh, H, "h_sample"));
+    CHECK(check_mat(v_mean, ldv, V, "v_mean"));
+    REQUIRE(hbias && vbias, "bias pointers are NULL");
+    REQUIRE(workspace != nullptr && aligned16(workspace), "workspace must be a 16-byte aligned device pointer");
+    for (const float* q : {(const float*)v_avg, (const float*)h_avg, (const float*)trace_h, (const float*)trace_v})
+        REQUIRE(q == nullptr || aligned16(q), "output not 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    float* acc_v = reinterpret_cast<float*>(workspace);
+    float* acc_h = acc_v + w.acc_v;
+    const bool noisy = gauss && (add_noise || gauss == 2);
+    const bool feed_sample = gauss != 1;            // gauss = 1: the hidden MEAN goes down (mdbn_gibbs_chain); 2: the sample
+
+    if (p == 1) {
+        ClampSmallArgs a{};
+        a.B = (int)B; a.V = (int)V; a.H = (int)H; a.gauss = gauss; a.add_noise = add_noise != 0;
+        a.ldv = ldv; a.ldh = ldh;
+        a.W = W; a.hbias = hbias; a.vbias = vbias;
+        a.v = v; a.obs = obs; a.mask = mask; a.mask_rows = (int)mask_rows;
+        a.n_steps = (int)n_steps; a.burn_in = (int)burn_in;
+        a.rng = make_key(*rng, 0u);
+        a.h_mean = h_mean; a.h_sample = h_sample; a.v_mean = v_mean; a.v_avg = v_avg; a.h_avg = h_avg;
+        a.acc_v = acc_v; a.acc_h = acc_h;
+        a.trace_h = trace_h; a.trace_v = trace_v;
+        const int64_t cut = steps_per_launch ? steps_per_launch : CLAMP_CUT;
+        for (int64_t t0 = 0; t0 < n_steps; t0 += cut) {       // a launch stays short; the state travels in v / acc_v / acc_h
+            a.t0 = (int)t0; a.t1 = (int)std::min(n_steps, t0 + cut);
+            HIP_OK(launch_clamp_small(a, s));
+        }
+        return MDBN_OK;
+    }
+
+    Workspace ws;
+    CHECK(carve(acc_h + w.acc_h, w.gemm_bytes, B, V, H, ws, false));
+    HIP_OK(hipMemsetAsync(acc_v, 0, sizeof(float) * (w.acc_v + w.acc_h), s));
+    ClampStepArgs c{};
+    c.B = (int)B; c.V = (int)V; c.H = (int)H;
+    c.ldv = ldv; c.ldh = ldh;
+    c.v = v; c.v_mean = v_mean; c.obs = obs; c.mask = mask; c.mask_rows = (int)mask_rows;
+    c.h_mean = h_mean; c.h_sample = h_sample;
+    c.n_avg = (float)(n_steps - burn_in);
+    c.acc_v = acc_v; c.acc_h = acc_h; c.v_avg = v_avg; c.h_avg = h_avg;
+    c.entry = 1; c.v_new = v;
+    HIP_OK(launch_clamp_step(c, s));
+    c.entry = 0;
+    for (int64_t t = 0; t < n_steps; ++t) {
+        const bool last = t + 1 == n_steps;
+        mdbn_rng rh = *rng, rv = *rng;
+        rh.step = rng->step + (uint32_t)(2 * t);     rh.draw = 0;
+        rv.step = rng->step + (uint32_t)(2 * t + 1); rv.draw = 0;
+        // the passes of mdbn_gibbs_chain.  The visible state may hold real observed values: never the 0/1 operand hint there
+        Affine up{v, B, ldv, W, V, H, ldh, 0, hbias, nullptr, h_mean, (feed_sample || last || trace_h) ? h_sample : nullptr, ldh, 1.0f, 0,
+                  nullptr, 0, false, &rh, 0u};
+        CHECK(run_affine(up, ws, s, nullptr));
+        Affine down{feed_sample ? h_sample : h_mean, B, ldh, W, V, H, ldh, 1, vbias, nullptr, v_mean, (!gauss || noisy) ? v : nullptr,
+                    ldv, 1.0f, gauss != 0, nullptr, 0, false, &rv, 0u};
+        down.x_binary = feed_sample;                     // our own 0/1 hidden samples
+        CHECK(run_affine(down, ws, s, nullptr));
+        c.v_new = (!gauss || noisy) ? v : v_mean;
+        c.accumulate = t >= burn_in; c.last = last;
+        c.trace_h = trace_h ? trace_h + t * B * ldh : nullptr;
+        c.trace_v = trace_v ? trace_v + t * B * ldv : nullptr;
+        HIP_OK(launch_clamp_step(c, s));
     }
     return MDBN_OK;
 }

@@ -1,5 +1,6 @@
-// The LDS-resident passes of the one-launch kernels (mdbn_small.hip: CD-k step; mdbn_ais.hip: annealed importance sampling):
-// D[4][N] = A[4][K] * op(W) on v_mfma_f32_4x4x1_16b_f32 with every operand in LDS.  Included by those two sources only; the
+// The LDS-resident passes of the one-launch kernels (mdbn_small.hip: CD-k step; mdbn_ais.hip: annealed importance sampling;
+// mdbn_clamp.hip: clamped Gibbs sampling):
+// D[4][N] = A[4][K] * op(W) on v_mfma_f32_4x4x1_16b_f32 with every operand in LDS.  Included by those three sources only; the
 // layout and the reasons for it are described at the top of mdbn_small.hip.
 #pragma once
 #include <hip/hip_runtime.h>

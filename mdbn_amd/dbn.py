@@ -147,6 +147,23 @@ class DBN(object):
             return None
         return self.engine.to_numpy(self._forward(input, layer))
 
+    def down_pass(self, h, layer=-1):
+        """Mean-field top-down pass, the inverse direction of ``get_output``: ``h`` (activations of ``sigmoid_layers[layer]``,
+        host or device matrix) is taken down through ``rbm_layers[layer] .. rbm_layers[0]`` by the layers' conditional means
+        (sigmoid(h W^T + vbias); the linear mean h W^T + vbias at a Gaussian bottom layer).  Returns a host array
+        [rows, n_ins].  No random number is consumed: no layer's RNG counter moves."""
+        if h is None:
+            return None
+        from .engine import RngAddr
+        top = range(self.n_layers)[layer]
+        x = self.engine.as_matrix(getattr(h, "tensor", h))
+        for i in range(top, -1, -1):
+            r = self.rbm_layers[i]
+            # (the propagation call wants an address for the sample it also offers; the mean does not depend on it)
+            x = self.engine.propdown(x, r.W.tensor, r.vbias.tensor, gauss=r.gauss, add_noise=False,
+                                     rng=RngAddr(r.theano_rng.seed, r.stream_id, 0, 0, 0))[1]
+        return self.engine.to_numpy(x)
+
     def layer_log_likelihood(self, i, data, **ais):
         """``(mean log p, std_err)`` of layer ``i``'s RBM on ``data`` seen through the frozen layers below it
         (``get_output(data, i - 1)``: the view ``training`` uses for the free-energy gap), by ``RBM.log_likelihood``."""

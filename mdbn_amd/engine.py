@@ -442,6 +442,63 @@ class HipEngine(object):
             "mdbn_gibbs_chain")
         return [pre_h, h_mean, h_sample, pre_v, v_mean, state]
 
+    def gibbs_clamped(self, v, obs, mask, W, hbias, vbias, gauss, n_steps, rng, burn_in=0, add_noise=False, path=0,
+                      steps_per_launch=0, trace=False, sampler=False):
+        """``n_steps`` of gibbs_vhv with the visibles where ``mask`` is 1 held at ``obs`` in ONE library call
+        (mdbn_gibbs_clamped): returns device tensors ``(v_final, h_mean, h_sample, v_mean, v_avg, h_avg)`` -- the last
+        step's values and the means of v_mean / h_mean over the steps ``burn_in .. n_steps - 1`` -- and, with ``trace``,
+        also ``trace_h [n_steps, B, H]`` (hidden samples) and ``trace_v [n_steps, B, V]`` (the state after the clamp).
+        ``mask``: [B, V], or [1, V] for the whole batch.  ``path``: 0 = by shape, 1 = the one-launch kernel (LDS-resident
+        layers), 2 = the general path.  ``sampler`` (Gaussian visibles; nothing changes for Bernoulli ones): the Gibbs sampler of
+        the model -- the hidden SAMPLE goes down and the visible draw always carries its N(0, 1) noise (the library's gauss = 2)
+        -- instead of the reference's chain, which feeds the hidden mean down and whose averages are not posterior means.
+        ``v`` is not modified; no host synchronisation.  Consumes 2 * n_steps RNG steps."""
+        v = self.as_matrix(v)
+        B, V = v.shape
+        H = W.shape[1]
+        ldh, ldv = W.stride(0), padded_ld(V)
+        gauss = (2 if sampler else 1) if gauss else 0
+        n_steps, burn_in = int(n_steps), int(burn_in)
+
+        def padded(x, rows):
+            x = self.as_matrix(x)
+            if tuple(x.shape) != (rows, V):
+                raise ValueError("expected a [%d, %d] matrix, got %r" % (rows, V, tuple(x.shape)))
+            if x.stride(0) != ldv:
+                t = self.alloc_matrix(rows, V, ldv)
+                t.copy_(x)
+                x = t
+            return x
+        mask = self.as_matrix(mask)
+        mask_rows = int(mask.shape[0])
+        if mask_rows not in (1, B):
+            raise ValueError("mask has %d rows: neither 1 nor the batch's %d" % (mask_rows, B))
+        obs, mask = padded(obs, B), padded(mask, mask_rows)
+        state = self.alloc_matrix(B, V, ldv)
+        state.copy_(v)
+        h_mean, h_sample, h_avg = (self.alloc_matrix(B, H, ldh) for _ in range(3))
+        v_mean, v_avg = self.alloc_matrix(B, V, ldv), self.alloc_matrix(B, V, ldv)
+        trace_h = torch.zeros((n_steps, B, ldh), dtype=torch.float32, device=self.device) if trace else None
+        trace_v = torch.zeros((n_steps, B, ldv), dtype=torch.float32, device=self.device) if trace else None
+        n, need = C.c_int64(), 0
+        for Hq in sorted({H, ldh}):        # (a weight matrix on a padded leading dimension: every buffer is as large as that width's)
+            _lib.check(self.lib.mdbn_gibbs_clamped_workspace_bytes(self.ctx, B, V, Hq, int(path) if Hq == H else 2, C.byref(n)),
+                       "mdbn_gibbs_clamped_workspace_bytes")
+            need = max(need, n.value)
+        ws = getattr(self, "_clamp_ws", None)          # kept between calls, grown to the largest requirement seen
+        if ws is None or ws.numel() * 4 < need:
+            ws = self._clamp_ws = torch.empty(need // 4 + 64, dtype=torch.float32, device=self.device)
+        r = rng.c()
+        _lib.check(self.lib.mdbn_gibbs_clamped(
+            self.ctx, self._stream(), self._p(state), self._p(obs), self._p(mask), mask_rows, B, ldv, self._p(W), V, H, ldh,
+            self._p(hbias), self._p(vbias), gauss, int(bool(add_noise)), n_steps, burn_in, self._p(h_mean),
+            self._p(h_sample), self._p(v_mean), self._p(v_avg), self._p(h_avg), self._p(trace_h), self._p(trace_v),
+            int(path), int(steps_per_launch), C.byref(r), self._p(ws), ws.numel() * 4), "mdbn_gibbs_clamped")
+        out = (state, h_mean, h_sample, v_mean, v_avg, h_avg)
+        if trace:
+            out += (trace_h[:, :, :H], trace_v[:, :, :V])
+        return out
+
     def free_energy(self, x, W, hbias, vbias, gauss):
         x = self.as_matrix(x)
         N, V = x.shape

@@ -682,6 +682,92 @@ class RBM(object):
                                       add_noise=self.gauss and not getattr(self, "error_free", True))
         return [self._wrap(t) for t in out]
 
+    # ------------------------------------------------------------------ clamped Gibbs sampling / imputation
+    def _clamp_mask(self, observed_mask, B):
+        m = numpy.asarray(getattr(observed_mask, "get_value", lambda: observed_mask)())
+        if m.ndim == 1:
+            m = m[None, :]
+        if m.ndim != 2 or m.shape[1] != self.n_visible or m.shape[0] not in (1, B):
+            raise ValueError("observed_mask must be [%d] or [1 | %d, %d], got %r" % (self.n_visible, B, self.n_visible, m.shape))
+        return (m != 0).astype(numpy.float32)
+
+    def gibbs_vhv_clamped(self, v, observed_mask, n_steps, burn_in=0, trace=False, path=0, sampler=False):
+        """``n_steps`` of ``gibbs_vhv`` with the visibles where ``observed_mask`` is nonzero held at their values in ``v``
+        (the other entries of ``v`` start the chain), as ONE device call (mdbn_gibbs_clamped).  ``observed_mask``: [B, V]
+        per element, or [V] / [1, V] for the whole batch.  Returns the six outputs of the LAST step as
+        ``gibbs_vhv_chain`` does -- v_mean and the visible sample after the clamp; the two pre-activations are None on
+        the device -- followed by ``v_avg`` and ``h_avg``, the means of v_mean / h_mean over the steps
+        ``burn_in .. n_steps - 1`` (the estimate of E[v | v_obs], E[h | v_obs]), and with ``trace`` by the hidden samples
+        [n_steps, B, H] and the clamped states [n_steps, B, V] of every step.  Consumes 2 * n_steps RNG steps.
+
+        A Bernoulli layer's chain is a Gibbs sampler, so its averages estimate the posterior means.  The GRBM chain of the
+        reference (``gibbs_vhv``: the hidden MEAN goes down, noise only if not ``error_free``) is a mean-field iteration, and
+        its averages are not posterior means; ``sampler=True`` runs the Gibbs sampler of the same model instead (the hidden
+        SAMPLE goes down, the visible draw always carries its N(0, 1) noise).  It changes nothing for a Bernoulli layer."""
+        sampler = bool(sampler and self.gauss)
+        n_steps, burn_in = int(n_steps), int(burn_in)
+        if n_steps < 1 or not 0 <= burn_in < n_steps:
+            raise ValueError("need n_steps >= 1 and 0 <= burn_in < n_steps, got %d, %d" % (n_steps, burn_in))
+        x = as_tensor(v, self.engine)
+        mask = self._clamp_mask(observed_mask, x.shape[0])
+        step = self._rng_step
+        if not hasattr(self.engine, "gibbs_clamped"):        # checker engine: compose the eager steps
+            held = as_tensor(numpy.broadcast_to(mask, tuple(x.shape)).copy(), self.engine) != 0
+            obs, state = x, x
+            v_acc, h_acc, out, th, tv = 0.0, 0.0, None, [], []
+            for t in range(n_steps):
+                pre_h, h_mean, h_sample = self.sample_h_given_v(state)
+                if sampler:
+                    mean, _, new = self.engine.propdown(h_sample.tensor, self.W.tensor, self.vbias.tensor, gauss=True,
+                                                        add_noise=True, rng=self._rng())
+                    pre_v, v_mean, v_new = self._wrap(mean), self._wrap(mean), self._wrap(new)
+                else:
+                    pre_v, v_mean, v_new = self.sample_v_given_h(h_mean if self.gauss else h_sample)
+                v_mean, state = torch.where(held, obs, v_mean.tensor), torch.where(held, obs, v_new.tensor)
+                if t >= burn_in:
+                    v_acc, h_acc = v_acc + v_mean, h_acc + h_mean.tensor
+                th.append(h_sample.tensor)
+                tv.append(state)
+                out = [pre_h, h_mean, h_sample, pre_v, self._wrap(v_mean), self._wrap(state)]
+            out += [self._wrap(v_acc / (n_steps - burn_in)), self._wrap(h_acc / (n_steps - burn_in))]
+            assert self._rng_step == step + 2 * n_steps
+            return out + ([self._wrap(torch.stack(th)), self._wrap(torch.stack(tv))] if trace else [])
+        self._rng_step = step + 2 * n_steps
+        res = self.engine.gibbs_clamped(x, x, mask, self.W.tensor, self.hbias.tensor, self.vbias.tensor, self.gauss, n_steps,
+                                        RngAddr(self.theano_rng.seed, self.stream_id, step, 0, 0), burn_in=burn_in,
+                                        add_noise=self.gauss and not sampler and not getattr(self, "error_free", True), path=path, trace=trace,
+                                        sampler=sampler)
+        state, h_mean, h_sample, v_mean, v_avg, h_avg = res[:6]
+        return [self._wrap(t) for t in (None, h_mean, h_sample, None, v_mean, state, v_avg, h_avg) + tuple(res[6:])]
+
+    def impute(self, v, observed_mask, n_steps=1000, burn_in=200, n_chains=1, path=0):
+        """Posterior means of the unobserved visibles and of the hidden layer given the observed visibles:
+        ``(v_hat [N, V], h_hat [N, H])`` as host arrays.  The unobserved entries of ``v`` (anything: they are ignored)
+        start at the model's base (``sigmoid(vbias)``; GRBM: ``vbias``), every row runs ``n_chains`` independent clamped
+        chains (consecutive Philox rows) of ``n_steps`` Gibbs steps (``sampler=True``: a GRBM runs the Gibbs sampler of its
+        model, not the reference's mean-field chain), and v_mean / h_mean are averaged over the steps from
+        ``burn_in`` on and over the chains.  Observed entries of ``v_hat`` are the observed values.  Consumes
+        2 * n_steps RNG steps."""
+        x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
+        N, n_chains = x.shape[0], int(n_chains)
+        mask = self._clamp_mask(observed_mask, N)
+        b = numpy.asarray(self.vbias.get_value(), dtype=numpy.float64)
+        base = (b if self.gauss else 1.0 / (1.0 + numpy.exp(-b))).astype(numpy.float32)
+        held = numpy.broadcast_to(mask != 0, x.shape)
+        start = numpy.where(held, x, base[None, :]).astype(numpy.float32)
+        if n_chains > 1:
+            start = numpy.repeat(start, n_chains, axis=0)
+            if mask.shape[0] != 1:
+                mask = numpy.repeat(mask, n_chains, axis=0)
+        out = self.gibbs_vhv_clamped(start, mask, n_steps, burn_in=burn_in, path=path, sampler=True)
+        v_hat, h_hat = (numpy.asarray(t.get_value(), dtype=numpy.float64) for t in out[6:8])
+        if n_chains > 1:
+            v_hat = v_hat.reshape(N, n_chains, -1).mean(axis=1)
+            h_hat = h_hat.reshape(N, n_chains, -1).mean(axis=1)
+        # (an observed entry is its observed value, not the float32 mean of n_steps copies of it)
+        v_hat = numpy.where(held, x, v_hat)
+        return v_hat.astype(numpy.float32), h_hat.astype(numpy.float32)
+
     def make_sample_fn(self, persistent_vis_chain, n_steps=500):
         """The ``sample_fn`` of rbm.py:844-853: each call runs ``n_steps`` Gibbs steps from the persistent visible
         chain, stores ``vis_samples[-1]`` back into it and returns ``(vis_mfs[-1], vis_samples[-1])`` as host arrays."""
