@@ -646,7 +646,9 @@ class HipEngine(object):
         keep = [data, idx, ws]
         # ... on the plane path; on the thin-batch path (B <= 32, ldh <= 512: the library decides and reports) the previous
         # step's update kernel gathered the rows AND left the partials of x W, so the parameters must be the ones it wrote
-        thin = sc.planes is None and B <= 32 and ldh <= 512 and persistent is None and not sample_stats
+        # (the step variants thin_eligible refuses never take part: nothing would honour the hand-over)
+        thin = sc.planes is None and B <= 32 and ldh <= 512 and persistent is None and not sample_stats and \
+            not (gauss and add_noise)
         if (sc.planes is not None or thin) and idx is not None and not self.keep_f32 and not self.trace_chain:
             # (the announcing step keeps the matrix and the index tensor alive, so an equal address is the same object)
             # ... and unchanged: an index buffer refilled IN PLACE between the announcing call and this one has another
