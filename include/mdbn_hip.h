@@ -466,6 +466,42 @@ int  mdbn_gibbs_clamped(mdbn_ctx *ctx, void *stream, float *v, const float *obs,
                         float *trace_h, float *trace_v, int path, int64_t steps_per_launch, const mdbn_rng *rng,
                         void *workspace, int64_t workspace_bytes);
 
+/* Parallel tempering (replica exchange; Desjardins et al. 2010, Cho et al. 2010) of a trained layer: M ladders of R Gibbs
+ * chains at the inverse temperatures 0 <= betas[0] < ... < betas[R-1] = 1 (a HOST array: checked before any launch) of the
+ * tempered family of mdbn_ais_run (b_beta = (1 - beta) base_vbias + beta vbias), with swaps between neighbouring
+ * temperatures.  Row m R + s of v [M R, ldv] / h [M R, ldh] is slot s of ladder m; rank [M][R] (int32, in and out) is the
+ * temperature index a slot holds -- swaps exchange ranks, never states.  The joint at beta is
+ *   log p_beta(v, h) = beta (v W h + hbias . h) + { b_beta . v  |  -|v - b_beta|^2 / 2 }        (gauss = 0 | 1)
+ * and sweep t = 0 .. n_sweeps - 1 does, for every row at the beta of its rank:
+ *   1. v ~ sigmoid(b_beta + beta h W^T)  |  b_beta + beta h W^T + N(0, 1)                               step rng->step + 3t
+ *   2. a = v W + hbias;  l(beta') = sum_j softplus(beta' a_j) + { v . b_beta' | -|v - b_beta'|^2 / 2 }
+ *   3. the rank pairs (rho, rho + 1) with rho = sweep0 + t (mod 2) swap iff log u < l_i(beta_j) + l_j(beta_i) - l_i(beta_i)
+ *      - l_j(beta_j), u = the uniform of row `ladder`, column rho                                       step rng->step + 3t + 1
+ *   4. h ~ sigmoid(beta a) at the rank after the swap                                                   step rng->step + 3t + 2
+ * (draw index 0, the row addressing of mdbn_gibbs_chain with the global replica row; the caller advances its step counter by
+ * 3 n_sweeps and passes the sweeps already run as sweep0, so that the parity continues).  The acceptance difference is formed
+ * from float32 row sums regrouped as in mdbn_ais_run (differences of softplus; s1 = sum_i (v_i - [gauss] base_vbias_i)
+ * (vbias - base_vbias)_i) and combined in double.  On return h and rank hold the state after the last sweep, v its visible
+ * draw, accepted [R - 1] (int32) the accepted swaps per pair summed over the ladders, and -- each nullable -- v_avg [M, ldv] /
+ * h_avg [M, ldh] the means over the sweeps burn_in .. n_sweeps - 1 of the beta = 1 visible mean (sigmoid(vbias + h W^T) |
+ * vbias + h W^T) of the slot that holds rank R - 1 when it draws v, and of sigmoid(a) of the slot that holds rank R - 1 when it
+ * draws h.  Taps (nullable): trace_v [n][M R][ldv], trace_h [n][M R][ldh], trace_swaps [n][M][2][R] int32 (the rank map after
+ * the swap; per lower rank 1 = accepted, 0 = refused, -1 = not attempted).
+ * path: 0 = by shape, 1 = the one-launch path (LDS-resident layers, R a multiple of 4 and <= 64: W staged once, a workgroup
+ * owns whole ladders and swaps inside its LDS; cut into launches of at most steps_per_launch sweeps, 0 = the default, the
+ * state carried in h, rank and the workspace -- the cut changes no bit) or MDBN_EINVAL if the shape does not fit, 2 = the
+ * general path (per sweep: the propdown GEMM, a visible-draw kernel, the propup GEMM, a swap + hidden-draw kernel).  The paths
+ * meet the same uniforms and differ by fp32 summation order only.  Bad arguments (R < 2, betas not rising strictly or not
+ * ending at exactly 1, burn_in outside [0, n_sweeps), path 1 on a shape that does not fit, a workspace shorter than
+ * mdbn_pt_workspace_bytes -- which answers for leading dimensions up to mdbn_padded_ld) return MDBN_EINVAL without a launch. */
+int  mdbn_pt_workspace_bytes(mdbn_ctx *ctx, int64_t M, int64_t R, int64_t V, int64_t H, int path, int64_t *bytes);
+int  mdbn_pt_run(mdbn_ctx *ctx, void *stream, const float *W, int64_t V, int64_t H, int64_t ldh,
+                 const float *hbias, const float *vbias, const float *base_vbias, int gauss,
+                 const float *betas, int64_t R, int64_t M, int64_t ldv, float *v, float *h, int32_t *rank,
+                 int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t *accepted, float *v_avg, float *h_avg,
+                 float *trace_v, float *trace_h, int32_t *trace_swaps, int path, int64_t steps_per_launch,
+                 const mdbn_rng *rng, void *workspace, int64_t workspace_bytes);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)). */

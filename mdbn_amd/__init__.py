@@ -13,8 +13,9 @@ from .utils import get_minibatches_idx
 from .mlp import HiddenLayer
 from .rbm import RBM, GRBM, Scalar, ais_estimate, function
 from .dbn import DBN
+from .temper import TemperedChains
 from . import MDBN, checkpoint, dist, utils
 
 __all__ = ["MdbnError", "HipEngine", "RngAddr", "get_engine", "set_engine", "RandomStreams",
            "SharedArray", "HostTable", "shared", "get_minibatches_idx", "HiddenLayer", "RBM", "GRBM",
-           "Scalar", "function", "ais_estimate", "DBN", "MDBN", "dist", "checkpoint", "utils"]
+           "Scalar", "function", "ais_estimate", "DBN", "TemperedChains", "MDBN", "dist", "checkpoint", "utils"]

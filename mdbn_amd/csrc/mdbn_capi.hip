@@ -26,6 +26,7 @@
 #include "mdbn_gchain.h"
 #include "mdbn_ais.h"
 #include "mdbn_clamp.h"
+#include "mdbn_temper.h"
 
 using namespace mdbn;
 
@@ -2443,6 +2444,165 @@ int mdbn_gibbs_clamped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, 
         c.trace_v = trace_v ? trace_v + t * B * ldv : nullptr;
         HIP_OK(launch_clamp_step(c, s));
     }
+    return MDBN_OK;
+}
+
+// ---------------------------------------------------------------------------------- parallel tempering
+namespace {
+
+// The caller's workspace of mdbn_pt_run: the betas on the device, the per-ladder swap counts and the two running sums (what a
+// cut run carries from launch to launch), then -- general path -- a zero bias, the pre-activations of a pass, s1
+// (mdbn_temper.hip) and the scratch of the propagation GEMMs over M R rows.
+struct PtWs {
+    int64_t betas, counts, v_sum, h_sum, zero, pre, s1, gemm_bytes;
+    int64_t total_bytes() const { return 4 * (betas + counts + v_sum + h_sum + zero + pre + s1) + gemm_bytes; }
+};
+
+PtWs pt_ws(int path, int64_t M, int64_t R, int64_t V, int64_t H, int64_t ldv, int64_t ldh)
+{
+    PtWs w{};
+    w.betas = ru64(R);
+    w.counts = ru64(M * (R - 1));
+    w.v_sum = ru64(M * ldv);
+    w.h_sum = ru64(M * ldh);
+    if (path == 2) {
+        const int64_t rows = M * R;
+        w.zero = ru64(std::max(ldv, ldh));
+        w.pre = ru64(rows * std::max(ldv, ldh));
+        w.s1 = ru64(rows);
+        // (as ais_ws: what the plans of `rows` rows ask for is not monotone in the rows; the largest over the tilings below)
+        int64_t g = ws_sizes(rows, V, H).total_bytes();
+        const int64_t step = std::max<int64_t>(32, ((rows >> 12) + 31) & ~int64_t(31));
+        for (int64_t m = step; m < rows; m += step) g = std::max(g, ws_sizes(m, V, H).total_bytes());
+        w.gemm_bytes = g + 4 * ((int64_t)(1 << 16) + 4096);
+    }
+    return w;
+}
+
+// path = 0: the one-launch kernel only where it was measured to win (pt_small_preferred)
+int pt_path(int path, int64_t M, int64_t R, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh)
+{
+    if (path == 0) return pt_small_preferred(M, R, V, H, gauss, ldv, ldh) ? 1 : 2;
+    return path;
+}
+
+}  // namespace
+
+int mdbn_pt_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t R, int64_t V, int64_t H, int path, int64_t* bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(bytes != nullptr, "bytes is NULL");
+    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
+    REQUIRE(R >= 2 && R <= PT_MAX_R_GENERAL, "R = %lld: a ladder has 2 to %d temperatures", (long long)R, PT_MAX_R_GENERAL);
+    REQUIRE(M * R < (1ll << 31), "M * R too large");
+    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
+    const int64_t ldv = padded_ld(V), ldh = padded_ld(H);
+    // (either visible type: the larger of the two answers, so that one buffer serves a layer whatever its type)
+    const bool any = pt_small_ok(M, R, V, H, 0, ldv, ldh) || pt_small_ok(M, R, V, H, 1, ldv, ldh);
+    const bool both = pt_small_preferred(M, R, V, H, 0, ldv, ldh) && pt_small_preferred(M, R, V, H, 1, ldv, ldh);
+    REQUIRE(path != 1 || any, "path 1: %lld -> %lld with R = %lld is not LDS-resident (or R is no multiple of 4)", (long long)V,
+            (long long)H, (long long)R);
+    *bytes = pt_ws(path == 1 || (path == 0 && both) ? 1 : 2, M, R, V, H, ldv, ldh).total_bytes();
+    return MDBN_OK;
+}
+
+int mdbn_pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+                const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t R, int64_t M, int64_t ldv,
+                float* v, float* h, int32_t* rank, int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t* accepted,
+                float* v_avg, float* h_avg, float* trace_v, float* trace_h, int32_t* trace_swaps, int path,
+                int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes)
+{
+    CtxScope ctx_scope(ctx);
+    // (the argument rules first: they need no device)
+    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
+    REQUIRE(R >= 2 && R <= PT_MAX_R_GENERAL, "R = %lld: a ladder has 2 to %d temperatures", (long long)R, PT_MAX_R_GENERAL);
+    REQUIRE(M * R < (1ll << 31), "M * R too large");
+    REQUIRE(betas != nullptr, "betas is NULL (a host array of R values)");
+    REQUIRE(betas[0] >= 0.0f, "betas[0] = %g is negative", (double)betas[0]);
+    for (int64_t r = 1; r < R; ++r)
+        REQUIRE(betas[r] > betas[r - 1], "betas must rise strictly: betas[%lld] = %g after %g", (long long)r, (double)betas[r],
+                (double)betas[r - 1]);
+    REQUIRE(betas[R - 1] == 1.0f, "betas must end at exactly 1, not %.9g", (double)betas[R - 1]);
+    REQUIRE(n_sweeps >= 1 && n_sweeps < (1ll << 29), "n_sweeps = %lld must be in [1, 2^29)", (long long)n_sweeps);
+    REQUIRE(burn_in >= 0 && burn_in < n_sweeps, "burn_in = %lld must be in [0, n_sweeps = %lld)", (long long)burn_in, (long long)n_sweeps);
+    REQUIRE(sweep0 >= 0, "sweep0 = %lld is negative", (long long)sweep0);
+    REQUIRE(gauss == 0 || gauss == 1, "gauss = %d is not 0 (Bernoulli) or 1 (Gaussian visibles)", gauss);
+    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
+    REQUIRE(steps_per_launch >= 0, "steps_per_launch = %lld is negative (0 = default)", (long long)steps_per_launch);
+    REQUIRE(ldv % 4 == 0 && ldv >= V && ldh % 4 == 0 && ldh >= H, "leading dimensions must be multiples of 4, ldv >= V, ldh >= H");
+    const bool fits = pt_small_ok(M, R, V, H, gauss, ldv, ldh);
+    REQUIRE(path != 1 || fits, "path 1: %lld -> %lld (ldv %lld, ldh %lld) with R = %lld is not LDS-resident (or R is no multiple of 4)",
+            (long long)V, (long long)H, (long long)ldv, (long long)ldh, (long long)R);
+    const int p = pt_path(path, M, R, V, H, gauss, ldv, ldh);
+    const PtWs w = pt_ws(p, M, R, V, H, ldv, ldh);
+    REQUIRE(workspace_bytes >= w.total_bytes(), "workspace %lld bytes < %lld needed (mdbn_pt_workspace_bytes)",
+            (long long)workspace_bytes, (long long)w.total_bytes());
+    REQUIRE(ctx != nullptr && rng != nullptr, "ctx / rng is NULL");
+    CHECK(check_mat(W, ldh, H, "W"));
+    CHECK(check_mat(v, ldv, V, "v"));
+    CHECK(check_mat(h, ldh, H, "h"));
+    REQUIRE(hbias && vbias && base_vbias && rank && accepted, "NULL pointer");
+    REQUIRE(workspace != nullptr && aligned16(workspace), "workspace must be a 16-byte aligned device pointer");
+    for (const float* q : {(const float*)v_avg, (const float*)h_avg, (const float*)trace_h, (const float*)trace_v})
+        REQUIRE(q == nullptr || aligned16(q), "output not 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    float* wsf = reinterpret_cast<float*>(workspace);
+    float* d_betas = wsf;
+    int* counts = reinterpret_cast<int*>(d_betas + w.betas);
+    float* v_sum = reinterpret_cast<float*>(counts) + w.counts;
+    float* h_sum = v_sum + w.v_sum;
+    HIP_OK(hipMemcpyAsync(d_betas, betas, sizeof(float) * R, hipMemcpyHostToDevice, s));
+
+    if (p == 1) {
+        PtSmallArgs a{};
+        a.M = (int)M; a.R = (int)R; a.V = (int)V; a.H = (int)H; a.gauss = gauss;
+        a.ldv = ldv; a.ldh = ldh;
+        a.W = W; a.hbias = hbias; a.vbias = vbias; a.base_vbias = base_vbias; a.betas = d_betas;
+        a.v = v; a.h = h; a.rank = rank; a.counts = counts;
+        a.v_sum = v_sum; a.h_sum = h_sum; a.v_avg = v_avg; a.h_avg = h_avg;
+        a.n = (int)n_sweeps; a.burn_in = (int)burn_in; a.sweep0 = sweep0;
+        a.rng = make_key(*rng, 0u);
+        a.trace_v = trace_v; a.trace_h = trace_h; a.trace_swaps = trace_swaps;
+        const int64_t cut = steps_per_launch ? steps_per_launch : pt_default_cut(R);
+        for (int64_t t0 = 0; t0 < n_sweeps; t0 += cut) {      // a launch stays short; the state travels in h / rank / counts / sums
+            a.t0 = (int)t0; a.t1 = (int)std::min(n_sweeps, t0 + cut);
+            HIP_OK(launch_pt_small(a, s));
+        }
+        HIP_OK(launch_pt_counts(counts, (int)M, (int)R, accepted, s));
+        return MDBN_OK;
+    }
+
+    const int64_t rows = M * R;
+    float* zero = h_sum + w.h_sum;
+    float* pre = zero + w.zero;
+    float* s1 = pre + w.pre;
+    void* gemm_ws = s1 + w.s1;
+    Workspace ws;
+    CHECK(carve(gemm_ws, w.gemm_bytes, rows, V, H, ws, false));
+    HIP_OK(hipMemsetAsync(counts, 0, sizeof(float) * (w.counts + w.v_sum + w.h_sum + w.zero), s));
+    PtStepArgs st{};
+    st.M = (int)M; st.R = (int)R; st.V = (int)V; st.H = (int)H; st.gauss = gauss;
+    st.ldv = ldv; st.ldh = ldh;
+    st.vbias = vbias; st.base_vbias = base_vbias; st.betas = d_betas;
+    st.pre = pre; st.v = v; st.h = h; st.rank = rank; st.counts = counts; st.s1 = s1;
+    st.v_sum = v_sum; st.h_sum = h_sum; st.v_avg = v_avg; st.h_avg = h_avg;
+    st.n_avg = (float)(n_sweeps - burn_in); st.sweep0 = sweep0;
+    st.rng = make_key(*rng, 0u);
+    for (int64_t t = 0; t < n_sweeps; ++t) {
+        st.t = (int)t; st.accumulate = t >= burn_in; st.last = t + 1 == n_sweeps;
+        st.trace_v = trace_v ? trace_v + t * rows * ldv : nullptr;
+        st.trace_h = trace_h ? trace_h + t * rows * ldh : nullptr;
+        st.trace_swaps = trace_swaps ? trace_swaps + t * M * 2 * R : nullptr;
+        Affine down{h, rows, ldh, W, V, H, ldh, 1, zero, pre, nullptr, nullptr, ldv, 1.0f, 1, nullptr, 0, false, nullptr, 0u};
+        down.x_binary = true;                            // our own 0/1 hidden samples
+        CHECK(run_affine(down, ws, s, nullptr));
+        HIP_OK(launch_pt_visible(st, s));
+        Affine up{v, rows, ldv, W, V, H, ldh, 0, hbias, pre, nullptr, nullptr, ldh, 1.0f, 0, nullptr, 0, false, nullptr, 0u};
+        up.x_binary = !gauss;
+        CHECK(run_affine(up, ws, s, nullptr));
+        HIP_OK(launch_pt_swap_hidden(st, s));
+    }
+    HIP_OK(launch_pt_counts(counts, (int)M, (int)R, accepted, s));
     return MDBN_OK;
 }
 

@@ -1,0 +1,537 @@
+// Parallel tempering (replica exchange; Desjardins et al. 2010, Cho et al. 2010) of a trained RBM / GRBM on gfx950 / MI355X:
+// M ladders of R Gibbs chains at the inverse temperatures 0 <= beta_0 < ... < beta_{R-1} = 1 of the tempered family of
+// mdbn_ais.hip (base-rate visible bias b_A, b_beta = b_A + beta (b - b_A)), with swaps between neighbouring temperatures.
+//
+//   joint at beta:  log p_beta(v, h) = beta (v W h + c h) + { b_beta . v  |  -|v - b_beta|^2 / 2 }
+//   row m R + s = slot s of ladder m;  rank[m][s] = the temperature index the slot holds (swaps exchange ranks, never states)
+//   sweep t (run step s = rng.step), every row at the beta of its rank:
+//     1. v ~ sigmoid(b_beta + beta h W^T)  |  b_beta + beta h W^T + N(0, 1)                                  (step s + 3t)
+//     2. a = v W + c;  l(beta') = sum_j softplus(beta' a_j) + { v . b_beta' | -|v - b_beta'|^2 / 2 }
+//     3. rank pairs (rho, rho + 1), rho = sweep0 + t (mod 2): accept iff log u < l_i(beta_j) + l_j(beta_i) - l_i(beta_i)
+//        - l_j(beta_j), u addressed by (ladder, rho) alone                                                  (step s + 3t + 1)
+//     4. h ~ sigmoid(beta a) at the rank after the swap                                                     (step s + 3t + 2)
+//   t >= burn_in: v_sum[m] += the beta = 1 mean of the slot that holds rank R - 1 when it draws v (sigmoid(b + h W^T) | b + h W^T),
+//                 h_sum[m] += sigmoid(a) of the slot that holds rank R - 1 when it draws h                  (float32, in sweep order)
+// The acceptance difference is formed with the regrouping of mdbn_ais.hip: per row the float32 sums
+//   hsum = sum_j softplus(beta_partner a_j) - softplus(beta_own a_j),   s1 = sum_i (v_i - [Gaussian] b_A,i) (b - b_A)_i
+// and  delta = hsum_lo + hsum_hi + (beta_hi - beta_lo) (s1_lo - s1_hi)  in double (the Gaussian |b - b_A|^2 terms of the two
+// rows cancel).  Both paths call pt_draw_v, pt_draw_h, pt_ell and pt_swap_accept below: the uniforms, their addressing and the
+// decision are stated once.
+//
+// pt_small_kernel (LDS-resident layers, R a multiple of 4): W staged once into the workgroup's LDS; a workgroup owns whole
+// ladders, the R rows of h and a stay in LDS, a sweep runs R / 4 four-row slabs through sm_down / sm_up of
+// mdbn_small_passes.h, the swap phase reads the per-row sums from LDS and exchanges ranks there.  Nothing crosses a workgroup.
+// pt_visible_kernel / pt_swap_hidden_kernel (any shape): the per-sweep epilogues around the library's propdown / propup GEMMs.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "mdbn_kernels.h"
+#include "mdbn_device.h"
+#include "mdbn_small.h"
+#include "mdbn_small_passes.h"
+#include "mdbn_temper.h"
+
+namespace mdbn {
+
+namespace {
+
+constexpr float PT_TWO_PI = 6.28318530717958647692f;
+typedef __attribute__((address_space(3))) int lds_i;
+
+// v | h for one (4-row group, column), every row at its own beta: pre = b_A + beta (b - b_A) + beta m, then the draw.
+// `s` receives the column's share of s1.
+template <bool GAUSS>
+__device__ __forceinline__ void pt_draw_v(const PhiloxKey& key, uint64_t grow0, int col, const float (&beta)[4], float bA, float db,
+                                          const float (&m)[4], const bool (&ok)[4], float (&v)[4], float (&pre)[4], float (&s)[4])
+{
+    uint32_t wa[4], wb[4] = {0u, 0u, 0u, 0u};
+    philox_rows4(key, 0u, grow0, (uint32_t)col, wa);
+    if (GAUSS) philox_rows4(key, MDBN_NORMAL_BIT, grow0, (uint32_t)col, wb);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        pre[e] = fmaf(beta[e], m[e], fmaf(beta[e], db, bA));
+        if (GAUSS) {
+            const float z = sqrtf(-2.0f * logf(philox_u01(wa[e]))) * cosf(PT_TWO_PI * philox_u01(wb[e]));
+            v[e] = ok[e] ? pre[e] + z : 0.f;
+            s[e] = ok[e] ? (v[e] - bA) * db : 0.f;
+        } else {
+            v[e] = ok[e] && philox_u01(wa[e]) < sigmoidf_(pre[e]) ? 1.0f : 0.0f;
+            s[e] = v[e] * db;
+        }
+    }
+}
+
+// h | v for one (4-row group, column): p = sigmoid(beta a), a = pre-activation (c included)
+__device__ __forceinline__ void pt_draw_h(const PhiloxKey& key, uint64_t grow0, int col, const float (&beta)[4], const float (&a)[4],
+                                          const bool (&ok)[4], float (&h)[4], float (&p)[4])
+{
+    uint32_t w[4];
+    philox_rows4(key, 0u, grow0, (uint32_t)col, w);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        p[e] = sigmoidf_(beta[e] * a[e]);
+        h[e] = ok[e] && philox_u01(w[e]) < p[e] ? 1.0f : 0.0f;
+    }
+}
+
+// one hidden unit's share of l(beta_partner) - l(beta_own)
+__device__ __forceinline__ float pt_ell(float a, float b_own, float b_partner)
+{
+    return softplusf_(b_partner * a) - softplusf_(b_own * a);
+}
+
+// the rank a row of rank `rho` is paired with in a sweep of parity `par` (pairs (r, r + 1), r = par mod 2), or -1
+__device__ __forceinline__ int pt_partner(int rho, int par, int R)
+{
+    const int p = ((rho ^ par) & 1) == 0 ? rho + 1 : rho - 1;
+    return p >= 0 && p < R ? p : -1;
+}
+
+// the swap of the ranks (rho, rho + 1) of ladder `ladder`: log u < delta.  key.step = the sweep's swap step.
+__device__ __forceinline__ bool pt_swap_accept(const PhiloxKey& key, uint64_t ladder, int rho, float hsum_lo, float hsum_hi,
+                                               float s1_lo, float s1_hi, float b_lo, float b_hi)
+{
+    uint32_t w[4];
+    philox4x32_10((uint32_t)rho, (uint32_t)(ladder >> 2), 0u, key.step, key.k0, key.k1, w);
+    const uint32_t ph = (uint32_t)(ladder & 3);
+    const uint32_t word = ph == 0 ? w[0] : ph == 1 ? w[1] : ph == 2 ? w[2] : w[3];
+    const double delta = (double)hsum_lo + (double)hsum_hi + ((double)b_hi - (double)b_lo) * ((double)s1_lo - (double)s1_hi);
+    return (double)logf(philox_u01(word)) < delta;
+}
+
+__device__ __forceinline__ float pt_wave_sum(float x)     // every lane of the wave active; the same tree in every call
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+}  // namespace
+
+template <bool GAUSS, bool TRACE>
+__global__ __launch_bounds__(SM_NT) void pt_small_kernel(PtSmallArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const SmallLayout& L = a.L;
+    const PtLayout& P = a.P;
+    lds_f* const lds = (lds_f*)sm;
+    lds_f* const Wl = lds + L.oW;
+    lds_f* const X = lds + L.oXa;           // [4][ldx] the slab's visible draw
+    lds_f* const part = lds + L.oPart;
+    lds_f* const hbl = lds + L.oHb;         // c
+    lds_f* const bAl = lds + L.oVb;         // b_A
+    lds_f* const dbl = lds + L.oCsV;        // b - b_A
+    lds_f* const Hs = lds + P.oHs;          // [R][ldhs] hidden samples of the ladder
+    lds_f* const Al = lds + P.oA;           // [R][ldhs] a = v W + c
+    lds_f* const redH = lds + P.oRedH;      // [R][8]
+    lds_f* const redV = lds + P.oRedV;      // [R][8]
+    lds_f* const betl = lds + P.oBeta;
+    lds_i* const rk = (lds_i*)(lds + P.oRank);
+    lds_i* const inv = (lds_i*)(lds + P.oInv);
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int V = a.V, H = a.H, M = a.M, R = a.R;
+    const int64_t ldv = a.ldv, ldh = a.ldh;
+    const int nq = R / SM_ROWS;
+
+    // ---- W image [Vp][ldw] (rows >= V and columns >= ldh zero, + the slack behind the last row), biases, betas, zeroed X
+    {
+        const int q4w = L.ldw >> 2, q4 = (int)(ldh >> 2);
+        const int total = L.Vp * q4w + 4;
+        for (int e = tid; e < total; e += SM_NT) {
+            const int r = e / q4w, c4 = e - r * q4w;
+            sf32x4 w = {0.f, 0.f, 0.f, 0.f};
+            if (r < V && c4 < q4) w = *reinterpret_cast<const sf32x4*>(a.W + (int64_t)r * ldh + 4 * c4);
+            *(lds_f4*)(Wl + 4 * e) = w;
+        }
+    }
+    if (tid < L.H64) hbl[tid] = tid < H ? a.hbias[tid] : 0.f;
+    if (tid < L.V64) {
+        const float bA = tid < V ? a.base_vbias[tid] : 0.f, b = tid < V ? a.vbias[tid] : 0.f;
+        bAl[tid] = bA; dbl[tid] = b - bA;
+    }
+    if (tid < R) betl[tid] = a.betas[tid];
+    for (int i = tid; i < SM_ROWS * L.ldx; i += SM_NT) X[i] = 0.f;
+
+    // Both passes hand column `tid` to thread `tid` (propup: one column per thread; propdown: wave w owns tile w, tiles_dn <= 8),
+    // so a thread keeps its column's two running sums in registers for the whole launch.
+    const bool vlive = tid < V, hlive = tid < H;
+
+    for (int m = blockIdx.x; m < M; m += gridDim.x) {
+        SM_SYNC();                                                       // (staging | the previous ladder's last readers are done)
+        // ---- the ladder's state: h, the rank map and its inverse, the counts and the sums
+        for (int i = tid; i < R * L.ldhs; i += SM_NT) {
+            const int r = i / L.ldhs, col = i - r * L.ldhs;
+            Hs[i] = col < H ? a.h[(int64_t)(m * R + r) * ldh + col] : 0.f;
+        }
+        if (tid < R) {
+            const int rho = a.rank[m * R + tid];
+            rk[tid] = rho;
+            inv[rho] = tid;
+        }
+        float vacc = 0.f, hacc = 0.f;
+        int cnt = 0;
+        if (a.t0 > 0) {
+            if (vlive) vacc = a.v_sum[(int64_t)m * ldv + tid];
+            if (hlive) hacc = a.h_sum[(int64_t)m * ldh + tid];
+            if (tid < R - 1) cnt = a.counts[m * (R - 1) + tid];
+        }
+        SM_SYNC();
+
+        for (int t = a.t0; t < a.t1; ++t) {
+            const bool acc = t >= a.burn_in, out_v = t == a.t1 - 1;
+            const int par = (int)((a.sweep0 + t) & 1);
+            PhiloxKey kv = a.rng, ks = a.rng, kh = a.rng;
+            kv.step = a.rng.step + (uint32_t)(3 * t);
+            ks.step = a.rng.step + (uint32_t)(3 * t + 1);
+            kh.step = a.rng.step + (uint32_t)(3 * t + 2);
+            const bool okv[4] = {vlive, vlive, vlive, vlive}, okh[4] = {hlive, hlive, hlive, hlive};
+            for (int q = 0; q < nq; ++q) {
+                const int row0 = m * R + SM_ROWS * q;
+                const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
+                float bo[4], bp[4];
+                bool top[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int rho = rk[SM_ROWS * q + e], pr = pt_partner(rho, par, R);
+                    bo[e] = betl[rho];
+                    bp[e] = pr >= 0 ? betl[pr] : bo[e];
+                    top[e] = rho == R - 1;
+                }
+                sm_down(Hs + SM_ROWS * q * L.ldhs, Wl, L, wave, lane,
+                        [&](const sf32x4& x, int col) {                    // col == tid
+                            const float bA = bAl[col], db = dbl[col];
+                            const float mm[4] = {x[0], x[1], x[2], x[3]};
+                            float v[4], pre[4], s[4];
+                            pt_draw_v<GAUSS>(kv, grow0, col, bo, bA, db, mm, okv, v, pre, s);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                X[e * L.ldx + col] = v[e];
+                                if (acc && top[e] && vlive) vacc += GAUSS ? pre[e] : sigmoidf_(pre[e]);
+                                const float ts = pt_wave_sum(s[e]);
+                                if (lane == 0) redV[(SM_ROWS * q + e) * 8 + (col >> 6)] = ts;
+                            }
+                            if (col < (int)ldv) {
+                                if (out_v) {
+#pragma unroll
+                                    for (int e = 0; e < 4; ++e) a.v[(int64_t)(row0 + e) * ldv + col] = v[e];
+                                }
+                                if (TRACE && a.trace_v) {
+#pragma unroll
+                                    for (int e = 0; e < 4; ++e) a.trace_v[((int64_t)t * M * R + row0 + e) * ldv + col] = v[e];
+                                }
+                            }
+                        });
+                sm_up(X, Wl, L, part, wave, lane, [] {},
+                      [&](const sf32x4& x, int col) {                      // col == tid
+                          const float bias = hbl[col];
+#pragma unroll
+                          for (int e = 0; e < 4; ++e) {
+                              const float pre = hlive ? x[e] + bias : 0.f;
+                              Al[(SM_ROWS * q + e) * L.ldhs + col] = pre;
+                              const float td = pt_wave_sum(hlive ? pt_ell(pre, bo[e], bp[e]) : 0.f);
+                              if (lane == 0) redH[(SM_ROWS * q + e) * 8 + (col >> 6)] = td;
+                          }
+                      });
+            }
+
+            // ---- the swaps of this sweep: thread rho decides the pair (rho, rho + 1)
+            int dec = -1;
+            if (tid < R - 1 && ((tid ^ par) & 1) == 0) {
+                const int i = inv[tid], j = inv[tid + 1];
+                float hl = 0.f, hh = 0.f, sl = 0.f, sh = 0.f;
+                for (int u = 0; u < L.tiles_up; ++u) { hl += redH[i * 8 + u]; hh += redH[j * 8 + u]; }
+                for (int u = 0; u < L.tiles_dn; ++u) { sl += redV[i * 8 + u]; sh += redV[j * 8 + u]; }
+                const uint64_t ladder = a.rng.row_offset / (uint64_t)R + (uint64_t)m;
+                dec = pt_swap_accept(ks, ladder, tid, hl, hh, sl, sh, betl[tid], betl[tid + 1]) ? 1 : 0;
+                if (dec) {
+                    rk[i] = tid + 1; rk[j] = tid;
+                    inv[tid] = j; inv[tid + 1] = i;
+                    ++cnt;
+                }
+            }
+            SM_SYNC();
+            if (TRACE && a.trace_swaps && tid < R) {
+                int* ts = a.trace_swaps + ((int64_t)t * M + m) * 2 * R;
+                ts[tid] = rk[tid];
+                ts[R + tid] = dec;
+            }
+
+            // ---- the hidden draw at the rank after the swap
+            if (tid < L.H64) {
+                const int col = tid;
+                for (int q = 0; q < nq; ++q) {
+                    const int row0 = m * R + SM_ROWS * q;
+                    const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
+                    float bn[4], pre[4], h[4], p[4];
+                    bool top[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int rho = rk[SM_ROWS * q + e];
+                        bn[e] = betl[rho];
+                        top[e] = rho == R - 1;
+                        pre[e] = Al[(SM_ROWS * q + e) * L.ldhs + col];
+                    }
+                    pt_draw_h(kh, grow0, col, bn, pre, okh, h, p);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        Hs[(SM_ROWS * q + e) * L.ldhs + col] = h[e];
+                        if (acc && top[e] && hlive) hacc += p[e];
+                    }
+                    if (TRACE && a.trace_h && col < (int)ldh) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) a.trace_h[((int64_t)t * M * R + row0 + e) * ldh + col] = h[e];
+                    }
+                }
+            }
+            SM_SYNC();
+        }
+
+        // ---- what the next launch (or the caller) reads
+        const bool last = a.t1 == a.n;
+        const float n_avg = (float)(a.n - a.burn_in);
+        for (int i = tid; i < R * (int)ldh; i += SM_NT) {
+            const int r = i / (int)ldh, col = i - r * (int)ldh;
+            a.h[(int64_t)(m * R + r) * ldh + col] = Hs[r * L.ldhs + col];
+        }
+        if (tid < R) a.rank[m * R + tid] = rk[tid];
+        if (tid < R - 1) a.counts[m * (R - 1) + tid] = cnt;
+        if (tid < (int)ldv) {
+            a.v_sum[(int64_t)m * ldv + tid] = vacc;
+            if (last && a.v_avg) a.v_avg[(int64_t)m * ldv + tid] = vacc / n_avg;
+        }
+        if (tid < (int)ldh) {
+            a.h_sum[(int64_t)m * ldh + tid] = hacc;
+            if (last && a.h_avg) a.h_avg[(int64_t)m * ldh + tid] = hacc / n_avg;
+        }
+    }
+}
+
+bool pt_small_ok(int64_t M, int64_t R, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh)
+{
+    if (M < 1 || R < 2 || R % SM_ROWS != 0 || R > PT_MAX_R || M * R >= (1ll << 31)) return false;
+    if (!small_shape_ok(M * R, V, H, gauss) || !small_ld_ok(V, H, ldv, ldh)) return false;
+    const SmallLayout L = small_layout((int)V, (int)H, gauss != 0);
+    return L.tiles_dn <= SM_NW && pt_layout(L, (int)R).bytes <= SM_MAX_LDS;
+}
+
+// path = 0 takes the one-launch kernel only where it was measured to win: at least two workgroups per CU (the
+// sweep of a ladder is a serial chain of R / 4 slab passes: a CU needs a second ladder to fill the gaps) and enough ladders to
+// occupy the chip that way.  Elsewhere the general path, whose kernels spread all M R rows over the chip, is as fast or faster.
+bool pt_small_preferred(int64_t M, int64_t R, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh)
+{
+    if (!pt_small_ok(M, R, V, H, gauss, ldv, ldh) || M < PT_SMALL_MIN_LADDERS) return false;
+    return 2 * pt_layout(small_layout((int)V, (int)H, gauss != 0), (int)R).bytes <= SM_MAX_LDS;
+}
+
+int pt_default_cut(int64_t R)
+{
+    const int64_t slabs = (R + SM_ROWS - 1) / SM_ROWS;
+    return (int)(PT_CUT / slabs > 1 ? PT_CUT / slabs : 1);
+}
+
+hipError_t launch_pt_small(const PtSmallArgs& a, hipStream_t s)
+{
+    if (!pt_small_ok(a.M, a.R, a.V, a.H, a.gauss, a.ldv, a.ldh) || a.t0 < 0 || a.t1 <= a.t0 || a.t1 > a.n || a.burn_in < 0 ||
+        a.burn_in >= a.n)
+        return hipErrorInvalidValue;
+    const SmallLayout L = small_layout(a.V, a.H, a.gauss != 0);
+    const PtLayout P = pt_layout(L, a.R);
+    const bool trace = a.trace_h || a.trace_v || a.trace_swaps;
+    const int variant = (a.gauss ? 2 : 0) | (trace ? 1 : 0);
+    static bool attr_set[4] = {false, false, false, false};
+    const void* kerns[4] = {reinterpret_cast<const void*>(pt_small_kernel<false, false>), reinterpret_cast<const void*>(pt_small_kernel<false, true>),
+                            reinterpret_cast<const void*>(pt_small_kernel<true, false>), reinterpret_cast<const void*>(pt_small_kernel<true, true>)};
+    if (!attr_set[variant]) {
+        hipError_t e = hipFuncSetAttribute(kerns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, SM_MAX_LDS);
+        if (e != hipSuccess) return e;
+        attr_set[variant] = true;
+    }
+    // one workgroup per ladder; beyond 1024 ladders a workgroup loops (a ladder never leaves its workgroup)
+    const dim3 grid(a.M < 1024 ? a.M : 1024), block(SM_NT);
+    PtSmallArgs k = a;
+    k.L = L; k.P = P;
+    switch (variant) {
+        case 0: hipLaunchKernelGGL((pt_small_kernel<false, false>), grid, block, P.bytes, s, k); break;
+        case 1: hipLaunchKernelGGL((pt_small_kernel<false, true>), grid, block, P.bytes, s, k); break;
+        case 2: hipLaunchKernelGGL((pt_small_kernel<true, false>), grid, block, P.bytes, s, k); break;
+        default: hipLaunchKernelGGL((pt_small_kernel<true, true>), grid, block, P.bytes, s, k); break;
+    }
+    return hipGetLastError();
+}
+
+// ----------------------------------------------------------------------------------
+// General path.  pt_visible_kernel: a workgroup owns four consecutive replica rows (one Philox block), a thread walks the
+// columns tid, tid + PT_NT, ...; the row sums of s1 are combined wave by wave in a fixed order.
+// ----------------------------------------------------------------------------------
+template <bool GAUSS>
+__global__ __launch_bounds__(PT_NT) void pt_visible_kernel(PtStepArgs a)
+{
+    __shared__ float red[4 * (PT_NT / 64)];
+    const int row0 = (int)blockIdx.x * 4, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int rows = a.M * a.R;
+    const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
+    PhiloxKey key = a.rng;
+    key.step = a.rng.step + (uint32_t)(3 * a.t);
+    float beta[4];
+    bool okr[4], top[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        okr[e] = row0 + e < rows;
+        const int rho = okr[e] ? a.rank[row0 + e] : 0;
+        beta[e] = a.betas[rho];
+        top[e] = okr[e] && rho == a.R - 1;
+    }
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int col = tid; col < (int)a.ldv; col += PT_NT) {
+        const bool live = col < a.V;
+        const float bA = live ? a.base_vbias[col] : 0.f, db = live ? a.vbias[col] - bA : 0.f;
+        bool ok[4];
+        float m[4], v[4], pre[4], s[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            ok[e] = live && okr[e];
+            m[e] = ok[e] ? a.pre[(int64_t)(row0 + e) * a.ldv + col] : 0.f;
+        }
+        pt_draw_v<GAUSS>(key, grow0, col, beta, bA, db, m, ok, v, pre, s);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[e] += s[e];
+            if (!okr[e]) continue;
+            a.v[(int64_t)(row0 + e) * a.ldv + col] = v[e];                 // (pad columns: zeros)
+            if (a.trace_v) a.trace_v[(int64_t)(row0 + e) * a.ldv + col] = v[e];
+            if (a.accumulate && top[e]) {                                  // (one row of a ladder holds the top rank: no other writer)
+                const int64_t o = (int64_t)((row0 + e) / a.R) * a.ldv + col;
+                const float t = a.v_sum[o] + (live ? (GAUSS ? pre[e] : sigmoidf_(pre[e])) : 0.f);
+                a.v_sum[o] = t;
+                if (a.last && a.v_avg) a.v_avg[o] = t / a.n_avg;
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float t = pt_wave_sum(acc[e]);
+        if (lane == 0) red[e * (PT_NT / 64) + wave] = t;
+    }
+    __syncthreads();
+    if (tid < 4 && okr[tid]) {
+        float t = 0.f;
+        for (int w = 0; w < PT_NT / 64; ++w) t += red[tid * (PT_NT / 64) + w];
+        a.s1[row0 + tid] = t;
+    }
+}
+
+// pt_swap_hidden_kernel: a workgroup owns one ladder: the hidden share of l per row (one wave per row, a fixed tree), the
+// swap decisions, the exchange of ranks, then the hidden draw of its R rows.
+__global__ __launch_bounds__(PT_NT) void pt_swap_hidden_kernel(PtStepArgs a)
+{
+    extern __shared__ float psm[];
+    const int R = a.R, m = (int)blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* const bet = psm;                  // [R]
+    float* const hs = psm + R;               // [R]
+    int* const rk = (int*)(psm + 2 * R);     // [R]
+    int* const inv = rk + R;                 // [R]
+    const int par = (int)((a.sweep0 + a.t) & 1);
+    const int row0 = m * R;
+    for (int s = tid; s < R; s += PT_NT) {
+        bet[s] = a.betas[s];
+        const int rho = a.rank[row0 + s];
+        rk[s] = rho;
+        inv[rho] = s;
+    }
+    __syncthreads();
+    for (int s = wave; s < R; s += PT_NT / 64) {
+        const int rho = rk[s], pr = pt_partner(rho, par, R);
+        const float bo = bet[rho], bp = pr >= 0 ? bet[pr] : bo;
+        float t = 0.f;
+        for (int col = lane; col < a.H; col += 64) t += pt_ell(a.pre[(int64_t)(row0 + s) * a.ldh + col], bo, bp);
+        t = pt_wave_sum(t);
+        if (lane == 0) hs[s] = t;
+    }
+    __syncthreads();
+    PhiloxKey ks = a.rng, kh = a.rng;
+    ks.step = a.rng.step + (uint32_t)(3 * a.t + 1);
+    kh.step = a.rng.step + (uint32_t)(3 * a.t + 2);
+    int* const ts = a.trace_swaps;
+    for (int rho = tid; rho < R; rho += PT_NT) {
+        int dec = -1;
+        if (rho < R - 1 && ((rho ^ par) & 1) == 0) {
+            const int i = inv[rho], j = inv[rho + 1];
+            const uint64_t ladder = a.rng.row_offset / (uint64_t)R + (uint64_t)m;
+            dec = pt_swap_accept(ks, ladder, rho, hs[i], hs[j], a.s1[row0 + i], a.s1[row0 + j], bet[rho], bet[rho + 1]) ? 1 : 0;
+            if (dec) {
+                rk[i] = rho + 1; rk[j] = rho;
+                a.counts[m * (R - 1) + rho] += 1;
+            }
+        }
+        if (ts) ts[(int64_t)m * 2 * R + R + rho] = dec;
+    }
+    __syncthreads();
+    for (int s = tid; s < R; s += PT_NT) {
+        a.rank[row0 + s] = rk[s];
+        if (ts) ts[(int64_t)m * 2 * R + s] = rk[s];
+    }
+    const int groups = (R + 3) / 4, ldh = (int)a.ldh;
+    for (int idx = tid; idx < groups * ldh; idx += PT_NT) {
+        const int g = idx / ldh, col = idx - g * ldh;
+        const bool live = col < a.H;
+        float bn[4], pre[4], h[4], p[4];
+        bool ok[4], top[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int s = 4 * g + e;
+            const bool in = s < R;
+            const int rho = in ? rk[s] : 0;
+            ok[e] = in && live;
+            bn[e] = bet[rho];
+            top[e] = in && rho == R - 1;
+            pre[e] = ok[e] ? a.pre[(int64_t)(row0 + s) * ldh + col] : 0.f;
+        }
+        pt_draw_h(kh, a.rng.row_offset + (uint64_t)(row0 + 4 * g), col, bn, pre, ok, h, p);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int s = 4 * g + e;
+            if (s >= R) continue;
+            a.h[(int64_t)(row0 + s) * ldh + col] = h[e];                   // (pad columns: zeros)
+            if (a.trace_h) a.trace_h[(int64_t)(row0 + s) * ldh + col] = h[e];
+            if (a.accumulate && top[e]) {
+                const int64_t o = (int64_t)m * ldh + col;
+                const float t = a.h_sum[o] + (live ? p[e] : 0.f);
+                a.h_sum[o] = t;
+                if (a.last && a.h_avg) a.h_avg[o] = t / a.n_avg;
+            }
+        }
+    }
+}
+
+// accepted[rho] = sum over the ladders of counts[m][rho] (integers: any order gives the same sum)
+__global__ __launch_bounds__(64) void pt_counts_kernel(const int* counts, int M, int R, int* accepted)
+{
+    for (int rho = (int)(blockIdx.x * 64 + threadIdx.x); rho < R - 1; rho += (int)gridDim.x * 64) {
+        int t = 0;
+        for (int m = 0; m < M; ++m) t += counts[m * (R - 1) + rho];
+        accepted[rho] = t;
+    }
+}
+
+hipError_t launch_pt_visible(const PtStepArgs& a, hipStream_t s)
+{
+    if (a.M < 1 || a.R < 2 || a.t < 0) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)(((int64_t)a.M * a.R + 3) / 4);
+    if (a.gauss) hipLaunchKernelGGL((pt_visible_kernel<true>), dim3(blocks), dim3(PT_NT), 0, s, a);
+    else hipLaunchKernelGGL((pt_visible_kernel<false>), dim3(blocks), dim3(PT_NT), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_pt_swap_hidden(const PtStepArgs& a, hipStream_t s)
+{
+    if (a.M < 1 || a.R < 2 || a.R > PT_MAX_R_GENERAL || a.t < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pt_swap_hidden_kernel, dim3((unsigned)a.M), dim3(PT_NT), (size_t)a.R * 16, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_pt_counts(const int* counts, int M, int R, int* accepted, hipStream_t s)
+{
+    hipLaunchKernelGGL(pt_counts_kernel, dim3((unsigned)((R - 1 + 63) / 64)), dim3(64), 0, s, counts, M, R, accepted);
+    return hipGetLastError();
+}
+
+}  // namespace mdbn

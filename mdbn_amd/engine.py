@@ -549,6 +549,51 @@ class HipEngine(object):
             return out, trace_h.cpu().numpy()[:K - 1, :, :H], trace_v.cpu().numpy()[:, :, :V]
         return out
 
+    def temper(self, W, hbias, vbias, base_vbias, gauss, betas, v, h, rank, n_sweeps, rng, burn_in=0, sweep0=0, path=0,
+               steps_per_launch=0, trace=False):
+        """``n_sweeps`` parallel-tempering sweeps of M ladders of R replicas in ONE library call (mdbn_pt_run).  ``v``
+        [M R, V] (ld = padded_ld(V)), ``h`` [M R, H] (ld = W's) and ``rank`` [M, R] (int32) are the ladders' state and are
+        updated IN PLACE; ``betas``: R float32 values on the host, rising strictly to exactly 1; ``base_vbias``: device vector.
+        Returns device tensors ``(accepted [R - 1] int32, v_avg [M, V], h_avg [M, H])`` and, with ``trace``, also
+        ``trace_v [n, M R, V]``, ``trace_h [n, M R, H]`` and ``trace_swaps [n, M, 2, R]`` (int32: the rank map after the swap;
+        per lower rank 1 / 0 / -1 = accepted / refused / not attempted).  ``path``: 0 = by shape, 1 = the one-launch kernel,
+        2 = the general path.  No host synchronisation.  Consumes 3 * n_sweeps RNG steps."""
+        V, H = W.shape
+        M, R = (int(x) for x in rank.shape)
+        ldh, ldv = W.stride(0), padded_ld(V)
+        n_sweeps, burn_in = int(n_sweeps), int(burn_in)
+        betas = numpy.ascontiguousarray(betas, dtype=numpy.float32)
+        if betas.shape != (R,):
+            raise ValueError("expected %d betas, got %r" % (R, betas.shape))
+        if tuple(v.shape) != (M * R, V) or v.stride(0) != ldv or tuple(h.shape) != (M * R, H) or h.stride(0) != ldh:
+            raise ValueError("v / h must be [%d, %d] on ld %d and [%d, %d] on ld %d" % (M * R, V, ldv, M * R, H, ldh))
+        if rank.dtype != torch.int32 or not rank.is_contiguous():
+            raise ValueError("rank must be a contiguous int32 tensor")
+        accepted = torch.zeros(max(R - 1, 1), dtype=torch.int32, device=self.device)
+        v_avg, h_avg = self.alloc_matrix(M, V, ldv), self.alloc_matrix(M, H, ldh)
+        n_t = max(n_sweeps, 1)
+        trace_v = torch.zeros((n_t, M * R, ldv), dtype=torch.float32, device=self.device) if trace else None
+        trace_h = torch.zeros((n_t, M * R, ldh), dtype=torch.float32, device=self.device) if trace else None
+        trace_s = torch.zeros((n_t, M, 2, R), dtype=torch.int32, device=self.device) if trace else None
+        n, need = C.c_int64(), 0
+        for Hq in sorted({H, ldh}):        # (a weight matrix on a padded leading dimension: every buffer is as large as that width's)
+            _lib.check(self.lib.mdbn_pt_workspace_bytes(self.ctx, M, R, V, Hq, int(path) if Hq == H else 2, C.byref(n)),
+                       "mdbn_pt_workspace_bytes")
+            need = max(need, n.value)
+        ws = getattr(self, "_pt_ws", None)             # kept between calls, grown to the largest requirement seen
+        if ws is None or ws.numel() * 4 < need:
+            ws = self._pt_ws = torch.empty(need // 4 + 64, dtype=torch.float32, device=self.device)
+        r = rng.c()
+        _lib.check(self.lib.mdbn_pt_run(
+            self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base_vbias),
+            int(bool(gauss)), betas.ctypes.data_as(C.c_void_p), R, M, ldv, self._p(v), self._p(h), self._p(rank), n_sweeps,
+            burn_in, int(sweep0), self._p(accepted), self._p(v_avg), self._p(h_avg), self._p(trace_v), self._p(trace_h),
+            self._p(trace_s), int(path), int(steps_per_launch), C.byref(r), self._p(ws), ws.numel() * 4), "mdbn_pt_run")
+        out = (accepted[:R - 1], v_avg, h_avg)
+        if trace:
+            out += (trace_v[:, :, :V], trace_h[:, :, :H], trace_s)
+        return out
+
     def gather_rows(self, src, indexes):
         src = self.as_matrix(src)
         idx = self.index_tensor(indexes, src.shape[0])

@@ -768,6 +768,32 @@ class RBM(object):
         v_hat = numpy.where(held, x, v_hat)
         return v_hat.astype(numpy.float32), h_hat.astype(numpy.float32)
 
+    # ------------------------------------------------------------------ parallel tempering
+    def tempered_chains(self, n_ladders, betas=None, n_betas=16, base_vbias=None, data=None, start_h=None):
+        """``n_ladders`` parallel-tempering ladders of this layer (``mdbn_amd.temper.TemperedChains``): Gibbs chains at the
+        inverse temperatures ``betas`` (None: ``linspace(0, 1, n_betas)``) of the tempered family of ``log_partition`` --
+        base-rate visible bias ``base_vbias`` (None: taken from ``data`` by ``base_rate_vbias``; with neither, the layer's own
+        visible bias) -- with swaps between neighbouring temperatures, so that the beta = 1 replica crosses between modes a
+        plain chain never leaves.  ``start_h``: [n_ladders, H] (every temperature of a ladder starts there) or
+        [n_ladders * R, H]; None: zeros.  A GRBM ladder runs the Gibbs sampler of its model (hidden sample down, unit noise),
+        not the reference's mean-field chain.  Each sweep consumes 3 RNG steps."""
+        from .temper import TemperedChains
+        if betas is None:
+            betas = numpy.linspace(0.0, 1.0, int(n_betas))
+        if base_vbias is None:
+            base_vbias = self.base_rate_vbias(data) if data is not None else self.vbias.get_value()
+        return TemperedChains(self, n_ladders, betas, base_vbias, start_h=start_h)
+
+    def sample_tempered(self, n_samples, n_sweeps=1000, burn_in=200, path=0, **ladder):
+        """``n_samples`` ladders run for ``n_sweeps`` sweeps: host arrays ``(v, h, v_avg, h_avg, acceptance)`` -- the state of
+        every ladder's beta = 1 replica after the last sweep, the means of its conditional expectations over the sweeps
+        from ``burn_in`` on, and the accepted share of the swap attempts per neighbour pair.  ``ladder``: the arguments of
+        ``tempered_chains``.  Consumes 3 * n_sweeps RNG steps."""
+        chains = self.tempered_chains(int(n_samples), **ladder)
+        v_avg, h_avg, acceptance = chains.run(n_sweeps, burn_in=burn_in, path=path)[:3]
+        v, h = chains.samples()
+        return tuple(numpy.asarray(t.get_value()) for t in (v, h, v_avg, h_avg, acceptance))
+
     def make_sample_fn(self, persistent_vis_chain, n_steps=500):
         """The ``sample_fn`` of rbm.py:844-853: each call runs ``n_steps`` Gibbs steps from the persistent visible
         chain, stores ``vis_samples[-1]`` back into it and returns ``(vis_mfs[-1], vis_samples[-1])`` as host arrays."""
@@ -838,8 +864,13 @@ class RBM(object):
     # ------------------------------------------------------------------ stand-alone trainer
     def training(self, train_set_x, validation_set_x, training_epochs, batch_size=10,
                  learning_rate=0.1, k=1, initial_momentum=0.0, final_momentum=0.0,
-                 weightcost=0.0, lambda_2=0.0, persistent=True, display_fn=None, graph_output=False):
-        """rbm.py:484-520 (note: like the reference, ``lambda_2`` is accepted but not used)."""
+                 weightcost=0.0, lambda_2=0.0, persistent=True, display_fn=None, graph_output=False, tempering=None):
+        """rbm.py:484-520 (note: like the reference, ``lambda_2`` is accepted but not used).
+
+        ``tempering=R`` (with ``persistent``): PCD whose negative chains are the beta = 1 replicas of ``batch_size``
+        parallel-tempering ladders of R temperatures (Desjardins et al. 2010) -- every step is ``chains.run(1)``,
+        ``chains.to_persistent``, the unchanged PCD step, ``chains.from_persistent``; the ladders stay in ``self.tempered``.
+        None: nothing changes."""
         if persistent:
             persistent_chain = shared(numpy.zeros((batch_size, self.n_hidden), dtype=numpy.float32),
                                       engine=self.engine)               # rbm.py:496-498
@@ -847,17 +878,30 @@ class RBM(object):
             persistent_chain = None
         cost, updates = self.get_cost_updates(lr=learning_rate, k=k, weightcost=weightcost,
                                               batch_size=batch_size, persistent=persistent_chain)
+        step_hooks = None
+        if tempering is not None:
+            if not persistent:
+                raise ValueError("tempering needs persistent=True: the ladders' beta = 1 replicas are the PCD chains")
+            chains = self.tempered = self.tempered_chains(batch_size, n_betas=int(tempering))
+            chain_buffer = updates.persistent              # (the buffer the step reads and writes: on W's leading dimension)
+
+            def before_step():
+                chains.run(1)
+                chains.to_persistent(chain_buffer)
+            step_hooks = (before_step, lambda: chains.from_persistent(chain_buffer))
         return self.learn_model(train_set_x=train_set_x, validation_set_x=validation_set_x,
                                 training_epochs=training_epochs, batch_size=batch_size,
                                 initial_momentum=initial_momentum, final_momentum=final_momentum,
                                 cost=cost, updates=updates, display_fn=display_fn,
-                                graph_output=graph_output)
+                                graph_output=graph_output, step_hooks=step_hooks)
 
     def learn_model(self, train_set_x, validation_set_x, training_epochs, batch_size,
                     initial_momentum, final_momentum, cost, updates, display_fn, graph_output,
-                    verbose=True, shuffle_rng=None):
+                    verbose=True, shuffle_rng=None, step_hooks=None):
         """Epoch loop of rbm.py:522-629.  ``display_fn`` / ``graph_output`` are accepted and
-        ignored (plotting is outside the engine).  Returns the per-epoch (cost, gap) list."""
+        ignored (plotting is outside the engine).  Returns the per-epoch (cost, gap) list.
+        ``step_hooks``: ``(before, after)`` callables run around every step (``training(tempering=...)``)."""
+        before_step, after_step = step_hooks if step_hooks is not None else (None, None)
         train_set_x = shared(train_set_x, engine=self.engine)
         validation_set_x = shared(validation_set_x, engine=self.engine) if validation_set_x is not None else None
         train_rbm = function(updates, train_set_x, name='train_rbm')
@@ -880,7 +924,11 @@ class RBM(object):
             for b_i in range(len(minibatches)):
                 # the next minibatch of the epoch as a hint (gathered inside this step's statistics kernel)
                 nxt = views[b_i + 1] if b_i + 1 < len(minibatches) else None
+                if before_step is not None:
+                    before_step()
                 costs.append(train_rbm(views[b_i], momentum, next_indexes=nxt))
+                if after_step is not None:
+                    after_step()
             train_rbm.flush()
             mean_cost = float(numpy.sum(numpy.asarray(self.engine.cost_values(costs), dtype=numpy.float64))) / len(minibatches)
             feg = None
