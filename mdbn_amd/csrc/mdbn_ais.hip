@@ -25,49 +25,33 @@
 #include "mdbn_device.h"
 #include "mdbn_small.h"
 #include "mdbn_small_passes.h"
+#include "mdbn_sampler_kit.h"
 #include "mdbn_ais.h"
 
 namespace mdbn {
 
 namespace {
 
-constexpr float AIS_TWO_PI = 6.28318530717958647692f;
-
-// v_{k+1} | h_k for one (4-chain group, column): pre = b_A + beta (b - b_A) + beta m, then the draw.  `s` receives the
-// column's share of s1.  The one statement of this arithmetic: both paths call it.
+// v_{k+1} | h_k for one (4-chain group, column): tempered_draw_v with every chain at the one beta of the temperature
 template <bool GAUSS>
 __device__ __forceinline__ void ais_draw_v(const PhiloxKey& key, uint64_t grow0, int col, float beta, float bA, float db,
                                            const float (&m)[4], const bool (&ok)[4], float (&v)[4], float (&s)[4])
 {
-    uint32_t wa[4], wb[4] = {0u, 0u, 0u, 0u};
-    philox_rows4(key, 0u, grow0, (uint32_t)col, wa);
-    if (GAUSS) philox_rows4(key, MDBN_NORMAL_BIT, grow0, (uint32_t)col, wb);
-    const float bb = fmaf(beta, db, bA);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float pre = fmaf(beta, m[e], bb);
-        if (GAUSS) {
-            const float z = sqrtf(-2.0f * logf(philox_u01(wa[e]))) * cosf(AIS_TWO_PI * philox_u01(wb[e]));
-            v[e] = ok[e] ? pre + z : 0.f;
-            s[e] = ok[e] ? (v[e] - bA) * db : 0.f;
-        } else {
-            v[e] = ok[e] && philox_u01(wa[e]) < sigmoidf_(pre) ? 1.0f : 0.0f;
-            s[e] = v[e] * db;
-        }
-    }
+    const float b4[4] = {beta, beta, beta, beta};
+    float pre[4];
+    tempered_draw_v<GAUSS>(key, grow0, col, b4, bA, db, m, ok, v, pre, s);
 }
 
-// h_k | v_k and the hidden share of the weight update for one (4-chain group, column); a = pre-activation (c included)
+// h_k | v_k (tempered_draw_h at beta_k = b1) and the hidden share of the weight update for one (4-chain group, column);
+// a = pre-activation (c included)
 __device__ __forceinline__ void ais_draw_h(const PhiloxKey& key, uint64_t grow0, int col, float b1, float b0, bool draw,
                                            const float (&a)[4], const bool (&ok)[4], float (&h)[4], float (&d)[4])
 {
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-    if (draw) philox_rows4(key, 0u, grow0, (uint32_t)col, w);
+    const float b4[4] = {b1, b1, b1, b1};
+    float p[4];
+    tempered_draw_h(key, grow0, col, b4, a, ok, draw, h, p);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        d[e] = ok[e] ? softplusf_(b1 * a[e]) - softplusf_(b0 * a[e]) : 0.f;
-        h[e] = draw && ok[e] && philox_u01(w[e]) < sigmoidf_(b1 * a[e]) ? 1.0f : 0.0f;
-    }
+    for (int e = 0; e < 4; ++e) d[e] = ok[e] ? softplus_gap(a[e], b0, b1) : 0.f;
 }
 
 // log w after one temperature (double: the increments are O(1 / K) of a total of hundreds of nats)
@@ -77,13 +61,6 @@ __device__ __forceinline__ double ais_logw_add(double lw, float hsum, float s1, 
     lw += (double)hsum + (B1 - B0) * (double)s1;
     if (gauss) lw -= 0.5 * (B1 * B1 - B0 * B0) * (double)d2;
     return lw;
-}
-
-__device__ __forceinline__ float wave_sum(float x)       // every lane of the wave active; the same tree in every call
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
 }
 
 }  // namespace
@@ -109,24 +86,12 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
     const int64_t ldv = a.ldv, ldh = a.ldh;
     const int nslabs = (M + SM_ROWS - 1) / SM_ROWS;
 
-    // ---- W image [Vp][ldw] (rows >= V and columns >= ldh zero, + the slack behind the last row), biases, zeroed row buffers
-    {
-        const int q4w = L.ldw >> 2, q4 = (int)(ldh >> 2);
-        const int total = L.Vp * q4w + 4;
-        for (int e = tid; e < total; e += SM_NT) {
-            const int r = e / q4w, c4 = e - r * q4w;
-            sf32x4 w = {0.f, 0.f, 0.f, 0.f};
-            if (r < V && c4 < q4) w = *reinterpret_cast<const sf32x4*>(a.W + (int64_t)r * ldh + 4 * c4);
-            *(lds_f4*)(Wl + 4 * e) = w;
-        }
-    }
-    if (tid < L.H64) hbl[tid] = tid < H ? a.hbias[tid] : 0.f;
-    if (tid < L.V64) {
-        const float bA = tid < V ? a.base_vbias[tid] : 0.f, b = tid < V ? a.vbias[tid] : 0.f;
-        bAl[tid] = bA; dbl[tid] = b - bA;
-    }
-    for (int i = tid; i < SM_ROWS * L.ldx; i += SM_NT) X[i] = 0.f;
-    for (int i = tid; i < SM_ROWS * L.ldhs; i += SM_NT) Hs[i] = 0.f;
+    // ---- the LDS image: W, the biases, zeroed row buffers
+    sm_stage_w(Wl, L, a.W, V, ldh, tid);
+    sm_stage_bias(hbl, a.hbias, L.H64, H, tid);
+    sm_stage_bias_pair(bAl, dbl, a.vbias, a.base_vbias, L.V64, V, tid);
+    sm_zero_rows(X, L.ldx, tid);
+    sm_zero_rows(Hs, L.ldhs, tid);
     SM_SYNC();
     float d2 = 0.f;                          // sum_i (b - b_A)_i^2: every thread sums it in the same order
     if (GAUSS) {
@@ -258,53 +223,20 @@ hipError_t launch_ais_small(const AisSmallArgs& a, hipStream_t s)
     const SmallLayout L = small_layout(a.V, a.H, a.gauss != 0);
     const bool trace = a.trace_h || a.trace_v;
     const int variant = (a.gauss ? 2 : 0) | (trace ? 1 : 0);
-    static bool attr_set[4] = {false, false, false, false};
-    const void* kerns[4] = {reinterpret_cast<const void*>(ais_small_kernel<false, false>), reinterpret_cast<const void*>(ais_small_kernel<false, true>),
-                            reinterpret_cast<const void*>(ais_small_kernel<true, false>), reinterpret_cast<const void*>(ais_small_kernel<true, true>)};
-    if (!attr_set[variant]) {
-        hipError_t e = hipFuncSetAttribute(kerns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, SM_MAX_LDS);
-        if (e != hipSuccess) return e;
-        attr_set[variant] = true;
-    }
+    void (*const kerns[4])(AisSmallArgs) = {ais_small_kernel<false, false>, ais_small_kernel<false, true>, ais_small_kernel<true, false>,
+                                            ais_small_kernel<true, true>};
     // one workgroup per slab up to one per CU of the chip (no partials to sum here: the cap only bounds the W stagings)
     const int nslabs = (a.M + SM_ROWS - 1) / SM_ROWS;
     const dim3 grid(nslabs < 256 ? nslabs : 256), block(SM_NT);
     AisSmallArgs k = a;
     k.L = L;
-    switch (variant) {
-        case 0: hipLaunchKernelGGL((ais_small_kernel<false, false>), grid, block, L.bytes, s, k); break;
-        case 1: hipLaunchKernelGGL((ais_small_kernel<false, true>), grid, block, L.bytes, s, k); break;
-        case 2: hipLaunchKernelGGL((ais_small_kernel<true, false>), grid, block, L.bytes, s, k); break;
-        default: hipLaunchKernelGGL((ais_small_kernel<true, true>), grid, block, L.bytes, s, k); break;
-    }
-    return hipGetLastError();
+    return launch_small_variant(kerns, variant, grid, block, L.bytes, s, k);
 }
 
 // ----------------------------------------------------------------------------------
 // General path: a workgroup of AIS_NT threads owns one four-chain group; a thread walks the columns tid, tid + AIS_NT, ...
 // and the four row sums are combined wave by wave in a fixed order.
 // ----------------------------------------------------------------------------------
-namespace {
-
-__device__ __forceinline__ void ais_rows_sum(float (&acc)[4], float* red /* [4][AIS_NT / 64] */)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float t = wave_sum(acc[e]);
-        if (lane == 0) red[e * (AIS_NT / 64) + wave] = t;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float t = 0.f;
-        for (int w = 0; w < AIS_NT / 64; ++w) t += red[e * (AIS_NT / 64) + w];
-        acc[e] = t;
-    }
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(64) void ais_d2_kernel(const float* vbias, const float* base_vbias, int V, float* d2)
 {
     float t = 0.f;
@@ -342,7 +274,7 @@ __global__ __launch_bounds__(AIS_NT) void ais_hidden_kernel(AisStepArgs a)
             }
         }
     }
-    ais_rows_sum(acc, red);
+    rows4_block_sum<AIS_NT>(acc, red);
     if (tid < 4 && row0 + tid < a.M) {
         const float hsum = tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3];
         const double lw = a.k == 1 ? 0.0 : a.logw[row0 + tid];
@@ -380,7 +312,7 @@ __global__ __launch_bounds__(AIS_NT) void ais_visible_kernel(AisStepArgs a)
             }
         }
     }
-    ais_rows_sum(acc, red);
+    rows4_block_sum<AIS_NT>(acc, red);
     if (tid < 4 && row0 + tid < a.M) a.s1[row0 + tid] = tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3];
 }
 

@@ -10,6 +10,7 @@
 #include <condition_variable>
 #include <cstdint>
 #include <deque>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <set>
@@ -2176,6 +2177,53 @@ int mdbn_free_energy(mdbn_ctx* ctx, void* stream, const float* x, int64_t N, int
     return MDBN_OK;
 }
 
+// ---------------------------------------------------------------------------------- what the three sampler drivers share
+namespace {
+
+// Scratch of the propagation GEMMs of a general path (carve: slabs + a fixed cost region).  Any size serves (a pass is chunked
+// until its split-K slabs fit); what the plans of `rows` rows ask for is not monotone in the rows (fewer rows: more split-K), so
+// with cover_fewer_rows the answer is the largest over `rows` and the whole 32-row tilings below it -- a buffer sized for
+// `rows` rows serves any fewer
+int64_t gemm_scratch_bytes(int64_t rows, int64_t V, int64_t H, bool cover_fewer_rows)
+{
+    int64_t g = ws_sizes(rows, V, H).total_bytes();
+    if (cover_fewer_rows) {
+        const int64_t step = std::max<int64_t>(32, ((rows >> 12) + 31) & ~int64_t(31));
+        for (int64_t m = step; m < rows; m += step) g = std::max(g, ws_sizes(m, V, H).total_bytes());
+    }
+    return g + 4 * ((int64_t)(1 << 16) + 4096);
+}
+
+// The path a *_workspace_bytes call sizes for.  One buffer serves a layer whatever its visible type, so path 1 needs the layer
+// to fit for either type, and path 0 sizes for the one-launch path only where a run would take it for both.  -1: path 1 was
+// asked for and the layer fits for neither.
+int sizing_path(int path, bool fits_either, bool taken_both)
+{
+    if (path == 1) return fits_either ? 1 : -1;
+    return path == 0 && taken_both ? 1 : 2;
+}
+
+// The path a run takes: path = 0 chooses by shape
+int run_path(int path, bool one_launch) { return path == 0 ? (one_launch ? 1 : 2) : path; }
+
+// Two groups of argument rules the three run entry points share; an entry point checks its own rules before, between and after
+// them (the API tests assert which error a bad call reports, and that it comes without a device: the order stays).
+int sampler_workspace_rules(int64_t workspace_bytes, int64_t need, const char* sizer, const mdbn_ctx* ctx, const mdbn_rng* rng)
+{
+    REQUIRE(workspace_bytes >= need, "workspace %lld bytes < %lld needed (%s)", (long long)workspace_bytes, (long long)need, sizer);
+    REQUIRE(ctx != nullptr && rng != nullptr, "ctx / rng is NULL");
+    return MDBN_OK;
+}
+
+int sampler_pointer_rules(const void* workspace, std::initializer_list<const void*> optional_outputs)
+{
+    REQUIRE(workspace != nullptr && aligned16(workspace), "workspace must be a 16-byte aligned device pointer");
+    for (const void* q : optional_outputs) REQUIRE(q == nullptr || aligned16(q), "output not 16-byte aligned");
+    return MDBN_OK;
+}
+
+}  // namespace
+
 // ---------------------------------------------------------------------------------- annealed importance sampling
 namespace {
 
@@ -2196,21 +2244,9 @@ AisWs ais_ws(int path, int64_t M, int64_t V, int64_t H, int64_t ldv, int64_t ldh
         w.pre = ru64(M * std::max(ldv, ldh));
         w.h = ru64(M * ldh);
         w.s1 = ru64(M);
-        // scratch of the propagation GEMMs (carve: slabs + a fixed cost region).  Any size serves (a pass is chunked until its
-        // split-K slabs fit); what the plans of M rows ask for is not monotone in M (fewer rows: more split-K), so the answer
-        // is the largest over M and the whole 32-row tilings below it -- a buffer sized for M chains serves any fewer
-        int64_t g = ws_sizes(M, V, H).total_bytes();
-        const int64_t step = std::max<int64_t>(32, ((M >> 12) + 31) & ~int64_t(31));
-        for (int64_t m = step; m < M; m += step) g = std::max(g, ws_sizes(m, V, H).total_bytes());
-        w.gemm_bytes = g + 4 * ((int64_t)(1 << 16) + 4096);
+        w.gemm_bytes = gemm_scratch_bytes(M, V, H, true);
     }
     return w;
-}
-
-int ais_path(int path, int64_t M, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh)
-{
-    if (path == 0) return ais_small_ok(M, V, H, gauss, ldv, ldh) ? 1 : 2;
-    return path;
 }
 
 }  // namespace
@@ -2223,13 +2259,10 @@ int mdbn_ais_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t V, int64_t H, int
     REQUIRE(n_betas >= 2, "n_betas = %lld: a schedule has at least beta_0 = 0 and beta_K = 1", (long long)n_betas);
     REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
     const int64_t ldv = padded_ld(V), ldh = padded_ld(H);
-    // (either visible type: the larger of the two answers, so that one buffer serves a layer whatever its type)
-    const bool fits = ais_small_ok(M, V, H, 0, ldv, ldh) || ais_small_ok(M, V, H, 1, ldv, ldh);
-    REQUIRE(path != 1 || fits, "path 1: %lld -> %lld is not LDS-resident", (long long)V, (long long)H);
-    int64_t need = ais_ws(2, M, V, H, ldv, ldh).total_bytes();
-    if (path == 1 || (path == 0 && ais_small_ok(M, V, H, 0, ldv, ldh) && ais_small_ok(M, V, H, 1, ldv, ldh)))
-        need = ais_ws(1, M, V, H, ldv, ldh).total_bytes();
-    *bytes = need;
+    const bool f0 = ais_small_ok(M, V, H, 0, ldv, ldh), f1 = ais_small_ok(M, V, H, 1, ldv, ldh);
+    const int p = sizing_path(path, f0 || f1, f0 && f1);
+    REQUIRE(p > 0, "path 1: %lld -> %lld is not LDS-resident", (long long)V, (long long)H);
+    *bytes = ais_ws(p, M, V, H, ldv, ldh).total_bytes();
     return MDBN_OK;
 }
 
@@ -2247,16 +2280,12 @@ int mdbn_ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t
     REQUIRE(ldv % 4 == 0 && ldv >= V && ldh % 4 == 0 && ldh >= H, "leading dimensions must be multiples of 4, ldv >= V, ldh >= H");
     REQUIRE(path != 1 || ais_small_ok(M, V, H, gauss, ldv, ldh),
             "path 1: %lld -> %lld (ldv %lld, ldh %lld) is not LDS-resident", (long long)V, (long long)H, (long long)ldv, (long long)ldh);
-    const int p = ais_path(path, M, V, H, gauss, ldv, ldh);
+    const int p = run_path(path, ais_small_ok(M, V, H, gauss, ldv, ldh));
     const AisWs w = ais_ws(p, M, V, H, ldv, ldh);
-    REQUIRE(workspace_bytes >= w.total_bytes(), "workspace %lld bytes < %lld needed (mdbn_ais_workspace_bytes)",
-            (long long)workspace_bytes, (long long)w.total_bytes());
-    REQUIRE(ctx != nullptr && rng != nullptr, "ctx / rng is NULL");
+    CHECK(sampler_workspace_rules(workspace_bytes, w.total_bytes(), "mdbn_ais_workspace_bytes", ctx, rng));
     CHECK(check_mat(W, ldh, H, "W"));
     REQUIRE(hbias && vbias && base_vbias && betas && logw, "NULL pointer");
-    REQUIRE(workspace != nullptr && aligned16(workspace), "workspace must be a 16-byte aligned device pointer");
-    for (const float* q : {(const float*)v_state, (const float*)trace_h, (const float*)trace_v})
-        REQUIRE(q == nullptr || aligned16(q), "output not 16-byte aligned");
+    CHECK(sampler_pointer_rules(workspace, {v_state, trace_h, trace_v}));
     hipStream_t s = (hipStream_t)stream;
     const int K = (int)n_betas - 1;
     float* wsf = reinterpret_cast<float*>(workspace);
@@ -2330,7 +2359,7 @@ ClampWs clamp_ws(int path, int64_t B, int64_t V, int64_t H, int64_t ldv, int64_t
     ClampWs w{};
     w.acc_v = ru64(B * ldv);
     w.acc_h = ru64(B * ldh);
-    if (path == 2) w.gemm_bytes = ws_sizes(B, V, H).total_bytes() + 4 * ((int64_t)(1 << 16) + 4096);
+    if (path == 2) w.gemm_bytes = gemm_scratch_bytes(B, V, H, false);
     return w;
 }
 
@@ -2343,11 +2372,10 @@ int mdbn_gibbs_clamped_workspace_bytes(mdbn_ctx* ctx, int64_t B, int64_t V, int6
     REQUIRE(B >= 1 && V >= 1 && H >= 1, "bad shape B=%lld V=%lld H=%lld", (long long)B, (long long)V, (long long)H);
     REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
     const int64_t ldv = padded_ld(V), ldh = padded_ld(H);
-    // (either visible type: the larger of the two answers, so that one buffer serves a layer whatever its type)
-    const bool any = clamp_small_ok(B, V, H, 0, ldv, ldh) || clamp_small_ok(B, V, H, 1, ldv, ldh);
-    const bool both = clamp_small_ok(B, V, H, 0, ldv, ldh) && clamp_small_ok(B, V, H, 1, ldv, ldh);
-    REQUIRE(path != 1 || any, "path 1: %lld -> %lld is not LDS-resident", (long long)V, (long long)H);
-    *bytes = clamp_ws(path == 1 || (path == 0 && both) ? 1 : 2, B, V, H, ldv, ldh).total_bytes();
+    const bool f0 = clamp_small_ok(B, V, H, 0, ldv, ldh), f1 = clamp_small_ok(B, V, H, 1, ldv, ldh);
+    const int p = sizing_path(path, f0 || f1, f0 && f1);
+    REQUIRE(p > 0, "path 1: %lld -> %lld is not LDS-resident", (long long)V, (long long)H);
+    *bytes = clamp_ws(p, B, V, H, ldv, ldh).total_bytes();
     return MDBN_OK;
 }
 
@@ -2371,11 +2399,9 @@ int mdbn_gibbs_clamped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, 
     const bool fits = clamp_small_ok(B, V, H, gauss, ldv, ldh);
     REQUIRE(path != 1 || fits, "path 1: %lld -> %lld (ldv %lld, ldh %lld) is not LDS-resident", (long long)V, (long long)H,
             (long long)ldv, (long long)ldh);
-    const int p = path == 0 ? (fits ? 1 : 2) : path;
+    const int p = run_path(path, fits);
     const ClampWs w = clamp_ws(p, B, V, H, ldv, ldh);
-    REQUIRE(workspace_bytes >= w.total_bytes(), "workspace %lld bytes < %lld needed (mdbn_gibbs_clamped_workspace_bytes)",
-            (long long)workspace_bytes, (long long)w.total_bytes());
-    REQUIRE(ctx != nullptr && rng != nullptr, "ctx / rng is NULL");
+    CHECK(sampler_workspace_rules(workspace_bytes, w.total_bytes(), "mdbn_gibbs_clamped_workspace_bytes", ctx, rng));
     CHECK(check_mat(v, ldv, V, "v"));
     CHECK(check_mat(obs, ldv, V, "obs"));
     CHECK(check_mat(mask, ldv, V, "mask"));
@@ -2384,9 +2410,7 @@ int mdbn_gibbs_clamped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, 
     CHECK(check_mat(h_sample, ldh, H, "h_sample"));
     CHECK(check_mat(v_mean, ldv, V, "v_mean"));
     REQUIRE(hbias && vbias, "bias pointers are NULL");
-    REQUIRE(workspace != nullptr && aligned16(workspace), "workspace must be a 16-byte aligned device pointer");
-    for (const float* q : {(const float*)v_avg, (const float*)h_avg, (const float*)trace_h, (const float*)trace_v})
-        REQUIRE(q == nullptr || aligned16(q), "output not 16-byte aligned");
+    CHECK(sampler_pointer_rules(workspace, {v_avg, h_avg, trace_h, trace_v}));
     hipStream_t s = (hipStream_t)stream;
     float* acc_v = reinterpret_cast<float*>(workspace);
     float* acc_h = acc_v + w.acc_v;
@@ -2470,20 +2494,9 @@ PtWs pt_ws(int path, int64_t M, int64_t R, int64_t V, int64_t H, int64_t ldv, in
         w.zero = ru64(std::max(ldv, ldh));
         w.pre = ru64(rows * std::max(ldv, ldh));
         w.s1 = ru64(rows);
-        // (as ais_ws: what the plans of `rows` rows ask for is not monotone in the rows; the largest over the tilings below)
-        int64_t g = ws_sizes(rows, V, H).total_bytes();
-        const int64_t step = std::max<int64_t>(32, ((rows >> 12) + 31) & ~int64_t(31));
-        for (int64_t m = step; m < rows; m += step) g = std::max(g, ws_sizes(m, V, H).total_bytes());
-        w.gemm_bytes = g + 4 * ((int64_t)(1 << 16) + 4096);
+        w.gemm_bytes = gemm_scratch_bytes(rows, V, H, true);
     }
     return w;
-}
-
-// path = 0: the one-launch kernel only where it was measured to win (pt_small_preferred)
-int pt_path(int path, int64_t M, int64_t R, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh)
-{
-    if (path == 0) return pt_small_preferred(M, R, V, H, gauss, ldv, ldh) ? 1 : 2;
-    return path;
 }
 
 }  // namespace
@@ -2497,12 +2510,11 @@ int mdbn_pt_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t R, int64_t V, int6
     REQUIRE(M * R < (1ll << 31), "M * R too large");
     REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
     const int64_t ldv = padded_ld(V), ldh = padded_ld(H);
-    // (either visible type: the larger of the two answers, so that one buffer serves a layer whatever its type)
-    const bool any = pt_small_ok(M, R, V, H, 0, ldv, ldh) || pt_small_ok(M, R, V, H, 1, ldv, ldh);
-    const bool both = pt_small_preferred(M, R, V, H, 0, ldv, ldh) && pt_small_preferred(M, R, V, H, 1, ldv, ldh);
-    REQUIRE(path != 1 || any, "path 1: %lld -> %lld with R = %lld is not LDS-resident (or R is no multiple of 4)", (long long)V,
-            (long long)H, (long long)R);
-    *bytes = pt_ws(path == 1 || (path == 0 && both) ? 1 : 2, M, R, V, H, ldv, ldh).total_bytes();
+    const int p = sizing_path(path, pt_small_ok(M, R, V, H, 0, ldv, ldh) || pt_small_ok(M, R, V, H, 1, ldv, ldh),
+                              pt_small_preferred(M, R, V, H, 0, ldv, ldh) && pt_small_preferred(M, R, V, H, 1, ldv, ldh));
+    REQUIRE(p > 0, "path 1: %lld -> %lld with R = %lld is not LDS-resident (or R is no multiple of 4)", (long long)V, (long long)H,
+            (long long)R);
+    *bytes = pt_ws(p, M, R, V, H, ldv, ldh).total_bytes();
     return MDBN_OK;
 }
 
@@ -2533,18 +2545,15 @@ int mdbn_pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t 
     const bool fits = pt_small_ok(M, R, V, H, gauss, ldv, ldh);
     REQUIRE(path != 1 || fits, "path 1: %lld -> %lld (ldv %lld, ldh %lld) with R = %lld is not LDS-resident (or R is no multiple of 4)",
             (long long)V, (long long)H, (long long)ldv, (long long)ldh, (long long)R);
-    const int p = pt_path(path, M, R, V, H, gauss, ldv, ldh);
+    // (path = 0: the one-launch kernel only where it was measured to win: pt_small_preferred)
+    const int p = run_path(path, pt_small_preferred(M, R, V, H, gauss, ldv, ldh));
     const PtWs w = pt_ws(p, M, R, V, H, ldv, ldh);
-    REQUIRE(workspace_bytes >= w.total_bytes(), "workspace %lld bytes < %lld needed (mdbn_pt_workspace_bytes)",
-            (long long)workspace_bytes, (long long)w.total_bytes());
-    REQUIRE(ctx != nullptr && rng != nullptr, "ctx / rng is NULL");
+    CHECK(sampler_workspace_rules(workspace_bytes, w.total_bytes(), "mdbn_pt_workspace_bytes", ctx, rng));
     CHECK(check_mat(W, ldh, H, "W"));
     CHECK(check_mat(v, ldv, V, "v"));
     CHECK(check_mat(h, ldh, H, "h"));
     REQUIRE(hbias && vbias && base_vbias && rank && accepted, "NULL pointer");
-    REQUIRE(workspace != nullptr && aligned16(workspace), "workspace must be a 16-byte aligned device pointer");
-    for (const float* q : {(const float*)v_avg, (const float*)h_avg, (const float*)trace_h, (const float*)trace_v})
-        REQUIRE(q == nullptr || aligned16(q), "output not 16-byte aligned");
+    CHECK(sampler_pointer_rules(workspace, {v_avg, h_avg, trace_h, trace_v}));
     hipStream_t s = (hipStream_t)stream;
     float* wsf = reinterpret_cast<float*>(workspace);
     float* d_betas = wsf;

@@ -25,6 +25,7 @@
 #include "mdbn_device.h"
 #include "mdbn_small.h"
 #include "mdbn_small_passes.h"
+#include "mdbn_sampler_kit.h"
 #include "mdbn_clamp.h"
 
 namespace mdbn {
@@ -48,21 +49,12 @@ __global__ __launch_bounds__(SM_NT) void clamp_small_kernel(ClampSmallArgs a)
     const bool feed_sample = !GAUSS || a.gauss == 2;        // what goes down: the hidden sample, or (the reference's GRBM chain) the mean
     const bool noisy = GAUSS && (a.add_noise || a.gauss == 2);
 
-    // ---- W image [Vp][ldw] (rows >= V and columns >= ldh zero, + the slack behind the last row), biases, zeroed row buffers
-    {
-        const int q4w = L.ldw >> 2, q4 = (int)(ldh >> 2);
-        const int total = L.Vp * q4w + 4;
-        for (int e = tid; e < total; e += SM_NT) {
-            const int r = e / q4w, c4 = e - r * q4w;
-            sf32x4 w = {0.f, 0.f, 0.f, 0.f};
-            if (r < V && c4 < q4) w = *reinterpret_cast<const sf32x4*>(a.W + (int64_t)r * ldh + 4 * c4);
-            *(lds_f4*)(Wl + 4 * e) = w;
-        }
-    }
-    if (tid < L.H64) hbl[tid] = tid < H ? a.hbias[tid] : 0.f;
-    if (tid < L.V64) vbl[tid] = tid < V ? a.vbias[tid] : 0.f;
-    for (int i = tid; i < SM_ROWS * L.ldx; i += SM_NT) X[i] = 0.f;
-    for (int i = tid; i < SM_ROWS * L.ldhs; i += SM_NT) Hs[i] = 0.f;
+    // ---- the LDS image: W, the biases, zeroed row buffers
+    sm_stage_w(Wl, L, a.W, V, ldh, tid);
+    sm_stage_bias(hbl, a.hbias, L.H64, H, tid);
+    sm_stage_bias(vbl, a.vbias, L.V64, V, tid);
+    sm_zero_rows(X, L.ldx, tid);
+    sm_zero_rows(Hs, L.ldhs, tid);
     SM_SYNC();
 
     const bool vthread = tid < L.V64, hthread = tid < L.H64;      // this thread owns visible / hidden column `tid`
@@ -139,7 +131,7 @@ __global__ __launch_bounds__(SM_NT) void clamp_small_kernel(ClampSmallArgs a)
                             if (GAUSS) {
                                 m = pre;
                                 s = m;
-                                if (noisy) s = m + sqrtf(-2.0f * logf(philox_u01(wa[e]))) * cosf(6.28318530717958647692f * philox_u01(wb[e]));
+                                if (noisy) s = m + box_muller(philox_u01(wa[e]), philox_u01(wb[e]));
                             } else {
                                 m = sigmoidf_(pre);
                                 s = philox_u01(wa[e]) < m ? 1.0f : 0.0f;
@@ -198,14 +190,8 @@ hipError_t launch_clamp_small(const ClampSmallArgs& a, hipStream_t s)
     const SmallLayout L = small_layout(a.V, a.H, a.gauss != 0);
     const bool trace = a.trace_h || a.trace_v;
     const int variant = (a.gauss ? 2 : 0) | (trace ? 1 : 0);
-    static bool attr_set[4] = {false, false, false, false};
-    const void* kerns[4] = {reinterpret_cast<const void*>(clamp_small_kernel<false, false>), reinterpret_cast<const void*>(clamp_small_kernel<false, true>),
-                            reinterpret_cast<const void*>(clamp_small_kernel<true, false>), reinterpret_cast<const void*>(clamp_small_kernel<true, true>)};
-    if (!attr_set[variant]) {
-        hipError_t e = hipFuncSetAttribute(kerns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, SM_MAX_LDS);
-        if (e != hipSuccess) return e;
-        attr_set[variant] = true;
-    }
+    void (*const kerns[4])(ClampSmallArgs) = {clamp_small_kernel<false, false>, clamp_small_kernel<false, true>, clamp_small_kernel<true, false>,
+                                              clamp_small_kernel<true, true>};
     // one workgroup per slab (small layers leave room for several on a CU); beyond 1024 slabs a workgroup loops.
     // The LDS request is small_layout's whole (the CD step's) so that the passes are shared unchanged: of it this kernel uses W,
     // Xa, Hs, the chunk partials and the two bias rows; X0, Xb, M0, Mn, the three column-sum rows and U lie unused.
@@ -213,13 +199,7 @@ hipError_t launch_clamp_small(const ClampSmallArgs& a, hipStream_t s)
     const dim3 grid(nslabs < 1024 ? nslabs : 1024), block(SM_NT);
     ClampSmallArgs k = a;
     k.L = L;
-    switch (variant) {
-        case 0: hipLaunchKernelGGL((clamp_small_kernel<false, false>), grid, block, L.bytes, s, k); break;
-        case 1: hipLaunchKernelGGL((clamp_small_kernel<false, true>), grid, block, L.bytes, s, k); break;
-        case 2: hipLaunchKernelGGL((clamp_small_kernel<true, false>), grid, block, L.bytes, s, k); break;
-        default: hipLaunchKernelGGL((clamp_small_kernel<true, true>), grid, block, L.bytes, s, k); break;
-    }
-    return hipGetLastError();
+    return launch_small_variant(kerns, variant, grid, block, L.bytes, s, k);
 }
 
 // ----------------------------------------------------------------------------------

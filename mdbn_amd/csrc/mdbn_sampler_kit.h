@@ -1,0 +1,128 @@
+// What the samplers of a trained layer share around the passes of mdbn_small_passes.h (mdbn_ais.hip: annealed importance
+// sampling; mdbn_clamp.hip: clamped Gibbs sampling; mdbn_temper.hip: parallel tempering): the staging of a one-launch
+// kernel's LDS image, the draws of the tempered family b_beta = b_A + beta (b - b_A) and the fixed-order sums.  Each is stated
+// once because the samplers must agree bit for bit -- with each other, between their two paths and across the cuts of a run.
+// Included by those three sources only, after mdbn_small_passes.h.
+#pragma once
+#include "mdbn_device.h"
+#include "mdbn_small_passes.h"
+
+namespace mdbn {
+
+namespace {
+
+// ---- staging of a one-launch kernel (every thread of the SM_NT calls; the caller's barrier follows)
+// W image [Vp][ldw]: rows >= V and columns >= ldh zero, + the slack behind the last row
+__device__ __forceinline__ void sm_stage_w(lds_f* Wl, const SmallLayout& L, const float* W, int V, int64_t ldh, int tid)
+{
+    const int q4w = L.ldw >> 2, q4 = (int)(ldh >> 2);
+    const int total = L.Vp * q4w + 4;
+    for (int e = tid; e < total; e += SM_NT) {
+        const int r = e / q4w, c4 = e - r * q4w;
+        sf32x4 w = {0.f, 0.f, 0.f, 0.f};
+        if (r < V && c4 < q4) w = *reinterpret_cast<const sf32x4*>(W + (int64_t)r * ldh + 4 * c4);
+        *(lds_f4*)(Wl + 4 * e) = w;
+    }
+}
+
+// a bias row of n values on its n64 columns (the pad columns zero)
+__device__ __forceinline__ void sm_stage_bias(lds_f* dst, const float* bias, int n64, int n, int tid)
+{
+    if (tid < n64) dst[tid] = tid < n ? bias[tid] : 0.f;
+}
+
+// the visible bias of the tempered family as the pair b_A, b - b_A
+__device__ __forceinline__ void sm_stage_bias_pair(lds_f* bAl, lds_f* dbl, const float* vbias, const float* base_vbias, int V64, int V, int tid)
+{
+    if (tid < V64) {
+        const float bA = tid < V ? base_vbias[tid] : 0.f, b = tid < V ? vbias[tid] : 0.f;
+        bAl[tid] = bA; dbl[tid] = b - bA;
+    }
+}
+
+// a 4-row operand buffer of the passes, pad columns included
+__device__ __forceinline__ void sm_zero_rows(lds_f* buf, int pitch, int tid)
+{
+    for (int i = tid; i < SM_ROWS * pitch; i += SM_NT) buf[i] = 0.f;
+}
+
+// ---- sums in a fixed order
+__device__ __forceinline__ float wave_sum(float x)       // every lane of the wave active; the same tree in every call
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+// the four row sums of a workgroup of NT threads: wave by wave through red[4][NT / 64], the waves in ascending order;
+// every thread leaves with all four (pt_visible_kernel, where four threads need one sum each, keeps a tail of its own)
+template <int NT>
+__device__ __forceinline__ void rows4_block_sum(float (&acc)[4], float* red)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float t = wave_sum(acc[e]);
+        if (lane == 0) red[e * (NT / 64) + wave] = t;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float t = 0.f;
+        for (int w = 0; w < NT / 64; ++w) t += red[e * (NT / 64) + w];
+        acc[e] = t;
+    }
+}
+
+// ---- draws
+__device__ __forceinline__ float box_muller(float u1, float u2)     // N(0, 1) from two philox_u01 uniforms (never 0)
+{
+    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+}
+
+// v | h for one (4-row group, column), every row at its own beta: pre = b_A + beta (b - b_A) + beta m, then the draw.
+// `s` receives the column's share of s1.
+template <bool GAUSS>
+__device__ __forceinline__ void tempered_draw_v(const PhiloxKey& key, uint64_t grow0, int col, const float (&beta)[4], float bA, float db,
+                                                const float (&m)[4], const bool (&ok)[4], float (&v)[4], float (&pre)[4], float (&s)[4])
+{
+    uint32_t wa[4], wb[4] = {0u, 0u, 0u, 0u};
+    philox_rows4(key, 0u, grow0, (uint32_t)col, wa);
+    if (GAUSS) philox_rows4(key, MDBN_NORMAL_BIT, grow0, (uint32_t)col, wb);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        pre[e] = fmaf(beta[e], m[e], fmaf(beta[e], db, bA));
+        if (GAUSS) {
+            const float z = box_muller(philox_u01(wa[e]), philox_u01(wb[e]));
+            v[e] = ok[e] ? pre[e] + z : 0.f;
+            s[e] = ok[e] ? (v[e] - bA) * db : 0.f;
+        } else {
+            v[e] = ok[e] && philox_u01(wa[e]) < sigmoidf_(pre[e]) ? 1.0f : 0.0f;
+            s[e] = v[e] * db;
+        }
+    }
+}
+
+// h | v for one (4-row group, column): p = sigmoid(beta a), a = pre-activation (c included); without `draw` h = 0 and no
+// uniforms are generated
+__device__ __forceinline__ void tempered_draw_h(const PhiloxKey& key, uint64_t grow0, int col, const float (&beta)[4], const float (&a)[4],
+                                                const bool (&ok)[4], bool draw, float (&h)[4], float (&p)[4])
+{
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (draw) philox_rows4(key, 0u, grow0, (uint32_t)col, w);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        p[e] = sigmoidf_(beta[e] * a[e]);
+        h[e] = draw && ok[e] && philox_u01(w[e]) < p[e] ? 1.0f : 0.0f;
+    }
+}
+
+// one hidden unit's share of l(beta_partner) - l(beta_own)
+__device__ __forceinline__ float softplus_gap(float a, float b_own, float b_partner)
+{
+    return softplusf_(b_partner * a) - softplusf_(b_own * a);
+}
+
+}  // namespace
+
+}  // namespace mdbn

@@ -99,6 +99,22 @@ struct SmallFinArgs {
     FinArgs fin;
 };
 
+// The launch of a one-launch kernel (the CD step's and the samplers'): `kerns` = its <GAUSS, TRACE> instantiations in the order
+// variant = 2 GAUSS + TRACE.  A variant's first launch raises its dynamic-LDS limit; plain statics, one set per argument struct.
+template <class Args>
+hipError_t launch_small_variant(void (*const (&kerns)[4])(Args), int variant, dim3 grid, dim3 block, int lds_bytes, hipStream_t s,
+                                const Args& k)
+{
+    static bool attr_set[4] = {false, false, false, false};
+    if (!attr_set[variant]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kerns[variant]), hipFuncAttributeMaxDynamicSharedMemorySize, SM_MAX_LDS);
+        if (e != hipSuccess) return e;
+        attr_set[variant] = true;
+    }
+    hipLaunchKernelGGL(kerns[variant], grid, block, lds_bytes, s, k);
+    return hipGetLastError();
+}
+
 extern int g_small_fin_lanes;
 int small_blocks(int64_t B);
 bool small_shape_ok(int64_t B, int64_t V, int64_t H, int gauss);

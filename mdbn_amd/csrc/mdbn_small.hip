@@ -409,24 +409,12 @@ hipError_t launch_small_cd(const SmallCdArgs& a, hipStream_t s)
     if (!small_shape_ok(a.B, a.V, a.H, a.gauss) || !small_ld_ok(a.V, a.H, a.ldv, a.ldh)) return hipErrorInvalidValue;
     const bool taps = a.keep || a.trace_h || a.trace_v;
     const int variant = (a.gauss ? 2 : 0) | (taps ? 1 : 0);
-    static bool attr_set[4] = {false, false, false, false};
-    const void* kerns[4] = {reinterpret_cast<const void*>(small_cd_kernel<false, false>), reinterpret_cast<const void*>(small_cd_kernel<false, true>),
-                            reinterpret_cast<const void*>(small_cd_kernel<true, false>), reinterpret_cast<const void*>(small_cd_kernel<true, true>)};
-    if (!attr_set[variant]) {
-        hipError_t e = hipFuncSetAttribute(kerns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, SM_MAX_LDS);
-        if (e != hipSuccess) return e;
-        attr_set[variant] = true;
-    }
+    void (*const kerns[4])(SmallCdArgs) = {small_cd_kernel<false, false>, small_cd_kernel<false, true>, small_cd_kernel<true, false>,
+                                           small_cd_kernel<true, true>};
     const dim3 grid(small_blocks(a.B)), block(SM_NT + 64 * SM_RNG_WAVE);
     SmallCdArgs k = a;
     k.L = L;
-    switch (variant) {
-        case 0: hipLaunchKernelGGL((small_cd_kernel<false, false>), grid, block, L.bytes, s, k); break;
-        case 1: hipLaunchKernelGGL((small_cd_kernel<false, true>), grid, block, L.bytes, s, k); break;
-        case 2: hipLaunchKernelGGL((small_cd_kernel<true, false>), grid, block, L.bytes, s, k); break;
-        default: hipLaunchKernelGGL((small_cd_kernel<true, true>), grid, block, L.bytes, s, k); break;
-    }
-    return hipGetLastError();
+    return launch_small_variant(kerns, variant, grid, block, L.bytes, s, k);
 }
 
 // ----------------------------------------------------------------------------------

@@ -15,8 +15,8 @@
 // The acceptance difference is formed with the regrouping of mdbn_ais.hip: per row the float32 sums
 //   hsum = sum_j softplus(beta_partner a_j) - softplus(beta_own a_j),   s1 = sum_i (v_i - [Gaussian] b_A,i) (b - b_A)_i
 // and  delta = hsum_lo + hsum_hi + (beta_hi - beta_lo) (s1_lo - s1_hi)  in double (the Gaussian |b - b_A|^2 terms of the two
-// rows cancel).  Both paths call pt_draw_v, pt_draw_h, pt_ell and pt_swap_accept below: the uniforms, their addressing and the
-// decision are stated once.
+// rows cancel).  Both paths call tempered_draw_v, tempered_draw_h and softplus_gap of mdbn_sampler_kit.h and pt_swap_accept
+// below: the uniforms, their addressing and the decision are stated once.
 //
 // pt_small_kernel (LDS-resident layers, R a multiple of 4): W staged once into the workgroup's LDS; a workgroup owns whole
 // ladders, the R rows of h and a stay in LDS, a sweep runs R / 4 four-row slabs through sm_down / sm_up of
@@ -28,56 +28,14 @@
 #include "mdbn_device.h"
 #include "mdbn_small.h"
 #include "mdbn_small_passes.h"
+#include "mdbn_sampler_kit.h"
 #include "mdbn_temper.h"
 
 namespace mdbn {
 
 namespace {
 
-constexpr float PT_TWO_PI = 6.28318530717958647692f;
 typedef __attribute__((address_space(3))) int lds_i;
-
-// v | h for one (4-row group, column), every row at its own beta: pre = b_A + beta (b - b_A) + beta m, then the draw.
-// `s` receives the column's share of s1.
-template <bool GAUSS>
-__device__ __forceinline__ void pt_draw_v(const PhiloxKey& key, uint64_t grow0, int col, const float (&beta)[4], float bA, float db,
-                                          const float (&m)[4], const bool (&ok)[4], float (&v)[4], float (&pre)[4], float (&s)[4])
-{
-    uint32_t wa[4], wb[4] = {0u, 0u, 0u, 0u};
-    philox_rows4(key, 0u, grow0, (uint32_t)col, wa);
-    if (GAUSS) philox_rows4(key, MDBN_NORMAL_BIT, grow0, (uint32_t)col, wb);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        pre[e] = fmaf(beta[e], m[e], fmaf(beta[e], db, bA));
-        if (GAUSS) {
-            const float z = sqrtf(-2.0f * logf(philox_u01(wa[e]))) * cosf(PT_TWO_PI * philox_u01(wb[e]));
-            v[e] = ok[e] ? pre[e] + z : 0.f;
-            s[e] = ok[e] ? (v[e] - bA) * db : 0.f;
-        } else {
-            v[e] = ok[e] && philox_u01(wa[e]) < sigmoidf_(pre[e]) ? 1.0f : 0.0f;
-            s[e] = v[e] * db;
-        }
-    }
-}
-
-// h | v for one (4-row group, column): p = sigmoid(beta a), a = pre-activation (c included)
-__device__ __forceinline__ void pt_draw_h(const PhiloxKey& key, uint64_t grow0, int col, const float (&beta)[4], const float (&a)[4],
-                                          const bool (&ok)[4], float (&h)[4], float (&p)[4])
-{
-    uint32_t w[4];
-    philox_rows4(key, 0u, grow0, (uint32_t)col, w);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        p[e] = sigmoidf_(beta[e] * a[e]);
-        h[e] = ok[e] && philox_u01(w[e]) < p[e] ? 1.0f : 0.0f;
-    }
-}
-
-// one hidden unit's share of l(beta_partner) - l(beta_own)
-__device__ __forceinline__ float pt_ell(float a, float b_own, float b_partner)
-{
-    return softplusf_(b_partner * a) - softplusf_(b_own * a);
-}
 
 // the rank a row of rank `rho` is paired with in a sweep of parity `par` (pairs (r, r + 1), r = par mod 2), or -1
 __device__ __forceinline__ int pt_partner(int rho, int par, int R)
@@ -96,13 +54,6 @@ __device__ __forceinline__ bool pt_swap_accept(const PhiloxKey& key, uint64_t la
     const uint32_t word = ph == 0 ? w[0] : ph == 1 ? w[1] : ph == 2 ? w[2] : w[3];
     const double delta = (double)hsum_lo + (double)hsum_hi + ((double)b_hi - (double)b_lo) * ((double)s1_lo - (double)s1_hi);
     return (double)logf(philox_u01(word)) < delta;
-}
-
-__device__ __forceinline__ float pt_wave_sum(float x)     // every lane of the wave active; the same tree in every call
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
 }
 
 }  // namespace
@@ -132,24 +83,12 @@ __global__ __launch_bounds__(SM_NT) void pt_small_kernel(PtSmallArgs a)
     const int64_t ldv = a.ldv, ldh = a.ldh;
     const int nq = R / SM_ROWS;
 
-    // ---- W image [Vp][ldw] (rows >= V and columns >= ldh zero, + the slack behind the last row), biases, betas, zeroed X
-    {
-        const int q4w = L.ldw >> 2, q4 = (int)(ldh >> 2);
-        const int total = L.Vp * q4w + 4;
-        for (int e = tid; e < total; e += SM_NT) {
-            const int r = e / q4w, c4 = e - r * q4w;
-            sf32x4 w = {0.f, 0.f, 0.f, 0.f};
-            if (r < V && c4 < q4) w = *reinterpret_cast<const sf32x4*>(a.W + (int64_t)r * ldh + 4 * c4);
-            *(lds_f4*)(Wl + 4 * e) = w;
-        }
-    }
-    if (tid < L.H64) hbl[tid] = tid < H ? a.hbias[tid] : 0.f;
-    if (tid < L.V64) {
-        const float bA = tid < V ? a.base_vbias[tid] : 0.f, b = tid < V ? a.vbias[tid] : 0.f;
-        bAl[tid] = bA; dbl[tid] = b - bA;
-    }
+    // ---- the LDS image: W, the biases, the betas, zeroed X
+    sm_stage_w(Wl, L, a.W, V, ldh, tid);
+    sm_stage_bias(hbl, a.hbias, L.H64, H, tid);
+    sm_stage_bias_pair(bAl, dbl, a.vbias, a.base_vbias, L.V64, V, tid);
     if (tid < R) betl[tid] = a.betas[tid];
-    for (int i = tid; i < SM_ROWS * L.ldx; i += SM_NT) X[i] = 0.f;
+    sm_zero_rows(X, L.ldx, tid);
 
     // Both passes hand column `tid` to thread `tid` (propup: one column per thread; propdown: wave w owns tile w, tiles_dn <= 8),
     // so a thread keeps its column's two running sums in registers for the whole launch.
@@ -201,12 +140,12 @@ __global__ __launch_bounds__(SM_NT) void pt_small_kernel(PtSmallArgs a)
                             const float bA = bAl[col], db = dbl[col];
                             const float mm[4] = {x[0], x[1], x[2], x[3]};
                             float v[4], pre[4], s[4];
-                            pt_draw_v<GAUSS>(kv, grow0, col, bo, bA, db, mm, okv, v, pre, s);
+                            tempered_draw_v<GAUSS>(kv, grow0, col, bo, bA, db, mm, okv, v, pre, s);
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
                                 X[e * L.ldx + col] = v[e];
                                 if (acc && top[e] && vlive) vacc += GAUSS ? pre[e] : sigmoidf_(pre[e]);
-                                const float ts = pt_wave_sum(s[e]);
+                                const float ts = wave_sum(s[e]);
                                 if (lane == 0) redV[(SM_ROWS * q + e) * 8 + (col >> 6)] = ts;
                             }
                             if (col < (int)ldv) {
@@ -227,7 +166,7 @@ __global__ __launch_bounds__(SM_NT) void pt_small_kernel(PtSmallArgs a)
                           for (int e = 0; e < 4; ++e) {
                               const float pre = hlive ? x[e] + bias : 0.f;
                               Al[(SM_ROWS * q + e) * L.ldhs + col] = pre;
-                              const float td = pt_wave_sum(hlive ? pt_ell(pre, bo[e], bp[e]) : 0.f);
+                              const float td = wave_sum(hlive ? softplus_gap(pre, bo[e], bp[e]) : 0.f);
                               if (lane == 0) redH[(SM_ROWS * q + e) * 8 + (col >> 6)] = td;
                           }
                       });
@@ -270,7 +209,7 @@ __global__ __launch_bounds__(SM_NT) void pt_small_kernel(PtSmallArgs a)
                         top[e] = rho == R - 1;
                         pre[e] = Al[(SM_ROWS * q + e) * L.ldhs + col];
                     }
-                    pt_draw_h(kh, grow0, col, bn, pre, okh, h, p);
+                    tempered_draw_h(kh, grow0, col, bn, pre, okh, true, h, p);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         Hs[(SM_ROWS * q + e) * L.ldhs + col] = h[e];
@@ -337,25 +276,13 @@ hipError_t launch_pt_small(const PtSmallArgs& a, hipStream_t s)
     const PtLayout P = pt_layout(L, a.R);
     const bool trace = a.trace_h || a.trace_v || a.trace_swaps;
     const int variant = (a.gauss ? 2 : 0) | (trace ? 1 : 0);
-    static bool attr_set[4] = {false, false, false, false};
-    const void* kerns[4] = {reinterpret_cast<const void*>(pt_small_kernel<false, false>), reinterpret_cast<const void*>(pt_small_kernel<false, true>),
-                            reinterpret_cast<const void*>(pt_small_kernel<true, false>), reinterpret_cast<const void*>(pt_small_kernel<true, true>)};
-    if (!attr_set[variant]) {
-        hipError_t e = hipFuncSetAttribute(kerns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, SM_MAX_LDS);
-        if (e != hipSuccess) return e;
-        attr_set[variant] = true;
-    }
+    void (*const kerns[4])(PtSmallArgs) = {pt_small_kernel<false, false>, pt_small_kernel<false, true>, pt_small_kernel<true, false>,
+                                           pt_small_kernel<true, true>};
     // one workgroup per ladder; beyond 1024 ladders a workgroup loops (a ladder never leaves its workgroup)
     const dim3 grid(a.M < 1024 ? a.M : 1024), block(SM_NT);
     PtSmallArgs k = a;
     k.L = L; k.P = P;
-    switch (variant) {
-        case 0: hipLaunchKernelGGL((pt_small_kernel<false, false>), grid, block, P.bytes, s, k); break;
-        case 1: hipLaunchKernelGGL((pt_small_kernel<false, true>), grid, block, P.bytes, s, k); break;
-        case 2: hipLaunchKernelGGL((pt_small_kernel<true, false>), grid, block, P.bytes, s, k); break;
-        default: hipLaunchKernelGGL((pt_small_kernel<true, true>), grid, block, P.bytes, s, k); break;
-    }
-    return hipGetLastError();
+    return launch_small_variant(kerns, variant, grid, block, P.bytes, s, k);
 }
 
 // ----------------------------------------------------------------------------------
@@ -391,7 +318,7 @@ __global__ __launch_bounds__(PT_NT) void pt_visible_kernel(PtStepArgs a)
             ok[e] = live && okr[e];
             m[e] = ok[e] ? a.pre[(int64_t)(row0 + e) * a.ldv + col] : 0.f;
         }
-        pt_draw_v<GAUSS>(key, grow0, col, beta, bA, db, m, ok, v, pre, s);
+        tempered_draw_v<GAUSS>(key, grow0, col, beta, bA, db, m, ok, v, pre, s);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             acc[e] += s[e];
@@ -408,7 +335,7 @@ __global__ __launch_bounds__(PT_NT) void pt_visible_kernel(PtStepArgs a)
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const float t = pt_wave_sum(acc[e]);
+        const float t = wave_sum(acc[e]);
         if (lane == 0) red[e * (PT_NT / 64) + wave] = t;
     }
     __syncthreads();
@@ -442,8 +369,8 @@ __global__ __launch_bounds__(PT_NT) void pt_swap_hidden_kernel(PtStepArgs a)
         const int rho = rk[s], pr = pt_partner(rho, par, R);
         const float bo = bet[rho], bp = pr >= 0 ? bet[pr] : bo;
         float t = 0.f;
-        for (int col = lane; col < a.H; col += 64) t += pt_ell(a.pre[(int64_t)(row0 + s) * a.ldh + col], bo, bp);
-        t = pt_wave_sum(t);
+        for (int col = lane; col < a.H; col += 64) t += softplus_gap(a.pre[(int64_t)(row0 + s) * a.ldh + col], bo, bp);
+        t = wave_sum(t);
         if (lane == 0) hs[s] = t;
     }
     __syncthreads();
@@ -485,7 +412,7 @@ __global__ __launch_bounds__(PT_NT) void pt_swap_hidden_kernel(PtStepArgs a)
             top[e] = in && rho == R - 1;
             pre[e] = ok[e] ? a.pre[(int64_t)(row0 + s) * ldh + col] : 0.f;
         }
-        pt_draw_h(kh, a.rng.row_offset + (uint64_t)(row0 + 4 * g), col, bn, pre, ok, h, p);
+        tempered_draw_h(kh, a.rng.row_offset + (uint64_t)(row0 + 4 * g), col, bn, pre, ok, true, h, p);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int s = 4 * g + e;

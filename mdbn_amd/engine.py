@@ -442,6 +442,21 @@ class HipEngine(object):
             "mdbn_gibbs_chain")
         return [pre_h, h_mean, h_sample, pre_v, v_mean, state]
 
+    def _sampler_workspace(self, query, name, dims, H, ldh, path, extra=(), cache_attr=None):
+        """The workspace of a sampler call: ``query(ctx, *dims, H, *extra, path, &bytes)`` is the library's sizer ``name``.
+        ``cache_attr``: the attribute a buffer is kept under between calls, grown to the largest requirement seen (None: a
+        fresh buffer per call)."""
+        n, need = C.c_int64(), 0
+        for Hq in sorted({H, ldh}):        # (a weight matrix on a padded leading dimension: every buffer is as large as that width's)
+            _lib.check(query(self.ctx, *dims, Hq, *extra, int(path) if Hq == H else 2, C.byref(n)), name)
+            need = max(need, n.value)
+        ws = getattr(self, cache_attr, None) if cache_attr else None
+        if ws is None or ws.numel() * 4 < need:
+            ws = torch.empty(need // 4 + 64, dtype=torch.float32, device=self.device)
+            if cache_attr:
+                setattr(self, cache_attr, ws)
+        return ws
+
     def gibbs_clamped(self, v, obs, mask, W, hbias, vbias, gauss, n_steps, rng, burn_in=0, add_noise=False, path=0,
                       steps_per_launch=0, trace=False, sampler=False):
         """``n_steps`` of gibbs_vhv with the visibles where ``mask`` is 1 held at ``obs`` in ONE library call
@@ -480,14 +495,8 @@ class HipEngine(object):
         v_mean, v_avg = self.alloc_matrix(B, V, ldv), self.alloc_matrix(B, V, ldv)
         trace_h = torch.zeros((n_steps, B, ldh), dtype=torch.float32, device=self.device) if trace else None
         trace_v = torch.zeros((n_steps, B, ldv), dtype=torch.float32, device=self.device) if trace else None
-        n, need = C.c_int64(), 0
-        for Hq in sorted({H, ldh}):        # (a weight matrix on a padded leading dimension: every buffer is as large as that width's)
-            _lib.check(self.lib.mdbn_gibbs_clamped_workspace_bytes(self.ctx, B, V, Hq, int(path) if Hq == H else 2, C.byref(n)),
-                       "mdbn_gibbs_clamped_workspace_bytes")
-            need = max(need, n.value)
-        ws = getattr(self, "_clamp_ws", None)          # kept between calls, grown to the largest requirement seen
-        if ws is None or ws.numel() * 4 < need:
-            ws = self._clamp_ws = torch.empty(need // 4 + 64, dtype=torch.float32, device=self.device)
+        ws = self._sampler_workspace(self.lib.mdbn_gibbs_clamped_workspace_bytes, "mdbn_gibbs_clamped_workspace_bytes", (B, V), H, ldh,
+                                     path, cache_attr="_clamp_ws")
         r = rng.c()
         _lib.check(self.lib.mdbn_gibbs_clamped(
             self.ctx, self._stream(), self._p(state), self._p(obs), self._p(mask), mask_rows, B, ldv, self._p(W), V, H, ldh,
@@ -529,12 +538,7 @@ class HipEngine(object):
         d_betas = torch.from_numpy(betas).to(self.device)
         base = self.to_device(numpy.asarray(base_vbias, dtype=numpy.float32)) if not isinstance(base_vbias, torch.Tensor) \
             else base_vbias.to(device=self.device, dtype=torch.float32).contiguous()
-        n, need = C.c_int64(), 0
-        for Hq in sorted({H, ldh}):        # (a weight matrix on a padded leading dimension: every buffer is as large as that width's)
-            _lib.check(self.lib.mdbn_ais_workspace_bytes(self.ctx, M, V, Hq, K + 1, int(path) if Hq == H else 2, C.byref(n)),
-                       "mdbn_ais_workspace_bytes")
-            need = max(need, n.value)
-        ws = torch.empty(need // 4 + 64, dtype=torch.float32, device=self.device)
+        ws = self._sampler_workspace(self.lib.mdbn_ais_workspace_bytes, "mdbn_ais_workspace_bytes", (M, V), H, ldh, path, extra=(K + 1,))
         logw = torch.zeros(M, dtype=torch.float64, device=self.device)
         v_state = self.alloc_matrix(M, V, ldv)
         trace_h = torch.zeros((max(K - 1, 1), M, ldh), dtype=torch.float32, device=self.device) if trace else None
@@ -575,14 +579,8 @@ class HipEngine(object):
         trace_v = torch.zeros((n_t, M * R, ldv), dtype=torch.float32, device=self.device) if trace else None
         trace_h = torch.zeros((n_t, M * R, ldh), dtype=torch.float32, device=self.device) if trace else None
         trace_s = torch.zeros((n_t, M, 2, R), dtype=torch.int32, device=self.device) if trace else None
-        n, need = C.c_int64(), 0
-        for Hq in sorted({H, ldh}):        # (a weight matrix on a padded leading dimension: every buffer is as large as that width's)
-            _lib.check(self.lib.mdbn_pt_workspace_bytes(self.ctx, M, R, V, Hq, int(path) if Hq == H else 2, C.byref(n)),
-                       "mdbn_pt_workspace_bytes")
-            need = max(need, n.value)
-        ws = getattr(self, "_pt_ws", None)             # kept between calls, grown to the largest requirement seen
-        if ws is None or ws.numel() * 4 < need:
-            ws = self._pt_ws = torch.empty(need // 4 + 64, dtype=torch.float32, device=self.device)
+        ws = self._sampler_workspace(self.lib.mdbn_pt_workspace_bytes, "mdbn_pt_workspace_bytes", (M, R, V), H, ldh, path,
+                                     cache_attr="_pt_ws")
         r = rng.c()
         _lib.check(self.lib.mdbn_pt_run(
             self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base_vbias),
