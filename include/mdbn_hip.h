@@ -502,6 +502,31 @@ int  mdbn_pt_run(mdbn_ctx *ctx, void *stream, const float *W, int64_t V, int64_t
                  float *trace_v, float *trace_h, int32_t *trace_swaps, int path, int64_t steps_per_launch,
                  const mdbn_rng *rng, void *workspace, int64_t workspace_bytes);
 
+/* mdbn_pt_run that also records the WORKS of its swap attempts: log Z from the ladder (Desjardins et al. 2011).  The four
+ * float32 row sums that decide the swap of the ranks (rho, rho + 1), held by the slots i / j, are the two halves of a bridge
+ * between the neighbouring temperatures; with db = betas[rho + 1] - betas[rho] and g = |vbias - base_vbias|^2,
+ *   d_fwd = l_i(beta_{rho+1}) - l_i(beta_rho)  =  hsum_i + db s1_i - [gauss] (beta_{rho+1}^2 - beta_rho^2) g / 2
+ *   d_rev = l_j(beta_rho) - l_j(beta_{rho+1})  =  hsum_j - db s1_j + [gauss] (beta_{rho+1}^2 - beta_rho^2) g / 2
+ * combined in double (g in double from the float32 differences), and at stationarity
+ *   log Z_{rho+1} / Z_rho  =  log E_rho[exp d_fwd]  =  -log E_{rho+1}[exp d_rev]
+ * (the first estimate is biased low, the second high).  zacc [M][R - 1][4] (double, in and out, nullable) holds per ladder
+ * and pair {m_f, s_f, m_r, s_r}: for every attempt of the sweeps t >= burn_in, m' = max(m, d), s = s exp(m - m') +
+ * exp(d - m'), m = m' (s in double, the two exponentials float32), so that sum exp(d) = s exp(m).  The caller starts it at
+ * m = -inf, s = 0; it is carried like rank, so two runs accumulate what one run of their sweeps does, bit for bit, and so
+ * does any steps_per_launch.  With betas[0] = 0, log Z_0 = H log 2 + sum softplus(base_vbias) | H log 2 + V / 2 log 2 pi and
+ * the host finishes log Z = log Z_0 + sum_rho log(sum_m s exp(m) / attempts).  trace_work [n][M][R - 1][2] (double,
+ * nullable) taps (d_fwd, d_rev) of every sweep, NaN where trace_swaps says -1.  Recording consumes no random number and
+ * alters no decision: every output of mdbn_pt_run is bit-identical.  Arguments, paths and rules are those of mdbn_pt_run
+ * (zacc / trace_work 16-byte aligned); the workspace is sized by mdbn_pt_run_z_workspace_bytes (the general path keeps g
+ * there). */
+int  mdbn_pt_run_z_workspace_bytes(mdbn_ctx *ctx, int64_t M, int64_t R, int64_t V, int64_t H, int path, int64_t *bytes);
+int  mdbn_pt_run_z(mdbn_ctx *ctx, void *stream, const float *W, int64_t V, int64_t H, int64_t ldh,
+                   const float *hbias, const float *vbias, const float *base_vbias, int gauss,
+                   const float *betas, int64_t R, int64_t M, int64_t ldv, float *v, float *h, int32_t *rank,
+                   int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t *accepted, float *v_avg, float *h_avg,
+                   float *trace_v, float *trace_h, int32_t *trace_swaps, int path, int64_t steps_per_launch,
+                   const mdbn_rng *rng, void *workspace, int64_t workspace_bytes, double *zacc, double *trace_work);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)). */

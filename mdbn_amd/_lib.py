@@ -117,6 +117,9 @@ SIGNATURES = {
     "mdbn_pt_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
     "mdbn_pt_run": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp,
                     _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _rngp, _vp, _i64],
+    "mdbn_pt_run_z_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
+    "mdbn_pt_run_z": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp,
+                      _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _rngp, _vp, _i64, _vp, _vp],
     "mdbn_round_flip": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
     "mdbn_pl_cost": [_vp, _vp, _vp, _vp, _i64, _i64, _vp],
     "mdbn_recon_cost": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64],

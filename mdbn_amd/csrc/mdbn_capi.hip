@@ -2476,19 +2476,21 @@ namespace {
 
 // The caller's workspace of mdbn_pt_run: the betas on the device, the per-ladder swap counts and the two running sums (what a
 // cut run carries from launch to launch), then -- general path -- a zero bias, the pre-activations of a pass, s1
-// (mdbn_temper.hip) and the scratch of the propagation GEMMs over M R rows.
+// (mdbn_temper.hip) and the scratch of the propagation GEMMs over M R rows.  mdbn_pt_run_z (`z`): on the general path also
+// g = |b - b_A|^2, a double, behind the running sums.
 struct PtWs {
-    int64_t betas, counts, v_sum, h_sum, zero, pre, s1, gemm_bytes;
-    int64_t total_bytes() const { return 4 * (betas + counts + v_sum + h_sum + zero + pre + s1) + gemm_bytes; }
+    int64_t betas, counts, v_sum, h_sum, g, zero, pre, s1, gemm_bytes;
+    int64_t total_bytes() const { return 4 * (betas + counts + v_sum + h_sum + g + zero + pre + s1) + gemm_bytes; }
 };
 
-PtWs pt_ws(int path, int64_t M, int64_t R, int64_t V, int64_t H, int64_t ldv, int64_t ldh)
+PtWs pt_ws(int path, int64_t M, int64_t R, int64_t V, int64_t H, int64_t ldv, int64_t ldh, bool z = false)
 {
     PtWs w{};
     w.betas = ru64(R);
     w.counts = ru64(M * (R - 1));
     w.v_sum = ru64(M * ldv);
     w.h_sum = ru64(M * ldh);
+    if (path == 2 && z) w.g = ru64(2);
     if (path == 2) {
         const int64_t rows = M * R;
         w.zero = ru64(std::max(ldv, ldh));
@@ -2501,9 +2503,10 @@ PtWs pt_ws(int path, int64_t M, int64_t R, int64_t V, int64_t H, int64_t ldv, in
 
 }  // namespace
 
-int mdbn_pt_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t R, int64_t V, int64_t H, int path, int64_t* bytes)
+namespace {
+
+int pt_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t R, int64_t V, int64_t H, int path, int64_t* bytes, bool z)
 {
-    CtxScope ctx_scope(ctx);
     REQUIRE(bytes != nullptr, "bytes is NULL");
     REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
     REQUIRE(R >= 2 && R <= PT_MAX_R_GENERAL, "R = %lld: a ladder has 2 to %d temperatures", (long long)R, PT_MAX_R_GENERAL);
@@ -2514,17 +2517,18 @@ int mdbn_pt_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t R, int64_t V, int6
                               pt_small_preferred(M, R, V, H, 0, ldv, ldh) && pt_small_preferred(M, R, V, H, 1, ldv, ldh));
     REQUIRE(p > 0, "path 1: %lld -> %lld with R = %lld is not LDS-resident (or R is no multiple of 4)", (long long)V, (long long)H,
             (long long)R);
-    *bytes = pt_ws(p, M, R, V, H, ldv, ldh).total_bytes();
+    *bytes = pt_ws(p, M, R, V, H, ldv, ldh, z).total_bytes();
     return MDBN_OK;
 }
 
-int mdbn_pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
-                const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t R, int64_t M, int64_t ldv,
-                float* v, float* h, int32_t* rank, int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t* accepted,
-                float* v_avg, float* h_avg, float* trace_v, float* trace_h, int32_t* trace_swaps, int path,
-                int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes)
+// mdbn_pt_run (z = false: zacc and trace_work NULL) and mdbn_pt_run_z: one statement of the rules and of the run
+int pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+           const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t R, int64_t M, int64_t ldv,
+           float* v, float* h, int32_t* rank, int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t* accepted,
+           float* v_avg, float* h_avg, float* trace_v, float* trace_h, int32_t* trace_swaps, int path,
+           int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes, bool z, double* zacc,
+           double* trace_work)
 {
-    CtxScope ctx_scope(ctx);
     // (the argument rules first: they need no device)
     REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
     REQUIRE(R >= 2 && R <= PT_MAX_R_GENERAL, "R = %lld: a ladder has 2 to %d temperatures", (long long)R, PT_MAX_R_GENERAL);
@@ -2547,13 +2551,13 @@ int mdbn_pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t 
             (long long)V, (long long)H, (long long)ldv, (long long)ldh, (long long)R);
     // (path = 0: the one-launch kernel only where it was measured to win: pt_small_preferred)
     const int p = run_path(path, pt_small_preferred(M, R, V, H, gauss, ldv, ldh));
-    const PtWs w = pt_ws(p, M, R, V, H, ldv, ldh);
-    CHECK(sampler_workspace_rules(workspace_bytes, w.total_bytes(), "mdbn_pt_workspace_bytes", ctx, rng));
+    const PtWs w = pt_ws(p, M, R, V, H, ldv, ldh, z);
+    CHECK(sampler_workspace_rules(workspace_bytes, w.total_bytes(), z ? "mdbn_pt_run_z_workspace_bytes" : "mdbn_pt_workspace_bytes", ctx, rng));
     CHECK(check_mat(W, ldh, H, "W"));
     CHECK(check_mat(v, ldv, V, "v"));
     CHECK(check_mat(h, ldh, H, "h"));
     REQUIRE(hbias && vbias && base_vbias && rank && accepted, "NULL pointer");
-    CHECK(sampler_pointer_rules(workspace, {v_avg, h_avg, trace_h, trace_v}));
+    CHECK(sampler_pointer_rules(workspace, {v_avg, h_avg, trace_h, trace_v, zacc, trace_work}));
     hipStream_t s = (hipStream_t)stream;
     float* wsf = reinterpret_cast<float*>(workspace);
     float* d_betas = wsf;
@@ -2572,6 +2576,7 @@ int mdbn_pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t 
         a.n = (int)n_sweeps; a.burn_in = (int)burn_in; a.sweep0 = sweep0;
         a.rng = make_key(*rng, 0u);
         a.trace_v = trace_v; a.trace_h = trace_h; a.trace_swaps = trace_swaps;
+        a.zacc = zacc; a.trace_work = trace_work;
         const int64_t cut = steps_per_launch ? steps_per_launch : pt_default_cut(R);
         for (int64_t t0 = 0; t0 < n_sweeps; t0 += cut) {      // a launch stays short; the state travels in h / rank / counts / sums
             a.t0 = (int)t0; a.t1 = (int)std::min(n_sweeps, t0 + cut);
@@ -2582,13 +2587,14 @@ int mdbn_pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t 
     }
 
     const int64_t rows = M * R;
-    float* zero = h_sum + w.h_sum;
+    double* g = reinterpret_cast<double*>(h_sum + w.h_sum);
+    float* zero = h_sum + w.h_sum + w.g;
     float* pre = zero + w.zero;
     float* s1 = pre + w.pre;
     void* gemm_ws = s1 + w.s1;
     Workspace ws;
     CHECK(carve(gemm_ws, w.gemm_bytes, rows, V, H, ws, false));
-    HIP_OK(hipMemsetAsync(counts, 0, sizeof(float) * (w.counts + w.v_sum + w.h_sum + w.zero), s));
+    HIP_OK(hipMemsetAsync(counts, 0, sizeof(float) * (w.counts + w.v_sum + w.h_sum + w.g + w.zero), s));
     PtStepArgs st{};
     st.M = (int)M; st.R = (int)R; st.V = (int)V; st.H = (int)H; st.gauss = gauss;
     st.ldv = ldv; st.ldh = ldh;
@@ -2597,8 +2603,14 @@ int mdbn_pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t 
     st.v_sum = v_sum; st.h_sum = h_sum; st.v_avg = v_avg; st.h_avg = h_avg;
     st.n_avg = (float)(n_sweeps - burn_in); st.sweep0 = sweep0;
     st.rng = make_key(*rng, 0u);
+    st.zacc = zacc;
+    if (zacc || trace_work) {
+        st.g = g;
+        if (gauss) HIP_OK(launch_pt_gnorm(vbias, base_vbias, (int)V, g, s));
+    }
     for (int64_t t = 0; t < n_sweeps; ++t) {
         st.t = (int)t; st.accumulate = t >= burn_in; st.last = t + 1 == n_sweeps;
+        st.trace_work = trace_work ? trace_work + t * M * (R - 1) * 2 : nullptr;
         st.trace_v = trace_v ? trace_v + t * rows * ldv : nullptr;
         st.trace_h = trace_h ? trace_h + t * rows * ldh : nullptr;
         st.trace_swaps = trace_swaps ? trace_swaps + t * M * 2 * R : nullptr;
@@ -2613,6 +2625,45 @@ int mdbn_pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t 
     }
     HIP_OK(launch_pt_counts(counts, (int)M, (int)R, accepted, s));
     return MDBN_OK;
+}
+
+}  // namespace
+
+int mdbn_pt_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t R, int64_t V, int64_t H, int path, int64_t* bytes)
+{
+    CtxScope ctx_scope(ctx);
+    return pt_workspace_bytes(ctx, M, R, V, H, path, bytes, false);
+}
+
+int mdbn_pt_run_z_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t R, int64_t V, int64_t H, int path, int64_t* bytes)
+{
+    CtxScope ctx_scope(ctx);
+    return pt_workspace_bytes(ctx, M, R, V, H, path, bytes, true);
+}
+
+int mdbn_pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+                const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t R, int64_t M, int64_t ldv,
+                float* v, float* h, int32_t* rank, int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t* accepted,
+                float* v_avg, float* h_avg, float* trace_v, float* trace_h, int32_t* trace_swaps, int path,
+                int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes)
+{
+    CtxScope ctx_scope(ctx);
+    return pt_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, gauss, betas, R, M, ldv, v, h, rank, n_sweeps, burn_in, sweep0,
+                  accepted, v_avg, h_avg, trace_v, trace_h, trace_swaps, path, steps_per_launch, rng, workspace, workspace_bytes, false,
+                  nullptr, nullptr);
+}
+
+int mdbn_pt_run_z(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+                  const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t R, int64_t M, int64_t ldv,
+                  float* v, float* h, int32_t* rank, int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t* accepted,
+                  float* v_avg, float* h_avg, float* trace_v, float* trace_h, int32_t* trace_swaps, int path,
+                  int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes, double* zacc,
+                  double* trace_work)
+{
+    CtxScope ctx_scope(ctx);
+    return pt_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, gauss, betas, R, M, ldv, v, h, rank, n_sweeps, burn_in, sweep0,
+                  accepted, v_avg, h_avg, trace_v, trace_h, trace_swaps, path, steps_per_launch, rng, workspace, workspace_bytes, true,
+                  zacc, trace_work);
 }
 
 int mdbn_round_flip(mdbn_ctx* ctx, void* stream, const float* x, int64_t rows, int64_t cols, int64_t ld, int64_t flip_col,

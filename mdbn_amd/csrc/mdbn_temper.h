@@ -53,6 +53,8 @@ struct PtSmallArgs {
     PhiloxKey rng;                                   // .step = the run's first step
     SmallLayout L; PtLayout P;                       // filled in by launch_pt_small
     float* trace_v; float* trace_h; int* trace_swaps;    // [n][M R][ldv], [n][M R][ldh], [n][M][2][R] or NULL
+    double* zacc;                                    // [M][R - 1][4] = {m_f, s_f, m_r, s_r} of the works (in and out) or NULL
+    double* trace_work;                              // [n][M][R - 1][2] = (d_fwd, d_rev), NaN where not attempted, or NULL
 };
 
 // General path, one sweep: pt_visible_kernel after the propdown GEMM, pt_swap_hidden_kernel after the propup GEMM.
@@ -69,6 +71,9 @@ struct PtStepArgs {
     int64_t sweep0;
     PhiloxKey rng;
     float* trace_v; float* trace_h; int* trace_swaps;    // this sweep's slots or NULL
+    double* zacc;                                    // [M][R - 1][4] (mdbn_temper.hip: the works) or NULL
+    double* trace_work;                              // this sweep's [M][R - 1][2] or NULL
+    const double* g;                                 // |b - b_A|^2 (launch_pt_gnorm); read when gauss and zacc / trace_work
 };
 
 bool pt_small_ok(int64_t M, int64_t R, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh);
@@ -78,5 +83,6 @@ hipError_t launch_pt_small(const PtSmallArgs& a, hipStream_t s);
 hipError_t launch_pt_visible(const PtStepArgs& a, hipStream_t s);
 hipError_t launch_pt_swap_hidden(const PtStepArgs& a, hipStream_t s);
 hipError_t launch_pt_counts(const int* counts, int M, int R, int* accepted, hipStream_t s);
+hipError_t launch_pt_gnorm(const float* vbias, const float* base_vbias, int V, double* g, hipStream_t s);
 
 }  // namespace mdbn

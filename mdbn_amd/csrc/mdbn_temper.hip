@@ -18,6 +18,15 @@
 // rows cancel).  Both paths call tempered_draw_v, tempered_draw_h and softplus_gap of mdbn_sampler_kit.h and pt_swap_accept
 // below: the uniforms, their addressing and the decision are stated once.
 //
+// The works (log Z from the ladder).  The same four sums are the two halves of a bridge between neighbouring
+// temperatures: for the attempted pair (rho, rho + 1) held by the slots i / j, with db = beta_hi - beta_lo, g = |b - b_A|^2,
+//   d_fwd = l_i(beta_hi) - l_i(beta_lo) = hsum_i + db s1_i - [Gaussian] (beta_hi^2 - beta_lo^2) g / 2
+//   d_rev = l_j(beta_lo) - l_j(beta_hi) = hsum_j - db s1_j + [Gaussian] (beta_hi^2 - beta_lo^2) g / 2
+// in double (pt_works; g in double from the float32 differences, pt_gnorm_wave).  From sweep burn_in on, zacc[m][rho] =
+// {m_f, s_f, m_r, s_r} keeps sum exp(d) per direction as a running maximum m and s = sum exp(d - m) (pt_z_add: s in double,
+// the two exponentials float32); the caller starts it at (-inf, 0) and it is in-and-out like the rank map.  trace_work taps
+// (d_fwd, d_rev) of every sweep (NaN: the pair was not tried).  Neither consumes a random number nor touches a decision.
+//
 // pt_small_kernel (LDS-resident layers, R a multiple of 4): W staged once into the workgroup's LDS; a workgroup owns whole
 // ladders, the R rows of h and a stay in LDS, a sweep runs R / 4 four-row slabs through sm_down / sm_up of
 // mdbn_small_passes.h, the swap phase reads the per-row sums from LDS and exchanges ranks there.  Nothing crosses a workgroup.
@@ -36,6 +45,7 @@ namespace mdbn {
 namespace {
 
 typedef __attribute__((address_space(3))) int lds_i;
+typedef __attribute__((address_space(3))) double lds_d;
 
 // the rank a row of rank `rho` is paired with in a sweep of parity `par` (pairs (r, r + 1), r = par mod 2), or -1
 __device__ __forceinline__ int pt_partner(int rho, int par, int R)
@@ -56,10 +66,50 @@ __device__ __forceinline__ bool pt_swap_accept(const PhiloxKey& key, uint64_t la
     return (double)logf(philox_u01(word)) < delta;
 }
 
+// the works of the pair (rho, rho + 1) from the row sums of its swap; gq = (beta_hi^2 - beta_lo^2) g / 2 or 0 (Bernoulli)
+__device__ __forceinline__ void pt_works(float hsum_lo, float hsum_hi, float s1_lo, float s1_hi, float b_lo, float b_hi, double gq,
+                                         double& d_fwd, double& d_rev)
+{
+    const double db = (double)b_hi - (double)b_lo;
+    d_fwd = (double)hsum_lo + db * (double)s1_lo - gq;
+    d_rev = (double)hsum_hi - db * (double)s1_hi + gq;
+}
+
+__device__ __forceinline__ double pt_gq(float b_lo, float b_hi, double g)
+{
+    return 0.5 * ((double)b_hi * (double)b_hi - (double)b_lo * (double)b_lo) * g;
+}
+
+// sum exp(d) as (m, s): m' = max(m, d), s = s exp(m - m') + exp(d - m'); from (-inf, 0) the first work gives (d, 1)
+__device__ __forceinline__ void pt_z_add(double& m, double& s, double d)
+{
+    const double m2 = d > m ? d : m;
+    s = s * (double)expf((float)(m - m2)) + (double)expf((float)(d - m2));
+    m = m2;
+}
+
+// |b - b_A|^2 by one whole wave: lane l sums the squares of the columns l, l + 64, ... in double, then the tree of wave_sum.
+// `db(i)` = the float32 difference of column i < n.  Both paths take it, so both hold the same g.
+template <class F>
+__device__ __forceinline__ double pt_gnorm_wave(int n, int lane, F db)
+{
+    double t = 0.0;
+    for (int i = lane; i < n; i += 64) {
+        const double d = (double)db(i);
+        t += d * d;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+    return t;
+}
+
 }  // namespace
 
-template <bool GAUSS, bool TRACE>
-__global__ __launch_bounds__(SM_NT) void pt_small_kernel(PtSmallArgs a)
+// Z: the variants of mdbn_pt_run_z (the works; their tap rides with TRACE).  The Bernoulli variant without taps is held to
+// the 128 VGPRs of two workgroups per CU, which pt_small_preferred counts on (127, no scratch; unbounded the compiler takes 129
+// and a sweep at 100 -> 24 with 512 ladders costs 43 instead of 24 us); the bound 1 leaves the other variants as they were.
+template <bool GAUSS, bool TRACE, bool Z = false>
+__global__ __launch_bounds__(SM_NT, (Z && !GAUSS && !TRACE) ? 4 : 1) void pt_small_kernel(PtSmallArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const SmallLayout& L = a.L;
@@ -78,6 +128,10 @@ __global__ __launch_bounds__(SM_NT) void pt_small_kernel(PtSmallArgs a)
     lds_f* const betl = lds + P.oBeta;
     lds_i* const rk = (lds_i*)(lds + P.oRank);
     lds_i* const inv = (lds_i*)(lds + P.oInv);
+    // [R - 1][4] the ladder's zacc: in small_layout's three 4-row hidden buffers (12 ldhs >= 864 floats; R - 1 <= 63 rows of 8),
+    // which this kernel leaves unused.  Thread rho alone touches row rho: no barrier.  (In registers, as cnt is, the four doubles
+    // are live across the passes: 140 VGPRs instead of 126, one workgroup per CU instead of two: DESIGN 3.7.)
+    lds_d* const zl = (lds_d*)(lds + L.oHs);
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int V = a.V, H = a.H, M = a.M, R = a.R;
     const int64_t ldv = a.ldv, ldh = a.ldh;
@@ -93,6 +147,8 @@ __global__ __launch_bounds__(SM_NT) void pt_small_kernel(PtSmallArgs a)
     // Both passes hand column `tid` to thread `tid` (propup: one column per thread; propdown: wave w owns tile w, tiles_dn <= 8),
     // so a thread keeps its column's two running sums in registers for the whole launch.
     const bool vlive = tid < V, hlive = tid < H;
+    double g = 0.0;                                                      // (the deciding threads tid < R - 1 sit in wave 0)
+    if (Z && GAUSS && wave == 0) g = pt_gnorm_wave(V, lane, [&](int i) { return a.vbias[i] - a.base_vbias[i]; });
 
     for (int m = blockIdx.x; m < M; m += gridDim.x) {
         SM_SYNC();                                                       // (staging | the previous ladder's last readers are done)
@@ -112,6 +168,11 @@ __global__ __launch_bounds__(SM_NT) void pt_small_kernel(PtSmallArgs a)
             if (vlive) vacc = a.v_sum[(int64_t)m * ldv + tid];
             if (hlive) hacc = a.h_sum[(int64_t)m * ldh + tid];
             if (tid < R - 1) cnt = a.counts[m * (R - 1) + tid];
+        }
+        if (Z && a.zacc && tid < R - 1) {
+            const double* z = a.zacc + ((int64_t)m * (R - 1) + tid) * 4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) zl[4 * tid + k] = z[k];
         }
         SM_SYNC();
 
@@ -186,6 +247,25 @@ __global__ __launch_bounds__(SM_NT) void pt_small_kernel(PtSmallArgs a)
                     inv[tid] = j; inv[tid + 1] = i;
                     ++cnt;
                 }
+                if (Z) {
+                    double df, dr;
+                    pt_works(hl, hh, sl, sh, betl[tid], betl[tid + 1], GAUSS ? pt_gq(betl[tid], betl[tid + 1], g) : 0.0, df, dr);
+                    if (TRACE && a.trace_work) {
+                        double* tw = a.trace_work + (((int64_t)t * M + m) * (R - 1) + tid) * 2;
+                        tw[0] = df; tw[1] = dr;
+                    }
+                    if (acc && a.zacc) {
+#pragma unroll 1
+                        for (int k = 0; k < 2; ++k) {                    // (one direction at a time: the registers of one)
+                            double mk = zl[4 * tid + 2 * k], sk = zl[4 * tid + 2 * k + 1];
+                            pt_z_add(mk, sk, k ? dr : df);
+                            zl[4 * tid + 2 * k] = mk; zl[4 * tid + 2 * k + 1] = sk;
+                        }
+                    }
+                }
+            } else if (Z && TRACE && a.trace_work && tid < R - 1) {
+                double* tw = a.trace_work + (((int64_t)t * M + m) * (R - 1) + tid) * 2;
+                tw[0] = tw[1] = __builtin_nan("");
             }
             SM_SYNC();
             if (TRACE && a.trace_swaps && tid < R) {
@@ -233,6 +313,11 @@ __global__ __launch_bounds__(SM_NT) void pt_small_kernel(PtSmallArgs a)
         }
         if (tid < R) a.rank[m * R + tid] = rk[tid];
         if (tid < R - 1) a.counts[m * (R - 1) + tid] = cnt;
+        if (Z && a.zacc && tid < R - 1) {
+            double* z = a.zacc + ((int64_t)m * (R - 1) + tid) * 4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) z[k] = zl[4 * tid + k];
+        }
         if (tid < (int)ldv) {
             a.v_sum[(int64_t)m * ldv + tid] = vacc;
             if (last && a.v_avg) a.v_avg[(int64_t)m * ldv + tid] = vacc / n_avg;
@@ -274,7 +359,7 @@ hipError_t launch_pt_small(const PtSmallArgs& a, hipStream_t s)
         return hipErrorInvalidValue;
     const SmallLayout L = small_layout(a.V, a.H, a.gauss != 0);
     const PtLayout P = pt_layout(L, a.R);
-    const bool trace = a.trace_h || a.trace_v || a.trace_swaps;
+    const bool trace = a.trace_h || a.trace_v || a.trace_swaps || a.trace_work;      // (the tap of the works rides with the others)
     const int variant = (a.gauss ? 2 : 0) | (trace ? 1 : 0);
     void (*const kerns[4])(PtSmallArgs) = {pt_small_kernel<false, false>, pt_small_kernel<false, true>, pt_small_kernel<true, false>,
                                            pt_small_kernel<true, true>};
@@ -282,7 +367,18 @@ hipError_t launch_pt_small(const PtSmallArgs& a, hipStream_t s)
     const dim3 grid(a.M < 1024 ? a.M : 1024), block(SM_NT);
     PtSmallArgs k = a;
     k.L = L; k.P = P;
-    return launch_small_variant(kerns, variant, grid, block, P.bytes, s, k);
+    if (!a.zacc && !a.trace_work) return launch_small_variant(kerns, variant, grid, block, P.bytes, s, k);
+    // the variants that record the works (their dynamic-LDS limits are raised apart from the four above)
+    void (*const zkerns[4])(PtSmallArgs) = {pt_small_kernel<false, false, true>, pt_small_kernel<false, true, true>,
+                                            pt_small_kernel<true, false, true>, pt_small_kernel<true, true, true>};
+    static bool attr_set[4] = {false, false, false, false};
+    if (!attr_set[variant]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(zkerns[variant]), hipFuncAttributeMaxDynamicSharedMemorySize, SM_MAX_LDS);
+        if (e != hipSuccess) return e;
+        attr_set[variant] = true;
+    }
+    hipLaunchKernelGGL(zkerns[variant], grid, block, P.bytes, s, k);
+    return hipGetLastError();
 }
 
 // ----------------------------------------------------------------------------------
@@ -388,6 +484,24 @@ __global__ __launch_bounds__(PT_NT) void pt_swap_hidden_kernel(PtStepArgs a)
                 rk[i] = rho + 1; rk[j] = rho;
                 a.counts[m * (R - 1) + rho] += 1;
             }
+            if (a.zacc || a.trace_work) {
+                double df, dr;
+                pt_works(hs[i], hs[j], a.s1[row0 + i], a.s1[row0 + j], bet[rho], bet[rho + 1],
+                         a.gauss ? pt_gq(bet[rho], bet[rho + 1], a.g[0]) : 0.0, df, dr);
+                if (a.zacc && a.accumulate) {
+                    double* z = a.zacc + ((int64_t)m * (R - 1) + rho) * 4;
+                    double mf = z[0], sf = z[1], mr = z[2], sr = z[3];
+                    pt_z_add(mf, sf, df); pt_z_add(mr, sr, dr);
+                    z[0] = mf; z[1] = sf; z[2] = mr; z[3] = sr;
+                }
+                if (a.trace_work) {
+                    double* tw = a.trace_work + ((int64_t)m * (R - 1) + rho) * 2;
+                    tw[0] = df; tw[1] = dr;
+                }
+            }
+        } else if (a.trace_work && rho < R - 1) {
+            double* tw = a.trace_work + ((int64_t)m * (R - 1) + rho) * 2;
+            tw[0] = tw[1] = __builtin_nan("");
         }
         if (ts) ts[(int64_t)m * 2 * R + R + rho] = dec;
     }
@@ -439,6 +553,13 @@ __global__ __launch_bounds__(64) void pt_counts_kernel(const int* counts, int M,
     }
 }
 
+// g[0] = |b - b_A|^2 (one wave; the order of pt_small_kernel)
+__global__ __launch_bounds__(64) void pt_gnorm_kernel(const float* vbias, const float* base_vbias, int V, double* g)
+{
+    const double t = pt_gnorm_wave(V, (int)threadIdx.x, [&](int i) { return vbias[i] - base_vbias[i]; });
+    if (threadIdx.x == 0) g[0] = t;
+}
+
 hipError_t launch_pt_visible(const PtStepArgs& a, hipStream_t s)
 {
     if (a.M < 1 || a.R < 2 || a.t < 0) return hipErrorInvalidValue;
@@ -452,6 +573,12 @@ hipError_t launch_pt_swap_hidden(const PtStepArgs& a, hipStream_t s)
 {
     if (a.M < 1 || a.R < 2 || a.R > PT_MAX_R_GENERAL || a.t < 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pt_swap_hidden_kernel, dim3((unsigned)a.M), dim3(PT_NT), (size_t)a.R * 16, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_pt_gnorm(const float* vbias, const float* base_vbias, int V, double* g, hipStream_t s)
+{
+    hipLaunchKernelGGL(pt_gnorm_kernel, dim3(1), dim3(64), 0, s, vbias, base_vbias, V, g);
     return hipGetLastError();
 }
 

@@ -554,14 +554,18 @@ class HipEngine(object):
         return out
 
     def temper(self, W, hbias, vbias, base_vbias, gauss, betas, v, h, rank, n_sweeps, rng, burn_in=0, sweep0=0, path=0,
-               steps_per_launch=0, trace=False):
+               steps_per_launch=0, trace=False, zacc=None, trace_work=False):
         """``n_sweeps`` parallel-tempering sweeps of M ladders of R replicas in ONE library call (mdbn_pt_run).  ``v``
         [M R, V] (ld = padded_ld(V)), ``h`` [M R, H] (ld = W's) and ``rank`` [M, R] (int32) are the ladders' state and are
         updated IN PLACE; ``betas``: R float32 values on the host, rising strictly to exactly 1; ``base_vbias``: device vector.
         Returns device tensors ``(accepted [R - 1] int32, v_avg [M, V], h_avg [M, H])`` and, with ``trace``, also
         ``trace_v [n, M R, V]``, ``trace_h [n, M R, H]`` and ``trace_swaps [n, M, 2, R]`` (int32: the rank map after the swap;
         per lower rank 1 / 0 / -1 = accepted / refused / not attempted).  ``path``: 0 = by shape, 1 = the one-launch kernel,
-        2 = the general path.  No host synchronisation.  Consumes 3 * n_sweeps RNG steps."""
+        2 = the general path.  No host synchronisation.  Consumes 3 * n_sweeps RNG steps.
+        ``zacc`` (a device float64 tensor [M, R - 1, 4], updated IN PLACE) and / or ``trace_work=True`` take the call through
+        mdbn_pt_run_z: the works of the swap attempts accumulated as {m_f, s_f, m_r, s_r} per ladder and pair (start it at
+        m = -inf, s = 0) and, appended to the returned tuple, ``trace_work [n, M, R - 1, 2]`` (float64: (d_fwd, d_rev), NaN
+        where the pair was not tried).  Every other output is bit-identical with and without them."""
         V, H = W.shape
         M, R = (int(x) for x in rank.shape)
         ldh, ldv = W.stride(0), padded_ld(V)
@@ -579,17 +583,26 @@ class HipEngine(object):
         trace_v = torch.zeros((n_t, M * R, ldv), dtype=torch.float32, device=self.device) if trace else None
         trace_h = torch.zeros((n_t, M * R, ldh), dtype=torch.float32, device=self.device) if trace else None
         trace_s = torch.zeros((n_t, M, 2, R), dtype=torch.int32, device=self.device) if trace else None
-        ws = self._sampler_workspace(self.lib.mdbn_pt_workspace_bytes, "mdbn_pt_workspace_bytes", (M, R, V), H, ldh, path,
-                                     cache_attr="_pt_ws")
+        works = zacc is not None or bool(trace_work)
+        if zacc is not None and (zacc.dtype != torch.float64 or tuple(zacc.shape) != (M, R - 1, 4) or not zacc.is_contiguous()):
+            raise ValueError("zacc must be a contiguous float64 tensor [%d, %d, 4]" % (M, R - 1))
+        trace_w = torch.zeros((n_t, M, R - 1, 2), dtype=torch.float64, device=self.device) if trace_work else None
+        sizer = "mdbn_pt_run_z_workspace_bytes" if works else "mdbn_pt_workspace_bytes"
+        ws = self._sampler_workspace(getattr(self.lib, sizer), sizer, (M, R, V), H, ldh, path, cache_attr="_pt_ws")
         r = rng.c()
-        _lib.check(self.lib.mdbn_pt_run(
-            self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base_vbias),
-            int(bool(gauss)), betas.ctypes.data_as(C.c_void_p), R, M, ldv, self._p(v), self._p(h), self._p(rank), n_sweeps,
-            burn_in, int(sweep0), self._p(accepted), self._p(v_avg), self._p(h_avg), self._p(trace_v), self._p(trace_h),
-            self._p(trace_s), int(path), int(steps_per_launch), C.byref(r), self._p(ws), ws.numel() * 4), "mdbn_pt_run")
+        args = (self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base_vbias),
+                int(bool(gauss)), betas.ctypes.data_as(C.c_void_p), R, M, ldv, self._p(v), self._p(h), self._p(rank), n_sweeps,
+                burn_in, int(sweep0), self._p(accepted), self._p(v_avg), self._p(h_avg), self._p(trace_v), self._p(trace_h),
+                self._p(trace_s), int(path), int(steps_per_launch), C.byref(r), self._p(ws), ws.numel() * 4)
+        if works:
+            _lib.check(self.lib.mdbn_pt_run_z(*(args + (self._p(zacc), self._p(trace_w)))), "mdbn_pt_run_z")
+        else:
+            _lib.check(self.lib.mdbn_pt_run(*args), "mdbn_pt_run")
         out = (accepted[:R - 1], v_avg, h_avg)
         if trace:
             out += (trace_v[:, :, :V], trace_h[:, :, :H], trace_s)
+        if trace_work:
+            out += (trace_w,)
         return out
 
     def gather_rows(self, src, indexes):

@@ -481,10 +481,9 @@ def ais_estimate(logw, base_vbias, n_hidden, gauss):
     """``(log_Z, std_err)`` from the per-chain log importance weights of an AIS run (float64 on the host):
     log Z_A + logsumexp(logw) - log M with log Z_A = H log 2 + sum softplus(b_A) (Bernoulli) | H log 2 + V/2 log 2 pi
     (unit-variance Gaussian visibles), and the delta-method standard error std(w) / (mean(w) sqrt(M))."""
+    from .temper import base_log_partition
     logw = numpy.asarray(logw, dtype=numpy.float64)
-    bA = numpy.asarray(base_vbias, dtype=numpy.float64)
-    log_ZA = n_hidden * numpy.log(2.0) + (0.5 * bA.size * numpy.log(2.0 * numpy.pi) if gauss
-                                          else numpy.logaddexp(0.0, bA).sum())
+    log_ZA = base_log_partition(base_vbias, n_hidden, gauss)
     top = logw.max()
     w = numpy.exp(logw - top)
     log_Z = log_ZA + top + numpy.log(w.mean())
@@ -596,14 +595,27 @@ class RBM(object):
         p = (x.shape[0] * mean + 0.05) / (x.shape[0] + 0.1)
         return (numpy.log(p) - numpy.log1p(-p)).astype(numpy.float32)
 
-    def log_partition(self, n_chains=512, betas=None, n_betas=1000, base_vbias=None, data=None, path=0):
+    def log_partition(self, n_chains=512, betas=None, n_betas=None, base_vbias=None, data=None, path=0, method="ais",
+                      n_ladders=64, n_sweeps=1200, burn_in=300, estimator="mid"):
         """``(log_Z, std_err)`` of the layer by annealed importance sampling (Salakhutdinov & Murray 2008) on the device:
-        ``n_chains`` chains through the inverse temperatures ``betas`` (None: ``linspace(0, 1, n_betas + 1)``) from the
-        base-rate model ``base_vbias`` (None: taken from ``data`` by ``base_rate_vbias``; with neither, the layer's own
-        visible bias).  The logsumexp and the delta-method standard error std(w) / (mean(w) sqrt(M)) are float64 numpy on
-        the host.  Consumes 2K - 1 RNG steps."""
+        ``n_chains`` chains through the inverse temperatures ``betas`` (None: ``linspace(0, 1, n_betas + 1)``, n_betas None:
+        1000) from the base-rate model ``base_vbias`` (None: taken from ``data`` by ``base_rate_vbias``; with neither, the
+        layer's own visible bias).  The logsumexp and the delta-method standard error std(w) / (mean(w) sqrt(M)) are float64
+        numpy on the host.  Consumes 2K - 1 RNG steps.
+
+        ``method="tempering"``: the estimate of ``TemperedChains.log_partition`` instead -- ``n_ladders`` parallel-tempering
+        ladders of ``n_betas`` temperatures (None: 16; or ``betas``, from 0 to 1) from the same base-rate model run
+        ``n_sweeps`` sweeps; the works of the swap attempts after ``burn_in`` bridge neighbouring temperatures
+        (``estimator``: "mid" or "bar"); the error is the delete-one-ladder jackknife.  Consumes 3 n_sweeps RNG steps.  Where
+        chains mix badly AIS under-estimates log Z without its error showing it; ``check_log_partition`` runs both."""
+        if method == "tempering":
+            r = self.tempered_chains(n_ladders, betas=betas, n_betas=16 if n_betas is None else n_betas, base_vbias=base_vbias,
+                                     data=data).log_partition(n_sweeps, burn_in, path=path, method=estimator)
+            return r.log_z, r.stderr
+        if method != "ais":
+            raise ValueError("method must be 'ais' or 'tempering', got %r" % (method,))
         if betas is None:
-            betas = numpy.linspace(0.0, 1.0, int(n_betas) + 1)
+            betas = numpy.linspace(0.0, 1.0, int(1000 if n_betas is None else n_betas) + 1)
         betas = numpy.asarray(betas, dtype=numpy.float32)
         K = betas.size - 1
         if base_vbias is None:
@@ -615,9 +627,26 @@ class RBM(object):
         self._rng_step = step + 2 * K - 1
         return ais_estimate(logw, base_vbias, self.n_hidden, self.gauss)
 
+    def check_log_partition(self, data=None, base_vbias=None, path=0, n_chains=512, n_betas=None, n_ladders=64,
+                            n_ladder_betas=16, n_sweeps=1200, burn_in=300, estimator="mid"):
+        """AIS and the tempering estimate of log Z from the SAME base-rate model (``base_vbias``; None: from ``data``; with
+        neither, the layer's own visible bias), side by side: a dict with ``ais`` / ``ais_stderr``, ``tempering`` /
+        ``tempering_stderr``, ``bracket`` = (log_z_fwd, log_z_rev) of the tempering run (biased low / high), ``z`` =
+        |ais - tempering| / sqrt(se_ais^2 + se_tempering^2) and ``detail`` (the ``LogZ`` of the tempering run).  Asserts
+        nothing: a large ``z``, or an AIS value below the bracket, says the AIS chains missed a mode (INTEGRATION)."""
+        if base_vbias is None:
+            base_vbias = self.base_rate_vbias(data) if data is not None else self.vbias.get_value()
+        ais, se_a = self.log_partition(n_chains=n_chains, n_betas=n_betas, base_vbias=base_vbias, path=path)
+        r = self.tempered_chains(n_ladders, n_betas=n_ladder_betas, base_vbias=base_vbias).log_partition(
+            n_sweeps, burn_in, path=path, method=estimator)
+        scale = float(numpy.sqrt(se_a ** 2 + r.stderr ** 2))
+        return dict(ais=ais, ais_stderr=se_a, tempering=r.log_z, tempering_stderr=r.stderr, bracket=(r.log_z_fwd, r.log_z_rev),
+                    z=abs(ais - r.log_z) / scale if scale > 0 else float("inf") if ais != r.log_z else 0.0, detail=r)
+
     def log_likelihood(self, data, **ais):
         """``(mean log p(data), std_err)``: mean(-free_energy(data)) - log_Z with ``log_partition(**ais)``'s estimate (the
-        standard error is that of log_Z; ``data`` also gives the base rate unless ``base_vbias`` / ``data`` is passed)."""
+        standard error is that of log_Z; ``data`` also gives the base rate unless ``base_vbias`` / ``data`` is passed;
+        ``method="tempering"`` and its keywords reach ``log_partition`` like any other)."""
         if "base_vbias" not in ais and "data" not in ais:
             ais = dict(ais, data=data)
         log_Z, err = self.log_partition(**ais)
