@@ -416,11 +416,12 @@ Plan plan_stats(int64_t V, int64_t H, int64_t K2, int64_t ldh, bool stream = tru
 
 static unsigned long long* g_stamps = nullptr;     // diagnostic builds only
 
-hipError_t timed_gemm(int la, int lb, const GemmArgs& g_in, hipStream_t s)
+// launch() between two events of the context's pool (made on first use, 8192 records at most) with `m` as its record, or
+// just launch() while kernel timing is off
+template <class Launch>
+hipError_t timed_launch(const GemmTiming::Meta& m, hipStream_t s, Launch launch)
 {
-    GemmArgs g = g_in;
-    g.stamps = g_stamps;
-    if (!g_timing.enabled || g_timing.used >= 8192) return launch_gemm(la, lb, g, s);
+    if (!g_timing.enabled || g_timing.used >= 8192) return launch();
     if (g_timing.used == g_timing.pool.size()) {
         hipEvent_t a, b;
         hipError_t e = hipEventCreate(&a);
@@ -429,22 +430,32 @@ hipError_t timed_gemm(int la, int lb, const GemmArgs& g_in, hipStream_t s)
         if (e != hipSuccess) return e;
         g_timing.pool.emplace_back(a, b);
     }
-    {
-        // kind = 100 * pipe (0 exact-f32 MFMA, 1 bf16 pipe with 6 products, 2 bf16 pipe with 3) + 10 * fused
-        //        + 2 * la + lb; (la, lb) = (K, MN) propup, (K, K) propdown, (MN, MN) statistics
-        const double alg = 2.0 * (double)g.M * (double)g.N * (double)g.K;
-        const int pipe = g.x6;
-        GemmTiming::Meta m{100 * pipe + 10 * g.fused + 2 * la + lb + (g.skinny ? 1000 : 0), alg,
-                           alg * (pipe == 1 ? 6.0 : pipe == 2 ? 3.0 : 1.0)};
-        if (g_timing.meta.size() <= g_timing.used) g_timing.meta.resize(g_timing.used + 1);
-        g_timing.meta[g_timing.used] = m;
-    }
+    if (g_timing.meta.size() <= g_timing.used) g_timing.meta.resize(g_timing.used + 1);
+    g_timing.meta[g_timing.used] = m;
     auto& ev = g_timing.pool[g_timing.used++];
     hipError_t e = hipEventRecord(ev.first, s);
     if (e != hipSuccess) return e;
-    e = launch_gemm(la, lb, g, s);
+    e = launch();
     if (e != hipSuccess) return e;
     return hipEventRecord(ev.second, s);
+}
+
+// pipe: 1 = six products per element on the bf16 pipe, 2 = three, anything else one
+GemmTiming::Meta gemm_meta(int kind, int pipe, double M, double N, double K)
+{
+    const double alg = 2.0 * M * N * K;
+    return {kind, alg, alg * (pipe == 1 ? 6.0 : pipe == 2 ? 3.0 : 1.0)};
+}
+
+hipError_t timed_gemm(int la, int lb, const GemmArgs& g_in, hipStream_t s)
+{
+    GemmArgs g = g_in;
+    g.stamps = g_stamps;
+    // kind = 100 * pipe (0 exact-f32 MFMA, 1 bf16 pipe with 6 products, 2 bf16 pipe with 3) + 10 * fused
+    //        + 2 * la + lb; (la, lb) = (K, MN) propup, (K, K) propdown, (MN, MN) statistics
+    const int pipe = g.x6;
+    return timed_launch(gemm_meta(100 * pipe + 10 * g.fused + 2 * la + lb + (g.skinny ? 1000 : 0), pipe, g.M, g.N, g.K), s,
+                        [&]() { return launch_gemm(la, lb, g, s); });
 }
 
 PhiloxKey make_key(const mdbn_rng& r, uint32_t draw)
@@ -574,20 +585,27 @@ int carve(void* ws, int64_t bytes, int64_t B, int64_t V, int64_t H, Workspace& o
 // One affine map + activation over `rows` rows, chunked so the split-K slabs fit.
 //   up   (dir 0): x[rows, V] * W        -> [rows, H]   (bias = hbias)
 //   down (dir 1): x[rows, H] * W^T      -> [rows, V]   (bias = vbias)
+// The constructors take the operands of a pass; its outputs and options are assigned by name at the call site.
 struct Affine {
-    const float* x; int64_t rows, ldx;
-    const float* W; int64_t V, H, ldw;
-    int dir;
-    const float* bias;
-    float* pre; float* mean; float* sample; int64_t ldo;
-    float mean_scale; int gauss;
-    const float* target; int64_t ld_target;
-    bool want_cost;
-    const mdbn_rng* rng; uint32_t draw;
+    const float* x = nullptr; int64_t rows = 0, ldx = 0;
+    const float* W = nullptr; int64_t V = 0, H = 0, ldw = 0;
+    int dir = 0;
+    const float* bias = nullptr;
+    float* pre = nullptr; float* mean = nullptr; float* sample = nullptr; int64_t ldo = 0;
+    float mean_scale = 1.0f; int gauss = 0;
+    const float* target = nullptr; int64_t ld_target = 0;
+    bool want_cost = false;
+    const mdbn_rng* rng = nullptr; uint32_t draw = 0u;
     float* colsum = nullptr; int colsum_kind = 0;
     // x holds 0/1 samples written by our own epilogues (a Gibbs chain state): exactly representable
     // in bf16, so the bf16x6 kernel needs one piece of it and three products instead of six
     bool x_binary = false;
+    // up pass: the output rides on W's leading dimension
+    Affine(const float* x, int64_t rows, int64_t ldx, const float* W, int64_t V, int64_t H, int64_t ldw, const float* hbias)
+        : x(x), rows(rows), ldx(ldx), W(W), V(V), H(H), ldw(ldw), dir(0), bias(hbias), ldo(ldw) {}
+    // down pass
+    Affine(const float* x, int64_t rows, int64_t ldx, const float* W, int64_t V, int64_t H, int64_t ldw, const float* vbias,
+           int64_t ldo, int gauss) : x(x), rows(rows), ldx(ldx), W(W), V(V), H(H), ldw(ldw), dir(1), bias(vbias), ldo(ldo), gauss(gauss) {}
 };
 
 int run_affine(const Affine& a, const Workspace& ws, hipStream_t s, int* n_cost_out)
@@ -675,35 +693,19 @@ hipError_t timed_gemm_planes(int la, int lb, const PlaneGemmArgs& g_in, hipStrea
     g.stamps = g_stamps;
     g.ms = g_opt_planes_mfma;
     if (g_opt_bf16_inputs) g.ap = 0;
-    auto launch = [&]() { return g.bal ? launch_gemm_planes_bal(la, lb, g, s) : launch_gemm_planes(la, lb, g, s); };
-    if (!g_timing.enabled || g_timing.used >= 8192) return launch();
-    if (g_timing.used == g_timing.pool.size()) {
-        hipEvent_t a, b;
-        hipError_t e = hipEventCreate(&a);
-        if (e != hipSuccess) return e;
-        e = hipEventCreate(&b);
-        if (e != hipSuccess) return e;
-        g_timing.pool.emplace_back(a, b);
-    }
-    {
-        const double alg = 2.0 * (double)g.M * (double)g.N * (double)g.K;
-        const int pipe = g.ap == 3 ? 1 : (g.ap == 1 ? 2 : 3);           // 3: one product (bf16-input reporting mode)
-        GemmTiming::Meta m{(g.bal ? 3000 : 2000) + 100 * pipe + 10 * g.fused + 2 * la + lb, alg, alg * (pipe == 1 ? 6.0 : pipe == 2 ? 3.0 : 1.0)};
-        if (g_timing.meta.size() <= g_timing.used) g_timing.meta.resize(g_timing.used + 1);
-        g_timing.meta[g_timing.used] = m;
-    }
-    auto& ev = g_timing.pool[g_timing.used++];
-    hipError_t e = hipEventRecord(ev.first, s);
-    if (e != hipSuccess) return e;
-    e = launch();
-    if (e != hipSuccess) return e;
-    return hipEventRecord(ev.second, s);
+    const int pipe = g.ap == 3 ? 1 : (g.ap == 1 ? 2 : 3);           // 3: one product (bf16-input reporting mode)
+    return timed_launch(gemm_meta((g.bal ? 3000 : 2000) + 100 * pipe + 10 * g.fused + 2 * la + lb, pipe, g.M, g.N, g.K), s,
+                        [&]() { return g.bal ? launch_gemm_planes_bal(la, lb, g, s) : launch_gemm_planes(la, lb, g, s); });
 }
 
-// carve-up of mdbn_cd_args.planes (bf16 elements): planes of X2 = [v0; nv] and P2 = [ph; -nh], hs, vs
-struct PlaneBufs {
+// What both halves of a plane step read (planes_setup): the carve-up of mdbn_cd_args.planes (bf16 elements) into planes of
+// X2 = [v0; nv] and P2 = [ph; -nh], hs, vs; the X2 buffer this step does NOT use (gather-ahead target); W's planes (split on
+// entry if stale: cd_step_impl); whether the float32 copies are made
+struct PlaneStep {
     unsigned short *Xp, *Pp, *hsp, *vsp;
     int64_t px, pp;          // elements between the planes of Xp / Pp
+    unsigned short *Xother = nullptr, *Wp = nullptr;
+    bool keep = false;
 };
 inline int64_t planes_elems(int64_t B, int64_t ldv, int64_t ldh) { return 6 * B * ldv + 6 * B * ldh + B * ldh + B * ldv; }
 
@@ -830,46 +832,78 @@ int run_affine_planes(mdbn_ctx* ctx, int comm_cus, const unsigned short* A, int6
     return MDBN_OK;
 }
 
-// The CD-k step on planes (same sequence, draws and outputs as cd_step_impl below; GRBM without noise and
-// Bernoulli RBM, CD only).  upd != NULL: single-device step with the update fused into the statistics GEMM.
-// mode: 0 = the whole step, 1 = everything before the statistics GEMM (mdbn_cd_forward), 2 = the statistics GEMM only
-// (mdbn_cd_statistics).  defer (modes 0 / 2, upd == NULL): the previous step's deferred update (phase 3), applied by the
-// statistics GEMM's loader waves when it qualifies, else launched as update_kernel right before that GEMM.
-int cd_step_planes(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const mdbn_update_args* upd, const Workspace& ws,
-                   int mode = 0, const mdbn_update_args* defer = nullptr)
+// ---------------------------------------------------------------------------------- what the CD-step paths share
+// The part of a CD step one call enqueues.  Forward (mdbn_cd_forward): gather, positive phase, Gibbs chain; it leaves cost
+// partials in the workspace and reports how many.  Statistics (mdbn_cd_statistics): the rest -- bias statistics, cost total,
+// statistics GEMM (and an update) -- given that number.  Every path is such a pair of halves; cd_step_impl strings them together.
+enum class StepPart { Whole, Forward, Statistics };
+
+// The packed statistics buffer of a step (mdbn_cd_args.stats, mdbn_stats_floats): [S: V x ldh | s_h: ldh | s_v: ldv | cost]
+struct StatsView {
+    float *S, *s_h, *s_v, *cost;
+    StatsView(float* stats, int64_t V, int64_t ldv, int64_t ldh) : S(stats), s_h(S + V * ldh), s_v(s_h + ldh), cost(s_v + ldv) {}
+};
+
+// Plain CD: no persistent chain, no sample statistics, no noisy GRBM -- all the one-launch, thin, plane and group-chain steps serve
+bool plain_cd(const mdbn_cd_args* a) { return !a->persistent && !a->sample_stats && !(a->gauss && a->add_noise); }
+// float32 inspection copies of v0 / nv / ph / -nh / samples that nothing on the one-launch, thin and plane paths reads
+bool keeps_f32(const mdbn_cd_args* a) { return a->keep_f32 != 0 || a->trace_h != nullptr || a->trace_v != nullptr; }
+
+// the weight half of an update rule as a kernel applies it to its own tile of S (Wp: planes of the new W, or NULL)
+void fill_upd(UpdEpi& e, const mdbn_update_args& u, int64_t V, int64_t ldh, unsigned short* Wp)
+{
+    e.W = u.W; e.Ws = u.W_speed; e.W0 = u.W0; e.ld = ldh; e.rows = (int)V;
+    e.lr = u.lr; e.l1 = u.lambda_1; e.l2 = u.lambda_2; e.wc = u.weightcost;
+    e.mu = u.momentum; e.inv_bs = 1.0f / u.batch_size;
+    e.Wp = Wp; e.wp_stride = V * ldh;
+}
+
+// ... and its bias / monitoring-cost half (H: the live hidden width)
+void fill_bias_upd(BiasUpd& b, const mdbn_update_args& u, int64_t H)
+{
+    b.hb = u.hbias; b.hbs = u.hbias_speed; b.vb = u.vbias; b.vbs = u.vbias_speed;
+    b.H = H; b.V = u.V; b.lr = u.lr; b.mu = u.momentum; b.inv_rows = 1.0f / u.n_rows;
+    b.cost_scale = u.cost_scale; b.cost_out = u.cost_out;
+}
+
+// an update as a launch of its own, W's planes rewritten with it; the whole rule of a step's own update
+hipError_t launch_whole_update(const mdbn_update_args& u, hipStream_t s)
+{
+    return launch_update(u, s, nullptr, 1, 0, reinterpret_cast<unsigned short*>(u.W_planes));
+}
+mdbn_update_args whole_rule(const mdbn_update_args& u) { mdbn_update_args w = u; w.phase = 0; return w; }
+
+int planes_setup(const mdbn_cd_args* a, PlaneStep& pb)
+{
+    const int64_t B = a->B, ldv = a->V, ldh = a->ldh;
+    unsigned short* q = reinterpret_cast<unsigned short*>(a->planes);
+    pb.Xp = q; pb.px = 2 * B * ldv; q += 6 * B * ldv;
+    pb.Pp = q; pb.pp = 2 * B * ldh; q += 6 * B * ldh;
+    pb.hsp = q; q += B * ldh;
+    pb.vsp = q;
+    if (a->planes_alt) {
+        REQUIRE(aligned16(a->planes_alt), "planes_alt not 16-byte aligned");
+        unsigned short* alt = reinterpret_cast<unsigned short*>(a->planes_alt);
+        if (a->x_buffer) { pb.Xother = pb.Xp; pb.Xp = alt; } else pb.Xother = alt;
+    } else {
+        REQUIRE(a->x_buffer == 0, "x_buffer = 1 needs planes_alt");
+    }
+    pb.Wp = reinterpret_cast<unsigned short*>(a->W_planes);
+    pb.keep = keeps_f32(a);
+    return MDBN_OK;
+}
+
+// The forward half of the CD-k step on planes (same sequence, draws and outputs as dense_forward below; GRBM without noise
+// and Bernoulli RBM, CD only).
+int planes_forward(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const Workspace& ws, const PlaneStep& pb, int* n_cost)
 {
     const int64_t B = a->B, V = a->V, Hlive = a->H, ldv = V, ldh = a->ldh;
     const int64_t H = ldh;          // the width the GEMMs run on (pad columns: exact zeros; plane_shape_ok)
-    PlaneBufs pb;
-    unsigned short* Xother = nullptr;        // the X2 buffer this step does NOT use (gather-ahead target)
-    {
-        unsigned short* p = reinterpret_cast<unsigned short*>(a->planes);
-        pb.Xp = p; pb.px = 2 * B * ldv; p += 6 * B * ldv;
-        pb.Pp = p; pb.pp = 2 * B * ldh; p += 6 * B * ldh;
-        pb.hsp = p; p += B * ldh;
-        pb.vsp = p;
-        if (a->planes_alt) {
-            REQUIRE(aligned16(a->planes_alt), "planes_alt not 16-byte aligned");
-            unsigned short* alt = reinterpret_cast<unsigned short*>(a->planes_alt);
-            if (a->x_buffer) { Xother = pb.Xp; pb.Xp = alt; } else Xother = alt;
-        } else {
-            REQUIRE(a->x_buffer == 0, "x_buffer = 1 needs planes_alt");
-        }
-    }
-    if (a->ahead_done) *a->ahead_done = 0;
-    unsigned short* Wp = reinterpret_cast<unsigned short*>(a->W_planes);    // (split on entry if stale: cd_step_impl)
-    // float32 copies nobody on the path reads (the GEMMs take planes, the bias statistics their column partials)
-    const bool keep = a->keep_f32 != 0 || a->trace_h != nullptr || a->trace_v != nullptr;
-
-    float* v0 = a->V2;
-    float* nv = a->V2 + B * ldv;
-    float* ph = a->P2;
-    float* nh = a->P2 + B * ldh;
+    unsigned short* const Wp = pb.Wp;  const bool keep = pb.keep;
+    float *v0 = a->V2, *nv = a->V2 + B * ldv, *ph = a->P2, *nh = a->P2 + B * ldh;
     // x = train_set_x[indexes] (dbn.py:307), as f32 (cost target, bias statistics) and as planes
     // (without `keep` the float32 copy of v0 is not made either: its one reader, the reconstruction-cost / bias-statistics
     // target of the last visible pass, reads the dataset rows through the index instead)
-    int n_cost = 0;
-    if (mode != 2) {
     // (gathered ahead by the previous call's statistics kernel: the planes are already there)
     if (!(a->v0_ready && !keep))
         HIP_OK(launch_gather_planes(a->data, a->n_data, ldv, ldv, a->indexes, a->index_is_64, B, keep ? v0 : nullptr, ldv, pb.Xp,
@@ -900,7 +934,7 @@ int cd_step_planes(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const md
                     e.target_idx = a->indexes; e.target_idx64 = a->index_is_64;       // NULL: rows 0..B-1 of the data
                 }
             }
-            CHECK(run_affine_planes(ctx, a->comm_cus, pb.hsp, ldh, B * ldh, 1, 1, Wp, V, H, V, B, e, last, ws, s, last ? &n_cost : nullptr));
+            CHECK(run_affine_planes(ctx, a->comm_cus, pb.hsp, ldh, B * ldh, 1, 1, Wp, V, H, V, B, e, last, ws, s, last ? n_cost : nullptr));
             if (a->trace_v && !a->gauss)
                 HIP_OK(hipMemcpyAsync(a->trace_v + (int64_t)(t - 1) * B * ldv, a->vs, sizeof(float) * B * ldv,
                                       hipMemcpyDeviceToDevice, s));
@@ -919,18 +953,17 @@ int cd_step_planes(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const md
                 HIP_OK(hipMemcpyAsync(a->trace_h + (int64_t)t * B * ldh, a->hs, sizeof(float) * B * ldh, hipMemcpyDeviceToDevice, s));
         }
     }
+    return MDBN_OK;
+}
 
-    }       // mode != 2
-    if (mode == 1) {
-        ctx->pending_n_cost = n_cost; ctx->pending_stats = a->stats;
-        return MDBN_OK;
-    }
-    if (mode == 2) n_cost = ctx->pending_n_cost;
-
-    float* S = a->stats;
-    float* s_h = a->stats + V * ldh;
-    float* s_v = s_h + ldh;
-    float* cost = s_v + ldv;
+// The statistics half on planes.  upd != NULL: single-device step with the update fused into the statistics GEMM.
+// defer (upd == NULL): the previous step's deferred update (phase 3), applied by the statistics GEMM's loader waves when it
+// qualifies, else launched as update_kernel right before that GEMM.
+int planes_statistics(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const Workspace& ws, const PlaneStep& pb, int n_cost,
+                      const mdbn_update_args* upd, const mdbn_update_args* defer)
+{
+    const int64_t B = a->B, V = a->V, Hlive = a->H, ldv = V, ldh = a->ldh, H = ldh;
+    const StatsView st(a->stats, V, ldv, ldh);
     // S = [v0; nv]^T [ph; -nh]: one GEMM over the stacked batch dimension, both operands used transposed
     const Plan sp = plan_stats(V, H, 2 * B, ldh, false);
     PlaneGemmArgs g{};
@@ -947,31 +980,26 @@ int cd_step_planes(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const md
     // gather-ahead of the next minibatch by the loader waves, after their W chunks (g.upd.early set): one 256-octet pass of
     // one row per stage; every workgroup takes rpw consecutive rows
     auto set_gather_ahead = [&]() {
-        if (g.upd.early && g_opt_gather_ahead && a->next_indexes && Xother && !keep) {
+        if (g.upd.early && g_opt_gather_ahead && a->next_indexes && pb.Xother && !pb.keep) {
             const int nwg = g.tiles_m * g.tiles_n, nt = (int)(2 * B / 32);
             const int rpw = (int)((B + nwg - 1) / nwg), passes = (int)((ldv / 8 + 255) / 256);
             if (rpw * passes <= 4 && 16 / (nt >= 20 ? 1 : 2) + 4 + 1 <= nt - 3) {      // (the kernel runs four unit slots, always)
                 g.ga.src = a->data; g.ga.n_rows = a->n_data; g.ga.ld_src = ldv;
                 g.ga.idx = a->next_indexes; g.ga.idx64 = a->index_is_64;
                 g.ga.B = (int)B; g.ga.rpw = rpw; g.ga.passes = passes;
-                g.ga.P = Xother; g.ga.plane_stride = pb.px; g.ga.ld = ldv;
+                g.ga.P = pb.Xother; g.ga.plane_stride = pb.px; g.ga.ld = ldv;
                 if (a->ahead_done) *a->ahead_done = 1;
             }
         }
     };
     if (fuse_upd) {
         BiasUpd bu;
-        bu.hb = upd->hbias; bu.hbs = upd->hbias_speed; bu.vb = upd->vbias; bu.vbs = upd->vbias_speed;
-        bu.H = Hlive; bu.V = V; bu.lr = upd->lr; bu.mu = upd->momentum; bu.inv_rows = 1.0f / upd->n_rows;
-        bu.cost_scale = upd->cost_scale; bu.cost_out = upd->cost_out;
+        fill_bias_upd(bu, *upd, Hlive);
         g.fused = 2;
         g.fin_enabled = 1;
-        g.fin = make_fin_args(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials, n_cost, s_h, s_v,
-                              cost, &bu);
-        g.upd.W = upd->W; g.upd.Ws = upd->W_speed; g.upd.W0 = upd->W0; g.upd.ld = ldh; g.upd.rows = (int)V;
-        g.upd.lr = upd->lr; g.upd.l1 = upd->lambda_1; g.upd.l2 = upd->lambda_2; g.upd.wc = upd->weightcost;
-        g.upd.mu = upd->momentum; g.upd.inv_bs = 1.0f / upd->batch_size;
-        g.upd.Wp = Wp; g.upd.wp_stride = V * ldh;
+        g.fin = make_fin_args(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials, n_cost, st.s_h, st.s_v,
+                              st.cost, &bu);
+        fill_upd(g.upd, *upd, V, ldh, pb.Wp);
         // parameter half applied by the loader waves during the main loop (mdbn_planes.hip, EARLYW): needs the split-phase
         // conditions of the update (no lambda_1; weight cost off or on a frozen snapshot) and >= 12 stages to spread over
         g.upd.early = g_opt_early_w && upd->lambda_1 == 0.f && (upd->weightcost == 0.f || upd->W0 != nullptr) &&
@@ -984,15 +1012,13 @@ int cd_step_planes(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const md
     // in flight) when that GEMM is one launch, a launch of its own (~6 us of dependent tiny kernel) otherwise
     if (sp.splitk == 1 && g_opt_fused_finalize) {
         g.fin_enabled = 1;
-        g.fin = make_fin_args(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials, n_cost, s_h, s_v,
-                              cost, nullptr);
+        g.fin = make_fin_args(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials, n_cost, st.s_h, st.s_v,
+                              st.cost, nullptr);
     } else {
-        HIP_OK(launch_finalize_stats(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials, n_cost, s_h,
-                                     s_v, cost, nullptr, s));
+        HIP_OK(launch_finalize_stats(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials, n_cost, st.s_h,
+                                     st.s_v, st.cost, nullptr, s));
     }
     g.fused = 0; g.ldc = ldh; g.slab_stride = V * ldh;
-    mdbn_update_args u;
-    if (upd) { u = *upd; u.phase = 0; }
     if (defer) {
         // the previous step's deferred update: inside this GEMM's loader waves (one workgroup per tile, unsplit, >= 20 stages,
         // the split-phase conditions), else as its own launch right here -- bitwise the same either way
@@ -1005,40 +1031,39 @@ int cd_step_planes(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const md
                                                : (sp.splitk == 1 && 2 * B / 32 >= 20));
         g.upd.flat_per_wg = flat;
         if (inside) {
-            g.upd.W = defer->W; g.upd.Ws = defer->W_speed; g.upd.W0 = defer->W0; g.upd.ld = ldh; g.upd.rows = (int)V;
-            g.upd.lr = defer->lr; g.upd.l1 = 0.f; g.upd.l2 = defer->lambda_2; g.upd.wc = defer->weightcost;
-            g.upd.mu = defer->momentum; g.upd.inv_bs = 1.0f / defer->batch_size;
-            g.upd.Wp = reinterpret_cast<unsigned short*>(defer->W_planes); g.upd.wp_stride = V * ldh;
-            g.upd.Sprev = defer->stats; g.upd.early = 2;
-            const float* ps_h = defer->stats + V * ldh;
-            g.db.on = 1; g.db.hb = defer->hbias; g.db.hbs = defer->hbias_speed; g.db.vb = defer->vbias; g.db.vbs = defer->vbias_speed;
-            g.db.s_h = ps_h; g.db.s_v = ps_h + ldh; g.db.cost_sum = ps_h + ldh + ldv; g.db.H = Hlive; g.db.V = V;
-            g.db.lr = defer->lr; g.db.mu = defer->momentum; g.db.inv_rows = 1.0f / defer->n_rows;
-            g.db.cost_scale = defer->cost_scale; g.db.cost_out = defer->cost_out;
+            fill_upd(g.upd, *defer, V, ldh, reinterpret_cast<unsigned short*>(defer->W_planes));
+            g.upd.l1 = 0.f; g.upd.Sprev = defer->stats; g.upd.early = 2;
+            // its bias / cost half reads the bias statistics and the cost total of THAT step's buffer
+            const StatsView prev(const_cast<float*>(defer->stats), V, ldv, ldh);
+            DeferredBias& d = g.db;
+            d.on = 1; d.hb = defer->hbias; d.hbs = defer->hbias_speed; d.vb = defer->vbias; d.vbs = defer->vbias_speed;
+            d.s_h = prev.s_h; d.s_v = prev.s_v; d.cost_sum = prev.cost; d.H = Hlive; d.V = V;
+            d.lr = defer->lr; d.mu = defer->momentum; d.inv_rows = 1.0f / defer->n_rows;
+            d.cost_scale = defer->cost_scale; d.cost_out = defer->cost_out;
             if (!bal) set_gather_ahead();
         } else {
-            HIP_OK(launch_update(*defer, s, nullptr, 1, 0, reinterpret_cast<unsigned short*>(defer->W_planes)));
+            HIP_OK(launch_whole_update(*defer, s));
         }
     }
     if (bal) {
         g.xcd_group = 1;
-        g.C = S; g.bal = bal; g.fused = 4; g.kchunk = (int)(2 * B); g.c_bytes = V * ldh * 4;
+        g.C = st.S; g.bal = bal; g.fused = 4; g.kchunk = (int)(2 * B); g.c_bytes = V * ldh * 4;
         g.scratch = ws.slabs;
         HIP_OK(timed_gemm_planes(LAY_MN, LAY_MN, g, s));
     } else if (sp.splitk == 1) {
-        g.C = S;
+        g.C = st.S;
         HIP_OK(timed_gemm_planes(LAY_MN, LAY_MN, g, s));
     } else {
         REQUIRE(sp.slab_floats(V, ldh) <= ws.slab_floats, "internal: statistic slabs exceed workspace");
         g.C = ws.slabs;
         HIP_OK(timed_gemm_planes(LAY_MN, LAY_MN, g, s));
         if (upd && g_opt_fused_update) {     // the update sums the slabs itself (same order as sum_slabs_kernel)
-            HIP_OK(launch_update(u, s, ws.slabs, sp.splitk, g.slab_stride, Wp));
+            HIP_OK(launch_update(whole_rule(*upd), s, ws.slabs, sp.splitk, g.slab_stride, pb.Wp));
             return MDBN_OK;
         }
-        HIP_OK(launch_sum_slabs(ws.slabs, sp.splitk, g.slab_stride, V * ldh, S, s));
+        HIP_OK(launch_sum_slabs(ws.slabs, sp.splitk, g.slab_stride, V * ldh, st.S, s));
     }
-    if (upd) HIP_OK(launch_update(u, s, nullptr, 1, 0, Wp));
+    if (upd) HIP_OK(launch_update(whole_rule(*upd), s, nullptr, 1, 0, pb.Wp));
     return MDBN_OK;
 }
 
@@ -1444,8 +1469,9 @@ int mdbn_propup_sample(mdbn_ctx* ctx, void* stream, const float* v, int64_t B, i
         REQUIRE(p == nullptr || aligned16(p), "output not 16-byte aligned");
     Workspace ws;
     CHECK(carve(workspace, workspace_bytes, B, V, H, ws, false));
-    Affine a{v, B, ldv, W, V, H, ldh, 0, hbias, pre, mean, sample, ldh, mean_scale, 0,
-             nullptr, 0, false, rng, rng ? rng->draw : 0u};
+    Affine a(v, B, ldv, W, V, H, ldh, hbias);
+    a.pre = pre; a.mean = mean; a.sample = sample; a.mean_scale = mean_scale;
+    a.rng = rng; a.draw = rng ? rng->draw : 0u;
     return run_affine(a, ws, (hipStream_t)stream, nullptr);
 }
 
@@ -1468,8 +1494,10 @@ int mdbn_propdown_sample(mdbn_ctx* ctx, void* stream, const float* h, int64_t B,
     CHECK(carve(workspace, workspace_bytes, B, V, H, ws, false));
     hipStream_t s = (hipStream_t)stream;
     // GRBM without noise: sample == mean (rbm.py:652-653): write the mean twice, no draw
-    Affine a{h, B, ldh, W, V, H, ldh, 1, vbias, pre, mean, draws ? sample : nullptr, ldv, 1.0f, gauss,
-             v0, ldv, v0 != nullptr, rng, rng ? rng->draw : 0u};
+    Affine a(h, B, ldh, W, V, H, ldh, vbias, ldv, gauss);
+    a.pre = pre; a.mean = mean; a.sample = draws ? sample : nullptr;
+    a.target = v0; a.ld_target = ldv; a.want_cost = v0 != nullptr;
+    a.rng = rng; a.draw = rng ? rng->draw : 0u;
     int n_cost = 0;
     CHECK(run_affine(a, ws, s, &n_cost));
     if (sample && !draws) {
@@ -1592,14 +1620,17 @@ int mdbn_gibbs_chain(mdbn_ctx* ctx, void* stream, float* v, int64_t B, int64_t l
         rv.step = rng->step + (uint32_t)(2 * t + 1); rv.draw = 0;
         // h | v: RBM feeds the SAMPLE on, GRBM the MEAN (rbm.py:253-254, :680)
         const bool need_mean = gauss || last;
-        Affine up{v, B, ldv, W, V, H, ldh, 0, hbias, last ? pre_h : nullptr, need_mean ? h_mean : nullptr,
-                  (!gauss || last) ? h_sample : nullptr, ldh, 1.0f, 0, nullptr, 0, false, &rh, 0u};
+        Affine up(v, B, ldv, W, V, H, ldh, hbias);
+        up.pre = last ? pre_h : nullptr; up.mean = need_mean ? h_mean : nullptr; up.sample = (!gauss || last) ? h_sample : nullptr;
+        up.rng = &rh;
         up.x_binary = !gauss && t > 0;              // from the second step on v holds our own 0/1 samples
         CHECK(run_affine(up, ws, s, nullptr));
         // v | h: the chain state v becomes the visible SAMPLE (RBM: Bernoulli; GRBM: mean, + N(0,1) if noisy)
-        Affine down{gauss ? h_mean : h_sample, B, ldh, W, V, H, ldh, 1, vbias, (last && !gauss) ? pre_v : nullptr,
-                    (gauss && !noisy) ? v : ((last || noisy) ? v_mean : nullptr), (!gauss || noisy) ? v : nullptr,
-                    ldv, 1.0f, gauss, nullptr, 0, false, &rv, 0u};
+        Affine down(gauss ? h_mean : h_sample, B, ldh, W, V, H, ldh, vbias, ldv, gauss);
+        down.pre = (last && !gauss) ? pre_v : nullptr;
+        down.mean = (gauss && !noisy) ? v : ((last || noisy) ? v_mean : nullptr);
+        down.sample = (!gauss || noisy) ? v : nullptr;
+        down.rng = &rv;
         down.x_binary = !gauss;
         CHECK(run_affine(down, ws, s, nullptr));
     }
@@ -1621,17 +1652,14 @@ int mdbn_cd_stats(mdbn_ctx* ctx, void* stream, const float* V2, const float* P2,
     Workspace ws;
     CHECK(carve(workspace, workspace_bytes, B, V, H, ws, true));
     hipStream_t s = (hipStream_t)stream;
-    float* S = stats;
-    float* s_h = stats + V * ldh;
-    float* s_v = s_h + ldh;
-    float* cost = s_v + ldv;
+    const StatsView st(stats, V, ldv, ldh);
 
     // bias statistics: P2's second half already holds -nh_mean; s_v = sum(v0 - nv_mean)
     const int ng = row_groups(B);
     HIP_OK(launch_colsum_groups(P2, nullptr, (int)B, ldh, ws.colPpos, s));
     HIP_OK(launch_colsum_groups(P2 + B * ldh, nullptr, (int)B, ldh, ws.colPneg, s));
     HIP_OK(launch_colsum_groups(V2, V2 + B * ldv, (int)B, ldv, ws.colV, s));
-    HIP_OK(launch_finalize_stats(ws.colPpos, ws.colPneg, ws.colV, ng, ldh, ldv, nullptr, 0, s_h, s_v, cost, nullptr, s));
+    HIP_OK(launch_finalize_stats(ws.colPpos, ws.colPneg, ws.colV, ng, ldh, ldv, nullptr, 0, st.s_h, st.s_v, st.cost, nullptr, s));
 
     // S = [v0 ; nv]^T [ph ; -nh]  : one GEMM over the stacked batch dimension (K = 2B)
     const Plan p = plan_stats(V, H, 2 * B, ldh);
@@ -1642,13 +1670,13 @@ int mdbn_cd_stats(mdbn_ctx* ctx, void* stream, const float* V2, const float* P2,
     p.fill(g);
     g.fused = 0;
     if (p.splitk == 1) {
-        g.C = S;
+        g.C = st.S;
         HIP_OK(timed_gemm(LAY_MN, LAY_MN, g, s));
     } else {
         REQUIRE(p.slab_floats(V, ldh) <= ws.slab_floats, "internal: statistic slabs exceed workspace");
         g.C = ws.slabs;
         HIP_OK(timed_gemm(LAY_MN, LAY_MN, g, s));
-        HIP_OK(launch_sum_slabs(ws.slabs, p.splitk, g.slab_stride, V * ldh, S, s));
+        HIP_OK(launch_sum_slabs(ws.slabs, p.splitk, g.slab_stride, V * ldh, st.S, s));
     }
     return MDBN_OK;
 }
@@ -1689,180 +1717,337 @@ static int check_update_args(const mdbn_update_args* a)
 // ---------------------------------------------------------------------------------- one-launch step (LDS-resident layers)
 static bool small_eligible(const mdbn_cd_args* a, const Workspace& ws)
 {
-    if (!g_opt_small_fused || g_opt_bf16_inputs) return false;
-    if (a->persistent || a->sample_stats || (a->gauss && a->add_noise)) return false;
-    if (!a->gauss && a->vs == nullptr) return false;
+    if (!g_opt_small_fused || g_opt_bf16_inputs || !plain_cd(a)) return false;
     if (a->B > 65535 * 16 || !small_shape_ok(a->B, a->V, a->H, a->gauss) || !small_ld_ok(a->V, a->H, a->ldv, a->ldh)) return false;
     const int nb = small_blocks(a->B);
     return (int64_t)nb * ((a->V + 63) & ~int64_t(63)) * a->ldh <= ws.slab_floats && (int64_t)nb * SM_NW <= ws.cost_floats && nb <= row_groups(a->B);
 }
 
-// mode 0: the whole step; 1: the chain + partials only (mdbn_cd_forward); 2: the finish launch (mdbn_cd_statistics).
-// upd: single-device step, the finish launch applies the update; else it stores [S | s_h | s_v | cost] into a->stats.
-static int cd_step_small(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const mdbn_update_args* upd, const Workspace& ws,
-                         int mode, const mdbn_update_args* defer)
+// forward half: the chain + one partial of everything per workgroup, in one launch
+static int small_forward(hipStream_t s, const mdbn_cd_args* a, const Workspace& ws, int* n_cost)
+{
+    const int64_t B = a->B, V = a->V, H = a->H, ldv = a->ldv, ldh = a->ldh;
+    SmallCdArgs k{};
+    k.data = a->data; k.n_data = a->n_data; k.ld_data = ldv;
+    k.idx = a->indexes; k.idx64 = a->index_is_64;
+    k.B = (int)B; k.V = (int)V; k.H = (int)H; k.k = a->k; k.gauss = a->gauss;
+    k.keep = keeps_f32(a);
+    k.ldv = ldv; k.ldh = ldh;
+    k.W = a->W; k.hbias = a->hbias; k.vbias = a->vbias;
+    k.rng = make_key(a->rng, 0u);
+    k.part_S = ws.slabs; k.posP = ws.colPpos; k.negP = ws.colPneg; k.partV = ws.colV; k.cost_partials = ws.cost_partials;
+    k.V2 = a->V2; k.P2 = a->P2; k.hs = a->hs; k.vs = a->vs;
+    k.trace_h = a->trace_h; k.trace_v = a->gauss ? nullptr : a->trace_v;
+    k.stamps = g_stamps;
+    HIP_OK(launch_small_cd(k, s));
+    *n_cost = small_blocks(B) * SM_NW;          // a cost partial per wave
+    return MDBN_OK;
+}
+
+// statistics half: the finish launch.  upd: single-device step, the finish launch applies the update; else it stores
+// [S | s_h | s_v | cost] into a->stats.
+static int small_statistics(hipStream_t s, const mdbn_cd_args* a, const Workspace& ws, int n_cost, const mdbn_update_args* upd)
 {
     const int64_t B = a->B, V = a->V, H = a->H, ldv = a->ldv, ldh = a->ldh;
     const int nb = small_blocks(B);
-    if (mode != 2) {
-        SmallCdArgs k{};
-        k.data = a->data; k.n_data = a->n_data; k.ld_data = ldv;
-        k.idx = a->indexes; k.idx64 = a->index_is_64;
-        k.B = (int)B; k.V = (int)V; k.H = (int)H; k.k = a->k; k.gauss = a->gauss;
-        k.keep = a->keep_f32 != 0 || a->trace_h || a->trace_v;     // inspection copies of v0 / nv / ph / -nh / samples (as the plane path)
-        k.ldv = ldv; k.ldh = ldh;
-        k.W = a->W; k.hbias = a->hbias; k.vbias = a->vbias;
-        k.rng = make_key(a->rng, 0u);
-        k.part_S = ws.slabs; k.posP = ws.colPpos; k.negP = ws.colPneg; k.partV = ws.colV; k.cost_partials = ws.cost_partials;
-        k.V2 = a->V2; k.P2 = a->P2; k.hs = a->hs; k.vs = a->vs;
-        k.trace_h = a->trace_h; k.trace_v = a->gauss ? nullptr : a->trace_v;
-        k.stamps = g_stamps;
-        HIP_OK(launch_small_cd(k, s));
-    }
-    if (mode == 1) {
-        ctx->pending_n_cost = nb * SM_NW; ctx->pending_stats = a->stats;
-        return MDBN_OK;
-    }
-    if (mode != 1) { ctx->pending_n_cost = -1; ctx->pending_stats = nullptr; }      // (any step that is not a forward half ends a pending hand-over: the workspace partials are gone)
-    // the previous step's deferred update (data-parallel order) is its own launch here, ahead of the finish launch
-    if (defer) HIP_OK(launch_update(*defer, s, nullptr, 1, 0, reinterpret_cast<unsigned short*>(defer->W_planes)));
-    float* s_h = a->stats + V * ldh;
-    float* s_v = s_h + ldh;
-    float* cost = s_v + ldv;
+    const StatsView st(a->stats, V, ldv, ldh);
     SmallFinArgs f{};
     {
         const SmallLayout L = small_layout((int)V, (int)H, a->gauss != 0);
         f.part = ws.slabs; f.nparts = nb; f.n4p = small_part_quads(L, (int)ldh);
         f.V = (int)V; f.q4 = (int)(ldh >> 2); f.tiles_dn = L.tiles_dn;
     }
-    f.S_out = a->stats;
+    f.S_out = st.S;
     BiasUpd bu;
     // mdbn_set_option("fused_update", 0): the statistics are materialised and the update is its own launch (update_kernel)
     const bool fuse_upd = upd && g_opt_fused_update;
     if (fuse_upd) {
         f.do_upd = 1;
-        f.upd.W = upd->W; f.upd.Ws = upd->W_speed; f.upd.W0 = upd->W0; f.upd.ld = ldh; f.upd.rows = (int)V;
-        f.upd.lr = upd->lr; f.upd.l1 = upd->lambda_1; f.upd.l2 = upd->lambda_2; f.upd.wc = upd->weightcost;
-        f.upd.mu = upd->momentum; f.upd.inv_bs = 1.0f / upd->batch_size;
-        f.upd.Wp = reinterpret_cast<unsigned short*>(upd->W_planes); f.upd.wp_stride = V * ldh;
-        bu.hb = upd->hbias; bu.hbs = upd->hbias_speed; bu.vb = upd->vbias; bu.vbs = upd->vbias_speed;
-        bu.H = H; bu.V = V; bu.lr = upd->lr; bu.mu = upd->momentum; bu.inv_rows = 1.0f / upd->n_rows;
-        bu.cost_scale = upd->cost_scale; bu.cost_out = upd->cost_out;
+        fill_upd(f.upd, *upd, V, ldh, reinterpret_cast<unsigned short*>(upd->W_planes));
+        fill_bias_upd(bu, *upd, H);
     }
-    f.fin = make_fin_args(ws.colPpos, ws.colPneg, ws.colV, nb, ldh, ldv, ws.cost_partials, nb * SM_NW, s_h, s_v, cost, fuse_upd ? &bu : nullptr);
+    f.fin = make_fin_args(ws.colPpos, ws.colPneg, ws.colV, nb, ldh, ldv, ws.cost_partials, n_cost, st.s_h, st.s_v, st.cost, fuse_upd ? &bu : nullptr);
     HIP_OK(launch_small_finish(f, s));
-    if (upd && !fuse_upd) {
-        mdbn_update_args u = *upd;
-        u.phase = 0;
-        HIP_OK(launch_update(u, s, nullptr, 1, 0, reinterpret_cast<unsigned short*>(u.W_planes)));
-    }
+    if (upd && !fuse_upd) HIP_OK(launch_whole_update(whole_rule(*upd), s));
     return MDBN_OK;
 }
 
 // ---------------------------------------------------------------------------------- thin-batch step (B <= 32, mdbn_thin.hip)
+// What both halves of a thin step read (thin_eligible, thin_setup).  ahead_ok: positive phase ahead (mdbn_cd_args.next_indexes
+// on this path) -- the previous call's update kernel left v0 in V2 and the partials of x W in planes_alt; this call's update
+// kernel may do the same for the next one.
+struct ThinStep { ThinGeom tg; bool ahead_ok = false; };
+
 static bool thin_eligible(const mdbn_ctx* ctx, const mdbn_cd_args* a, const Workspace& ws, ThinGeom& tg)
 {
-    if (!g_opt_thin_fused || g_opt_bf16_inputs) return false;
-    if (a->persistent || a->sample_stats || (a->gauss && a->add_noise)) return false;
-    if (!a->gauss && a->vs == nullptr) return false;
+    if (!g_opt_thin_fused || g_opt_bf16_inputs || !plain_cd(a)) return false;
     if (!thin_geom(a->B, a->V, a->H, a->ldv, a->ldh, std::min(ctx->num_cu, kTargetJobs), tg)) return false;      // (the workspace is sized for <= 256 CUs)
     return (int64_t)tg.G * tg.Bq * a->ldh <= ws.slab_floats && tg.G <= ws.cost_floats;
 }
 
-// mode 0: the whole step; 1: gather + positive phase + chain (mdbn_cd_forward); 2: statistics (+ update) (mdbn_cd_statistics).
-// upd: single-device step, the update kernel consumes each row of S as it forms it; else it stores [S | s_h | s_v | cost].
-static int cd_step_thin(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const mdbn_update_args* upd, const Workspace& ws,
-                        const ThinGeom& tg, int mode, const mdbn_update_args* defer)
+static int thin_setup(const mdbn_cd_args* a, ThinStep& t)
+{
+    t.ahead_ok = a->planes_alt != nullptr && !keeps_f32(a) && t.tg.lds_ahead > 0 && a->indexes != nullptr;
+    if (a->planes_alt) REQUIRE(aligned16(a->planes_alt), "planes_alt not 16-byte aligned");
+    return MDBN_OK;
+}
+
+// forward half: gather + positive phase + chain, W streamed once per pass
+static int thin_forward(hipStream_t s, const mdbn_cd_args* a, const Workspace& ws, const ThinStep& ts, int* n_cost)
 {
     const int64_t B = a->B, V = a->V, H = a->H, ldv = a->ldv, ldh = a->ldh;
-    float* v0 = a->V2;
-    float* nv = a->V2 + B * ldv;
-    float* ph = a->P2;
-    float* nh = a->P2 + B * ldh;
-    int n_cost = tg.G;
-    // positive phase ahead (mdbn_cd_args.next_indexes on the thin path): the previous call's update kernel left v0 in V2 and
-    // the partials of x W in planes_alt; this call's update kernel may do the same for the next one
-    const bool keep = a->keep_f32 != 0 || a->trace_h != nullptr || a->trace_v != nullptr;
-    const bool ahead_ok = a->planes_alt != nullptr && !keep && tg.lds_ahead > 0 && a->indexes != nullptr;
-    const bool ahead_in = ahead_ok && a->v0_ready && mode != 2;
-    if (a->planes_alt) REQUIRE(aligned16(a->planes_alt), "planes_alt not 16-byte aligned");
-    float* part_ahead = reinterpret_cast<float*>(a->planes_alt);
-    if (mode != 2) {
-        ThinPassArgs p{};
-        p.B = (int)B; p.Bq = tg.Bq; p.V = (int)V; p.H = (int)H; p.ldv = ldv; p.ldh = ldh;
-        p.G = tg.G; p.rpw = tg.rpw; p.PW = tg.PW;
-        p.W = a->W; p.part = ws.slabs;
-        p.data = a->data; p.n_data = a->n_data; p.ld_data = ldv; p.idx = a->indexes; p.idx64 = a->index_is_64; p.v0_out = v0;
-        p.vbias = a->vbias; p.gauss = a->gauss;
-        p.stamps = g_stamps;
-        // x = train_set_x[indexes] and the partials of x W                      (dbn.py:307, rbm.py:303)
-        if (!ahead_in) HIP_OK(launch_thin_pass(0, p, tg, s));
-        ThinActArgs act{};
-        act.part = ahead_in ? part_ahead : ws.slabs; act.G = tg.G; act.Bq = tg.Bq;
-        act.e.rows = (int)B; act.e.cols = (int)H; act.e.ld = ldh; act.e.bias = a->hbias;
-        act.e.mean = ph; act.e.mean_scale = 1.0f; act.e.sample = a->hs; act.e.rng = make_key(a->rng, 0u);
+    const ThinGeom& tg = ts.tg;
+    float *v0 = a->V2, *nv = a->V2 + B * ldv, *ph = a->P2, *nh = a->P2 + B * ldh;
+    const bool ahead_in = ts.ahead_ok && a->v0_ready;
+    ThinPassArgs p{};
+    p.B = (int)B; p.Bq = tg.Bq; p.V = (int)V; p.H = (int)H; p.ldv = ldv; p.ldh = ldh;
+    p.G = tg.G; p.rpw = tg.rpw; p.PW = tg.PW;
+    p.W = a->W; p.part = ws.slabs;
+    p.data = a->data; p.n_data = a->n_data; p.ld_data = ldv; p.idx = a->indexes; p.idx64 = a->index_is_64; p.v0_out = v0;
+    p.vbias = a->vbias; p.gauss = a->gauss;
+    p.stamps = g_stamps;
+    // x = train_set_x[indexes] and the partials of x W                      (dbn.py:307, rbm.py:303)
+    if (!ahead_in) HIP_OK(launch_thin_pass(0, p, tg, s));
+    ThinActArgs act{};
+    act.part = ahead_in ? reinterpret_cast<float*>(a->planes_alt) : ws.slabs; act.G = tg.G; act.Bq = tg.Bq;
+    act.e.rows = (int)B; act.e.cols = (int)H; act.e.ld = ldh; act.e.bias = a->hbias;
+    act.e.mean = ph; act.e.mean_scale = 1.0f; act.e.sample = a->hs; act.e.rng = make_key(a->rng, 0u);
+    HIP_OK(launch_thin_act(act, s));
+    act.part = ws.slabs;
+    if (a->trace_h) HIP_OK(hipMemcpyAsync(a->trace_h, a->hs, sizeof(float) * B * ldh, hipMemcpyDeviceToDevice, s));
+    for (int t = 1; t <= a->k; ++t) {                                  // gibbs_hvh x k (rbm.py:318-336)
+        const bool last = t == a->k;
+        p.chain = a->hs; p.nv = nv; p.vs = a->gauss ? nullptr : a->vs; p.last = last ? 1 : 0;
+        p.target = last ? v0 : nullptr; p.ld_target = ldv; p.cost_partials = last ? ws.cost_partials : nullptr;
+        p.rng = make_key(a->rng, (uint32_t)(2 * t - 1));
+        HIP_OK(launch_thin_pass(1, p, tg, s));
+        if (a->trace_v && !a->gauss)
+            HIP_OK(hipMemcpyAsync(a->trace_v + (int64_t)(t - 1) * B * ldv, a->vs, sizeof(float) * B * ldv, hipMemcpyDeviceToDevice, s));
+        act.e.mean = nh; act.e.mean_scale = -1.0f; act.e.sample = last ? nullptr : a->hs;
+        act.e.rng = make_key(a->rng, (uint32_t)(2 * t));
         HIP_OK(launch_thin_act(act, s));
-        act.part = ws.slabs;
-        if (a->trace_h) HIP_OK(hipMemcpyAsync(a->trace_h, a->hs, sizeof(float) * B * ldh, hipMemcpyDeviceToDevice, s));
-        for (int t = 1; t <= a->k; ++t) {                                  // gibbs_hvh x k (rbm.py:318-336)
-            const bool last = t == a->k;
-            p.chain = a->hs; p.nv = nv; p.vs = a->gauss ? nullptr : a->vs; p.last = last ? 1 : 0;
-            p.target = last ? v0 : nullptr; p.ld_target = ldv; p.cost_partials = last ? ws.cost_partials : nullptr;
-            p.rng = make_key(a->rng, (uint32_t)(2 * t - 1));
-            HIP_OK(launch_thin_pass(1, p, tg, s));
-            if (a->trace_v && !a->gauss)
-                HIP_OK(hipMemcpyAsync(a->trace_v + (int64_t)(t - 1) * B * ldv, a->vs, sizeof(float) * B * ldv, hipMemcpyDeviceToDevice, s));
-            act.e.mean = nh; act.e.mean_scale = -1.0f; act.e.sample = last ? nullptr : a->hs;
-            act.e.rng = make_key(a->rng, (uint32_t)(2 * t));
-            HIP_OK(launch_thin_act(act, s));
-            if (a->trace_h && !last)
-                HIP_OK(hipMemcpyAsync(a->trace_h + (int64_t)t * B * ldh, a->hs, sizeof(float) * B * ldh, hipMemcpyDeviceToDevice, s));
-        }
+        if (a->trace_h && !last)
+            HIP_OK(hipMemcpyAsync(a->trace_h + (int64_t)t * B * ldh, a->hs, sizeof(float) * B * ldh, hipMemcpyDeviceToDevice, s));
     }
-    if (mode == 1) {
-        ctx->pending_n_cost = n_cost; ctx->pending_stats = a->stats;
-        return MDBN_OK;
-    }
-    if (mode == 2) n_cost = ctx->pending_n_cost;
-    ctx->pending_n_cost = -1; ctx->pending_stats = nullptr;
-    // the previous step's deferred update (data-parallel order) is its own launch here, ahead of the statistics
-    if (defer) HIP_OK(launch_update(*defer, s, nullptr, 1, 0, reinterpret_cast<unsigned short*>(defer->W_planes)));
+    *n_cost = tg.G;
+    return MDBN_OK;
+}
+
+// statistics half.  upd: single-device step, the update kernel consumes each row of S as it forms it; else it stores
+// [S | s_h | s_v | cost].
+static int thin_statistics(hipStream_t s, const mdbn_cd_args* a, const Workspace& ws, const ThinStep& ts, int n_cost,
+                           const mdbn_update_args* upd)
+{
+    const int64_t B = a->B, V = a->V, H = a->H, ldv = a->ldv, ldh = a->ldh;
+    const ThinGeom& tg = ts.tg;
+    const StatsView st(a->stats, V, ldv, ldh);
     ThinUpdArgs u{};
     u.B = (int)B; u.Bq = tg.Bq; u.V = (int)V; u.H = (int)H; u.ldv = ldv; u.ldh = ldh; u.G = tg.Gu; u.rpw = tg.rpu;
     u.V2 = a->V2; u.P2 = a->P2;
-    u.S = a->stats; u.s_h = a->stats + V * ldh; u.s_v = u.s_h + ldh; u.cost = u.s_v + ldv;
+    u.S = st.S; u.s_h = st.s_h; u.s_v = st.s_v; u.cost = st.cost;
     u.cost_partials = ws.cost_partials; u.n_cost = n_cost;
     const bool fuse_upd = upd && g_opt_fused_update;
     u.do_upd = fuse_upd ? 1 : 0;
     if (fuse_upd) {
-        u.upd.W = upd->W; u.upd.Ws = upd->W_speed; u.upd.W0 = upd->W0; u.upd.ld = ldh; u.upd.rows = (int)V;
-        u.upd.lr = upd->lr; u.upd.l1 = upd->lambda_1; u.upd.l2 = upd->lambda_2; u.upd.wc = upd->weightcost;
-        u.upd.mu = upd->momentum; u.upd.inv_bs = 1.0f / upd->batch_size;
-        u.upd.Wp = reinterpret_cast<unsigned short*>(upd->W_planes); u.upd.wp_stride = V * ldh;
-        u.bu.hb = upd->hbias; u.bu.hbs = upd->hbias_speed; u.bu.vb = upd->vbias; u.bu.vbs = upd->vbias_speed;
-        u.bu.H = H; u.bu.V = V; u.bu.lr = upd->lr; u.bu.mu = upd->momentum; u.bu.inv_rows = 1.0f / upd->n_rows;
-        u.bu.cost_scale = upd->cost_scale; u.bu.cost_out = upd->cost_out;
+        fill_upd(u.upd, *upd, V, ldh, reinterpret_cast<unsigned short*>(upd->W_planes));
+        fill_bias_upd(u.bu, *upd, H);
     }
-    if (fuse_upd && mode == 0 && ahead_ok && a->next_indexes && g_opt_gather_ahead) {
+    // (an update comes with a whole step only: mdbn_cd_train_step)
+    if (fuse_upd && ts.ahead_ok && a->next_indexes && g_opt_gather_ahead) {
         // update(t) + gather and positive-phase partials of step t + 1 in one pass over W
         u.G = tg.G; u.rpw = tg.rpw; u.PW = tg.PW;
         u.data = a->data; u.n_data = a->n_data; u.ld_data = ldv; u.next_idx = a->next_indexes; u.idx64 = a->index_is_64;
-        u.part_next = part_ahead; u.v0_next = a->V2;
+        u.part_next = reinterpret_cast<float*>(a->planes_alt); u.v0_next = a->V2;
         HIP_OK(launch_thin_update_ahead(u, tg, s));
         if (a->ahead_done) *a->ahead_done = 1;
         return MDBN_OK;
     }
     HIP_OK(launch_thin_update(u, tg, s));
-    if (upd && !fuse_upd) {
-        mdbn_update_args uu = *upd;
-        uu.phase = 0;
-        HIP_OK(launch_update(uu, s, nullptr, 1, 0, reinterpret_cast<unsigned short*>(uu.W_planes)));
+    if (upd && !fuse_upd) HIP_OK(launch_whole_update(whole_rule(*upd), s));
+    return MDBN_OK;
+}
+
+// ---------------------------------------------------------------------------------- group-chain step (mdbn_gchain.hip)
+// Mid-size layers: gather + positive phase + the whole Gibbs chain in ONE launch on groups of workgroups that hold W in
+// their LDS between them; it leaves V2 / P2 / the column and cost partials exactly as dense_forward would, so the
+// statistics half of the step is the dense one
+static bool gchain_eligible(const mdbn_ctx* ctx, const mdbn_cd_args* a, const Workspace& ws, GChainGeom& gg)
+{
+    return g_opt_gchain && !g_opt_bf16_inputs && plain_cd(a) &&
+           gchain_geom(a->B, a->V, a->H, a->ldv, a->ldh, a->gauss, std::min(ctx->num_cu, kTargetJobs), gg) &&
+           gg.xbuf_floats <= ws.slab_floats && (int64_t)gg.nslab * gg.g <= ws.cost_floats;
+}
+
+static int gchain_forward(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const Workspace& ws, const GChainGeom& gg, int* n_cost)
+{
+    const int64_t B = a->B, V = a->V, H = a->H, ldv = a->ldv, ldh = a->ldh;
+    if (!ctx->gc_flags) {
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&ctx->gc_flags), sizeof(unsigned) * (GC_MAX_FLAGS + 4)));
+        HIP_OK(hipMemsetAsync(ctx->gc_flags, 0, sizeof(unsigned) * (GC_MAX_FLAGS + 4), s));
+    }
+    GChainArgs c{};
+    c.B = (int)B; c.V = (int)V; c.H = (int)H; c.k = a->k; c.gauss = a->gauss; c.ldv = ldv; c.ldh = ldh;
+    c.g = gg.g; c.Vb = gg.Vb; c.nslab = gg.nslab; c.nsg = gg.nsg; c.PW = gg.PW; c.S1 = gg.S1;
+    c.W = a->W; c.hbias = a->hbias; c.vbias = a->vbias;
+    c.data = a->data; c.n_data = a->n_data; c.ld_data = ldv; c.idx = a->indexes; c.idx64 = a->index_is_64;
+    c.V2 = a->V2; c.P2 = a->P2; c.hs = a->hs; c.vs = a->gauss ? nullptr : a->vs;
+    c.trace_h = a->trace_h; c.trace_v = a->gauss ? nullptr : a->trace_v;
+    c.colPpos = ws.colPpos; c.colPneg = ws.colPneg; c.colV = ws.colV; c.cost_partials = ws.cost_partials;
+    c.xbuf = ws.slabs; c.flags = ctx->gc_flags; c.error = ctx->gc_flags + GC_MAX_FLAGS;
+    c.seq0 = ctx->gc_seq;
+    ctx->gc_seq += (unsigned)(((gg.nslab + gg.nsg - 1) / gg.nsg) * (a->k + 1)) + 1u;
+    c.rng = make_key(a->rng, 0u);
+    HIP_OK(launch_gchain(c, gg.lds, s));
+    *n_cost = gg.nslab * gg.g;
+    return MDBN_OK;
+}
+
+// ---------------------------------------------------------------------------------- dense step (one GEMM launch per pass)
+static int dense_forward(hipStream_t s, const mdbn_cd_args* a, const Workspace& ws, int* n_cost)
+{
+    const int64_t B = a->B, V = a->V, H = a->H, ldv = a->ldv, ldh = a->ldh;
+    float *v0 = a->V2, *nv = a->V2 + B * ldv, *ph = a->P2, *nh = a->P2 + B * ldh;
+    // x = train_set_x[indexes]                                        (dbn.py:307)
+    // (its own launch: read through the index list inside the first propup of the streaming kernel, the rows come from HBM
+    //  at HBM latency into every workgroup's operand stream -- bit-identical and 3 - 10 us per step SLOWER,
+    //  profiles/r05zi_stream_gather_ab.log; gathered AHEAD by extra workgroups of the previous step's statistics launch
+    //  into a second V2 buffer: bit-identical too, and that launch grows by more than the gather launch it saves,
+    //  profiles/r05zm_gather_ahead_dense_ab.log, r05zl_*)
+    HIP_OK(launch_gather(a->data, a->n_data, ldv, ldv, a->indexes, a->index_is_64, B, v0, ldv, s));
+
+    // positive phase: ph_mean, ph_sample                              (rbm.py:303)
+    {
+        Affine up(v0, B, ldv, a->W, V, H, ldh, a->hbias);
+        up.mean = ph; up.sample = a->hs; up.rng = &a->rng;
+        up.colsum = ws.colPpos;                                         // sum_rows ph_mean
+        CHECK(run_affine(up, ws, s, nullptr));
+        if (a->trace_h) HIP_OK(hipMemcpyAsync(a->trace_h, a->hs, sizeof(float) * B * ldh, hipMemcpyDeviceToDevice, s));
+    }
+    for (int t = 1; t <= a->k; ++t) {                                  // gibbs_hvh x k (rbm.py:318-336)
+        const bool last = t == a->k;
+        const float* chain = (t == 1 && a->persistent) ? a->persistent : a->hs;   // rbm.py:308-311
+        // v_t | h_{t-1}: RBM sigmoid + Bernoulli (rbm.py:229-240); GRBM linear mean (rbm.py:647-660;
+        // its noisy sample never feeds the chain, rbm.py:669, so it is not materialised here)
+        // sample_stats (compute_symbolic_grad, rbm.py:339-342,378-390): the negative visible data is
+        // the SAMPLE nv_samples[-1]; it then also is the input of the last propup, as in rbm.py:246
+        const bool samp_stats = last && a->sample_stats && !a->gauss;
+        Affine down(chain, B, ldh, a->W, V, H, ldh, a->vbias, ldv, a->gauss);
+        down.mean = samp_stats ? nullptr : nv;
+        down.sample = a->gauss ? nullptr : (samp_stats ? nv : a->vs);
+        down.target = last ? v0 : nullptr; down.ld_target = ldv; down.want_cost = last;
+        down.rng = &a->rng; down.draw = (uint32_t)(2 * t - 1);
+        down.x_binary = chain == a->hs;         // our own 0/1 hidden samples (a caller's persistent chain may hold anything)
+        if (last) { down.colsum = ws.colV; down.colsum_kind = samp_stats ? 2 : 1; }   // sum_rows (v0 - nv)
+        CHECK(run_affine(down, ws, s, last ? n_cost : nullptr));
+        if (a->trace_v && !a->gauss)
+            HIP_OK(hipMemcpyAsync(a->trace_v + (int64_t)(t - 1) * B * ldv, samp_stats ? nv : a->vs, sizeof(float) * B * ldv,
+                                  hipMemcpyDeviceToDevice, s));
+        // h_t | v_t: from the mean for GRBM (rbm.py:669), from the sample for RBM (rbm.py:246)
+        const bool need_sample = !last || a->persistent != nullptr;
+        float* hdst = (last && a->persistent) ? a->persistent : a->hs;            // rbm.py:369
+        Affine up((a->gauss || samp_stats) ? nv : a->vs, B, ldv, a->W, V, H, ldh, a->hbias);
+        up.mean = nh; up.sample = need_sample ? hdst : nullptr; up.mean_scale = -1.0f;
+        up.rng = &a->rng; up.draw = (uint32_t)(2 * t);
+        up.x_binary = !a->gauss;                // Bernoulli visibles: the chain feeds the 0/1 sample upward
+        if (last) up.colsum = ws.colPneg;                               // sum_rows (-nh_mean)
+        CHECK(run_affine(up, ws, s, nullptr));
+        if (a->trace_h && need_sample)
+            HIP_OK(hipMemcpyAsync(a->trace_h + (int64_t)t * B * ldh, hdst, sizeof(float) * B * ldh, hipMemcpyDeviceToDevice, s));
     }
     return MDBN_OK;
 }
 
-static int cd_step_impl(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a, const mdbn_update_args* upd, int mode = 0,
-                        const mdbn_update_args* defer = nullptr)
+// statistics half of the dense and the group-chain step
+static int dense_statistics(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const Workspace& ws, int n_cost,
+                            const mdbn_update_args* upd)
+{
+    const int64_t B = a->B, V = a->V, H = a->H, ldv = a->ldv, ldh = a->ldh;
+    const StatsView st(a->stats, V, ldv, ldh);
+
+    // The statistics GEMM reads only V2 / P2 -- never W -- and the parameter half of the update
+    // (theta * m + OLD speed * lr, rbm.py:364-365) does not need its result.  With an update
+    // attached (single device) the bias/cost finalize and that parameter half run on a side
+    // stream UNDER the compute-bound GEMM; only the speed half waits for S.
+    bool overlap = false;
+    mdbn_update_args u;
+    if (upd) {
+        u = *upd;
+        overlap = g_opt_update_overlap != 0 && u.lambda_1 == 0.f && (u.weightcost == 0.f || u.W0 != nullptr);
+        if (overlap && ctx->side == nullptr) {
+            HIP_OK(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+            HIP_OK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+            HIP_OK(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+        }
+    }
+    if (overlap) {
+        HIP_OK(hipEventRecord(ctx->ev_fork, s));
+        HIP_OK(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+        HIP_OK(launch_finalize_stats(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials,
+                                     n_cost, st.s_h, st.s_v, st.cost, nullptr, ctx->side));
+        u.phase = 2;
+        HIP_OK(launch_whole_update(u, ctx->side));
+        HIP_OK(hipEventRecord(ctx->ev_join, ctx->side));
+    }
+    const Plan p = plan_stats(V, H, 2 * B, ldh);
+    // Single device, unsplit statistics GEMM: the GEMM applies the weight update to its own tiles
+    // (S never reaches HBM) and the bias / cost half rides on the finalize kernel -- no update launch.
+    const bool fuse_upd = upd && !overlap && g_opt_fused_update && p.splitk == 1;
+    BiasUpd bu;
+    if (fuse_upd) fill_bias_upd(bu, u, H);
+    // ... and even the finalize units run inside the GEMM (its MFMA waves are idle while the first slice is in flight), with
+    // the bias half of a fused update or, on the unfused GEMM of a data-parallel step, without: no finalize launch either
+    const bool fin_in_gemm = !overlap && g_opt_fused_finalize;
+    if (!overlap && !fin_in_gemm)
+        HIP_OK(launch_finalize_stats(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials,
+                                     n_cost, st.s_h, st.s_v, st.cost, fuse_upd ? &bu : nullptr, s));
+    GemmArgs g{};
+    g.A = a->V2; g.lda = ldv; g.B = a->P2; g.ldb = ldh;
+    g.ldc = ldh; g.slab_stride = V * ldh;
+    g.M = (int)V; g.N = (int)H; g.K = (int)(2 * B); g.Nst = (int)ldh;
+    p.fill(g);
+    g.fin_enabled = fin_in_gemm;
+    if (fin_in_gemm)
+        g.fin = make_fin_args(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials, n_cost,
+                              st.s_h, st.s_v, st.cost, fuse_upd ? &bu : nullptr);
+    if (fuse_upd) {
+        g.C = nullptr;
+        g.fused = 2;
+        fill_upd(g.upd, u, V, ldh, reinterpret_cast<unsigned short*>(u.W_planes));
+        HIP_OK(timed_gemm(LAY_MN, LAY_MN, g, s));
+        return MDBN_OK;
+    }
+    if (p.splitk == 1) {
+        g.C = st.S;
+        HIP_OK(timed_gemm(LAY_MN, LAY_MN, g, s));
+    } else {
+        g.C = ws.slabs;
+        HIP_OK(timed_gemm(LAY_MN, LAY_MN, g, s));
+        if (upd && !overlap && g_opt_fused_update) {
+            // single device: the update sums the slabs itself (same order as sum_slabs_kernel, so the
+            // same bits); S is not materialised, as in the fused unsplit case
+            HIP_OK(launch_update(whole_rule(u), s, ws.slabs, p.splitk, g.slab_stride, reinterpret_cast<unsigned short*>(u.W_planes)));
+            return MDBN_OK;
+        }
+        HIP_OK(launch_sum_slabs(ws.slabs, p.splitk, g.slab_stride, V * ldh, st.S, s));
+    }
+    if (upd && !overlap) HIP_OK(launch_whole_update(whole_rule(u), s));
+    if (overlap) {                  // the speed half, once the side stream's parameter half is done: it leaves W's planes alone
+        HIP_OK(hipStreamWaitEvent(s, ctx->ev_join, 0));
+        u.phase = 1;
+        HIP_OK(launch_update(u, s, nullptr, 1, 0, nullptr));
+    }
+    return MDBN_OK;
+}
+
+// ---------------------------------------------------------------------------------- the CD step
+enum class StepPath { OneLaunch, Thin, Planes, GroupChain, Dense };
+
+// One CD-k step, or one half of it; the only place that knows the protocol of the halves: it validates the arguments, chooses
+// the path once, keeps the mdbn_cd_forward -> mdbn_cd_statistics hand-over and runs the path's forward half, its statistics
+// half, or both.  upd: single-device step, the statistics half applies the update.  defer (upd == NULL): the previous step's
+// deferred update (data-parallel order), a launch of its own ahead of the statistics half unless the plane GEMM takes it in.
+static int cd_step_impl(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a, const mdbn_update_args* upd, StepPart part,
+                        const mdbn_update_args* defer)
 {
     REQUIRE(ctx != nullptr && a != nullptr, "NULL argument");
     REQUIRE(a->struct_size == sizeof(mdbn_cd_args),
@@ -1899,228 +2084,64 @@ static int cd_step_impl(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a, cons
         REQUIRE(aligned16(a->W_planes), "W_planes not 16-byte aligned");
         HIP_OK(launch_split_planes(a->W, V, ldh, reinterpret_cast<unsigned short*>(a->W_planes), V * ldh, s));
     }
-    if (mode == 2)
+    // The hand-over: the number of cost partials a forward half left in the workspace, parked under the step's statistics
+    // buffer.  A statistics half that finds its own takes it -- it is consumed from here on, whether or not the call then
+    // succeeds.  Any other call ends a pending one: a forward half or a whole step overwrites the partials in the workspace
+    // (shared by all shapes), whichever path serves it.
+    int n_cost = 0;
+    if (part == StepPart::Statistics) {
         REQUIRE(ctx->pending_stats == a->stats && ctx->pending_n_cost >= 0, "mdbn_cd_statistics must follow mdbn_cd_forward of the same step");
-    // a whole step between a forward half and its statistics half overwrites the partials that half left in the workspace
-    // (shared by all shapes): it ends the hand-over, whichever path serves it
-    if (mode == 0) { ctx->pending_n_cost = -1; ctx->pending_stats = nullptr; }
+        n_cost = ctx->pending_n_cost;
+    }
+    ctx->pending_n_cost = -1; ctx->pending_stats = nullptr;
     if (defer) {
-        REQUIRE(upd == nullptr && mode != 1, "a deferred update goes with the statistics half of a step without its own update");
+        REQUIRE(upd == nullptr && part != StepPart::Forward, "a deferred update goes with the statistics half of a step without its own update");
         REQUIRE(defer->W == a->W && defer->ldh == ldh && defer->ldv == ldv && defer->V == V && defer->H == H,
                 "deferred update does not match the step's parameters");
     }
-    if (small_eligible(a, ws) && !(upd && g_opt_update_overlap)) return cd_step_small(ctx, s, a, upd, ws, mode, defer);
-    {
-        ThinGeom tg;
-        if (thin_eligible(ctx, a, ws, tg) && !(upd && g_opt_update_overlap)) return cd_step_thin(ctx, s, a, upd, ws, tg, mode, defer);
-    }
-    if (planes_eligible(a) && !(upd && g_opt_update_overlap)) {
-        const int rc = cd_step_planes(ctx, s, a, upd, ws, mode, defer);
-        if (mode != 1) { ctx->pending_n_cost = -1; ctx->pending_stats = nullptr; }
-        return rc;
-    }
+    // the side-stream update (update_overlap) exists on the dense path only
+    const bool overlap_upd = upd && g_opt_update_overlap;
+    StepPath path = StepPath::Dense;
+    ThinStep thin;  PlaneStep planes;  GChainGeom gg;
+    if (!overlap_upd && small_eligible(a, ws)) path = StepPath::OneLaunch;
+    else if (!overlap_upd && thin_eligible(ctx, a, ws, thin.tg)) { path = StepPath::Thin; CHECK(thin_setup(a, thin)); }
+    else if (!overlap_upd && planes_eligible(a)) { path = StepPath::Planes; CHECK(planes_setup(a, planes)); }
+    else if (gchain_eligible(ctx, a, ws, gg)) path = StepPath::GroupChain;
 
-    float* v0 = a->V2;
-    float* nv = a->V2 + B * ldv;
-    float* ph = a->P2;
-    float* nh = a->P2 + B * ldh;
-    int n_cost = 0;
-    // Mid-size layers: gather + positive phase + the whole Gibbs chain in ONE launch on groups of workgroups that hold W in
-    // their LDS between them (mdbn_gchain.hip); it leaves V2 / P2 / the column and cost partials exactly as the launches
-    // below would, so the statistics half of the step is unchanged
-    GChainGeom gg;
-    const bool use_gchain = mode != 2 && g_opt_gchain && !g_opt_bf16_inputs && !a->persistent && !a->sample_stats &&
-                            !(a->gauss && a->add_noise) && (a->gauss || a->vs != nullptr) &&
-                            gchain_geom(B, V, H, ldv, ldh, a->gauss, std::min(ctx->num_cu, kTargetJobs), gg) &&
-                            gg.xbuf_floats <= ws.slab_floats && (int64_t)gg.nslab * gg.g <= ws.cost_floats;
-    if (use_gchain) {
-        if (!ctx->gc_flags) {
-            HIP_OK(hipMalloc(reinterpret_cast<void**>(&ctx->gc_flags), sizeof(unsigned) * (GC_MAX_FLAGS + 4)));
-            HIP_OK(hipMemsetAsync(ctx->gc_flags, 0, sizeof(unsigned) * (GC_MAX_FLAGS + 4), s));
+    if (part != StepPart::Statistics) {
+        switch (path) {
+        case StepPath::OneLaunch:  CHECK(small_forward(s, a, ws, &n_cost)); break;
+        case StepPath::Thin:       CHECK(thin_forward(s, a, ws, thin, &n_cost)); break;
+        case StepPath::Planes:     CHECK(planes_forward(ctx, s, a, ws, planes, &n_cost)); break;
+        case StepPath::GroupChain: CHECK(gchain_forward(ctx, s, a, ws, gg, &n_cost)); break;
+        case StepPath::Dense:      CHECK(dense_forward(s, a, ws, &n_cost)); break;
         }
-        GChainArgs c{};
-        c.B = (int)B; c.V = (int)V; c.H = (int)H; c.k = a->k; c.gauss = a->gauss; c.ldv = ldv; c.ldh = ldh;
-        c.g = gg.g; c.Vb = gg.Vb; c.nslab = gg.nslab; c.nsg = gg.nsg; c.PW = gg.PW; c.S1 = gg.S1;
-        c.W = a->W; c.hbias = a->hbias; c.vbias = a->vbias;
-        c.data = a->data; c.n_data = a->n_data; c.ld_data = ldv; c.idx = a->indexes; c.idx64 = a->index_is_64;
-        c.V2 = a->V2; c.P2 = a->P2; c.hs = a->hs; c.vs = a->gauss ? nullptr : a->vs;
-        c.trace_h = a->trace_h; c.trace_v = a->gauss ? nullptr : a->trace_v;
-        c.colPpos = ws.colPpos; c.colPneg = ws.colPneg; c.colV = ws.colV; c.cost_partials = ws.cost_partials;
-        c.xbuf = ws.slabs; c.flags = ctx->gc_flags; c.error = ctx->gc_flags + GC_MAX_FLAGS;
-        c.seq0 = ctx->gc_seq;
-        ctx->gc_seq += (unsigned)(((gg.nslab + gg.nsg - 1) / gg.nsg) * (a->k + 1)) + 1u;
-        c.rng = make_key(a->rng, 0u);
-        HIP_OK(launch_gchain(c, gg.lds, s));
-        n_cost = gg.nslab * gg.g;
     }
-    if (mode != 2 && !use_gchain) {
-
-    // x = train_set_x[indexes]                                        (dbn.py:307)
-    // (its own launch: read through the index list inside the first propup of the streaming kernel, the rows come from HBM
-    //  at HBM latency into every workgroup's operand stream -- bit-identical and 3 - 10 us per step SLOWER,
-    //  profiles/r05zi_stream_gather_ab.log; gathered AHEAD by extra workgroups of the previous step's statistics launch
-    //  into a second V2 buffer: bit-identical too, and that launch grows by more than the gather launch it saves,
-    //  profiles/r05zm_gather_ahead_dense_ab.log, r05zl_*)
-    HIP_OK(launch_gather(a->data, a->n_data, ldv, ldv, a->indexes, a->index_is_64, B, v0, ldv, s));
-
-    // positive phase: ph_mean, ph_sample                              (rbm.py:303)
-    {
-        Affine up{v0, B, ldv, a->W, V, H, ldh, 0, a->hbias, nullptr, ph, a->hs, ldh, 1.0f, 0,
-                  nullptr, 0, false, &a->rng, 0u};
-        up.colsum = ws.colPpos;                                         // sum_rows ph_mean
-        CHECK(run_affine(up, ws, s, nullptr));
-        if (a->trace_h) HIP_OK(hipMemcpyAsync(a->trace_h, a->hs, sizeof(float) * B * ldh, hipMemcpyDeviceToDevice, s));
-    }
-    for (int t = 1; t <= a->k; ++t) {                                  // gibbs_hvh x k (rbm.py:318-336)
-        const bool last = t == a->k;
-        const float* chain = (t == 1 && a->persistent) ? a->persistent : a->hs;   // rbm.py:308-311
-        // v_t | h_{t-1}: RBM sigmoid + Bernoulli (rbm.py:229-240); GRBM linear mean (rbm.py:647-660;
-        // its noisy sample never feeds the chain, rbm.py:669, so it is not materialised here)
-        // sample_stats (compute_symbolic_grad, rbm.py:339-342,378-390): the negative visible data is
-        // the SAMPLE nv_samples[-1]; it then also is the input of the last propup, as in rbm.py:246
-        const bool samp_stats = last && a->sample_stats && !a->gauss;
-        Affine down{chain, B, ldh, a->W, V, H, ldh, 1, a->vbias, nullptr, samp_stats ? nullptr : nv,
-                    a->gauss ? nullptr : (samp_stats ? nv : a->vs),
-                    ldv, 1.0f, a->gauss, last ? v0 : nullptr, ldv, last, &a->rng, (uint32_t)(2 * t - 1)};
-        down.x_binary = chain == a->hs;         // our own 0/1 hidden samples (a caller's persistent chain may hold anything)
-        if (last) { down.colsum = ws.colV; down.colsum_kind = samp_stats ? 2 : 1; }   // sum_rows (v0 - nv)
-        CHECK(run_affine(down, ws, s, last ? &n_cost : nullptr));
-        if (a->trace_v && !a->gauss)
-            HIP_OK(hipMemcpyAsync(a->trace_v + (int64_t)(t - 1) * B * ldv, samp_stats ? nv : a->vs, sizeof(float) * B * ldv,
-                                  hipMemcpyDeviceToDevice, s));
-        // h_t | v_t: from the mean for GRBM (rbm.py:669), from the sample for RBM (rbm.py:246)
-        const bool need_sample = !last || a->persistent != nullptr;
-        float* hdst = (last && a->persistent) ? a->persistent : a->hs;            // rbm.py:369
-        Affine up{(a->gauss || samp_stats) ? nv : a->vs, B, ldv, a->W, V, H, ldh, 0, a->hbias, nullptr, nh,
-                  need_sample ? hdst : nullptr, ldh, -1.0f, 0, nullptr, 0, false, &a->rng, (uint32_t)(2 * t)};
-        up.x_binary = !a->gauss;                // Bernoulli visibles: the chain feeds the 0/1 sample upward
-        if (last) up.colsum = ws.colPneg;                               // sum_rows (-nh_mean)
-        CHECK(run_affine(up, ws, s, nullptr));
-        if (a->trace_h && need_sample)
-            HIP_OK(hipMemcpyAsync(a->trace_h + (int64_t)t * B * ldh, hdst, sizeof(float) * B * ldh, hipMemcpyDeviceToDevice, s));
-    }
-
-    }       // mode != 2
-    if (mode == 1) {
+    if (part == StepPart::Forward) {
         ctx->pending_n_cost = n_cost; ctx->pending_stats = a->stats;
         return MDBN_OK;
     }
-    if (mode == 2) { n_cost = ctx->pending_n_cost; ctx->pending_n_cost = -1; ctx->pending_stats = nullptr; }
-    // (f32-operand kernels: the previous step's deferred update is its own launch, ahead of the statistics GEMM)
-    if (defer) HIP_OK(launch_update(*defer, s, nullptr, 1, 0, reinterpret_cast<unsigned short*>(defer->W_planes)));
-
-    float* S = a->stats;
-    float* s_h = a->stats + V * ldh;
-    float* s_v = s_h + ldh;
-    float* cost = s_v + ldv;
-
-    // The statistics GEMM reads only V2 / P2 -- never W -- and the parameter half of the update
-    // (theta * m + OLD speed * lr, rbm.py:364-365) does not need its result.  With an update
-    // attached (single device) the bias/cost finalize and that parameter half run on a side
-    // stream UNDER the compute-bound GEMM; only the speed half waits for S.
-    bool overlap = false;
-    mdbn_update_args u;
-    if (upd) {
-        u = *upd;
-        REQUIRE(u.stats == a->stats && u.W == a->W && u.ldh == ldh && u.ldv == ldv && u.V == V && u.H == H,
-                "update arguments do not match the step's buffers");
-        overlap = g_opt_update_overlap != 0 && u.lambda_1 == 0.f && (u.weightcost == 0.f || u.W0 != nullptr);
-        if (overlap && ctx->side == nullptr) {
-            HIP_OK(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-            HIP_OK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-            HIP_OK(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        }
+    if (defer && path != StepPath::Planes) HIP_OK(launch_whole_update(*defer, s));
+    switch (path) {
+    case StepPath::OneLaunch:  return small_statistics(s, a, ws, n_cost, upd);
+    case StepPath::Thin:       return thin_statistics(s, a, ws, thin, n_cost, upd);
+    case StepPath::Planes:     return planes_statistics(ctx, s, a, ws, planes, n_cost, upd, defer);
+    case StepPath::GroupChain:
+    case StepPath::Dense:      break;
     }
-    if (overlap) {
-        HIP_OK(hipEventRecord(ctx->ev_fork, s));
-        HIP_OK(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-        HIP_OK(launch_finalize_stats(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials,
-                                     n_cost, s_h, s_v, cost, nullptr, ctx->side));
-        u.phase = 2;
-        HIP_OK(launch_update(u, ctx->side, nullptr, 1, 0, reinterpret_cast<unsigned short*>(u.W_planes)));
-        HIP_OK(hipEventRecord(ctx->ev_join, ctx->side));
-    }
-    const Plan p = plan_stats(V, H, 2 * B, ldh);
-    // Single device, unsplit statistics GEMM: the GEMM applies the weight update to its own tiles
-    // (S never reaches HBM) and the bias / cost half rides on the finalize kernel -- no update launch.
-    const bool fuse_upd = upd && !overlap && g_opt_fused_update && p.splitk == 1;
-    // ... and in the LDS-tiled kernel even the finalize units run inside the GEMM (its MFMA waves are
-    // idle while the first slice is in flight): no finalize launch either
-    const bool fin_in_gemm = fuse_upd && g_opt_fused_finalize;
-    BiasUpd bu;
-    if (fuse_upd) {
-        bu.hb = u.hbias; bu.hbs = u.hbias_speed; bu.vb = u.vbias; bu.vbs = u.vbias_speed;
-        bu.H = H; bu.V = V; bu.lr = u.lr; bu.mu = u.momentum; bu.inv_rows = 1.0f / u.n_rows;
-        bu.cost_scale = u.cost_scale; bu.cost_out = u.cost_out;
-    }
-    // the unfused LDS-tiled statistics GEMM (data-parallel step) runs the plain finalize units the same way
-    const bool fin_in_plain_gemm = !fuse_upd && !overlap && g_opt_fused_finalize;
-    if (!overlap && !fin_in_gemm && !fin_in_plain_gemm)
-        HIP_OK(launch_finalize_stats(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials,
-                                     n_cost, s_h, s_v, cost, fuse_upd ? &bu : nullptr, s));
-    GemmArgs g{};
-    g.A = a->V2; g.lda = ldv; g.B = a->P2; g.ldb = ldh;
-    g.ldc = ldh; g.slab_stride = V * ldh;
-    g.M = (int)V; g.N = (int)H; g.K = (int)(2 * B); g.Nst = (int)ldh;
-    p.fill(g);
-    g.fin_enabled = 0;
-    if (fuse_upd) {
-        g.C = nullptr;
-        g.fused = 2;
-        if (fin_in_gemm) {
-            g.fin_enabled = 1;
-            g.fin = make_fin_args(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials, n_cost,
-                                  s_h, s_v, cost, &bu);
-        }
-        g.upd.W = u.W; g.upd.Ws = u.W_speed; g.upd.W0 = u.W0; g.upd.ld = ldh; g.upd.rows = (int)V;
-        g.upd.lr = u.lr; g.upd.l1 = u.lambda_1; g.upd.l2 = u.lambda_2; g.upd.wc = u.weightcost;
-        g.upd.mu = u.momentum; g.upd.inv_bs = 1.0f / u.batch_size;
-        g.upd.Wp = reinterpret_cast<unsigned short*>(u.W_planes); g.upd.wp_stride = V * ldh;
-        HIP_OK(timed_gemm(LAY_MN, LAY_MN, g, s));
-        return MDBN_OK;
-    }
-    if (fin_in_plain_gemm) {
-        g.fin_enabled = 1;
-        g.fin = make_fin_args(ws.colPpos, ws.colPneg, ws.colV, row_groups(B), ldh, ldv, ws.cost_partials, n_cost,
-                              s_h, s_v, cost, nullptr);
-    }
-    if (p.splitk == 1) {
-        g.C = S;
-        HIP_OK(timed_gemm(LAY_MN, LAY_MN, g, s));
-    } else {
-        g.C = ws.slabs;
-        HIP_OK(timed_gemm(LAY_MN, LAY_MN, g, s));
-        if (upd && !overlap && g_opt_fused_update) {
-            // single device: the update sums the slabs itself (same order as sum_slabs_kernel, so the
-            // same bits); S is not materialised, as in the fused unsplit case
-            u.phase = 0;
-            HIP_OK(launch_update(u, s, ws.slabs, p.splitk, g.slab_stride, reinterpret_cast<unsigned short*>(u.W_planes)));
-            return MDBN_OK;
-        }
-        HIP_OK(launch_sum_slabs(ws.slabs, p.splitk, g.slab_stride, V * ldh, S, s));
-    }
-    if (upd) {
-        if (overlap) {
-            HIP_OK(hipStreamWaitEvent(s, ctx->ev_join, 0));
-            u.phase = 1;
-        } else {
-            u.phase = 0;
-        }
-        HIP_OK(launch_update(u, s, nullptr, 1, 0, u.phase != 1 ? reinterpret_cast<unsigned short*>(u.W_planes) : nullptr));
-    }
-    return MDBN_OK;
+    return dense_statistics(ctx, s, a, ws, n_cost, upd);
 }
 
 int mdbn_cd_step(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a)
 {
     CtxScope ctx_scope(ctx);
-    return cd_step_impl(ctx, stream, a, nullptr);
+    return cd_step_impl(ctx, stream, a, nullptr, StepPart::Whole, nullptr);
 }
 
 int mdbn_cd_forward(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a)
 {
     CtxScope ctx_scope(ctx);
-    return cd_step_impl(ctx, stream, a, nullptr, 1, nullptr);
+    return cd_step_impl(ctx, stream, a, nullptr, StepPart::Forward, nullptr);
 }
 
 int mdbn_cd_statistics(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a, const mdbn_update_args* deferred)
@@ -2130,7 +2151,7 @@ int mdbn_cd_statistics(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a, const
         CHECK(check_update_args(deferred));
         REQUIRE(deferred->phase == 3 || deferred->phase == 0, "a deferred update is phase 3 (or the whole rule, phase 0)");
     }
-    return cd_step_impl(ctx, stream, a, nullptr, 2, deferred);
+    return cd_step_impl(ctx, stream, a, nullptr, StepPart::Statistics, deferred);
 }
 
 int mdbn_cd_train_step(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a, const mdbn_update_args* upd)
@@ -2138,7 +2159,7 @@ int mdbn_cd_train_step(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a, const
     CtxScope ctx_scope(ctx);
     REQUIRE(upd != nullptr, "update arguments are NULL");
     CHECK(check_update_args(upd));
-    return cd_step_impl(ctx, stream, a, upd);
+    return cd_step_impl(ctx, stream, a, upd, StepPart::Whole, nullptr);
 }
 
 int mdbn_free_energy(mdbn_ctx* ctx, void* stream, const float* x, int64_t N, int64_t ldv, const float* W,
@@ -2329,13 +2350,15 @@ int mdbn_ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t
     HIP_OK(launch_ais_visible(st, s));
     for (int k = 1; k <= K; ++k) {
         st.k = k;
-        Affine up{v, M, ldv, W, V, H, ldh, 0, hbias, pre, nullptr, nullptr, ldh, 1.0f, 0, nullptr, 0, false, nullptr, 0u};
+        Affine up(v, M, ldv, W, V, H, ldh, hbias);
+        up.pre = pre;
         up.x_binary = !gauss;
         CHECK(run_affine(up, ws, s, nullptr));
         st.trace = trace_h && k < K ? trace_h + (int64_t)(k - 1) * M * ldh : nullptr;
         HIP_OK(launch_ais_hidden(st, s));
         if (k == K) break;
-        Affine down{h, M, ldh, W, V, H, ldh, 1, zero, pre, nullptr, nullptr, ldv, 1.0f, 1, nullptr, 0, false, nullptr, 0u};
+        Affine down(h, M, ldh, W, V, H, ldh, zero, ldv, 1);
+        down.pre = pre;
         down.x_binary = true;
         CHECK(run_affine(down, ws, s, nullptr));
         st.trace = trace_v ? trace_v + (int64_t)k * M * ldv : nullptr;
@@ -2455,11 +2478,11 @@ int mdbn_gibbs_clamped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, 
         rh.step = rng->step + (uint32_t)(2 * t);     rh.draw = 0;
         rv.step = rng->step + (uint32_t)(2 * t + 1); rv.draw = 0;
         // the passes of mdbn_gibbs_chain.  The visible state may hold real observed values: never the 0/1 operand hint there
-        Affine up{v, B, ldv, W, V, H, ldh, 0, hbias, nullptr, h_mean, (feed_sample || last || trace_h) ? h_sample : nullptr, ldh, 1.0f, 0,
-                  nullptr, 0, false, &rh, 0u};
+        Affine up(v, B, ldv, W, V, H, ldh, hbias);
+        up.mean = h_mean; up.sample = (feed_sample || last || trace_h) ? h_sample : nullptr; up.rng = &rh;
         CHECK(run_affine(up, ws, s, nullptr));
-        Affine down{feed_sample ? h_sample : h_mean, B, ldh, W, V, H, ldh, 1, vbias, nullptr, v_mean, (!gauss || noisy) ? v : nullptr,
-                    ldv, 1.0f, gauss != 0, nullptr, 0, false, &rv, 0u};
+        Affine down(feed_sample ? h_sample : h_mean, B, ldh, W, V, H, ldh, vbias, ldv, gauss != 0);
+        down.mean = v_mean; down.sample = (!gauss || noisy) ? v : nullptr; down.rng = &rv;
         down.x_binary = feed_sample;                     // our own 0/1 hidden samples
         CHECK(run_affine(down, ws, s, nullptr));
         c.v_new = (!gauss || noisy) ? v : v_mean;
@@ -2614,11 +2637,13 @@ int pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, in
         st.trace_v = trace_v ? trace_v + t * rows * ldv : nullptr;
         st.trace_h = trace_h ? trace_h + t * rows * ldh : nullptr;
         st.trace_swaps = trace_swaps ? trace_swaps + t * M * 2 * R : nullptr;
-        Affine down{h, rows, ldh, W, V, H, ldh, 1, zero, pre, nullptr, nullptr, ldv, 1.0f, 1, nullptr, 0, false, nullptr, 0u};
+        Affine down(h, rows, ldh, W, V, H, ldh, zero, ldv, 1);
+        down.pre = pre;
         down.x_binary = true;                            // our own 0/1 hidden samples
         CHECK(run_affine(down, ws, s, nullptr));
         HIP_OK(launch_pt_visible(st, s));
-        Affine up{v, rows, ldv, W, V, H, ldh, 0, hbias, pre, nullptr, nullptr, ldh, 1.0f, 0, nullptr, 0, false, nullptr, 0u};
+        Affine up(v, rows, ldv, W, V, H, ldh, hbias);
+        up.pre = pre;
         up.x_binary = !gauss;
         CHECK(run_affine(up, ws, s, nullptr));
         HIP_OK(launch_pt_swap_hidden(st, s));
