@@ -431,6 +431,39 @@ int  mdbn_ais_run(mdbn_ctx *ctx, void *stream, const float *W, int64_t V, int64_
                   double *logw, float *trace_h, float *trace_v, int path, const mdbn_rng *rng,
                   void *workspace, int64_t workspace_bytes);
 
+/* Clamped annealed importance sampling: the conditional partition function of a layer with part of its visible layer held
+ * -- log p(v_F | v_O) of a held-out block F given the observed block O (Srivastava & Salakhutdinov 2012).  With the columns
+ * O_r of data row r held at obs (mask = 1) the layer is an RBM over the free columns F_r (mask = 0) alone, with the row's own
+ * hidden bias hbias + v_O W_O; its partition function Z_r differs from row to row, so every data row r = 0 .. N - 1 gets
+ * C chains of its own: chain m = 0 .. N C - 1 is clamped to data row m / C (C >= 1, any value: a four-chain Philox block may
+ * span two data rows).  obs [N, ldv]; mask [mask_rows, ldv] holds 0 / 1, mask_rows = N (per element) or 1 (one row for all).
+ * With a(v) = v W + hbias over the WHOLE visible row (held columns included: beta a is the tempered pre-activation of the
+ * conditional RBM) and b_beta = (1 - beta) base_vbias + beta vbias:
+ *   log p*_beta(v_F) = sum_j softplus(beta a_j(v)) + { sum_{i in F} v_i b_beta,i  |  -1/2 sum_{i in F} (v_i - b_beta,i)^2 }
+ * The run is mdbn_ais_run's with M = N C chains and three changes:
+ *   1. after every visible draw, v_1 ~ p_0 included, v := mask ? obs : v;
+ *   2. the bias term of the weight update sums over the free columns only;
+ *   3. (Gaussian) its quadratic term sum_i (vbias - base_vbias)_i^2 becomes the per-mask-row sum over the free columns.
+ * Everything else is mdbn_ais_run's: the arithmetic (float32 products, softplus and row sums in the same order, a held
+ * column entering as 0.f; the per-chain logw [N C] a double), the Philox addressing (steps rng->step, + 2k - 1, + 2k, draw
+ * index 0, the global chain row; a held column's uniform is not used), the paths (0 = by shape, 1 = one launch for
+ * LDS-resident layers -- the observed values and mask bits of a thread's column kept in registers --, 2 = the general path
+ * with the two propagation GEMMs per temperature), v_state [N C, ldv] (nullable) and trace_h [K-1][N C][ldh] / trace_v
+ * [K][N C][ldv] (nullable); the caller advances its step counter by 2K - 1.  The caller finishes in float64, per data row:
+ *   log Z_A,r = H log 2 + { sum_{i in F_r} softplus(base_vbias_i)  |  |F_r| / 2 log 2 pi },
+ *   log Z_r ~ log Z_A,r + logsumexp_c(logw[r C + c]) - log C.
+ * Two limits: with no held column the run IS mdbn_ais_run with M = N C, bit for bit in logw, v_state and the traces; with
+ * every column of a row held nothing is random, v = obs, and logw = sum_j softplus(a_j(obs)) - H log 2 up to the float32
+ * rounding of the telescoping sum.  Bad arguments (N < 1, C < 1, n_betas < 2, mask_rows neither 1 nor N, path 1 on a shape
+ * that does not fit, a workspace shorter than mdbn_ais_cond_workspace_bytes) return MDBN_EINVAL without a launch. */
+int  mdbn_ais_cond_workspace_bytes(mdbn_ctx *ctx, int64_t N, int64_t C, int64_t V, int64_t H, int64_t n_betas, int path, int64_t *bytes);
+int  mdbn_ais_cond_run(mdbn_ctx *ctx, void *stream, const float *W, int64_t V, int64_t H, int64_t ldh,
+                       const float *hbias, const float *vbias, const float *base_vbias, int gauss,
+                       const float *betas, int64_t n_betas,
+                       const float *obs, const float *mask, int64_t mask_rows, int64_t N, int64_t C, int64_t ldv,
+                       float *v_state, double *logw, float *trace_h, float *trace_v, int path,
+                       const mdbn_rng *rng, void *workspace, int64_t workspace_bytes);
+
 /* Clamped Gibbs sampling: the chain of mdbn_gibbs_chain with part of the visible layer held at observed values, and the
  * running means of its conditional expectations -- the posterior of the unobserved visibles (a missing modality under the
  * joint layer of a multimodal DBN, Srivastava & Salakhutdinov 2012) and of the hidden layer given the observed ones.

@@ -141,3 +141,44 @@ def impute_modalities(nets, joint, inputs, n_steps=1000, burn_in=200, n_chains=8
     joint_visible, _ = joint.rbm_layers[0].impute(visible, mask, n_steps=n_steps, burn_in=burn_in, n_chains=n_chains)
     return joint_visible, joint.get_output(joint_visible), {i: nets[i].down_pass(joint_visible[:, lo:lo + w])
                                                            for i, lo, w in missing}
+
+
+def modality_log_likelihood(nets, joint, inputs, target, n_chains=64, n_betas=1000, path=0, base_data=None):
+    """How well the joint layer predicts modality ``target`` from the others, in nats per row (Srivastava & Salakhutdinov
+    2012): log p(block_target | the other blocks) under the joint DBN's first RBM.
+
+    ``nets`` / ``joint`` as ``impute_modalities``; ``inputs[i]``: the data matrix of modality i -- every modality is given.
+    All modalities go up (``get_output``); the target block is scored as the 0 / 1 state ``activation >= 0.5`` (a Bernoulli
+    joint layer gives probability to 0 / 1 states only), the other blocks are held at their activations, and
+    ``RBM.conditional_log_likelihood`` -- clamped AIS on the device, ``n_chains`` chains per row through ``n_betas``
+    temperatures from the base-rate model -- scores it.  ``base_data``: the stacked training activations the base rates are
+    taken from (``RBM.base_rate_vbias``; None: the rows' own activations).  Returns a dict: ``log_p [N]``, ``std_err [N]``
+    (that of the AIS estimate of each row's partition function), ``baseline [N]`` (the same 0 / 1 block under independent
+    Bernoulli units at the block's base rate, float64 on the host), ``gain`` = mean(log_p - baseline) and ``gain_std_err`` =
+    sqrt(sum std_err^2) / N.  Consumes 2 n_betas - 1 RNG steps of the joint layer's first RBM."""
+    import numpy
+    widths = [net.stacked_layers_sizes[-1] for net in nets]
+    if len(inputs) != len(nets) or any(x is None for x in inputs):
+        raise ValueError("one input per modality: every modality is given")
+    if not 0 <= int(target) < len(nets):
+        raise ValueError("target %r is not one of the %d modalities" % (target, len(nets)))
+    rbm = joint.rbm_layers[0]
+    if rbm.gauss:
+        raise ValueError("the joint layer has Gaussian visibles: a block of it is not a 0 / 1 state")
+    blocks = [numpy.asarray(net.get_output(numpy.asarray(getattr(x, "get_value", lambda: x)(), dtype=numpy.float32)), dtype=numpy.float32)
+              for net, x in zip(nets, inputs)]
+    if len(set(len(b) for b in blocks)) != 1:
+        raise ValueError("all modalities need the same number of rows")
+    stacked = numpy.concatenate(blocks, axis=1)
+    lo = sum(widths[:int(target)])
+    hi = lo + widths[int(target)]
+    visible = stacked.copy()
+    visible[:, lo:hi] = (stacked[:, lo:hi] >= 0.5).astype(numpy.float32)
+    mask = numpy.ones((1, stacked.shape[1]), dtype=numpy.float32)
+    mask[:, lo:hi] = 0.0
+    base_vbias = rbm.base_rate_vbias(stacked if base_data is None else base_data)
+    log_p, err = rbm.conditional_log_likelihood(visible, mask, n_chains=n_chains, n_betas=n_betas, base_vbias=base_vbias, path=path)
+    bA = numpy.asarray(base_vbias, dtype=numpy.float64)[lo:hi]
+    baseline = visible[:, lo:hi].astype(numpy.float64) @ bA - numpy.logaddexp(0.0, bA).sum()
+    return dict(log_p=log_p, std_err=err, baseline=baseline, gain=float(numpy.mean(log_p - baseline)),
+                gain_std_err=float(numpy.sqrt((err ** 2).sum()) / len(err)))

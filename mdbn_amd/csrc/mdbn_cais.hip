@@ -1,0 +1,385 @@
+// Clamped annealed importance sampling of a trained RBM / GRBM on gfx950 / MI355X: the run of mdbn_ais.hip with part of the
+// visible layer held at observed values -- the conditional partition function Z_r of the RBM over the free columns of data
+// row r, whose hidden bias is the row's own c + v_O W_O; log p(v_F | v_O) = -F(v) - (bias term of the held columns) - log Z_r.
+// Chain m of the M = N C chains belongs to data row m / C.
+//
+//   a(v) = v W + c over the WHOLE visible row (held columns at obs),  b_beta = b_A + beta (b - b_A)
+//   the run of mdbn_ais.hip with  v := mask ? obs : v   after every visible draw (v_1 ~ p_0 included),
+//                                 s1(v) = sum over the FREE columns of (v_i - [Gaussian] b_A,i) (b - b_A)_i,
+//                                 d2_r  = sum over the FREE columns of mask row r of (b - b_A)_i^2  (Gaussian)
+// A held column enters every sum as 0.f at its own place in mdbn_ais.hip's tree, so with no held column the run is
+// mdbn_ais_run bit for bit; the Philox addressing is unchanged (a held column's uniform is drawn and not used).
+//
+// cais_small_kernel (LDS-resident layers): ais_small_kernel with the clamp of clamp_small_kernel -- both passes hand column
+// `tid` to thread `tid`, so a thread keeps the observed values and mask bits of its column for the slab's four chains (two
+// data rows where C is no multiple of 4) in registers.
+// cais_hidden_kernel / cais_visible_kernel (any shape): ais_hidden_kernel with the chain's own d2, ais_visible_kernel with
+// the clamp and the masked s1.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "mdbn_kernels.h"
+#include "mdbn_device.h"
+#include "mdbn_small.h"
+#include "mdbn_small_passes.h"
+#include "mdbn_sampler_kit.h"
+#include "mdbn_cais.h"
+
+namespace mdbn {
+
+namespace {
+
+// the three helpers of mdbn_ais.hip, restated to the letter (that file keeps its own: the two must agree bit for bit)
+template <bool GAUSS>
+__device__ __forceinline__ void cais_draw_v(const PhiloxKey& key, uint64_t grow0, int col, float beta, float bA, float db,
+                                            const float (&m)[4], const bool (&ok)[4], float (&v)[4], float (&s)[4])
+{
+    const float b4[4] = {beta, beta, beta, beta};
+    float pre[4];
+    tempered_draw_v<GAUSS>(key, grow0, col, b4, bA, db, m, ok, v, pre, s);
+}
+
+__device__ __forceinline__ void cais_draw_h(const PhiloxKey& key, uint64_t grow0, int col, float b1, float b0, bool draw,
+                                            const float (&a)[4], const bool (&ok)[4], float (&h)[4], float (&d)[4])
+{
+    const float b4[4] = {b1, b1, b1, b1};
+    float p[4];
+    tempered_draw_h(key, grow0, col, b4, a, ok, draw, h, p);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) d[e] = ok[e] ? softplus_gap(a[e], b0, b1) : 0.f;
+}
+
+__device__ __forceinline__ double cais_logw_add(double lw, float hsum, float s1, float d2, float b1, float b0, bool gauss)
+{
+    const double B1 = (double)b1, B0 = (double)b0;
+    lw += (double)hsum + (B1 - B0) * (double)s1;
+    if (gauss) lw -= 0.5 * (B1 * B1 - B0 * B0) * (double)d2;
+    return lw;
+}
+
+// the clamp of one (4-chain group, column): a held chain takes its observed value and leaves s1 alone
+__device__ __forceinline__ void cais_clamp(const float (&ob)[4], const bool (&held)[4], float (&v)[4], float (&s)[4])
+{
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        v[e] = held[e] ? ob[e] : v[e];
+        s[e] = held[e] ? 0.f : s[e];
+    }
+}
+
+}  // namespace
+
+template <bool GAUSS, bool TRACE>
+__global__ __launch_bounds__(SM_NT) void cais_small_kernel(CaisSmallArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const SmallLayout& L = a.L;
+    lds_f* const lds = (lds_f*)sm;
+    // small_layout's buffers under the roles they have in ais_small_kernel
+    lds_f* const Wl = lds + L.oW;
+    lds_f* const X = lds + L.oXa;           // [4][ldx] visible state v_k (after the clamp)
+    lds_f* const Hs = lds + L.oHs;          // [4][ldhs] hidden sample h_k
+    lds_f* const part = lds + L.oPart;
+    lds_f* const hbl = lds + L.oHb;         // c
+    lds_f* const bAl = lds + L.oVb;         // b_A
+    lds_f* const dbl = lds + L.oCsV;        // b - b_A
+    lds_f* const redH = lds + L.oM0;        // [4][8] per-wave row partials of the hidden share (one per 64-column tile)
+    lds_f* const redV = redH + 32;          // [4][8] ... of s1
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int V = a.V, H = a.H, M = a.M, K = a.K, C = a.C;
+    const int64_t ldv = a.ldv, ldh = a.ldh;
+    const int nslabs = (M + SM_ROWS - 1) / SM_ROWS;
+
+    // ---- the LDS image: W, the biases, zeroed row buffers
+    sm_stage_w(Wl, L, a.W, V, ldh, tid);
+    sm_stage_bias(hbl, a.hbias, L.H64, H, tid);
+    sm_stage_bias_pair(bAl, dbl, a.vbias, a.base_vbias, L.V64, V, tid);
+    sm_zero_rows(X, L.ldx, tid);
+    sm_zero_rows(Hs, L.ldhs, tid);
+    SM_SYNC();
+
+    for (int slab = blockIdx.x; slab < nslabs; slab += gridDim.x) {
+        const int row0 = slab * SM_ROWS;
+        const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
+        bool ok[4];
+        int64_t mrow[4];                     // where the chain's mask row starts
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            ok[e] = row0 + e < M;
+            mrow[e] = a.mask_rows == 1 ? 0 : (int64_t)((row0 + e) / C) * ldv;
+        }
+        if (slab != (int)blockIdx.x) SM_SYNC();                        // (the previous slab's last readers are done)
+
+        // ---- the clamp of this thread's column, in registers for the whole slab
+        float ob[4] = {0.f, 0.f, 0.f, 0.f};
+        bool held[4] = {false, false, false, false};
+        if (tid < V) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (!ok[e]) continue;
+                held[e] = a.mask[mrow[e] + tid] != 0.f;
+                ob[e] = a.obs[(int64_t)((row0 + e) / C) * ldv + tid];
+            }
+        }
+        // d2 of the chain's mask row: ais_small_kernel's sum (lane-strided, then the wave's tree) with a held column as 0.f.
+        // Only the first wave needs it (thread e < 4 keeps chain e's log w).
+        float d2 = 0.f;
+        if (GAUSS && wave == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float t = 0.f;
+                for (int i = lane; i < L.V64; i += 64) {
+                    const bool free_col = !(ok[e] && i < V && a.mask[mrow[e] + i] != 0.f);
+                    const float d = free_col ? dbl[i] : 0.f;
+                    t += d * d;
+                }
+                t = wave_sum(t);
+                if (tid == e) d2 = t;
+            }
+        }
+
+        // a visible state goes into X; its share of s1 into redV (whole waves: V64 is a multiple of 64)
+        auto put_v = [&](const float (&v)[4], const float (&s)[4], int col, float* trace) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) X[e * L.ldx + col] = v[e];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float t = wave_sum(s[e]);
+                if (lane == 0) redV[e * 8 + (col >> 6)] = t;
+            }
+            if (TRACE && trace && col < (int)ldv) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (ok[e]) trace[(int64_t)(row0 + e) * ldv + col] = v[e];
+            }
+        };
+        // ---- the chain's start: v_1 ~ p_0 (step s) under the clamp, or the state an earlier launch left
+        double lw = 0.0;
+        if (tid < L.V64) {
+            const int col = tid;
+            const bool live = col < V;
+            const float bA = bAl[col], db = dbl[col];
+            const bool okc[4] = {ok[0] && live, ok[1] && live, ok[2] && live, ok[3] && live};
+            float v[4], s[4];
+            if (a.k0 == 0) {
+                const float m0[4] = {0.f, 0.f, 0.f, 0.f};
+                cais_draw_v<GAUSS>(a.rng, grow0, col, 0.0f, bA, db, m0, okc, v, s);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = okc[e] ? a.v_state[(int64_t)(row0 + e) * ldv + col] : 0.f;
+                    s[e] = okc[e] ? (GAUSS ? (v[e] - bA) * db : v[e] * db) : 0.f;
+                }
+            }
+            cais_clamp(ob, held, v, s);
+            put_v(v, s, col, a.k0 == 0 ? a.trace_v : nullptr);
+        }
+        if (a.k0 > 0 && tid < SM_ROWS && row0 + tid < M) lw = a.logw[row0 + tid];
+        SM_SYNC();
+        float s1 = 0.f;
+        if (tid < SM_ROWS)
+            for (int t = 0; t < L.tiles_dn; ++t) s1 += redV[tid * 8 + t];
+
+        // ---- the temperatures of this launch (beta_{k+1} is requested one temperature ahead of its use)
+        float b0 = a.betas[a.k0], b1 = a.betas[a.k0 + 1];
+        for (int k = a.k0 + 1; k <= a.k1; ++k) {
+            const float b_next = a.betas[min(k + 1, K)];
+            const bool draw = k < K;
+            PhiloxKey kh = a.rng, kv = a.rng;
+            kh.step = a.rng.step + (uint32_t)(2 * k - 1);
+            kv.step = a.rng.step + (uint32_t)(2 * k);
+            sm_up(X, Wl, L, part, wave, lane, [] {},
+                  [&](const sf32x4& x, int col) {
+                      const bool live = col < H;
+                      const float bias = hbl[col];
+                      const bool okc[4] = {ok[0] && live, ok[1] && live, ok[2] && live, ok[3] && live};
+                      const float pre[4] = {x[0] + bias, x[1] + bias, x[2] + bias, x[3] + bias};
+                      float h[4], d[4];
+                      cais_draw_h(kh, grow0, col, b1, b0, draw, pre, okc, h, d);
+#pragma unroll
+                      for (int e = 0; e < 4; ++e) Hs[e * L.ldhs + col] = h[e];
+#pragma unroll
+                      for (int e = 0; e < 4; ++e) {
+                          const float t = wave_sum(d[e]);
+                          if (lane == 0) redH[e * 8 + (col >> 6)] = t;
+                      }
+                      if (TRACE && a.trace_h && draw && col < (int)ldh) {
+#pragma unroll
+                          for (int e = 0; e < 4; ++e)
+                              if (ok[e]) a.trace_h[((int64_t)(k - 1) * M + row0 + e) * ldh + col] = h[e];
+                      }
+                  });
+            if (tid < SM_ROWS) {
+                float hsum = 0.f;
+                for (int t = 0; t < L.tiles_up; ++t) hsum += redH[tid * 8 + t];
+                lw = cais_logw_add(lw, hsum, s1, d2, b1, b0, GAUSS);
+            }
+            if (draw) {
+                sm_down(Hs, Wl, L, wave, lane,
+                        [&](const sf32x4& x, int col) {                // col == tid: ob / held are this column's
+                            const bool live = col < V;
+                            const float bA = bAl[col], db = dbl[col];
+                            const bool okc[4] = {ok[0] && live, ok[1] && live, ok[2] && live, ok[3] && live};
+                            const float m[4] = {x[0], x[1], x[2], x[3]};
+                            float v[4], s[4];
+                            cais_draw_v<GAUSS>(kv, grow0, col, b1, bA, db, m, okc, v, s);
+                            cais_clamp(ob, held, v, s);
+                            put_v(v, s, col, TRACE && a.trace_v ? a.trace_v + (int64_t)k * M * ldv : nullptr);
+                        });
+                if (tid < SM_ROWS) {
+                    s1 = 0.f;
+                    for (int t = 0; t < L.tiles_dn; ++t) s1 += redV[tid * 8 + t];
+                }
+            }
+            b0 = b1; b1 = b_next;
+        }
+
+        // ---- what the next launch (or the caller) reads: the visible state and log w
+        if (a.v_state) {
+            for (int i = tid; i < SM_ROWS * (int)ldv; i += SM_NT) {
+                const int e = i / (int)ldv, col = i - e * (int)ldv;
+                if (row0 + e < M) a.v_state[(int64_t)(row0 + e) * ldv + col] = X[e * L.ldx + col];
+            }
+        }
+        if (tid < SM_ROWS && row0 + tid < M) a.logw[row0 + tid] = lw;
+    }
+}
+
+hipError_t launch_cais_small(const CaisSmallArgs& a, hipStream_t s)
+{
+    if (!ais_small_ok(a.M, a.V, a.H, a.gauss, a.ldv, a.ldh) || a.k0 < 0 || a.k1 <= a.k0 || a.k1 > a.K || a.C < 1 || a.M % a.C != 0 ||
+        (a.mask_rows != 1 && a.mask_rows != a.M / a.C))
+        return hipErrorInvalidValue;
+    const SmallLayout L = small_layout(a.V, a.H, a.gauss != 0);
+    const bool trace = a.trace_h || a.trace_v;
+    const int variant = (a.gauss ? 2 : 0) | (trace ? 1 : 0);
+    void (*const kerns[4])(CaisSmallArgs) = {cais_small_kernel<false, false>, cais_small_kernel<false, true>, cais_small_kernel<true, false>,
+                                             cais_small_kernel<true, true>};
+    // launch_ais_small's grid: one workgroup per slab up to one per CU of the chip
+    const int nslabs = (a.M + SM_ROWS - 1) / SM_ROWS;
+    const dim3 grid(nslabs < 256 ? nslabs : 256), block(SM_NT);
+    CaisSmallArgs k = a;
+    k.L = L;
+    return launch_small_variant(kerns, variant, grid, block, L.bytes, s, k);
+}
+
+// ----------------------------------------------------------------------------------
+// General path: the kernels of mdbn_ais.hip's general path (a workgroup of AIS_NT threads owns one four-chain group; a thread
+// walks the columns tid, tid + AIS_NT, ... and the four row sums are combined wave by wave in a fixed order) under the clamp.
+// ----------------------------------------------------------------------------------
+// one wave per mask row: ais_d2_kernel's sum with a held column as 0.f
+__global__ __launch_bounds__(64) void cais_d2_kernel(const float* vbias, const float* base_vbias, const float* mask, int V, int64_t ldv, float* d2)
+{
+    const float* mrow = mask + (int64_t)blockIdx.x * ldv;
+    float t = 0.f;
+    for (int i = threadIdx.x; i < V; i += 64) { const float d = mrow[i] != 0.f ? 0.f : vbias[i] - base_vbias[i]; t += d * d; }
+    t = wave_sum(t);
+    if (threadIdx.x == 0) d2[blockIdx.x] = t;
+}
+
+__global__ __launch_bounds__(AIS_NT) void cais_hidden_kernel(CaisStepArgs a)
+{
+    __shared__ float red[4 * (AIS_NT / 64)];
+    const int row0 = (int)blockIdx.x * 4, tid = threadIdx.x;
+    const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
+    const float b1 = a.betas[a.k], b0 = a.betas[a.k - 1];
+    const bool draw = a.k < a.K;
+    PhiloxKey key = a.rng;
+    key.step = a.rng.step + (uint32_t)(2 * a.k - 1);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int col = tid; col < (int)a.ldh; col += AIS_NT) {
+        const bool live = col < a.H;
+        bool ok[4];
+        float pre[4], h[4], d[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            ok[e] = live && row0 + e < a.M;
+            pre[e] = ok[e] ? a.pre[(int64_t)(row0 + e) * a.ldh + col] : 0.f;
+        }
+        cais_draw_h(key, grow0, col, b1, b0, draw, pre, ok, h, d);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[e] += d[e];
+            if (row0 + e < a.M) {
+                a.h[(int64_t)(row0 + e) * a.ldh + col] = h[e];          // (pad columns: zeros)
+                if (a.trace && draw) a.trace[(int64_t)(row0 + e) * a.ldh + col] = h[e];
+            }
+        }
+    }
+    rows4_block_sum<AIS_NT>(acc, red);
+    if (tid < 4 && row0 + tid < a.M) {
+        const float hsum = tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3];
+        const double lw = a.k == 1 ? 0.0 : a.logw[row0 + tid];
+        const float d2 = a.gauss ? a.d2[a.mask_rows == 1 ? 0 : (row0 + tid) / a.C] : 0.f;
+        a.logw[row0 + tid] = cais_logw_add(lw, hsum, a.s1[row0 + tid], d2, b1, b0, a.gauss != 0);
+    }
+}
+
+template <bool GAUSS>
+__global__ __launch_bounds__(AIS_NT) void cais_visible_kernel(CaisStepArgs a)
+{
+    __shared__ float red[4 * (AIS_NT / 64)];
+    const int row0 = (int)blockIdx.x * 4, tid = threadIdx.x;
+    const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
+    const float beta = a.k == 0 ? 0.0f : a.betas[a.k];
+    PhiloxKey key = a.rng;
+    key.step = a.rng.step + (uint32_t)(2 * a.k);
+    int64_t drow[4];                         // where the chain's data row starts in obs (and in a per-row mask)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) drow[e] = (int64_t)((row0 + e) / a.C) * a.ldv;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int col = tid; col < (int)a.ldv; col += AIS_NT) {
+        const bool live = col < a.V;
+        const float bA = live ? a.base_vbias[col] : 0.f, db = live ? a.vbias[col] - bA : 0.f;
+        bool ok[4], held[4];
+        float m[4], v[4], s[4], ob[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            ok[e] = live && row0 + e < a.M;
+            m[e] = ok[e] && a.k > 0 ? a.pre[(int64_t)(row0 + e) * a.ldv + col] : 0.f;
+            held[e] = ok[e] && a.mask[(a.mask_rows == 1 ? 0 : drow[e]) + col] != 0.f;
+            ob[e] = held[e] ? a.obs[drow[e] + col] : 0.f;
+        }
+        cais_draw_v<GAUSS>(key, grow0, col, beta, bA, db, m, ok, v, s);
+        cais_clamp(ob, held, v, s);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[e] += s[e];
+            if (row0 + e < a.M) {
+                a.v[(int64_t)(row0 + e) * a.ldv + col] = v[e];
+                if (a.trace) a.trace[(int64_t)(row0 + e) * a.ldv + col] = v[e];
+            }
+        }
+    }
+    rows4_block_sum<AIS_NT>(acc, red);
+    if (tid < 4 && row0 + tid < a.M) a.s1[row0 + tid] = tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3];
+}
+
+hipError_t launch_cais_d2(const float* vbias, const float* base_vbias, const float* mask, int mask_rows, int V, int64_t ldv, float* d2,
+                          hipStream_t s)
+{
+    if (mask_rows < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cais_d2_kernel, dim3(mask_rows), dim3(64), 0, s, vbias, base_vbias, mask, V, ldv, d2);
+    return hipGetLastError();
+}
+
+static bool cais_step_ok(const CaisStepArgs& a)
+{
+    return a.M >= 1 && a.C >= 1 && a.M % a.C == 0 && (a.mask_rows == 1 || a.mask_rows == a.M / a.C);
+}
+
+hipError_t launch_cais_hidden(const CaisStepArgs& a, hipStream_t s)
+{
+    if (!cais_step_ok(a) || a.k < 1 || a.k > a.K) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cais_hidden_kernel, dim3((a.M + 3) / 4), dim3(AIS_NT), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cais_visible(const CaisStepArgs& a, hipStream_t s)
+{
+    if (!cais_step_ok(a) || a.k < 0 || a.k >= a.K) return hipErrorInvalidValue;
+    if (a.gauss) hipLaunchKernelGGL((cais_visible_kernel<true>), dim3((a.M + 3) / 4), dim3(AIS_NT), 0, s, a);
+    else hipLaunchKernelGGL((cais_visible_kernel<false>), dim3((a.M + 3) / 4), dim3(AIS_NT), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace mdbn

@@ -553,6 +553,63 @@ class HipEngine(object):
             return out, trace_h.cpu().numpy()[:K - 1, :, :H], trace_v.cpu().numpy()[:, :, :V]
         return out
 
+    def ais_conditional(self, W, hbias, vbias, base_vbias, gauss, betas, obs, mask, n_chains, rng, path=0, trace=False, state=False):
+        """Annealed importance sampling of the layer with the visibles where ``mask`` is 1 held at ``obs``, ``n_chains`` chains
+        for each of the N rows of ``obs``, in ONE library call (mdbn_ais_cond_run): the log importance weights of the
+        conditional partition functions as a float64 numpy array [N, n_chains] (one device -> host copy) and, with ``trace``,
+        the hidden [K-1, N n_chains, H] and visible [K, N n_chains, V] samples of every temperature (chain m belongs to row
+        m // n_chains) and, with ``state``, last of all the final visible state [N n_chains, V].  ``mask``: [N, V], or [1, V] for
+        every row.  ``betas``, ``base_vbias`` and ``path`` as ``ais``.  Consumes 2K - 1 RNG steps from ``rng.step``."""
+        obs = self.as_matrix(obs)
+        N, V = (int(x) for x in obs.shape)
+        if V != W.shape[0]:
+            raise ValueError("obs has %d columns, the layer %d visible units" % (V, W.shape[0]))
+        H = W.shape[1]
+        Cn = int(n_chains)
+        if N < 1 or Cn < 1:
+            raise ValueError("need at least one row and one chain per row, got %d, %d" % (N, Cn))
+        M = N * Cn
+        ldh, ldv = W.stride(0), padded_ld(V)
+        betas = numpy.ascontiguousarray(betas, dtype=numpy.float32)
+        if betas.ndim != 1 or betas.size < 2 or betas[0] != 0.0 or betas[-1] != 1.0 or not (numpy.diff(betas) > 0).all():
+            raise ValueError("betas must rise strictly from 0 to 1")
+        K = betas.size - 1
+
+        def padded(x, rows):
+            x = self.as_matrix(x)
+            if tuple(x.shape) != (rows, V):
+                raise ValueError("expected a [%d, %d] matrix, got %r" % (rows, V, tuple(x.shape)))
+            if x.stride(0) != ldv:
+                t = self.alloc_matrix(rows, V, ldv)
+                t.copy_(x)
+                x = t
+            return x
+        mask = self.as_matrix(mask)
+        mask_rows = int(mask.shape[0])
+        if mask_rows not in (1, N):
+            raise ValueError("mask has %d rows: neither 1 nor the %d rows of obs" % (mask_rows, N))
+        obs, mask = padded(obs, N), padded(mask, mask_rows)
+        d_betas = torch.from_numpy(betas).to(self.device)
+        base = self.to_device(numpy.asarray(base_vbias, dtype=numpy.float32)) if not isinstance(base_vbias, torch.Tensor) \
+            else base_vbias.to(device=self.device, dtype=torch.float32).contiguous()
+        ws = self._sampler_workspace(self.lib.mdbn_ais_cond_workspace_bytes, "mdbn_ais_cond_workspace_bytes", (N, Cn, V), H, ldh, path,
+                                     extra=(K + 1,))
+        logw = torch.zeros(M, dtype=torch.float64, device=self.device)
+        v_state = self.alloc_matrix(M, V, ldv)
+        trace_h = torch.zeros((max(K - 1, 1), M, ldh), dtype=torch.float32, device=self.device) if trace else None
+        trace_v = torch.zeros((K, M, ldv), dtype=torch.float32, device=self.device) if trace else None
+        r = rng.c()
+        _lib.check(self.lib.mdbn_ais_cond_run(
+            self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base), int(bool(gauss)),
+            self._p(d_betas), K + 1, self._p(obs), self._p(mask), mask_rows, N, Cn, ldv, self._p(v_state), self._p(logw),
+            self._p(trace_h), self._p(trace_v), int(path), C.byref(r), self._p(ws), ws.numel() * 4), "mdbn_ais_cond_run")
+        out = (logw.cpu().numpy().reshape(N, Cn),)
+        if trace:
+            out += (trace_h.cpu().numpy()[:K - 1, :, :H], trace_v.cpu().numpy()[:, :, :V])
+        if state:
+            out += (v_state.cpu().numpy()[:, :V],)
+        return out if len(out) > 1 else out[0]
+
     def temper(self, W, hbias, vbias, base_vbias, gauss, betas, v, h, rank, n_sweeps, rng, burn_in=0, sweep0=0, path=0,
                steps_per_launch=0, trace=False, zacc=None, trace_work=False):
         """``n_sweeps`` parallel-tempering sweeps of M ladders of R replicas in ONE library call (mdbn_pt_run).  ``v``

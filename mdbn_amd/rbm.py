@@ -491,6 +491,22 @@ def ais_estimate(logw, base_vbias, n_hidden, gauss):
     return float(log_Z), float(err)
 
 
+def ais_estimate_rows(logw, base_vbias, mask, n_hidden, gauss):
+    """``(log_Z [N], std_err [N])`` from the log importance weights ``logw`` [N, C] of a clamped AIS run (float64 on the host),
+    per data row r: log Z_A,r + logsumexp_c(logw[r]) - log C, with the base-rate model over the row's free columns (``mask``
+    [1 | N, V] zero) alone -- log Z_A,r = H log 2 + sum_free softplus(b_A) (Bernoulli) | H log 2 + |free| / 2 log 2 pi
+    (Gaussian) -- and ``ais_estimate``'s delta-method standard error std(w) / (mean(w) sqrt(C)) of each row."""
+    logw = numpy.asarray(logw, dtype=numpy.float64)
+    free = numpy.broadcast_to(numpy.asarray(mask) == 0, (logw.shape[0], numpy.asarray(mask).shape[1]))
+    bA = numpy.asarray(base_vbias, dtype=numpy.float64)
+    per_col = numpy.full(bA.shape, 0.5 * numpy.log(2.0 * numpy.pi)) if gauss else numpy.logaddexp(0.0, bA)
+    log_ZA = n_hidden * numpy.log(2.0) + (free * per_col[None, :]).sum(axis=1)
+    top = logw.max(axis=1)
+    w = numpy.exp(logw - top[:, None])
+    mean = w.mean(axis=1)
+    return log_ZA + top + numpy.log(mean), w.std(axis=1) / (mean * numpy.sqrt(logw.shape[1]))
+
+
 class RBM(object):
     """Restricted Boltzmann Machine (RBM) -- Bernoulli visible and hidden units."""
 
@@ -796,6 +812,58 @@ class RBM(object):
         # (an observed entry is its observed value, not the float32 mean of n_steps copies of it)
         v_hat = numpy.where(held, x, v_hat)
         return v_hat.astype(numpy.float32), h_hat.astype(numpy.float32)
+
+    # ------------------------------------------------------------------ conditional likelihood (clamped AIS)
+    def conditional_log_partition(self, v, observed_mask, n_chains=64, betas=None, n_betas=None, base_vbias=None, data=None, path=0):
+        """``(log_Z [N], std_err [N])``: for every row of ``v`` the log partition function of the layer with the visibles where
+        ``observed_mask`` is nonzero held at their values in ``v`` -- an RBM over the row's free visibles with the hidden bias
+        hbias + v_O W_O -- by annealed importance sampling on the device (mdbn_ais_cond_run), ``n_chains`` chains per row.
+        ``observed_mask``: [N, V] per element, or [V] / [1, V] for every row; the free entries of ``v`` are ignored.
+        ``betas`` / ``n_betas`` / ``base_vbias`` / ``data``: the schedule and the base-rate model, as ``log_partition`` (the
+        base-rate model of a row is ``base_vbias`` on its free columns).  The logsumexp and the delta-method standard error of
+        every row are float64 numpy on the host (``ais_estimate_rows``); a row with no free column has std_err 0.  Consumes
+        2K - 1 RNG steps."""
+        x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
+        if x.ndim != 2 or x.shape[1] != self.n_visible or x.shape[0] < 1:
+            raise ValueError("v must be [N >= 1, %d], got %r" % (self.n_visible, x.shape))
+        mask = self._clamp_mask(observed_mask, x.shape[0])
+        if betas is None:
+            betas = numpy.linspace(0.0, 1.0, int(1000 if n_betas is None else n_betas) + 1)
+        betas = numpy.asarray(betas, dtype=numpy.float32)
+        K = betas.size - 1
+        if base_vbias is None:
+            base_vbias = self.base_rate_vbias(data) if data is not None else self.vbias.get_value()
+        base_vbias = numpy.asarray(base_vbias, dtype=numpy.float32)
+        step = self._rng_step
+        logw = self.engine.ais_conditional(self.W.tensor, self.hbias.tensor, self.vbias.tensor, base_vbias, self.gauss, betas,
+                                           numpy.where(numpy.broadcast_to(mask != 0, x.shape), x, numpy.float32(0)), mask, int(n_chains),
+                                           RngAddr(self.theano_rng.seed, self.stream_id, step, 0, 0), path=path)
+        self._rng_step = step + 2 * K - 1
+        return ais_estimate_rows(logw, base_vbias, mask, self.n_hidden, self.gauss)
+
+    def conditional_log_likelihood(self, v, observed_mask, **ais):
+        """``(log_p [N], std_err [N])``: log p(v_F | v_O) of every row of ``v`` -- its free block F (``observed_mask`` zero)
+        given its observed block O, Srivastava & Salakhutdinov 2012 --
+            -free_energy(v) - sum_{i in O} v_i b_i - log_Z_r                (Bernoulli visibles)
+            -free_energy(v) + 1/2 sum_{i in O} (v_i - b_i)^2 - log_Z_r      (Gaussian visibles)
+        with ``conditional_log_partition(v, observed_mask, **ais)``'s estimate of log_Z_r (the standard error is that
+        estimate's); the free energy is the device's, the rest float64 on the host.  A row with no free column gets log_p = 0,
+        std_err = 0.  A Bernoulli layer gives probability to 0 / 1 states only: free entries of ``v`` that are neither are
+        refused (observed entries may hold any real value: they enter through v W alone)."""
+        x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
+        if x.ndim != 2 or x.shape[1] != self.n_visible or x.shape[0] < 1:
+            raise ValueError("v must be [N >= 1, %d], got %r" % (self.n_visible, x.shape))
+        held = numpy.broadcast_to(self._clamp_mask(observed_mask, x.shape[0]) != 0, x.shape)
+        if not self.gauss and not numpy.isin(x[~held], (0.0, 1.0)).all():
+            raise ValueError("a Bernoulli layer scores 0 / 1 states: a free entry of v is neither")
+        log_Z, err = self.conditional_log_partition(x, observed_mask, **ais)
+        neg_F = -numpy.asarray(self.free_energy(x).get_value(), dtype=numpy.float64)
+        b = numpy.asarray(self.vbias.get_value(), dtype=numpy.float64)[None, :]
+        x64 = x.astype(numpy.float64)
+        held_term = 0.5 * (held * (x64 - b) ** 2).sum(axis=1) if self.gauss else -(held * x64 * b).sum(axis=1)
+        log_p = neg_F + held_term - log_Z
+        none_free = held.all(axis=1)
+        return numpy.where(none_free, 0.0, log_p), numpy.where(none_free, 0.0, err)
 
     # ------------------------------------------------------------------ parallel tempering
     def tempered_chains(self, n_ladders, betas=None, n_betas=16, base_vbias=None, data=None, start_h=None):
