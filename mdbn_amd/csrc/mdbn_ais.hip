@@ -14,9 +14,20 @@
 // draw index 0, the usual (column, global row >> 2) addressing -- so a run cut into several launches, the one-launch path and
 // the general path all meet the same uniforms.
 //
+// The clamp (mdbn_ais_cond_run): part of the visible layer held at observed values -- the conditional partition function Z_r of
+// the RBM over the free columns of data row r, whose hidden bias is the row's own c + v_O W_O; log p(v_F | v_O) = -F(v) - (bias
+// term of the held columns) - log Z_r.  Chain m of the M = N C chains belongs to data row m / C.
+//   a(v) over the WHOLE visible row (held columns at obs);  v := mask ? obs : v  after every visible draw (v_1 ~ p_0 included),
+//   s1(v) and d2_r = sum_i (b - b_A)_i^2 over the FREE columns (of mask row r)
+// A held column enters every sum as 0.f at its own place in the free run's tree, so with no held column the clamped kernels give
+// the free run bit for bit; the Philox addressing is unchanged (a held column's uniform is drawn and not used).  CLAMP = false
+// is the free run: no mask, no obs, one d2 for all chains.
+//
 // ais_small_kernel (LDS-resident layers): the shape of small_cd_kernel -- W staged once into one CU's LDS, a workgroup owns
 // four-chain slabs (one Philox block) and runs the whole loop over the temperatures on the exact-f32 4x4x1 MFMA passes of
-// mdbn_small_passes.h.  No workgroup ever waits for, or exchanges anything with, another.
+// mdbn_small_passes.h.  No workgroup ever waits for, or exchanges anything with, another.  Both passes hand column `tid` to
+// thread `tid`, so under the clamp a thread keeps the observed values and mask bits of its column for the slab's four chains (two
+// data rows where C is no multiple of 4) in registers.
 // ais_hidden_kernel / ais_visible_kernel (any shape): the per-temperature epilogues around the library's propup / propdown
 // GEMMs; a workgroup owns a four-chain group and reduces its rows in a fixed order.
 #include <hip/hip_runtime.h>
@@ -63,9 +74,28 @@ __device__ __forceinline__ double ais_logw_add(double lw, float hsum, float s1, 
     return lw;
 }
 
+// the clamp of one (4-chain group, column): a held chain takes its observed value and leaves s1 alone
+__device__ __forceinline__ void ais_clamp(const float (&ob)[4], const bool (&held)[4], float (&v)[4], float (&s)[4])
+{
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        v[e] = held[e] ? ob[e] : v[e];
+        s[e] = held[e] ? 0.f : s[e];
+    }
+}
+
+// what a launcher asks of the clamp's description (both argument structs): whole data rows, one mask row or one per data row,
+// and without a mask the shape of "one data row per chain"
+template <class Args>
+bool ais_clamp_ok(const Args& a)
+{
+    return a.M >= 1 && a.C >= 1 && a.M % a.C == 0 && (a.mask_rows == 1 || a.mask_rows == a.M / a.C) &&
+           (a.mask != nullptr || (a.C == 1 && a.mask_rows == 1));
+}
+
 }  // namespace
 
-template <bool GAUSS, bool TRACE>
+template <bool GAUSS, bool TRACE, bool CLAMP>
 __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -73,7 +103,7 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
     lds_f* const lds = (lds_f*)sm;
     // small_layout's buffers under the roles they have here
     lds_f* const Wl = lds + L.oW;
-    lds_f* const X = lds + L.oXa;           // [4][ldx] visible state v_k
+    lds_f* const X = lds + L.oXa;           // [4][ldx] visible state v_k (after the clamp)
     lds_f* const Hs = lds + L.oHs;          // [4][ldhs] hidden sample h_k
     lds_f* const part = lds + L.oPart;
     lds_f* const hbl = lds + L.oHb;         // c
@@ -93,8 +123,8 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
     sm_zero_rows(X, L.ldx, tid);
     sm_zero_rows(Hs, L.ldhs, tid);
     SM_SYNC();
-    float d2 = 0.f;                          // sum_i (b - b_A)_i^2: every thread sums it in the same order
-    if (GAUSS) {
+    float d2 = 0.f;                          // sum_i (b - b_A)_i^2: every thread sums it in the same order (clamp: per slab, below)
+    if (GAUSS && !CLAMP) {
         for (int i = lane; i < L.V64; i += 64) d2 += dbl[i] * dbl[i];
         d2 = wave_sum(d2);
     }
@@ -103,9 +133,43 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
         const int row0 = slab * SM_ROWS;
         const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
         bool ok[4];
+        int64_t mrow[4];                     // (clamp) where the chain's mask row starts
 #pragma unroll
-        for (int e = 0; e < 4; ++e) ok[e] = row0 + e < M;
+        for (int e = 0; e < 4; ++e) {
+            ok[e] = row0 + e < M;
+            if constexpr (CLAMP) mrow[e] = a.mask_rows == 1 ? 0 : (int64_t)((row0 + e) / a.C) * ldv;
+        }
         if (slab != (int)blockIdx.x) SM_SYNC();                        // (the previous slab's last readers are done)
+
+        // ---- the clamp of this thread's column, in registers for the whole slab
+        float ob[4] = {0.f, 0.f, 0.f, 0.f};
+        bool held[4] = {false, false, false, false};
+        if constexpr (CLAMP) {
+            if (tid < V) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (!ok[e]) continue;
+                    held[e] = a.mask[mrow[e] + tid] != 0.f;
+                    ob[e] = a.obs[(int64_t)((row0 + e) / a.C) * ldv + tid];
+                }
+            }
+            // d2 of the chain's mask row: the free run's sum (lane-strided, then the wave's tree) with a held column as 0.f.
+            // Only the first wave needs it (thread e < 4 keeps chain e's log w).
+            d2 = 0.f;
+            if (GAUSS && wave == 0) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float t = 0.f;
+                    for (int i = lane; i < L.V64; i += 64) {
+                        const bool free_col = !(ok[e] && i < V && a.mask[mrow[e] + i] != 0.f);
+                        const float d = free_col ? dbl[i] : 0.f;
+                        t += d * d;
+                    }
+                    t = wave_sum(t);
+                    if (tid == e) d2 = t;
+                }
+            }
+        }
 
         // a visible state goes into X; its share of s1 into redV (whole waves: V64 is a multiple of 64)
         auto put_v = [&](const float (&v)[4], const float (&s)[4], int col, float* trace) {
@@ -122,7 +186,7 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
                     if (ok[e]) trace[(int64_t)(row0 + e) * ldv + col] = v[e];
             }
         };
-        // ---- the chain's start: v_1 ~ p_0 (step s), or the state an earlier launch left
+        // ---- the chain's start: v_1 ~ p_0 (step s) under the clamp, or the state an earlier launch left
         double lw = 0.0;
         if (tid < L.V64) {
             const int col = tid;
@@ -140,6 +204,7 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
                     s[e] = okc[e] ? (GAUSS ? (v[e] - bA) * db : v[e] * db) : 0.f;
                 }
             }
+            if constexpr (CLAMP) ais_clamp(ob, held, v, s);
             put_v(v, s, col, a.k0 == 0 ? a.trace_v : nullptr);
         }
         if (a.k0 > 0 && tid < SM_ROWS && row0 + tid < M) lw = a.logw[row0 + tid];
@@ -184,13 +249,14 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
             }
             if (draw) {
                 sm_down(Hs, Wl, L, wave, lane,
-                        [&](const sf32x4& x, int col) {
+                        [&](const sf32x4& x, int col) {                // col == tid: ob / held are this column's
                             const bool live = col < V;
                             const float bA = bAl[col], db = dbl[col];
                             const bool okc[4] = {ok[0] && live, ok[1] && live, ok[2] && live, ok[3] && live};
                             const float m[4] = {x[0], x[1], x[2], x[3]};
                             float v[4], s[4];
                             ais_draw_v<GAUSS>(kv, grow0, col, b1, bA, db, m, okc, v, s);
+                            if constexpr (CLAMP) ais_clamp(ob, held, v, s);
                             put_v(v, s, col, TRACE && a.trace_v ? a.trace_v + (int64_t)k * M * ldv : nullptr);
                         });
                 if (tid < SM_ROWS) {
@@ -219,12 +285,15 @@ bool ais_small_ok(int64_t M, int64_t V, int64_t H, int gauss, int64_t ldv, int64
 
 hipError_t launch_ais_small(const AisSmallArgs& a, hipStream_t s)
 {
-    if (!ais_small_ok(a.M, a.V, a.H, a.gauss, a.ldv, a.ldh) || a.k0 < 0 || a.k1 <= a.k0 || a.k1 > a.K) return hipErrorInvalidValue;
+    if (!ais_small_ok(a.M, a.V, a.H, a.gauss, a.ldv, a.ldh) || a.k0 < 0 || a.k1 <= a.k0 || a.k1 > a.K || !ais_clamp_ok(a))
+        return hipErrorInvalidValue;
     const SmallLayout L = small_layout(a.V, a.H, a.gauss != 0);
     const bool trace = a.trace_h || a.trace_v;
-    const int variant = (a.gauss ? 2 : 0) | (trace ? 1 : 0);
-    void (*const kerns[4])(AisSmallArgs) = {ais_small_kernel<false, false>, ais_small_kernel<false, true>, ais_small_kernel<true, false>,
-                                            ais_small_kernel<true, true>};
+    const int variant = (a.mask ? 4 : 0) | (a.gauss ? 2 : 0) | (trace ? 1 : 0);
+    void (*const kerns[8])(AisSmallArgs) = {
+        ais_small_kernel<false, false, false>, ais_small_kernel<false, true, false>, ais_small_kernel<true, false, false>,
+        ais_small_kernel<true, true, false>,   ais_small_kernel<false, false, true>, ais_small_kernel<false, true, true>,
+        ais_small_kernel<true, false, true>,   ais_small_kernel<true, true, true>};
     // one workgroup per slab up to one per CU of the chip (no partials to sum here: the cap only bounds the W stagings)
     const int nslabs = (a.M + SM_ROWS - 1) / SM_ROWS;
     const dim3 grid(nslabs < 256 ? nslabs : 256), block(SM_NT);
@@ -237,12 +306,14 @@ hipError_t launch_ais_small(const AisSmallArgs& a, hipStream_t s)
 // General path: a workgroup of AIS_NT threads owns one four-chain group; a thread walks the columns tid, tid + AIS_NT, ...
 // and the four row sums are combined wave by wave in a fixed order.
 // ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void ais_d2_kernel(const float* vbias, const float* base_vbias, int V, float* d2)
+// one wave per mask row (no mask: one row with nothing held): a held column enters the sum as 0.f
+__global__ __launch_bounds__(64) void ais_d2_kernel(const float* vbias, const float* base_vbias, const float* mask, int V, int64_t ldv, float* d2)
 {
+    const float* mrow = mask ? mask + (int64_t)blockIdx.x * ldv : nullptr;
     float t = 0.f;
-    for (int i = threadIdx.x; i < V; i += 64) { const float d = vbias[i] - base_vbias[i]; t += d * d; }
+    for (int i = threadIdx.x; i < V; i += 64) { const float d = mrow && mrow[i] != 0.f ? 0.f : vbias[i] - base_vbias[i]; t += d * d; }
     t = wave_sum(t);
-    if (threadIdx.x == 0) d2[0] = t;
+    if (threadIdx.x == 0) d2[blockIdx.x] = t;
 }
 
 __global__ __launch_bounds__(AIS_NT) void ais_hidden_kernel(AisStepArgs a)
@@ -278,11 +349,12 @@ __global__ __launch_bounds__(AIS_NT) void ais_hidden_kernel(AisStepArgs a)
     if (tid < 4 && row0 + tid < a.M) {
         const float hsum = tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3];
         const double lw = a.k == 1 ? 0.0 : a.logw[row0 + tid];
-        a.logw[row0 + tid] = ais_logw_add(lw, hsum, a.s1[row0 + tid], a.gauss ? a.d2[0] : 0.f, b1, b0, a.gauss != 0);
+        const float d2 = a.gauss ? a.d2[a.mask_rows == 1 ? 0 : (row0 + tid) / a.C] : 0.f;      // the chain's mask row's
+        a.logw[row0 + tid] = ais_logw_add(lw, hsum, a.s1[row0 + tid], d2, b1, b0, a.gauss != 0);
     }
 }
 
-template <bool GAUSS>
+template <bool GAUSS, bool CLAMP>
 __global__ __launch_bounds__(AIS_NT) void ais_visible_kernel(AisStepArgs a)
 {
     __shared__ float red[4 * (AIS_NT / 64)];
@@ -291,18 +363,28 @@ __global__ __launch_bounds__(AIS_NT) void ais_visible_kernel(AisStepArgs a)
     const float beta = a.k == 0 ? 0.0f : a.betas[a.k];
     PhiloxKey key = a.rng;
     key.step = a.rng.step + (uint32_t)(2 * a.k);
+    int64_t drow[4];                         // (clamp) where the chain's data row starts in obs (and in a per-row mask)
+    if constexpr (CLAMP) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) drow[e] = (int64_t)((row0 + e) / a.C) * a.ldv;
+    }
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int col = tid; col < (int)a.ldv; col += AIS_NT) {
         const bool live = col < a.V;
         const float bA = live ? a.base_vbias[col] : 0.f, db = live ? a.vbias[col] - bA : 0.f;
-        bool ok[4];
-        float m[4], v[4], s[4];
+        bool ok[4], held[4];
+        float m[4], v[4], s[4], ob[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             ok[e] = live && row0 + e < a.M;
             m[e] = ok[e] && a.k > 0 ? a.pre[(int64_t)(row0 + e) * a.ldv + col] : 0.f;
+            if constexpr (CLAMP) {
+                held[e] = ok[e] && a.mask[(a.mask_rows == 1 ? 0 : drow[e]) + col] != 0.f;
+                ob[e] = held[e] ? a.obs[drow[e] + col] : 0.f;
+            }
         }
         ais_draw_v<GAUSS>(key, grow0, col, beta, bA, db, m, ok, v, s);
+        if constexpr (CLAMP) ais_clamp(ob, held, v, s);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             acc[e] += s[e];
@@ -316,24 +398,31 @@ __global__ __launch_bounds__(AIS_NT) void ais_visible_kernel(AisStepArgs a)
     if (tid < 4 && row0 + tid < a.M) a.s1[row0 + tid] = tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3];
 }
 
-hipError_t launch_ais_d2(const float* vbias, const float* base_vbias, int V, float* d2, hipStream_t s)
+hipError_t launch_ais_d2(const AisStepArgs& a, float* d2, hipStream_t s)
 {
-    hipLaunchKernelGGL(ais_d2_kernel, dim3(1), dim3(64), 0, s, vbias, base_vbias, V, d2);
+    if (!ais_clamp_ok(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ais_d2_kernel, dim3(a.mask_rows), dim3(64), 0, s, a.vbias, a.base_vbias, a.mask, a.V, a.ldv, d2);
     return hipGetLastError();
 }
 
 hipError_t launch_ais_hidden(const AisStepArgs& a, hipStream_t s)
 {
-    if (a.M < 1 || a.k < 1 || a.k > a.K) return hipErrorInvalidValue;
+    if (!ais_clamp_ok(a) || a.k < 1 || a.k > a.K) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ais_hidden_kernel, dim3((a.M + 3) / 4), dim3(AIS_NT), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_ais_visible(const AisStepArgs& a, hipStream_t s)
 {
-    if (a.M < 1 || a.k < 0 || a.k >= a.K) return hipErrorInvalidValue;
-    if (a.gauss) hipLaunchKernelGGL((ais_visible_kernel<true>), dim3((a.M + 3) / 4), dim3(AIS_NT), 0, s, a);
-    else hipLaunchKernelGGL((ais_visible_kernel<false>), dim3((a.M + 3) / 4), dim3(AIS_NT), 0, s, a);
+    if (!ais_clamp_ok(a) || a.k < 0 || a.k >= a.K) return hipErrorInvalidValue;
+    const dim3 grid((a.M + 3) / 4), block(AIS_NT);
+    if (a.mask) {
+        if (a.gauss) hipLaunchKernelGGL((ais_visible_kernel<true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((ais_visible_kernel<false, true>), grid, block, 0, s, a);
+    } else {
+        if (a.gauss) hipLaunchKernelGGL((ais_visible_kernel<true, false>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((ais_visible_kernel<false, false>), grid, block, 0, s, a);
+    }
     return hipGetLastError();
 }
 

@@ -26,7 +26,6 @@
 #include "mdbn_thin.h"
 #include "mdbn_gchain.h"
 #include "mdbn_ais.h"
-#include "mdbn_cais.h"
 #include "mdbn_clamp.h"
 #include "mdbn_temper.h"
 
@@ -2249,68 +2248,91 @@ int sampler_pointer_rules(const void* workspace, std::initializer_list<const voi
 // ---------------------------------------------------------------------------------- annealed importance sampling
 namespace {
 
-// The caller's workspace of mdbn_ais_run.  One-launch path: the visible state carried between launches.  General path: a
-// zero bias (the propdown product is taken without bias), the pre-activations of a pass, the hidden and the visible state,
-// s1 and d2 (mdbn_ais.hip), then the scratch of the propagation GEMMs.
-struct AisWs {
-    int64_t zero, pre, h, v, s1, gemm_bytes;
-    int64_t total_bytes() const { return 4 * (zero + pre + h + v + s1 + 64) + gemm_bytes; }
+// The clamp of mdbn_ais_cond_run: chain m of the N C chains keeps the columns where its data row's mask is 1 at obs.  A run
+// without one (mdbn_ais_run) is the same run with no held column: one data row per chain, nothing to read.
+struct AisClamp {
+    const float* obs; const float* mask;
+    int64_t mask_rows, N, C;
 };
 
-AisWs ais_ws(int path, int64_t M, int64_t V, int64_t H, int64_t ldv, int64_t ldh)
+// The caller's workspace of an AIS run.  One-launch path: the visible state carried between launches.  General path: a
+// zero bias (the propdown product is taken without bias), the pre-activations of a pass, the hidden and the visible state,
+// s1 and d2 (mdbn_ais.hip: 64 floats, and under a clamp one sum per data row behind them), then the scratch of the
+// propagation GEMMs.
+struct AisWs {
+    int64_t zero, pre, h, v, s1, d2, gemm_bytes;
+    int64_t total_bytes() const { return 4 * (zero + pre + h + v + s1 + d2) + gemm_bytes; }
+};
+
+AisWs ais_ws(int path, int64_t M, int64_t clamp_rows, int64_t V, int64_t H, int64_t ldv, int64_t ldh)
 {
     AisWs w{};
     w.v = ru64(M * ldv);
+    w.d2 = 64;
     if (path == 2) {
         w.zero = ru64(std::max(ldv, ldh));
         w.pre = ru64(M * std::max(ldv, ldh));
         w.h = ru64(M * ldh);
         w.s1 = ru64(M);
+        if (clamp_rows) w.d2 += ru64(clamp_rows);
         w.gemm_bytes = gemm_scratch_bytes(M, V, H, true);
     }
     return w;
 }
 
-}  // namespace
-
-int mdbn_ais_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t V, int64_t H, int64_t n_betas, int path, int64_t* bytes)
+// N C chains as mdbn_ais_run counts them
+int cais_chain_rules(int64_t N, int64_t C, int64_t V, int64_t H)
 {
-    CtxScope ctx_scope(ctx);
-    REQUIRE(bytes != nullptr, "bytes is NULL");
-    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
+    REQUIRE(N >= 1 && C >= 1 && V >= 1 && H >= 1, "bad shape N=%lld C=%lld V=%lld H=%lld", (long long)N, (long long)C, (long long)V, (long long)H);
+    REQUIRE(N < (1ll << 31) && C < (1ll << 31) && N * C < (1ll << 31), "N C = %lld x %lld chains: too many", (long long)N, (long long)C);
+    return MDBN_OK;
+}
+
+// What both sizers answer once their own shape rule holds: M chains, clamp_rows = the data rows of a clamp or 0
+int ais_workspace_bytes(int64_t M, int64_t clamp_rows, int64_t V, int64_t H, int64_t n_betas, int path, int64_t* bytes)
+{
     REQUIRE(n_betas >= 2, "n_betas = %lld: a schedule has at least beta_0 = 0 and beta_K = 1", (long long)n_betas);
     REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
     const int64_t ldv = padded_ld(V), ldh = padded_ld(H);
     const bool f0 = ais_small_ok(M, V, H, 0, ldv, ldh), f1 = ais_small_ok(M, V, H, 1, ldv, ldh);
     const int p = sizing_path(path, f0 || f1, f0 && f1);
     REQUIRE(p > 0, "path 1: %lld -> %lld is not LDS-resident", (long long)V, (long long)H);
-    *bytes = ais_ws(p, M, V, H, ldv, ldh).total_bytes();
+    *bytes = ais_ws(p, M, clamp_rows, V, H, ldv, ldh).total_bytes();
     return MDBN_OK;
 }
 
-int mdbn_ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
-                 const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t n_betas, int64_t M,
-                 int64_t ldv, float* v_state, double* logw, float* trace_h, float* trace_v, int path, const mdbn_rng* rng,
-                 void* workspace, int64_t workspace_bytes)
+// Both runs once their own shape rule holds (the rules that need no device still come first): M chains, free (clamp == NULL)
+// or clamped; `sizer` names the entry point's own *_workspace_bytes
+int ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias, const float* vbias,
+            const float* base_vbias, int gauss, const float* betas, int64_t n_betas, int64_t M, const AisClamp* clamp, int64_t ldv,
+            float* v_state, double* logw, float* trace_h, float* trace_v, int path, const mdbn_rng* rng, void* workspace,
+            int64_t workspace_bytes, const char* sizer)
 {
-    CtxScope ctx_scope(ctx);
-    // (the argument rules first: they need no device)
-    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
-    REQUIRE(M < (1ll << 31) && n_betas < (1ll << 30), "M / n_betas too large");
     REQUIRE(n_betas >= 2, "n_betas = %lld: a schedule has at least beta_0 = 0 and beta_K = 1", (long long)n_betas);
+    if (clamp)
+        REQUIRE(clamp->mask_rows == 1 || clamp->mask_rows == clamp->N, "mask_rows = %lld is neither 1 nor N = %lld",
+                (long long)clamp->mask_rows, (long long)clamp->N);
     REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
     REQUIRE(ldv % 4 == 0 && ldv >= V && ldh % 4 == 0 && ldh >= H, "leading dimensions must be multiples of 4, ldv >= V, ldh >= H");
-    REQUIRE(path != 1 || ais_small_ok(M, V, H, gauss, ldv, ldh),
-            "path 1: %lld -> %lld (ldv %lld, ldh %lld) is not LDS-resident", (long long)V, (long long)H, (long long)ldv, (long long)ldh);
-    const int p = run_path(path, ais_small_ok(M, V, H, gauss, ldv, ldh));
-    const AisWs w = ais_ws(p, M, V, H, ldv, ldh);
-    CHECK(sampler_workspace_rules(workspace_bytes, w.total_bytes(), "mdbn_ais_workspace_bytes", ctx, rng));
+    const bool fits = ais_small_ok(M, V, H, gauss, ldv, ldh);
+    REQUIRE(path != 1 || fits, "path 1: %lld -> %lld (ldv %lld, ldh %lld) is not LDS-resident", (long long)V, (long long)H,
+            (long long)ldv, (long long)ldh);
+    const int p = run_path(path, fits);
+    const AisWs w = ais_ws(p, M, clamp ? clamp->N : 0, V, H, ldv, ldh);
+    CHECK(sampler_workspace_rules(workspace_bytes, w.total_bytes(), sizer, ctx, rng));
     CHECK(check_mat(W, ldh, H, "W"));
+    if (clamp) {
+        CHECK(check_mat(clamp->obs, ldv, V, "obs"));
+        CHECK(check_mat(clamp->mask, ldv, V, "mask"));
+    }
     REQUIRE(hbias && vbias && base_vbias && betas && logw, "NULL pointer");
     CHECK(sampler_pointer_rules(workspace, {v_state, trace_h, trace_v}));
     hipStream_t s = (hipStream_t)stream;
     const int K = (int)n_betas - 1;
     float* wsf = reinterpret_cast<float*>(workspace);
+    const float* obs = clamp ? clamp->obs : nullptr;
+    const float* mask = clamp ? clamp->mask : nullptr;
+    const int mask_rows = clamp ? (int)clamp->mask_rows : 1, C = clamp ? (int)clamp->C : 1;
 
     if (p == 1) {
         AisSmallArgs a{};
@@ -2319,6 +2341,7 @@ int mdbn_ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t
         a.W = W; a.hbias = hbias; a.vbias = vbias; a.base_vbias = base_vbias; a.betas = betas;
         a.K = K;
         a.rng = make_key(*rng, 0u);
+        a.obs = obs; a.mask = mask; a.mask_rows = mask_rows; a.C = C;
         a.v_state = v_state ? v_state : wsf;
         a.logw = logw;
         a.trace_h = trace_h; a.trace_v = trace_v;
@@ -2335,32 +2358,35 @@ int mdbn_ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t
     float* v = h + w.h;
     float* s1 = v + w.v;
     float* d2 = s1 + w.s1;
-    void* gemm_ws = d2 + 64;
+    void* gemm_ws = d2 + w.d2;
     if (v_state) v = v_state;
     Workspace ws;
     CHECK(carve(gemm_ws, w.gemm_bytes, M, V, H, ws, false));
     HIP_OK(hipMemsetAsync(zero, 0, sizeof(float) * w.zero, s));
-    HIP_OK(launch_ais_d2(vbias, base_vbias, (int)V, d2, s));
     AisStepArgs st{};
     st.M = (int)M; st.V = (int)V; st.H = (int)H; st.gauss = gauss != 0; st.K = K;
     st.ldv = ldv; st.ldh = ldh;
     st.betas = betas; st.vbias = vbias; st.base_vbias = base_vbias;
     st.rng = make_key(*rng, 0u);
+    st.obs = obs; st.mask = mask; st.mask_rows = mask_rows; st.C = C;
     st.pre = pre; st.h = h; st.v = v; st.s1 = s1; st.d2 = d2; st.logw = logw;
+    if (gauss) HIP_OK(launch_ais_d2(st, d2, s));         // (read under gauss only)
     st.k = 0; st.trace = trace_v;
     HIP_OK(launch_ais_visible(st, s));
     for (int k = 1; k <= K; ++k) {
         st.k = k;
         Affine up(v, M, ldv, W, V, H, ldh, hbias);
         up.pre = pre;
-        up.x_binary = !gauss;
+        // A held column may hold any real value: never the 0/1 operand hint on the way up under a clamp (where the state is 0/1
+        // the six-product kernel adds exact zeros to the three products of the hinted one: the same bits)
+        up.x_binary = !gauss && !clamp;
         CHECK(run_affine(up, ws, s, nullptr));
         st.trace = trace_h && k < K ? trace_h + (int64_t)(k - 1) * M * ldh : nullptr;
         HIP_OK(launch_ais_hidden(st, s));
         if (k == K) break;
         Affine down(h, M, ldh, W, V, H, ldh, zero, ldv, 1);
         down.pre = pre;
-        down.x_binary = true;
+        down.x_binary = true;                            // our own 0/1 hidden samples
         CHECK(run_affine(down, ws, s, nullptr));
         st.trace = trace_v ? trace_v + (int64_t)k * M * ldv : nullptr;
         HIP_OK(launch_ais_visible(st, s));
@@ -2368,47 +2394,34 @@ int mdbn_ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t
     return MDBN_OK;
 }
 
-// ---------------------------------------------------------------------------------- clamped annealed importance sampling
-namespace {
-
-// The caller's workspace of mdbn_ais_cond_run: that of mdbn_ais_run for its N C chains, then -- general path -- d2 per mask row
-struct CaisWs {
-    AisWs ais;
-    int64_t d2;
-    int64_t total_bytes() const { return ais.total_bytes() + 4 * d2; }
-};
-
-CaisWs cais_ws(int path, int64_t N, int64_t C, int64_t V, int64_t H, int64_t ldv, int64_t ldh)
-{
-    CaisWs w{};
-    w.ais = ais_ws(path, N * C, V, H, ldv, ldh);
-    if (path == 2) w.d2 = ru64(N);
-    return w;
-}
-
-// N C chains as mdbn_ais_run counts them
-int cais_chain_rules(int64_t N, int64_t C, int64_t V, int64_t H)
-{
-    REQUIRE(N >= 1 && C >= 1 && V >= 1 && H >= 1, "bad shape N=%lld C=%lld V=%lld H=%lld", (long long)N, (long long)C, (long long)V, (long long)H);
-    REQUIRE(N < (1ll << 31) && C < (1ll << 31) && N * C < (1ll << 31), "N C = %lld x %lld chains: too many", (long long)N, (long long)C);
-    return MDBN_OK;
-}
-
 }  // namespace
+
+int mdbn_ais_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t V, int64_t H, int64_t n_betas, int path, int64_t* bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(bytes != nullptr, "bytes is NULL");
+    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
+    return ais_workspace_bytes(M, 0, V, H, n_betas, path, bytes);
+}
+
+int mdbn_ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+                 const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t n_betas, int64_t M,
+                 int64_t ldv, float* v_state, double* logw, float* trace_h, float* trace_v, int path, const mdbn_rng* rng,
+                 void* workspace, int64_t workspace_bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
+    REQUIRE(M < (1ll << 31) && n_betas < (1ll << 30), "M / n_betas too large");
+    return ais_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, gauss, betas, n_betas, M, nullptr, ldv, v_state, logw, trace_h,
+                   trace_v, path, rng, workspace, workspace_bytes, "mdbn_ais_workspace_bytes");
+}
 
 int mdbn_ais_cond_workspace_bytes(mdbn_ctx* ctx, int64_t N, int64_t C, int64_t V, int64_t H, int64_t n_betas, int path, int64_t* bytes)
 {
     CtxScope ctx_scope(ctx);
     REQUIRE(bytes != nullptr, "bytes is NULL");
     CHECK(cais_chain_rules(N, C, V, H));
-    REQUIRE(n_betas >= 2, "n_betas = %lld: a schedule has at least beta_0 = 0 and beta_K = 1", (long long)n_betas);
-    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
-    const int64_t ldv = padded_ld(V), ldh = padded_ld(H), M = N * C;
-    const bool f0 = ais_small_ok(M, V, H, 0, ldv, ldh), f1 = ais_small_ok(M, V, H, 1, ldv, ldh);
-    const int p = sizing_path(path, f0 || f1, f0 && f1);
-    REQUIRE(p > 0, "path 1: %lld -> %lld is not LDS-resident", (long long)V, (long long)H);
-    *bytes = cais_ws(p, N, C, V, H, ldv, ldh).total_bytes();
-    return MDBN_OK;
+    return ais_workspace_bytes(N * C, N, V, H, n_betas, path, bytes);
 }
 
 int mdbn_ais_cond_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
@@ -2418,86 +2431,11 @@ int mdbn_ais_cond_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, in
                       int64_t workspace_bytes)
 {
     CtxScope ctx_scope(ctx);
-    // (the argument rules first: they need no device)
     CHECK(cais_chain_rules(N, C, V, H));
     REQUIRE(n_betas < (1ll << 30), "n_betas too large");
-    REQUIRE(n_betas >= 2, "n_betas = %lld: a schedule has at least beta_0 = 0 and beta_K = 1", (long long)n_betas);
-    REQUIRE(mask_rows == 1 || mask_rows == N, "mask_rows = %lld is neither 1 nor N = %lld", (long long)mask_rows, (long long)N);
-    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
-    REQUIRE(ldv % 4 == 0 && ldv >= V && ldh % 4 == 0 && ldh >= H, "leading dimensions must be multiples of 4, ldv >= V, ldh >= H");
-    const int64_t M = N * C;
-    const bool fits = ais_small_ok(M, V, H, gauss, ldv, ldh);
-    REQUIRE(path != 1 || fits, "path 1: %lld -> %lld (ldv %lld, ldh %lld) is not LDS-resident", (long long)V, (long long)H,
-            (long long)ldv, (long long)ldh);
-    const int p = run_path(path, fits);
-    const CaisWs w = cais_ws(p, N, C, V, H, ldv, ldh);
-    CHECK(sampler_workspace_rules(workspace_bytes, w.total_bytes(), "mdbn_ais_cond_workspace_bytes", ctx, rng));
-    CHECK(check_mat(W, ldh, H, "W"));
-    CHECK(check_mat(obs, ldv, V, "obs"));
-    CHECK(check_mat(mask, ldv, V, "mask"));
-    REQUIRE(hbias && vbias && base_vbias && betas && logw, "NULL pointer");
-    CHECK(sampler_pointer_rules(workspace, {v_state, trace_h, trace_v}));
-    hipStream_t s = (hipStream_t)stream;
-    const int K = (int)n_betas - 1;
-    float* wsf = reinterpret_cast<float*>(workspace);
-
-    if (p == 1) {
-        CaisSmallArgs a{};
-        a.M = (int)M; a.V = (int)V; a.H = (int)H; a.gauss = gauss != 0;
-        a.ldv = ldv; a.ldh = ldh;
-        a.W = W; a.hbias = hbias; a.vbias = vbias; a.base_vbias = base_vbias; a.betas = betas;
-        a.K = K;
-        a.rng = make_key(*rng, 0u);
-        a.obs = obs; a.mask = mask; a.mask_rows = (int)mask_rows; a.C = (int)C;
-        a.v_state = v_state ? v_state : wsf;
-        a.logw = logw;
-        a.trace_h = trace_h; a.trace_v = trace_v;
-        for (int k0 = 0; k0 < K; k0 += AIS_CUT) {       // a launch stays short; the state travels in v_state / logw
-            a.k0 = k0; a.k1 = std::min(K, k0 + AIS_CUT);
-            HIP_OK(launch_cais_small(a, s));
-        }
-        return MDBN_OK;
-    }
-
-    float* zero = wsf;
-    float* pre = zero + w.ais.zero;
-    float* h = pre + w.ais.pre;
-    float* v = h + w.ais.h;
-    float* s1 = v + w.ais.v;
-    float* d2 = s1 + w.ais.s1;                           // (behind mdbn_ais_run's 64-float slot: one sum per mask row)
-    void* gemm_ws = d2 + 64 + w.d2;
-    if (v_state) v = v_state;
-    Workspace ws;
-    CHECK(carve(gemm_ws, w.ais.gemm_bytes, M, V, H, ws, false));
-    HIP_OK(hipMemsetAsync(zero, 0, sizeof(float) * w.ais.zero, s));
-    if (gauss) HIP_OK(launch_cais_d2(vbias, base_vbias, mask, (int)mask_rows, (int)V, ldv, d2, s));
-    CaisStepArgs st{};
-    st.M = (int)M; st.V = (int)V; st.H = (int)H; st.gauss = gauss != 0; st.K = K;
-    st.ldv = ldv; st.ldh = ldh;
-    st.betas = betas; st.vbias = vbias; st.base_vbias = base_vbias;
-    st.rng = make_key(*rng, 0u);
-    st.obs = obs; st.mask = mask; st.mask_rows = (int)mask_rows; st.C = (int)C;
-    st.pre = pre; st.h = h; st.v = v; st.s1 = s1; st.d2 = d2; st.logw = logw;
-    st.k = 0; st.trace = trace_v;
-    HIP_OK(launch_cais_visible(st, s));
-    for (int k = 1; k <= K; ++k) {
-        st.k = k;
-        // the passes of mdbn_ais_run.  A held column may hold any real value: never the 0/1 operand hint on the way up (where the
-        // state is 0/1 the six-product kernel adds exact zeros to the three products of the hinted one: the same bits)
-        Affine up(v, M, ldv, W, V, H, ldh, hbias);
-        up.pre = pre;
-        CHECK(run_affine(up, ws, s, nullptr));
-        st.trace = trace_h && k < K ? trace_h + (int64_t)(k - 1) * M * ldh : nullptr;
-        HIP_OK(launch_cais_hidden(st, s));
-        if (k == K) break;
-        Affine down(h, M, ldh, W, V, H, ldh, zero, ldv, 1);
-        down.pre = pre;
-        down.x_binary = true;                            // our own 0/1 hidden samples
-        CHECK(run_affine(down, ws, s, nullptr));
-        st.trace = trace_v ? trace_v + (int64_t)k * M * ldv : nullptr;
-        HIP_OK(launch_cais_visible(st, s));
-    }
-    return MDBN_OK;
+    const AisClamp clamp{obs, mask, mask_rows, N, C};
+    return ais_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, gauss, betas, n_betas, N * C, &clamp, ldv, v_state, logw,
+                   trace_h, trace_v, path, rng, workspace, workspace_bytes, "mdbn_ais_cond_workspace_bytes");
 }
 
 // ---------------------------------------------------------------------------------- clamped Gibbs sampling

@@ -1,8 +1,8 @@
 // What the samplers of a trained layer share around the passes of mdbn_small_passes.h (mdbn_ais.hip: annealed importance
-// sampling; mdbn_cais.hip: the same under a clamp; mdbn_clamp.hip: clamped Gibbs sampling; mdbn_temper.hip: parallel
+// sampling, free and under a clamp; mdbn_clamp.hip: clamped Gibbs sampling; mdbn_temper.hip: parallel
 // tempering): the staging of a one-launch kernel's LDS image, the draws of the tempered family b_beta = b_A + beta (b - b_A)
 // and the fixed-order sums.  Each is stated once because the samplers must agree bit for bit -- with each other, between their
-// two paths and across the cuts of a run.  Included by those four sources only, after mdbn_small_passes.h.
+// two paths and across the cuts of a run.  Included by those three sources only, after mdbn_small_passes.h.
 #pragma once
 #include "mdbn_device.h"
 #include "mdbn_small_passes.h"

@@ -100,12 +100,13 @@ struct SmallFinArgs {
 };
 
 // The launch of a one-launch kernel (the CD step's and the samplers'): `kerns` = its <GAUSS, TRACE> instantiations in the order
-// variant = 2 GAUSS + TRACE.  A variant's first launch raises its dynamic-LDS limit; plain statics, one set per argument struct.
-template <class Args>
-hipError_t launch_small_variant(void (*const (&kerns)[4])(Args), int variant, dim3 grid, dim3 block, int lds_bytes, hipStream_t s,
+// variant = 2 GAUSS + TRACE (annealed importance sampling: eight, + 4 CLAMP).  A variant's first launch raises its dynamic-LDS
+// limit; plain statics, one set per argument struct.
+template <class Args, int N>
+hipError_t launch_small_variant(void (*const (&kerns)[N])(Args), int variant, dim3 grid, dim3 block, int lds_bytes, hipStream_t s,
                                 const Args& k)
 {
-    static bool attr_set[4] = {false, false, false, false};
+    static bool attr_set[N] = {};
     if (!attr_set[variant]) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kerns[variant]), hipFuncAttributeMaxDynamicSharedMemorySize, SM_MAX_LDS);
         if (e != hipSuccess) return e;

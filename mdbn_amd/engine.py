@@ -474,21 +474,11 @@ class HipEngine(object):
         ldh, ldv = W.stride(0), padded_ld(V)
         gauss = (2 if sampler else 1) if gauss else 0
         n_steps, burn_in = int(n_steps), int(burn_in)
-
-        def padded(x, rows):
-            x = self.as_matrix(x)
-            if tuple(x.shape) != (rows, V):
-                raise ValueError("expected a [%d, %d] matrix, got %r" % (rows, V, tuple(x.shape)))
-            if x.stride(0) != ldv:
-                t = self.alloc_matrix(rows, V, ldv)
-                t.copy_(x)
-                x = t
-            return x
         mask = self.as_matrix(mask)
         mask_rows = int(mask.shape[0])
         if mask_rows not in (1, B):
             raise ValueError("mask has %d rows: neither 1 nor the batch's %d" % (mask_rows, B))
-        obs, mask = padded(obs, B), padded(mask, mask_rows)
+        obs, mask = self._padded(obs, B, V, ldv), self._padded(mask, mask_rows, V, ldv)
         state = self.alloc_matrix(B, V, ldv)
         state.copy_(v)
         h_mean, h_sample, h_avg = (self.alloc_matrix(B, H, ldh) for _ in range(3))
@@ -522,14 +512,22 @@ class HipEngine(object):
             self._p(ws), ws.numel() * 4), "mdbn_free_energy")
         return out
 
-    def ais(self, W, hbias, vbias, base_vbias, gauss, betas, n_chains, rng, path=0, trace=False):
-        """Annealed importance sampling of the layer (W, hbias, vbias) from the base-rate model ``base_vbias`` through
-        the inverse temperatures ``betas`` (0 = betas[0] < ... < betas[K] = 1) in ONE library call (mdbn_ais_run):
-        the per-chain log importance weights as a float64 numpy vector (one device -> host copy) and, with ``trace``,
-        the hidden [K-1, M, H] and visible [K, M, V] samples of every temperature.  ``path``: 0 = by shape, 1 = the
-        one-launch kernel (LDS-resident layers), 2 = the general path.  Consumes 2K - 1 RNG steps from ``rng.step``."""
+    def _padded(self, x, rows, V, ldv):
+        """``x`` as a [rows, V] device matrix on the leading dimension ``ldv`` (copied where it is on another)."""
+        x = self.as_matrix(x)
+        if tuple(x.shape) != (rows, V):
+            raise ValueError("expected a [%d, %d] matrix, got %r" % (rows, V, tuple(x.shape)))
+        if x.stride(0) != ldv:
+            t = self.alloc_matrix(rows, V, ldv)
+            t.copy_(x)
+            x = t
+        return x
+
+    def _ais(self, W, hbias, vbias, base_vbias, gauss, betas, M, rng, path, trace, clamp=None):
+        """What ``ais`` and ``ais_conditional`` share: M chains through mdbn_ais_run, or with ``clamp`` = (obs, mask, mask_rows,
+        N, chains per row), padded device matrices, through mdbn_ais_cond_run.  Returns ``(logw [M] float64 numpy, trace_h,
+        trace_v, v_state)``: the traces numpy (None without ``trace``), the final visible state [M, V] a device tensor."""
         V, H = W.shape
-        M = int(n_chains)
         ldh, ldv = W.stride(0), padded_ld(V)
         betas = numpy.ascontiguousarray(betas, dtype=numpy.float32)
         if betas.ndim != 1 or betas.size < 2 or betas[0] != 0.0 or betas[-1] != 1.0 or not (numpy.diff(betas) > 0).all():
@@ -538,20 +536,32 @@ class HipEngine(object):
         d_betas = torch.from_numpy(betas).to(self.device)
         base = self.to_device(numpy.asarray(base_vbias, dtype=numpy.float32)) if not isinstance(base_vbias, torch.Tensor) \
             else base_vbias.to(device=self.device, dtype=torch.float32).contiguous()
-        ws = self._sampler_workspace(self.lib.mdbn_ais_workspace_bytes, "mdbn_ais_workspace_bytes", (M, V), H, ldh, path, extra=(K + 1,))
+        name = "mdbn_ais_run" if clamp is None else "mdbn_ais_cond_run"
+        sizer = name.replace("run", "workspace_bytes")
+        ws = self._sampler_workspace(getattr(self.lib, sizer), sizer, ((M,) if clamp is None else clamp[3:]) + (V,), H, ldh, path,
+                                     extra=(K + 1,))
         logw = torch.zeros(M, dtype=torch.float64, device=self.device)
         v_state = self.alloc_matrix(M, V, ldv)
         trace_h = torch.zeros((max(K - 1, 1), M, ldh), dtype=torch.float32, device=self.device) if trace else None
         trace_v = torch.zeros((K, M, ldv), dtype=torch.float32, device=self.device) if trace else None
         r = rng.c()
-        _lib.check(self.lib.mdbn_ais_run(
+        chains = (M,) if clamp is None else (self._p(clamp[0]), self._p(clamp[1])) + tuple(clamp[2:])
+        _lib.check(getattr(self.lib, name)(
             self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base), int(bool(gauss)),
-            self._p(d_betas), K + 1, M, ldv, self._p(v_state), self._p(logw), self._p(trace_h), self._p(trace_v),
-            int(path), C.byref(r), self._p(ws), ws.numel() * 4), "mdbn_ais_run")
-        out = logw.cpu().numpy()
+            self._p(d_betas), K + 1, *chains, ldv, self._p(v_state), self._p(logw), self._p(trace_h), self._p(trace_v),
+            int(path), C.byref(r), self._p(ws), ws.numel() * 4), name)
         if trace:
-            return out, trace_h.cpu().numpy()[:K - 1, :, :H], trace_v.cpu().numpy()[:, :, :V]
-        return out
+            trace_h, trace_v = trace_h.cpu().numpy()[:K - 1, :, :H], trace_v.cpu().numpy()[:, :, :V]
+        return logw.cpu().numpy(), trace_h, trace_v, v_state
+
+    def ais(self, W, hbias, vbias, base_vbias, gauss, betas, n_chains, rng, path=0, trace=False):
+        """Annealed importance sampling of the layer (W, hbias, vbias) from the base-rate model ``base_vbias`` through
+        the inverse temperatures ``betas`` (0 = betas[0] < ... < betas[K] = 1) in ONE library call (mdbn_ais_run):
+        the per-chain log importance weights as a float64 numpy vector (one device -> host copy) and, with ``trace``,
+        the hidden [K-1, M, H] and visible [K, M, V] samples of every temperature.  ``path``: 0 = by shape, 1 = the
+        one-launch kernel (LDS-resident layers), 2 = the general path.  Consumes 2K - 1 RNG steps from ``rng.step``."""
+        logw, trace_h, trace_v, _ = self._ais(W, hbias, vbias, base_vbias, gauss, betas, int(n_chains), rng, path, trace)
+        return (logw, trace_h, trace_v) if trace else logw
 
     def ais_conditional(self, W, hbias, vbias, base_vbias, gauss, betas, obs, mask, n_chains, rng, path=0, trace=False, state=False):
         """Annealed importance sampling of the layer with the visibles where ``mask`` is 1 held at ``obs``, ``n_chains`` chains
@@ -564,48 +574,19 @@ class HipEngine(object):
         N, V = (int(x) for x in obs.shape)
         if V != W.shape[0]:
             raise ValueError("obs has %d columns, the layer %d visible units" % (V, W.shape[0]))
-        H = W.shape[1]
         Cn = int(n_chains)
         if N < 1 or Cn < 1:
             raise ValueError("need at least one row and one chain per row, got %d, %d" % (N, Cn))
-        M = N * Cn
-        ldh, ldv = W.stride(0), padded_ld(V)
-        betas = numpy.ascontiguousarray(betas, dtype=numpy.float32)
-        if betas.ndim != 1 or betas.size < 2 or betas[0] != 0.0 or betas[-1] != 1.0 or not (numpy.diff(betas) > 0).all():
-            raise ValueError("betas must rise strictly from 0 to 1")
-        K = betas.size - 1
-
-        def padded(x, rows):
-            x = self.as_matrix(x)
-            if tuple(x.shape) != (rows, V):
-                raise ValueError("expected a [%d, %d] matrix, got %r" % (rows, V, tuple(x.shape)))
-            if x.stride(0) != ldv:
-                t = self.alloc_matrix(rows, V, ldv)
-                t.copy_(x)
-                x = t
-            return x
+        ldv = padded_ld(V)
         mask = self.as_matrix(mask)
         mask_rows = int(mask.shape[0])
         if mask_rows not in (1, N):
             raise ValueError("mask has %d rows: neither 1 nor the %d rows of obs" % (mask_rows, N))
-        obs, mask = padded(obs, N), padded(mask, mask_rows)
-        d_betas = torch.from_numpy(betas).to(self.device)
-        base = self.to_device(numpy.asarray(base_vbias, dtype=numpy.float32)) if not isinstance(base_vbias, torch.Tensor) \
-            else base_vbias.to(device=self.device, dtype=torch.float32).contiguous()
-        ws = self._sampler_workspace(self.lib.mdbn_ais_cond_workspace_bytes, "mdbn_ais_cond_workspace_bytes", (N, Cn, V), H, ldh, path,
-                                     extra=(K + 1,))
-        logw = torch.zeros(M, dtype=torch.float64, device=self.device)
-        v_state = self.alloc_matrix(M, V, ldv)
-        trace_h = torch.zeros((max(K - 1, 1), M, ldh), dtype=torch.float32, device=self.device) if trace else None
-        trace_v = torch.zeros((K, M, ldv), dtype=torch.float32, device=self.device) if trace else None
-        r = rng.c()
-        _lib.check(self.lib.mdbn_ais_cond_run(
-            self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base), int(bool(gauss)),
-            self._p(d_betas), K + 1, self._p(obs), self._p(mask), mask_rows, N, Cn, ldv, self._p(v_state), self._p(logw),
-            self._p(trace_h), self._p(trace_v), int(path), C.byref(r), self._p(ws), ws.numel() * 4), "mdbn_ais_cond_run")
-        out = (logw.cpu().numpy().reshape(N, Cn),)
+        clamp = (self._padded(obs, N, V, ldv), self._padded(mask, mask_rows, V, ldv), mask_rows, N, Cn)
+        logw, trace_h, trace_v, v_state = self._ais(W, hbias, vbias, base_vbias, gauss, betas, N * Cn, rng, path, trace, clamp)
+        out = (logw.reshape(N, Cn),)
         if trace:
-            out += (trace_h.cpu().numpy()[:K - 1, :, :H], trace_v.cpu().numpy()[:, :, :V])
+            out += (trace_h, trace_v)
         if state:
             out += (v_state.cpu().numpy()[:, :V],)
         return out if len(out) > 1 else out[0]

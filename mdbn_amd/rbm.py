@@ -611,6 +611,17 @@ class RBM(object):
         p = (x.shape[0] * mean + 0.05) / (x.shape[0] + 0.1)
         return (numpy.log(p) - numpy.log1p(-p)).astype(numpy.float32)
 
+    def _ais_schedule(self, betas, n_betas, base_vbias, data):
+        """``(betas float32, K, base_vbias float32)`` of an AIS run from the arguments of ``log_partition``: ``betas`` None:
+        ``linspace(0, 1, n_betas + 1)`` (n_betas None: 1000); ``base_vbias`` None: from ``data``, with neither the layer's own
+        visible bias."""
+        if betas is None:
+            betas = numpy.linspace(0.0, 1.0, int(1000 if n_betas is None else n_betas) + 1)
+        betas = numpy.asarray(betas, dtype=numpy.float32)
+        if base_vbias is None:
+            base_vbias = self.base_rate_vbias(data) if data is not None else self.vbias.get_value()
+        return betas, betas.size - 1, numpy.asarray(base_vbias, dtype=numpy.float32)
+
     def log_partition(self, n_chains=512, betas=None, n_betas=None, base_vbias=None, data=None, path=0, method="ais",
                       n_ladders=64, n_sweeps=1200, burn_in=300, estimator="mid"):
         """``(log_Z, std_err)`` of the layer by annealed importance sampling (Salakhutdinov & Murray 2008) on the device:
@@ -630,13 +641,7 @@ class RBM(object):
             return r.log_z, r.stderr
         if method != "ais":
             raise ValueError("method must be 'ais' or 'tempering', got %r" % (method,))
-        if betas is None:
-            betas = numpy.linspace(0.0, 1.0, int(1000 if n_betas is None else n_betas) + 1)
-        betas = numpy.asarray(betas, dtype=numpy.float32)
-        K = betas.size - 1
-        if base_vbias is None:
-            base_vbias = self.base_rate_vbias(data) if data is not None else self.vbias.get_value()
-        base_vbias = numpy.asarray(base_vbias, dtype=numpy.float32)
+        betas, K, base_vbias = self._ais_schedule(betas, n_betas, base_vbias, data)
         step = self._rng_step
         logw = self.engine.ais(self.W.tensor, self.hbias.tensor, self.vbias.tensor, base_vbias, self.gauss, betas,
                                int(n_chains), RngAddr(self.theano_rng.seed, self.stream_id, step, 0, 0), path=path)
@@ -827,13 +832,7 @@ class RBM(object):
         if x.ndim != 2 or x.shape[1] != self.n_visible or x.shape[0] < 1:
             raise ValueError("v must be [N >= 1, %d], got %r" % (self.n_visible, x.shape))
         mask = self._clamp_mask(observed_mask, x.shape[0])
-        if betas is None:
-            betas = numpy.linspace(0.0, 1.0, int(1000 if n_betas is None else n_betas) + 1)
-        betas = numpy.asarray(betas, dtype=numpy.float32)
-        K = betas.size - 1
-        if base_vbias is None:
-            base_vbias = self.base_rate_vbias(data) if data is not None else self.vbias.get_value()
-        base_vbias = numpy.asarray(base_vbias, dtype=numpy.float32)
+        betas, K, base_vbias = self._ais_schedule(betas, n_betas, base_vbias, data)
         step = self._rng_step
         logw = self.engine.ais_conditional(self.W.tensor, self.hbias.tensor, self.vbias.tensor, base_vbias, self.gauss, betas,
                                            numpy.where(numpy.broadcast_to(mask != 0, x.shape), x, numpy.float32(0)), mask, int(n_chains),

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Device time of one clamped annealed-importance-sampling run (mdbn_ais_cond_run, csrc/mdbn_cais.hip) beside mdbn_ais_run at
+"""Device time of one clamped annealed-importance-sampling run (mdbn_ais_cond_run, csrc/mdbn_ais.hip) beside mdbn_ais_run at
 the same number of chains, V, H and K from the same build: what the clamp costs.  N = 16 data rows of C = 64 chains
 (N C = 1024), K = 1000 temperatures, a random mask holding about half the columns of every row: 100 -> 24 on the one-launch
 path, 1024 -> 256 on the general path (Gaussian and Bernoulli visibles: a Bernoulli layer's held columns may hold real

@@ -1,4 +1,4 @@
-"""numpy twin of the device's clamped annealed importance sampling (csrc/mdbn_cais.hip; TEST-ONLY).
+"""numpy twin of the device's clamped annealed importance sampling (csrc/mdbn_ais.hip under a clamp; TEST-ONLY).
 
 ``cais_twin`` restates the run of mdbn_ais_cond_run with the conventions of ``_ais_np.ais_twin``: N data rows, C chains each
 (chain m belongs to row m // C), the visibles where ``mask`` is 1 held at ``obs`` after every visible draw, the bias term of

@@ -28,8 +28,8 @@ def test_declared_exported_and_bound(lib):
         decl = header[header.index(name + "("):]
         assert len(_lib.SIGNATURES[name]) == decl[:decl.index(");")].count(",") + 1, name
     from mdbn_amd import build
-    assert "mdbn_cais.hip" in build.SOURCES and "mdbn_cais.h" in build.HEADERS
-    assert "mdbn_ais.hip" in build.SOURCES and "mdbn_sampler_kit.h" in build.HEADERS
+    # (the clamped run is mdbn_ais.hip's kernels with a mask: no source of its own)
+    assert "mdbn_ais.hip" in build.SOURCES and "mdbn_ais.h" in build.HEADERS and "mdbn_sampler_kit.h" in build.HEADERS
 
 
 def test_public_names():
@@ -70,6 +70,20 @@ def test_workspace_bytes_rules(lib):
     assert _bytes(lib, 16, 4, 400, 40, path=0) == _bytes(lib, 16, 4, 400, 40, path=1)
     assert _bytes(lib, 16, 4, 400, 40, path=1)[1] < _bytes(lib, 16, 4, 400, 40, path=2)[1]
     assert _bytes(lib, 16, 4, 4096, 1024, path=0) == _bytes(lib, 16, 4, 4096, 1024, path=2)
+
+
+def test_workspace_is_the_free_runs_plus_d2_per_row(lib):
+    """The one driver behind both runs carves one workspace: the clamped run's is mdbn_ais_run's for its N C chains, and on
+    the general path one d2 sum per data row (rounded up to 64 floats) behind it."""
+    n = C.c_int64(-1)
+    for N, Cn in ((16, 4), (7, 3)):
+        for V, H in ((100, 24), (1024, 256)):
+            assert lib.mdbn_ais_workspace_bytes(None, N * Cn, V, H, 9, 2, C.byref(n)) == 0
+            assert _bytes(lib, N, Cn, V, H, path=2) == (0, n.value + 4 * ((N + 63) // 64 * 64))
+            n.value = -1                     # (path 1: equal where the layer is LDS-resident, refused alike where it is not)
+            rc = lib.mdbn_ais_workspace_bytes(None, N * Cn, V, H, 9, 1, C.byref(n))
+            assert rc == (0 if V <= 512 else MDBN_EINVAL) and (rc != 0 or n.value > 0)
+            assert _bytes(lib, N, Cn, V, H, path=1) == (rc, n.value)
 
 
 def _run(lib, N=16, Cn=4, V=100, H=24, n_betas=9, path=0, ws_bytes=0, ldv=None, ldh=None, mask_rows=None):

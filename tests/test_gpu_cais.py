@@ -1,4 +1,4 @@
-"""Clamped annealed importance sampling on the device (csrc/mdbn_cais.hip: mdbn_ais_cond_run, RBM.conditional_log_partition /
+"""Clamped annealed importance sampling on the device (csrc/mdbn_ais.hip: mdbn_ais_cond_run, RBM.conditional_log_partition /
 conditional_log_likelihood, MDBN.modality_log_likelihood) against the float64 numpy twin (tests/_cais_np.py) teacher-forced
 along the device's own samples, against mdbn_ais_run (no held column: bit for bit), against the closed form (every column
 held), against brute-force conditional partition functions, and the one-launch path beside the general path.
