@@ -58,6 +58,7 @@ struct Options {
     int planes_mfma = 16;
     int early_w = 1;
     int narrow_tiles = 1;
+    int slab_tail = 1;
     int feed_copy_streams = 1;
     int gather_ahead = 1;
     int bf16_inputs = 0;
@@ -308,6 +309,10 @@ bool prefer_skinny(int64_t M, int64_t N, int64_t K)
 // mdbn_set_option("narrow_tiles"): forward passes whose 128 x 128 plan would split K two ways run unsplit on 128 x 64 tiles
 // with the fused activation epilogue instead (default on)
 #define g_opt_narrow_tiles (t_opt->narrow_tiles)
+// mdbn_set_option("slab_tail"): the split-K propup on planes (16x16x32 shape) walks its last stages quarter by quarter and
+// stores each quarter's partials, 16 bytes per lane, while the other quarters' MFMAs run (gemm_planes_slabtail_kernel);
+// 0 = every slab store behind the last MFMA.  Same bits either way.
+#define g_opt_slab_tail (t_opt->slab_tail)
 // mdbn_set_option("feed_copy_streams"): a row feeder created afterwards moves each minibatch as 1 or 2 copies on as many
 // streams (two SDMA engines side by side)
 #define g_opt_feed_copy_streams (t_opt->feed_copy_streams)
@@ -693,6 +698,11 @@ hipError_t timed_gemm_planes(int la, int lb, const PlaneGemmArgs& g_in, hipStrea
     g.stamps = g_stamps;
     g.ms = g_opt_planes_mfma;
     if (g_opt_bf16_inputs) g.ap = 0;
+    // "slab_tail" asks for gemm_planes_slabtail_kernel wherever that kernel exists (16x16x32 shape, one or three planes of A).
+    // Its 16-byte stores into 32-bit-addressable slabs are a property of the workspace, not a choice: a launch that cannot
+    // take them is an error, never a quiet return to the other kernel.
+    g.slab_tail = g.slab_tail && g.ms == 16 && g.ap != 0;
+    if (g.slab_tail && !slab_tail_ok(g, la, lb)) return hipErrorInvalidValue;
     const int pipe = g.ap == 3 ? 1 : (g.ap == 1 ? 2 : 3);           // 3: one product (bf16-input reporting mode)
     return timed_launch(gemm_meta((g.bal ? 3000 : 2000) + 100 * pipe + 10 * g.fused + 2 * la + lb, pipe, g.M, g.N, g.K), s,
                         [&]() { return g.bal ? launch_gemm_planes_bal(la, lb, g, s) : launch_gemm_planes(la, lb, g, s); });
@@ -826,6 +836,7 @@ int run_affine_planes(mdbn_ctx* ctx, int comm_cus, const unsigned short* A, int6
         REQUIRE((int64_t)g.splitk * rows * e.ld <= ws.slab_floats, "internal: plane GEMM slabs exceed the workspace");
         g.fused = 0; g.C = ws.slabs; g.ldc = e.ld; g.slab_stride = rows * e.ld;
         e.slabs = ws.slabs; e.slab_stride = g.slab_stride; e.nsplit = g.splitk;
+        g.slab_tail = g_opt_slab_tail && dir == 0;          // propup only (timed_gemm_planes: on the 16x16x32 shape)
         HIP_OK(timed_gemm_planes(LAY_K, lb, g, s));
         HIP_OK(launch_act_epilogue(e, s));
     }
@@ -1141,10 +1152,23 @@ int mdbn_bal_segment(int32_t tiles, int32_t stages, int32_t workgroups, int32_t 
     return MDBN_OK;
 }
 
+// Options whose registry is their own test file rather than tests/_knobs.py (default, accepted values, documentation and
+// the GPU tests that drive them are checked there).  "slab_tail": tests/test_slab_tail_option.py, tests/test_gpu_slab_tail.py.
+// Returns true when `name` is one of them.
+static bool set_plane_kernel_option(mdbn_ctx* ctx, const char* name, int64_t value)
+{
+    if (strcmp(name, "slab_tail") == 0) {
+        ctx->opt.slab_tail = value != 0;
+        return true;
+    }
+    return false;
+}
+
 int mdbn_set_option(mdbn_ctx* ctx, const char* name, int64_t value)
 {
     CtxScope ctx_scope(ctx);
     REQUIRE(ctx != nullptr && name != nullptr, "NULL argument");
+    if (set_plane_kernel_option(ctx, name, value)) return MDBN_OK;
     if (strcmp(name, "gemm_bk") == 0) {
         REQUIRE(value == 0 || value == 32 || value == 64, "gemm_bk must be 0 (auto), 32 or 64");
         ctx->opt.gemm_bk = (int)value;

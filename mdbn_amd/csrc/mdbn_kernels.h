@@ -141,6 +141,8 @@ struct PlaneGemmArgs {
     int ms;                // MFMA shape: 16 = v_mfma_f32_16x16x32_bf16 (default), 32 = v_mfma_f32_32x32x16_bf16
     int bn;                // 0 / 128: 128 x 128 tiles; 64: 128 x 64 tiles (unsplit ROW-operand forward pass, fused == 1)
     int fused;             // 0 | 1 activation epilogue (epi) | 2 parameter update (upd) + finalize units (fin)
+    int slab_tail;         // split-K propup (fused == 0, ms == 16): 1 = slab stores under the last stages' MFMAs (mdbn_planes.hip);
+                           // sits in what was padding: no other field moves
     // balanced launches (launch_gemm_planes_bal): `bal` workgroups share tiles x (K / 32) stages evenly;
     // fused = 0: slabs, one per piece of a tile; fused = 4: result in place, pieces of shared tiles through `scratch`
     unsigned long long* stamps;   // diagnostic builds only (-DMDBN_STAMP): 8 wall-clock stamps per workgroup (propup)
@@ -176,6 +178,7 @@ __host__ __device__ inline int bal_tile_slabs(int t, int tiles, int S, int P)
     return bal_block_of(u0 + S - 1, Pr, Ur) - bal_block_of(u0, Pr, Ur) + 1;
 }
 hipError_t launch_gemm_planes(int la, int lb, const PlaneGemmArgs& g, hipStream_t s);
+bool slab_tail_ok(const PlaneGemmArgs& g, int la, int lb);     // may this launch set g.slab_tail?
 hipError_t launch_gemm_planes_bal(int la, int lb, const PlaneGemmArgs& g, hipStream_t s);
 int bal_max_segments(int tiles, int stages, int P);     // slabs a balanced fused == 0 launch needs
 int bal_segment_host(int tiles, int S, int P, int w, int k, int* tile, int* s0, int* s1, int* nseg, int* nt);

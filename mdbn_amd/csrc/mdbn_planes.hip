@@ -38,6 +38,7 @@ typedef short ps16x4 __attribute__((ext_vector_type(4)));
 typedef short ps16x8 __attribute__((ext_vector_type(8)));
 typedef float pf32x16 __attribute__((ext_vector_type(16)));
 typedef float pf32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int pu32x4b __attribute__((ext_vector_type(4)));
 
 #ifndef PL_ARGS_EARLY
 #define PL_ARGS_EARLY 1
@@ -466,22 +467,28 @@ __device__ __forceinline__ void pl_offsets16(int lane, int wm, int wn, int (&off
 #ifndef PL_STAGE_ACC
 #define PL_STAGE_ACC 1
 #endif
+// PL_SWP (PL_CONSUME_CONSTS_SW): the two operands of every MFMA change places, so the accumulator of a tile holds the
+// TRANSPOSED 16x16 block -- row = lane & 15, columns 4 * (lane >> 4) + e: four neighbouring columns of one row, 16 bytes of
+// a slab row per lane.  Every element is the same chain of the same products (x y = y x exactly) summed in the same order.
+#define PL_MF16(X, Y, T, c0_, c1_, c2_)                                                       \
+    (PL_SWP ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(Y, X, T, c0_, c1_, c2_)                 \
+            : __builtin_amdgcn_mfma_f32_16x16x32_bf16(X, Y, T, c0_, c1_, c2_))
 #define MMQ_CHAIN(T, FA, FB, a, b, C0)                                                        \
     do {                                                                                      \
         T = (C0);                                                                             \
         if constexpr (AP == 3) {              /* smallest products first */                   \
-            T = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[2][a], FB[0][b], T, 0, 0, 0);      \
-            T = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[0][a], FB[2][b], T, 0, 0, 0);      \
-            T = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[1][a], FB[1][b], T, 0, 0, 0);      \
-            T = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[1][a], FB[0][b], T, 0, 0, 0);      \
-            T = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[0][a], FB[1][b], T, 0, 0, 0);      \
-            T = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[0][a], FB[0][b], T, 0, 0, 0);      \
+            T = PL_MF16(FA[2][a], FB[0][b], T, 0, 0, 0);      \
+            T = PL_MF16(FA[0][a], FB[2][b], T, 0, 0, 0);      \
+            T = PL_MF16(FA[1][a], FB[1][b], T, 0, 0, 0);      \
+            T = PL_MF16(FA[1][a], FB[0][b], T, 0, 0, 0);      \
+            T = PL_MF16(FA[0][a], FB[1][b], T, 0, 0, 0);      \
+            T = PL_MF16(FA[0][a], FB[0][b], T, 0, 0, 0);      \
         } else if constexpr (AP == 1) {   /* A = a1 exactly: a1 b3 + a1 b2 + a1 b1 is the full product */ \
-            T = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[0][a], FB[2][b], T, 0, 0, 0);      \
-            T = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[0][a], FB[1][b], T, 0, 0, 0);      \
-            T = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[0][a], FB[0][b], T, 0, 0, 0);      \
+            T = PL_MF16(FA[0][a], FB[2][b], T, 0, 0, 0);      \
+            T = PL_MF16(FA[0][a], FB[1][b], T, 0, 0, 0);      \
+            T = PL_MF16(FA[0][a], FB[0][b], T, 0, 0, 0);      \
         } else {        /* bf16 inputs: the leading pieces only */                            \
-            T = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[0][a], FB[0][b], T, 0, 0, 0);      \
+            T = PL_MF16(FA[0][a], FB[0][b], T, 0, 0, 0);      \
         }                                                                                     \
     } while (0)
 #if PL_STAGE_ACC
@@ -560,7 +567,9 @@ __device__ __forceinline__ void pl_offsets16(int lane, int wm, int wn, int (&off
 #endif
 #endif
 // NBH = 16-column blocks per B half of a wave's tile: 2 (64 x 64 per wave, 128-column tile) or 1 (64 x 32, 64-column tile)
-#define PL_CONSUME_CONSTS()                                                                   \
+#define PL_CONSUME_CONSTS() PL_CONSUME_CONSTS_SW(false)
+#define PL_CONSUME_CONSTS_SW(SW)                                                              \
+    constexpr bool PL_SWP = (SW);                                                             \
     constexpr int NA = AP == 3 ? 3 : 1, NB = AP == 0 ? 1 : 3;      /* AP = 0: bf16-input reporting mode */ \
     constexpr int RA = 2 * NA * (LA == LAY_MN ? 2 : 1), RB = NBH * NB * (LB == LAY_MN ? 2 : 1), \
                   NM = 2 * NBH * (AP == 3 ? 6 : (AP == 1 ? 3 : 1));
@@ -918,6 +927,186 @@ static hipError_t launch_planes_t(const PlaneGemmArgs& g, hipStream_t s)
     else return g.ms == 32 ? launch_planes_m<LA, LB, AP, FUSED, 32>(g, s) : launch_planes_m<LA, LB, AP, FUSED, 16>(g, s);
 }
 
+// ---------------------------------------------------------------------------------- split-K propup, "slab_tail"
+// The split-K propup (x planes ROW x W planes COL, 16x16x32 shape, slabs out) with its slab stores UNDER the MFMAs of its
+// last stages instead of behind them.  Once the last LDS-DMA stage has landed no ring slot is written again, and the MFMA
+// waves may use the resident stages in any order: the last T <= PL_NSTAGE stages are walked QUARTER-major -- quarter 0 of
+// the wave's 64 x 64 tile over all tail stages, then quarter 1, ... -- so quarter q's accumulators are final after
+// (q + 1) / 4 of the tail and are stored while the other quarters' MFMAs still occupy the matrix pipe.  Every accumulator
+// sums the same stage-local sums in the same stage order as gemm_planes_kernel's: same bits.
+//   Stores: 16 bytes per lane.  The MFMA operands change places (PL_SWP), which leaves the transposed 16x16 block in the
+//   accumulator -- four neighbouring columns of one row per lane -- so no exchange between lanes and NO LDS is needed for
+//   it (neither a barrier nor a private region: the ring is only ever read here).  The early quarters go out write-through
+//   (sc1: they leave the L2 while the kernel still computes; at 16 bytes per lane that costs what a plain store costs), the
+//   last one plain (PL_TAIL_WT = 1; 0 = all plain, 2 = all write-through).
+//   Barriers: the loader waves meet the opening barrier and one barrier per stage (LD_SYNC), nt + 1 in all, and return.
+//   The body (stages < nt - T) meets one per stage as before; barrier j proves stage j + 1 landed.  The tail meets its T
+//   barriers in quarter 0, one ahead of each stage's first fragment reads (the last one proves nothing and only keeps the
+//   count), and none afterwards.
+// T and the store policy by same-box A/B on the headline step (profiles/r06a_slab_tail_ab.log): T = 2 with write-through
+// early quarters 128.6 us against 134.4 with the stores behind the last MFMA; T = 3 129.7 (its first tail barrier waits for a
+// stage issued only ~0.8 us earlier), T = 1 129.1; all-plain stores 131.2 - 131.8.
+#ifndef PL_TAIL_T
+#define PL_TAIL_T 2
+#endif
+#ifndef PL_TAIL_WT
+#define PL_TAIL_WT 1
+#endif
+struct PlSlabOut {
+    __amdgpu_buffer_rsrc_t rsrc;     // this workgroup's slab
+    int lane_off, ldc4;              // bytes: the lane's row / column share of the wave's tile; one slab row
+};
+
+// The tail: TC stages from stage nb on, quarter-major.  Enters holding the first quarter's fragments of stage nb in
+// (A0, B0) -- (Alo, Blo) behind an even body, (Alo, Bhi) behind an odd one (PAR) -- and double-buffers (A0, B0) / (A1, B1).
+template <int LA, int LB, int AP, int TC, int PAR, int WT>
+__device__ __forceinline__ void pl_tail16(const char* smem, int nb, const int (&offA)[4][2], const int (&offB)[4][2],
+                                          pf32x4a (&acc)[4][4], pbf16x8 (&A0)[3][2], pbf16x8 (&B0)[3][2], pbf16x8 (&A1)[3][2],
+                                          pbf16x8 (&B1)[3][2], const PlSlabOut& so)
+{
+    constexpr int NBH = 2;
+    PL_CONSUME_CONSTS_SW(true);
+    int sb[TC];                      // ring slot (byte offset) of tail stage s
+#pragma unroll
+    for (int s = 0; s < TC; ++s) sb[s] = ((nb + s) % PL_NSTAGE) * PL_STAGE;
+    // item I = (quarter I / TC, tail stage I % TC); quarters (lo, PAR) (lo, !PAR) (hi, !PAR) (hi, PAR)
+#define PL_TAIL_ITEM(I, CA, CB, NXA, NXB)                                                     \
+    do {                                                                                      \
+        const int q_ = (I) / TC, s_ = (I) % TC, q1_ = ((I) + 1) / TC, s1_ = ((I) + 1) % TC;   \
+        const int ah_ = q_ >> 1, bh_ = (((q_ + 1) >> 1) & 1) ^ PAR;                           \
+        const int ah1_ = q1_ >> 1, bh1_ = (((q1_ + 1) >> 1) & 1) ^ PAR;                       \
+        if (q_ == 0) PL_RAW_BARRIER();            /* stage nb + s_ + 1 landed (s_ + 1 < TC) */ \
+        /* (the slot offset is made opaque per item: hipcc otherwise keeps the fragment addresses of every tail stage */ \
+        /* live across the quarters, 12 VGPRs per stage, and spills) */                       \
+        int o1_ = sb[s1_];                                                                    \
+        asm volatile("" : "+s"(o1_));                                                         \
+        if ((I) + 1 < 4 * TC) { RD_A(NXA, smem + o1_, ah1_); RD_B(NXB, smem + o1_, bh1_); }   \
+        MMQ(CA, CB, ah_, bh_);                                                                \
+        if ((I) + 1 < 4 * TC) { ORD(RA + RB); }                                               \
+        if (s_ == TC - 1) {                       /* the quarter is final: 16 bytes per lane and 16-row block */ \
+            _Pragma("unroll") for (int a = 0; a < 2; ++a)                                     \
+                _Pragma("unroll") for (int b = 0; b < 2; ++b) {                               \
+                    const pu32x4b v_ = __builtin_bit_cast(pu32x4b, acc[2 * ah_ + a][2 * bh_ + b]); \
+                    const int off_ = 16 * (2 * ah_ + a) * so.ldc4 + 64 * (2 * bh_ + b);       \
+                    if (WT == 2 || (WT == 1 && q_ < 3)) __builtin_amdgcn_raw_buffer_store_b128(v_, so.rsrc, so.lane_off, off_, 16); \
+                    else __builtin_amdgcn_raw_buffer_store_b128(v_, so.rsrc, so.lane_off, off_, 0); \
+                }                                                                             \
+        }                                                                                     \
+        __builtin_amdgcn_sched_barrier(0);        /* an item is one scheduling region, as a half stage of the body is */ \
+    } while (0)
+#pragma unroll
+    for (int j = 0; j < 2 * TC; ++j) {
+        PL_TAIL_ITEM(2 * j, A0, B0, A1, B1);
+        PL_TAIL_ITEM(2 * j + 1, A1, B1, A0, B0);
+    }
+#undef PL_TAIL_ITEM
+}
+
+// pl_consume16 with the tail: the body is pl_consume16's (serpentine, barriers, PINs) on stages [0, nt - tc)
+template <int LA, int LB, int AP, int T, int WT>
+__device__ __forceinline__ void pl_consume16_tail(char* smem, int nt, int lane, int wm, int wn, pf32x4a (&acc)[4][4], const PlSlabOut& so)
+{
+    static_assert(T >= 1 && T <= PL_NSTAGE, "the tail stages must all be resident in the ring");
+    long long bar_wait = 0;
+    (void)bar_wait;
+    constexpr int NBH = 2;
+    int offA[4][2], offB[4][2];
+    pl_offsets16<LA, LB>(lane, wm, wn, offA, offB);
+    PL_CONSUME_CONSTS_SW(true);
+    pbf16x8 Alo[3][2], Ahi[3][2], Blo[3][2], Bhi[3][2];
+    // T is clamped to the stages the workgroup has: one with fewer than T (nt = 1, 2; a plan's smallest chunks) takes a
+    // one-stage tail, whose code is the smallest
+    const int tc = nt < T ? 1 : T, nb = nt - tc;
+    RD_A(Alo, smem, 0);
+    RD_B(Blo, smem, 0);
+    for (int it = 0; it < nb; it += 2) {
+        {   // even stage
+            const char* base = smem + (it % PL_NSTAGE) * PL_STAGE;
+            const char* next = smem + ((it + 1) % PL_NSTAGE) * PL_STAGE;
+            PL_STAGE_EVEN(base, next, PL_MAIN_BARRIER());
+        }
+        if (it + 1 < nb) {   // odd stage
+            const char* base = smem + ((it + 1) % PL_NSTAGE) * PL_STAGE;
+            const char* next = smem + ((it + 2) % PL_NSTAGE) * PL_STAGE;
+            PL_STAGE_ODD(base, next, PL_MAIN_BARRIER());
+        }
+    }
+    // the hand-over: an even number of body stages leaves (Alo, Blo) of stage nb, an odd number (Alo, Bhi)
+    if (tc == T) {
+        if (nb & 1) pl_tail16<LA, LB, AP, T, 1, WT>(smem, nb, offA, offB, acc, Alo, Bhi, Ahi, Blo, so);
+        else pl_tail16<LA, LB, AP, T, 0, WT>(smem, nb, offA, offB, acc, Alo, Blo, Ahi, Bhi, so);
+    } else if constexpr (T > 1) {
+        if (nb & 1) pl_tail16<LA, LB, AP, 1, 1, WT>(smem, nb, offA, offB, acc, Alo, Bhi, Ahi, Blo, so);
+        else pl_tail16<LA, LB, AP, 1, 0, WT>(smem, nb, offA, offB, acc, Alo, Blo, Ahi, Bhi, so);
+    }
+}
+
+template <int AP, int T, int WT>
+__global__ __launch_bounds__(64 * (4 + PL_LW)) void gemm_planes_slabtail_kernel(PlaneGemmArgs g)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+#if PL_ARGS_EARLY
+    asm volatile("" :: "s"(g.A), "s"(g.lda), "s"(g.pa), "s"(g.B), "s"(g.ldb), "s"(g.pb), "s"(g.C), "s"(g.ldc), "s"(g.slab_stride),
+                 "s"(g.kchunk), "s"(g.tiles_m), "s"(g.tiles_n), "s"((int)gridDim.x));
+#endif
+    // (split, tile) order and wave roles as gemm_planes_kernel
+    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int xcd = bid & 7, slot = bid >> 3;
+    const int qq = nwg >> 3, rem = nwg & 7;
+    const int w = (xcd < rem ? xcd * (qq + 1) : rem * (qq + 1) + (xcd - rem) * qq) + slot;
+    const int tiles = g.tiles_m * g.tiles_n;
+    const int ks = w / tiles, t = w - ks * tiles;
+    int tm, tn;
+    if (g.tiles_m <= g.tiles_n) { tn = t / g.tiles_m; tm = t - tn * g.tiles_m; }
+    else { tm = t / g.tiles_n; tn = t - tm * g.tiles_n; }
+    const int m0 = tm * 128, n0 = tn * 128;
+    const int kbeg = ks * g.kchunk;
+    const int nt = g.kchunk / 32;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (wave >= 4) {
+        pl_loader<LAY_K, LAY_MN, AP, 16, false, 128>(g, smem, wave - 4, lane, m0, n0, kbeg, nt);
+        return;
+    }
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    pf32x4a acc[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = pf32x4a{0.f, 0.f, 0.f, 0.f};
+    // transposed accumulator blocks (PL_SWP): row = lane & 15, columns 4 * (lane >> 4) .. + 3.  Offsets inside the slab
+    // are 32-bit and the descriptor bounds every store to it (host: slab bytes < 2^31, 16-byte aligned rows)
+    PlSlabOut so;
+    so.ldc4 = (int)g.ldc * 4;
+    so.rsrc = __builtin_amdgcn_make_buffer_rsrc(g.C + (int64_t)ks * g.slab_stride, 0, g.M * so.ldc4, 0x00020000);
+    so.lane_off = (m0 + wm + (lane & 15)) * so.ldc4 + (n0 + wn + 4 * (lane >> 4)) * 4;
+    __syncthreads();                                 // stage 0 landed
+    pl_consume16_tail<LAY_K, LAY_MN, AP, T, WT>(smem, nt, lane, wm, wn, acc, so);
+}
+
+template <int AP>
+static hipError_t launch_planes_slabtail(const PlaneGemmArgs& g, hipStream_t s)
+{
+    auto kern = gemm_planes_slabtail_kernel<AP, PL_TAIL_T, PL_TAIL_WT>;
+    static bool attr_set = false;
+    constexpr int lds = PL_NSTAGE * PL_STAGE;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n * g.splitk), dim3(64 * (4 + PL_LW)), lds, s, g);
+    return hipGetLastError();
+}
+
+// what a slab_tail launch needs beyond launch_gemm_planes' own checks: 16-byte stores into 32-bit-addressable slabs
+bool slab_tail_ok(const PlaneGemmArgs& g, int la, int lb)
+{
+    return la == LAY_K && lb == LAY_MN && (g.ap == 1 || g.ap == 3) && g.fused == 0 && g.ms == 16 && g.bn != 64 && !g.bal &&
+           (g.ldc & 3) == 0 && (g.slab_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(g.C) & 15) == 0 &&
+           (int64_t)g.M * g.ldc * 4 < ((int64_t)1 << 31);
+}
+
 hipError_t launch_gemm_planes(int la, int lb, const PlaneGemmArgs& g, hipStream_t s)
 {
     if (g.bn == 64) {       // unsplit forward pass on 128 x 64 tiles with the fused activation epilogue (propdown)
@@ -930,6 +1119,10 @@ hipError_t launch_gemm_planes(int la, int lb, const PlaneGemmArgs& g, hipStream_
         g.tiles_n != g.N / 128 || (g.lda & 7) || (g.ldb & 7) || ((g.fused == 1 || g.fused == 2) && g.splitk != 1) ||
         (g.ap != 0 && g.ap != 1 && g.ap != 3))
         return hipErrorInvalidValue;
+    if (g.slab_tail) {      // split-K propup with the slab stores under its last stages (the caller checked slab_tail_ok)
+        if (!slab_tail_ok(g, la, lb)) return hipErrorInvalidValue;
+        return g.ap == 1 ? launch_planes_slabtail<1>(g, s) : launch_planes_slabtail<3>(g, s);
+    }
 #define PL_CASE(LAV, LBV, APV, FV) \
     if (la == LAV && lb == LBV && g.ap == APV && g.fused == FV) return launch_planes_t<LAV, LBV, APV, FV>(g, s)
     // propup: x planes (ROW) x W planes (COL)
@@ -1138,7 +1331,6 @@ __device__ __forceinline__ void pl_loader_bal(const PlaneGemmArgs& g, char* smem
 #undef PL_ISSUE
 }
 
-typedef unsigned int pu32x4b __attribute__((ext_vector_type(4)));
 
 template <int LA, int LB, int AP, int FIX>
 __global__ __launch_bounds__(64 * (4 + PL_LW)) void gemm_planes_bal_kernel(PlaneGemmArgs g)
@@ -1353,6 +1545,7 @@ hipError_t launch_gemm_planes_bal(int la, int lb, const PlaneGemmArgs& g, hipStr
 #undef RD_B
 #undef MMQ
 #undef MMQ_CHAIN
+#undef PL_MF16
 #undef ORD
 #undef PIN
 #undef PL_STAGE_EVEN

@@ -1,7 +1,14 @@
-"""Interleaved A/B of a library option on the full CD-1 step (bench workload)."""
+"""Interleaved A/B of a library option on the full CD-1 step (bench workload).
+    python scripts/step_ab.py OPTION VALUE VALUE ...
+A value may be repeated (``slab_tail 0 0``): every position is an arm of its own, so two arms with the same setting show
+what identical settings differ by on this box.  MDBN_AB_LIBRARY=path times a library built with diagnostic -D flags from the
+current sources instead of the in-tree one (scripts/build_variants.py)."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, mdbn_amd
+if os.environ.get("MDBN_AB_LIBRARY"):
+    from mdbn_amd import _lib
+    _lib.use_diagnostic_library(os.environ["MDBN_AB_LIBRARY"])
 opt, values = sys.argv[1], [int(v) for v in sys.argv[2:]]
 eng = mdbn_amd.set_engine(mdbn_amd.HipEngine())
 # MDBN_AB_SHAPE="V,H,B,k,gauss" selects another layer (default: the c2 headline shape)
@@ -22,18 +29,18 @@ def run(n):
     for it in range(n):
         mb, nb = it % (N // B), (it + 1) % (N // B)
         fn(indexes=perm[mb * B:(mb + 1) * B], momentum=0.0, next_indexes=perm[nb * B:(nb + 1) * B])
-res = {v: [] for v in values}
+res = [[] for v in values]
 run(20); eng.synchronize()
-for rnd in range(5):
-    for v in values:
+for rnd in range(int(os.environ.get("MDBN_AB_ROUNDS", "5"))):
+    for arm, v in enumerate(values):
         eng.set_option(opt, v)
         run(5); eng.synchronize()
         t0 = time.perf_counter(); run(100); eng.synchronize()
-        res[v].append((time.perf_counter() - t0) * 1e4)
-for v in values:
-    print("%s=%d: median %.1f us/step (min %.1f)" % (opt, v, np.median(res[v]), min(res[v])))
+        res[arm].append((time.perf_counter() - t0) * 1e4)
+for arm, v in enumerate(values):
+    print("arm %d %s=%d: median %.2f us/step (min %.2f, max %.2f)" % (arm, opt, v, np.median(res[arm]), min(res[arm]), max(res[arm])))
 # per-GEMM averages (HIP events around each launch) under every value
-for v in values:
+for v in sorted(set(values)):
     eng.set_option(opt, v)
     run(5); eng.synchronize()
     eng.kernel_timing(True); run(50); eng.synchronize()
