@@ -21,7 +21,9 @@ def softplus(x):
 
 
 def sigmoid(x):
-    return 1.0 / (1.0 + np.exp(-x))
+    # exp(-x) may overflow to +inf on a saturated layer (float32: from x = -88.7 down): 1 / (1 + inf) = 0 is the right limit
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-x))
 
 
 def log_pstar(v, W, c, b_beta, beta, gauss):

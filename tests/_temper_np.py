@@ -26,7 +26,9 @@ TIE = 4e-6          # near-tie mask of the drift tests (tests/test_gpu_surface.p
 
 
 def sigmoid(x):
-    return 1.0 / (1.0 + np.exp(-x))
+    # exp(-x) may overflow to +inf on a saturated layer (float32: from x = -88.7 down): 1 / (1 + inf) = 0 is the right limit
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-x))
 
 
 def softplus(x):

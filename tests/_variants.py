@@ -88,13 +88,17 @@ def w_planes_in_step(eng, W):
     return bool(torch.equal(wp, split_planes(eng, W)))
 
 
-def cd(eng, V, H, B, k, gauss, opts, chain=None, sample_stats=False, add_noise=False, seed=5):
+def cd(eng, V, H, B, k, gauss, opts, chain=None, sample_stats=False, add_noise=False, seed=5, params=None):
     """One eng.cd_step with keep_f32 and the chain taps on under `opts`: inputs, statistics, V2, P2, taps, the caller's chain
-    before and after the call, the GEMM launch kinds, and what the scratch / the engine hold of bf16 planes."""
+    before and after the call, the GEMM launch kinds, and what the scratch / the engine hold of bf16 planes.  `params`: the
+    layer's (W, hbias, vbias) in place of init_W and N(0, 0.2) biases (the data and the index list stay those of `seed`)."""
     from mdbn_amd import RngAddr
     rs = np.random.RandomState(seed)
     W = rbm_np.init_W(rs, V, H, np.float32)
     hb, vb = rs.normal(0, 0.2, H).astype(np.float32), rs.normal(0, 0.2, V).astype(np.float32)
+    if params is not None:
+        W, hb, vb = [np.ascontiguousarray(a, dtype=np.float32) for a in params]
+        assert W.shape == (V, H) and hb.shape == (H,) and vb.shape == (V,), (W.shape, hb.shape, vb.shape)
     N = B + 13
     data = rs.normal(size=(N, V)).astype(np.float32) if gauss else (rs.uniform(size=(N, V)) < 0.3).astype(np.float32)
     idx = rs.permutation(N)[:B].astype(np.int64)
@@ -121,6 +125,10 @@ def cd(eng, V, H, B, k, gauss, opts, chain=None, sample_stats=False, add_noise=F
             kinds = [kd for _, _, _, kd in eng.kernel_timing_detail()]
             wp, _ = eng.w_planes(dW)
             planes_ok = None if wp is None else w_planes_in_step(eng, dW)
+            outputs = dict(stats=stats, P2=sc.P2, V2=sc.V2, trace_h=sc.trace_h)
+            if not gauss:
+                outputs["trace_v"] = sc.trace_v
+            nonfinite = {name: eng.count_nonfinite(t) for name, t in outputs.items()}   # pad columns included
     finally:
         eng.kernel_timing(False)
         eng.keep_f32, eng.trace_chain = keep
@@ -130,7 +138,7 @@ def cd(eng, V, H, B, k, gauss, opts, chain=None, sample_stats=False, add_noise=F
                 P2=sc.P2.cpu().numpy(), V2=sc.V2.cpu().numpy(), th=sc.trace_h.cpu().numpy()[:n_h, :, :H],
                 tv=None if gauss else sc.trace_v.cpu().numpy()[:, :, :V],
                 chain1=None if pers is None else pers.cpu().numpy(), kinds=kinds, eligible=eligible,
-                scratch_planes=sc.planes is not None, planes_ok=planes_ok)
+                scratch_planes=sc.planes is not None, planes_ok=planes_ok, nonfinite=nonfinite)
 
 
 def run_variant(eng, name, V, H, B, opts, **kw):

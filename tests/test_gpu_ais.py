@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import _ais_np as A
+import _saturated as S
 from _margins import check
 
 pytestmark = pytest.mark.gpu
@@ -32,6 +33,18 @@ def _params(V, H, gauss, s, seed=3):
     W = rs.normal(0, s, (V, H)).astype(np.float32)
     c, b = rs.normal(0, 0.5, H).astype(np.float32), rs.normal(0, 0.5, V).astype(np.float32)
     bA = (b + rs.normal(0, 0.3, V)).astype(np.float32)
+    return W, c, b, bA
+
+
+# the layers of the first two PARITY rows with their biases on the ladder of tests/_saturated.py
+SATURATED = [row for row in PARITY if row[:2] in ((100, 24), (400, 40))]
+
+
+def _saturated_params(V, H, gauss, s, seed=3):
+    """`_params` with c and (Bernoulli) b from tests/_saturated.py: pre-activations from -120 to 120; bA = b + N(0, 0.3)."""
+    W, _, b, _ = _params(V, H, gauss, s, seed)
+    c, b = S.sampler_biases(V, H, gauss, b, seed)
+    bA = (b + np.random.RandomState(seed + 1).normal(0, 0.3, V)).astype(np.float32)
     return W, c, b, bA
 
 
@@ -79,6 +92,21 @@ def test_forced_parity(hip_engine, V, H, gauss, s, paths, M):
         assert th.shape == (7, M, H) and tv.shape == (8, M, V) and np.isfinite(logw).all()
         r64, gap = _forced(W, c, b, bA, gauss, betas, M, th, tv)
         _check_forced("AIS forced %d->%d %s M=%d path %d" % (V, H, "GRBM" if gauss else "RBM", M, path), logw, r64, gap)
+
+
+@pytest.mark.parametrize("V,H,gauss,s,paths", SATURATED)
+def test_forced_parity_on_a_saturated_layer(hip_engine, V, H, gauss, s, paths):
+    """The first M of test_forced_parity on a layer whose hidden (and Bernoulli visible) pre-activations reach +-120: the
+    same bound rule, tie share and flip count."""
+    M = 64
+    W, c, b, bA = _saturated_params(V, H, gauss, s)
+    betas = np.linspace(0, 1, 9)
+    for path in paths:
+        logw, th, tv = _device(hip_engine, W, c, b, bA, gauss, betas, M, path)
+        assert th.shape == (7, M, H) and tv.shape == (8, M, V) and np.isfinite(logw).all()
+        S.assert_bands("AIS saturated hidden", [tv[-1].astype(np.float64) @ W + c], S.REGIMES)
+        r64, gap = _forced(W, c, b, bA, gauss, betas, M, th, tv)
+        _check_forced("AIS forced saturated %d->%d %s M=%d path %d" % (V, H, "GRBM" if gauss else "RBM", M, path), logw, r64, gap)
 
 
 def _layer(eng, V, H, gauss, W, c, b, seed=7):

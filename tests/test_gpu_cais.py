@@ -13,7 +13,7 @@ import pytest
 import _ais_np as A
 import _cais_np as CA
 from _margins import check
-from test_gpu_ais import PARITY, SEED, STEP, STREAM, TIE_SHARE, V_ATOL, _layer, _params
+from test_gpu_ais import PARITY, SATURATED, SEED, STEP, STREAM, TIE_SHARE, V_ATOL, _layer, _params, _saturated_params
 
 pytestmark = pytest.mark.gpu
 
@@ -78,6 +78,22 @@ def test_forced_parity(hip_engine, V, H, gauss, s, paths, N, C):
             r64, gap = _forced(W, c, b, bA, gauss, betas, obs, mask, C, th, tv)
             _check_forced("CAIS forced %d->%d %s N=%d C=%d mask rows %d path %d" % (V, H, "GRBM" if gauss else "RBM", N, C, mask_rows, path),
                           logw, r64, gap, obs, mask, C, tv)
+
+
+@pytest.mark.parametrize("V,H,gauss,s,paths", SATURATED)
+def test_forced_parity_on_a_saturated_layer(hip_engine, V, H, gauss, s, paths):
+    """The first (N, C) of test_forced_parity with the biases on the ladder of tests/_saturated.py (pre-activations to +-120):
+    the same bound rule, tie share and flip count."""
+    N, C = SHAPES[0]
+    W, c, b, bA = _saturated_params(V, H, gauss, s)
+    betas = np.linspace(0, 1, 9)
+    obs, mask = _clamp_inputs(N, V, gauss, N)
+    for path in paths:
+        logw, th, tv = _device(hip_engine, W, c, b, bA, gauss, betas, obs, mask, C, path)
+        assert logw.shape == (N, C) and th.shape == (7, N * C, H) and tv.shape == (8, N * C, V) and np.isfinite(logw).all()
+        r64, gap = _forced(W, c, b, bA, gauss, betas, obs, mask, C, th, tv)
+        _check_forced("CAIS forced saturated %d->%d %s N=%d C=%d path %d" % (V, H, "GRBM" if gauss else "RBM", N, C, path),
+                      logw, r64, gap, obs, mask, C, tv)
 
 
 @pytest.mark.parametrize("V,H,gauss,s,path", [(100, 24, False, 0.3, 1), (100, 24, False, 0.3, 2), (400, 40, True, 0.05, 1)])

@@ -13,6 +13,7 @@ import pytest
 
 import _ais_np as A
 import _clamp_np as Cn
+import _saturated as S
 from _margins import check
 
 pytestmark = pytest.mark.gpu
@@ -116,6 +117,33 @@ def test_forced_parity(hip_engine, V, H, gauss, noise, s, paths, B, per_row):
         r64, r32 = _forced(W, c, b, gauss, v0, obs, mask, n_steps, burn_in, noise, d)
         _check_forced("clamp forced %d->%d %s%s B=%d %s mask path %d" % (V, H, "GRBM" if gauss else "RBM", "+" + str(noise) if noise else "", B,
                                                                         "row" if per_row else "shared", path), d, r64, r32, gauss)
+
+
+@pytest.mark.parametrize("V,H,gauss,noise,s,paths", [PARITY[0], PARITY[2]])
+def test_forced_parity_on_a_saturated_layer(hip_engine, V, H, gauss, noise, s, paths):
+    """B = 64 with per-row masks (the first case of test_forced_parity) on 100 -> 24 RBM and 400 -> 40 GRBM with the biases
+    on the ladder of tests/_saturated.py (pre-activations to +-120): the same tolerances and bound rule, and the final means
+    held to the exactness rules of a saturated sigmoid."""
+    B, n_steps, burn_in = 64, 8, 2
+    W, c, b = _params(V, H, s)
+    c, b = S.sampler_biases(V, H, gauss, b)
+    v0, obs, mask = _inputs(V, gauss, B, True)
+    for path in paths:
+        d = _device(hip_engine, W, c, b, gauss, v0, obs, mask, n_steps, burn_in, path, add_noise=noise)
+        assert all(np.isfinite(d[k]).all() for k in NAMES)
+        held = np.broadcast_to(mask != 0, (B, V))
+        assert (d["trace_v"][:, held] == obs[held][None]).all(), "an observed entry moved"
+        r64, r32 = _forced(W, c, b, gauss, v0, obs, mask, n_steps, burn_in, noise, d)
+        tag = "clamp forced saturated %d->%d %s B=%d path %d" % (V, H, "GRBM" if gauss else "RBM", B, path)
+        _check_forced(tag, d, r64, r32, gauss)
+        # the last step: h_mean from the visible state before it, a Bernoulli v_mean from its hidden sample (where not held)
+        pre_h = d["trace_v"][-2].astype(np.float64) @ W + c
+        S.assert_bands(tag, [pre_h], S.REGIMES)
+        S.check_saturation(tag + " h_mean", pre_h, d["h_mean"], d["h_sample"])
+        if not gauss:
+            pre_v = d["trace_h"][-1].astype(np.float64) @ W.T + b
+            S.assert_bands(tag, [pre_v[~held]])
+            S.check_saturation(tag + " v_mean", pre_v[~held], d["v_mean"][~held], d["v"][~held])
 
 
 def test_path_1_refused_where_it_does_not_fit(hip_engine):

@@ -14,7 +14,7 @@ import _ais_np as A
 import _ptz_np as Z
 import _temper_np as T
 from _margins import check
-from test_gpu_temper import _params, _start, _layer, SEED, STREAM, STEP
+from test_gpu_temper import SATURATED, _params, _saturated_params, _start, _layer, SEED, STREAM, STEP
 
 pytestmark = pytest.mark.gpu
 
@@ -67,14 +67,25 @@ def _run(eng, W, c, b, bA, gauss, betas, h0, n, burn_in, path, spl=0, works=True
     return d
 
 
+@pytest.mark.parametrize("V,H,gauss,s,paths", SATURATED)
+def test_works_along_the_device_trace_on_a_saturated_layer(hip_engine, V, H, gauss, s, paths):
+    """M, R and sweeps of the first TRACE row with the biases on the ladder of tests/_saturated.py (test_gpu_temper.py)."""
+    M, R, n = TRACE[0][4:7]
+    _works_along_the_trace(hip_engine, "saturated ", _saturated_params(V, H, gauss, s), V, H, gauss, M, R, n, paths)
+
+
 @pytest.mark.parametrize("V,H,gauss,s,M,R,n,paths", TRACE)
 def test_works_along_the_device_trace(hip_engine, V, H, gauss, s, M, R, n, paths):
-    W, c, b, bA = _params(V, H, s)
+    _works_along_the_trace(hip_engine, "", _params(V, H, s), V, H, gauss, M, R, n, paths)
+
+
+def _works_along_the_trace(hip_engine, what, params, V, H, gauss, M, R, n, paths):
+    W, c, b, bA = params
     betas = np.linspace(0, 1, R).astype(np.float32)
     h0 = _start(M, R, H)
     burn = n // 4
     for path in paths:
-        tag = "ptz %d->%d %s M=%d R=%d path %d" % (V, H, "GRBM" if gauss else "RBM", M, R, path)
+        tag = "ptz %s%d->%d %s M=%d R=%d path %d" % (what, V, H, "GRBM" if gauss else "RBM", M, R, path)
         d = _run(hip_engine, W, c, b, bA, gauss, betas, h0, n, burn, path, trace=True)
         w = d["works"]
         assert w.shape == (n, M, R - 1, 2) and w.dtype == np.float64

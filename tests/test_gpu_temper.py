@@ -12,6 +12,7 @@ Measured on MI355X: see DESIGN 3.6."""
 import numpy as np
 import pytest
 
+import _saturated as S
 import _temper_np as T
 from _margins import check
 from test_temper_twin import M as GT_M, R as GT_R, N_SWEEPS, BURN_IN, ladder_error
@@ -118,6 +119,31 @@ def test_device_against_twin(hip_engine, V, H, gauss, s, M, R, n, paths):
         assert tries == sum(M * len(range(t % 2, R - 1, 2)) for t in range(n)) and d["accepted"].sum() > 0
         r64, r32 = _forced(W, c, b, bA, gauss, betas, h0, n, burn, d)
         _check_forced("pt forced %d->%d %s M=%d R=%d path %d" % (V, H, "GRBM" if gauss else "RBM", M, R, path), d, r64, r32)
+
+
+# 100 -> 24 RBM on both paths and 400 -> 40 GRBM (the general path) at the M, R and sweeps of the first PARITY row
+SATURATED = [(100, 24, False, 0.3, (1, 2)), (400, 40, True, 0.05, (2,))]
+
+
+def _saturated_params(V, H, gauss, s):
+    """`_params` with c and (Bernoulli) b on the ladder of tests/_saturated.py: pre-activations from -120 to 120 at beta = 1."""
+    W, _, b, bA = _params(V, H, s)
+    c, b = S.sampler_biases(V, H, gauss, b)
+    return W, c, b, bA
+
+
+@pytest.mark.parametrize("V,H,gauss,s,paths", SATURATED)
+def test_device_against_twin_on_a_saturated_layer(hip_engine, V, H, gauss, s, paths):
+    M, R, n = PARITY[0][4:7]
+    W, c, b, bA = _saturated_params(V, H, gauss, s)
+    betas = np.linspace(0, 1, R).astype(np.float32)
+    h0 = _start(M, R, H)
+    burn = n // 4
+    for path in paths:
+        d = _device(hip_engine, W, c, b, bA, gauss, betas, h0, n, burn, path)
+        assert all(np.isfinite(d[k]).all() for k in ("v_avg", "h_avg", "trace_v", "trace_h"))
+        r64, r32 = _forced(W, c, b, bA, gauss, betas, h0, n, burn, d)
+        _check_forced("pt forced saturated %d->%d %s M=%d R=%d path %d" % (V, H, "GRBM" if gauss else "RBM", M, R, path), d, r64, r32)
 
 
 def test_path_1_refused_where_it_does_not_fit(hip_engine):
