@@ -11,6 +11,7 @@ Matrix convention: a device matrix is a torch view [rows, cols] over storage
 """
 import ctypes as C
 import os as _os
+from collections import namedtuple
 
 import numpy
 import torch
@@ -59,6 +60,19 @@ class RngAddr(object):
                         self.step & 0xFFFFFFFF, self.draw & 0xFFFFFFFF, 0, self.row_offset)
 
 
+# Ahead: what a step prepared for the next one (CDScratch.ahead; before the call: what it announces) -- the data matrix and the
+# index tensor (kept alive) with their version counters, the X2 buffer the rows are in; ``params``: None on the plane path, on
+# the thin-batch path, whose hand-over also covers x W, the AheadParams those products were computed from.
+# CdCall: what _cd_args resolved for one call (``keep``: what else must live until it is enqueued; ``announce``: an Ahead without
+# params, or None; ``thin``: the thin-batch hand-over rules apply); with W the token of cd_forward.
+# StepCache: the argument structs a step function keeps for its next single-device call (cd_train_step_cached), their byref()s,
+# the key they are valid under (_step_cache_key), the scratch and the tensors the structs point into.
+Ahead = namedtuple("Ahead", "data data_version indexes buffer index_version params")
+AheadParams = namedtuple("AheadParams", "W_ptr W_version W_serial options_epoch")
+CdCall = namedtuple("CdCall", "args stats scratch data indexes keep announce thin")
+StepCache = namedtuple("StepCache", "args update args_ref update_ref key scratch W tensors")
+
+
 class CDScratch(object):
     """Per-(B, V, H) buffers of one CD step; see mdbn_cd_args in include/mdbn_hip.h."""
 
@@ -76,7 +90,7 @@ class CDScratch(object):
             _lib.check(engine.lib.mdbn_planes_bytes(B, ldv, ldh, C.byref(n)), "mdbn_planes_bytes")
             self.planes = torch.empty(n.value // 2, dtype=torch.int16, device=engine.device)
         # gather-ahead (mdbn_cd_args.next_indexes): second X2-plane buffer (made on first use), the buffer the current
-        # step uses, and what the last step gathered ahead: (data pointer, data version, index tensor kept alive, buffer)
+        # step uses, and what the last step gathered ahead (an Ahead, or None)
         self.planes_alt = None
         self.x_buffer = 0
         self.ahead = None
@@ -687,13 +701,17 @@ class HipEngine(object):
         """Was THIS minibatch prepared by the previous step (CDScratch.ahead)?  Same matrix, unchanged since, same index
         list; thin-batch path, whose record also covers x W: the same parameters, written by nobody since that step
         (torch-side writes move W._version, library-side ones _w_serial) under the same options."""
-        if ahead is None or ahead[0].data_ptr() != data.data_ptr() or ahead[1] != data._version or \
-                not self._same_index_tensor(ahead[2], idx) or ahead[4] != idx._version:
+        if ahead is None or ahead.data.data_ptr() != data.data_ptr() or ahead.data_version != data._version or \
+                not self._same_index_tensor(ahead.indexes, idx) or ahead.index_version != idx._version:
             return False
-        return not thin or (len(ahead) == 9 and ahead[5:] == (W.data_ptr(), W._version, self._w_serial, self._options_epoch))
+        return not thin or ahead.params == (W.data_ptr(), W._version, self._w_serial, self._options_epoch)
 
-    def _ahead_record(self, announce, W):
-        return announce + (W.data_ptr(), W._version, self._w_serial, self._options_epoch)
+    def _gathered_ahead(self, sc, announce, flag, W, thin):
+        """The kernel's ``flag`` says it prepared the announced minibatch: the next call finds the rows (``sc.ahead``).  The flag
+        is the caller's: every uncached call replaces the engine's ``_ahead_flag``, so cached structs carry one of their own."""
+        if announce is not None and flag:
+            params = AheadParams(W.data_ptr(), W._version, self._w_serial, self._options_epoch) if thin else None
+            sc.ahead = announce._replace(params=params)
 
     def _cd_args(self, data, indexes, W, hbias, vbias, gauss, k, rng, persistent, add_noise, stats_slot,
                  sample_stats=False, stats=None, comm_cus=0, next_indexes=None):
@@ -737,7 +755,7 @@ class HipEngine(object):
         # gather-ahead: was this minibatch gathered by the previous step's statistics kernel?  (same matrix, unchanged since,
         # same index list: the announced tensor has been kept alive, so an equal address means the same list)
         ahead, sc.ahead = sc.ahead, None
-        keep = [data, idx, ws]
+        keep, announce = [ws], None
         # ... on the plane path; on the thin-batch path (B <= 32, ldh <= 512: the library decides and reports) the previous
         # step's update kernel gathered the rows AND left the partials of x W, so the parameters must be the ones it wrote
         # (the step variants thin_eligible refuses never take part: nothing would honour the hand-over)
@@ -748,7 +766,7 @@ class HipEngine(object):
             # ... and unchanged: an index buffer refilled IN PLACE between the announcing call and this one has another
             # version counter, and the rows are gathered afresh
             if self._ahead_valid(ahead, data, idx, W, thin):
-                sc.x_buffer = ahead[3]
+                sc.x_buffer = ahead.buffer
                 a.v0_ready = 1
             if sc.planes_alt is not None or next_indexes is not None:
                 a.planes_alt = sc.alt_planes(self, ldv).data_ptr()
@@ -760,14 +778,14 @@ class HipEngine(object):
                     self._ahead_flag = C.c_int32(0)
                     a.ahead_done = C.pointer(self._ahead_flag)
                     keep.append(nxt)
-                    sc._announce = (data, data._version, nxt, 0 if thin else 1 - sc.x_buffer, nxt._version)
+                    announce = Ahead(data, data._version, nxt, 0 if thin else 1 - sc.x_buffer, nxt._version, None)
         if self.trace_chain:
             if sc.trace_h is None or sc.trace_h.shape[0] != k + 1:
                 sc.trace_h = torch.zeros((k + 1, B, ldh), dtype=torch.float32, device=self.device)
                 sc.trace_v = None if gauss else torch.zeros((k, B, ldv), dtype=torch.float32, device=self.device)
             a.trace_h = sc.trace_h.data_ptr()
             a.trace_v = sc.trace_v.data_ptr() if sc.trace_v is not None else None
-        return a, stats, sc, keep                   # keep the tensors alive until enqueued
+        return CdCall(a, stats, sc, data, idx, keep, announce, thin)
 
     def cd_step(self, data, indexes, W, hbias, vbias, gauss, k, rng, persistent=None, add_noise=False,
                 stats_slot=0, sample_stats=False, stats=None, comm_cus=0):
@@ -775,33 +793,33 @@ class HipEngine(object):
         Returns (stats, scratch): the packed [S | s_h | s_v | cost_sum] buffer and the
         CDScratch holding ph_mean / nv_mean / nh_mean for inspection.  ``comm_cus`` > 0 (data-parallel
         mode): CUs left to the collective that runs beside this step (mdbn_cd_args.comm_cus)."""
-        a, stats, sc, _keep = self._cd_args(data, indexes, W, hbias, vbias, gauss, k, rng, persistent,
-                                            add_noise, stats_slot, sample_stats, stats, comm_cus)
-        _lib.check(self.lib.mdbn_cd_step(self.ctx, self._stream(), C.byref(a)), "mdbn_cd_step")
-        if a.W_planes:
+        call = self._cd_args(data, indexes, W, hbias, vbias, gauss, k, rng, persistent,
+                             add_noise, stats_slot, sample_stats, stats, comm_cus)
+        _lib.check(self.lib.mdbn_cd_step(self.ctx, self._stream(), C.byref(call.args)), "mdbn_cd_step")
+        if call.args.W_planes:
             self._w_planes_written(W)            # (split on entry if they were stale)
-        return stats, sc
+        return call.stats, call.scratch
 
     def cd_forward(self, data, indexes, W, hbias, vbias, gauss, k, rng, add_noise=False, sample_stats=False, stats=None,
                    comm_cus=0, next_indexes=None):
         """The first half of ``cd_step`` (mdbn_cd_forward): gather, positive phase and the Gibbs chain -- everything that
         reads the parameters.  Returns the token ``cd_statistics`` completes the step with."""
-        a, stats, sc, keep = self._cd_args(data, indexes, W, hbias, vbias, gauss, k, rng, None, add_noise, 0,
-                                           sample_stats, stats, comm_cus, next_indexes=next_indexes)
-        sc._announce, announce = None, getattr(sc, "_announce", None)
-        keep.append(announce)
+        call = self._cd_args(data, indexes, W, hbias, vbias, gauss, k, rng, None, add_noise, 0,
+                             sample_stats, stats, comm_cus, next_indexes=next_indexes)
+        a = call.args
         _lib.check(self.lib.mdbn_cd_forward(self.ctx, self._stream(), C.byref(a)), "mdbn_cd_forward")
         if a.W_planes:
             self._w_planes_written(W)
             a.W_planes_valid = 1
-        return (a, stats, sc, keep, W)
+        return (call, W)
 
     def cd_statistics(self, token, deferred=None):
         """The second half (mdbn_cd_statistics): bias statistics + statistics GEMM of the step ``cd_forward`` began.
         ``deferred``: the arguments of ``apply_update(..., phase=3)`` for the PREVIOUS step (whose all-reduced statistics
         the current stream has just been made to wait for) -- the library applies that update inside the statistics GEMM
         when it can, as its own launch otherwise; returns (stats, scratch, cost of the deferred update or None)."""
-        a, stats, sc, keep, W = token
+        call, W = token
+        a = call.args
         u, cost = (None, None)
         if deferred is not None:
             u, cost = self._update_args(*deferred)
@@ -810,17 +828,12 @@ class HipEngine(object):
         if u is not None:
             self._w_planes_written(W)
             self._w_serial += 1
-        announce = keep[-1]
-        if announce is not None and a.ahead_done and self._ahead_flag.value:
-            sc.ahead = self._ahead_record(announce, W)              # the next call finds its rows in the other X2 buffer
-        return stats, sc, cost
+        self._gathered_ahead(call.scratch, call.announce, a.ahead_done and self._ahead_flag.value, W, call.thin)
+        return call.stats, call.scratch, cost
 
     def _update_args(self, W, W_speed, W0, hbias, hbias_speed, vbias, vbias_speed, stats, lr, lambda_1,
                      lambda_2, weightcost, momentum, batch_size, n_rows, cost_scale, phase, ldv):
         V, H = W.shape
-        # Step costs are 0-d views into a block of 1024 floats.  A block is never reused: when it is full a fresh one is
-        # allocated (4 KB per 1024 steps) and the old one lives as long as a caller still holds one of its views, so a
-        # cost kept unread for any number of steps can never show another step's value.
         cost = self._next_cost_slot()
         u = _lib.UpdateArgs()
         u.W, u.W_speed = W.data_ptr(), W_speed.data_ptr()
@@ -840,7 +853,8 @@ class HipEngine(object):
 
     def _next_cost_slot(self):
         # Step costs are 0-d views into a block of 1024 floats.  A block is never reused: when it is full a fresh one is
-        # allocated (4 KB per 1024 steps) and the old one lives as long as a caller still holds one of its views.
+        # allocated (4 KB per 1024 steps) and the old one lives as long as a caller still holds one of its views, so a
+        # cost kept unread for any number of steps can never show another step's value.
         if self._cost_slot >= self._cost_ring.numel():
             self._cost_ring = torch.zeros(1024, dtype=torch.float32, device=self.device)
             self._cost_slot = 0
@@ -848,22 +862,28 @@ class HipEngine(object):
         self._cost_slot = slot + 1
         return self._cost_ring[slot]
 
-    def cd_train_step_cached(self, cache, data, idx, rng_step, lr, momentum, next_indexes=None):
+    def _step_cache_key(self, data, idx, params, batch_size, n_rows):
+        """What cached argument structs (StepCache) were built from that a later call may find changed; the one statement of
+        it, for filling the cache and for checking it.  ``params``: (W, W_speed, W0, hbias, hbias_speed, vbias, vbias_speed)."""
+        W, W_speed, W0, hbias, _, vbias, _ = params
+        return (data.data_ptr(), data.shape[0], data.stride(0), idx.dtype, idx.numel(), batch_size, n_rows,
+                self._workspace.data_ptr() if self._workspace is not None else 0, self.keep_f32, self.trace_chain,
+                self._options_epoch, torch._C._cuda_getCurrentRawStream(self.device.index), W.data_ptr(), W_speed.data_ptr(),
+                W0.data_ptr() if W0 is not None else 0, hbias.data_ptr(), vbias.data_ptr())
+
+    def cd_train_step_cached(self, cache, data, idx, params, batch_size, n_rows, rng_step, lr, momentum, next_indexes=None):
         """The step of ``cd_train_step`` through argument structs a step function keeps from its previous call
-        (``cache`` = what ``cd_train_step(..., cache_out=)`` left): for small layers, whose step is two short launches, the
-        host side -- building two ctypes structs of ~70 fields, resolving scratch, statistics and workspace buffers -- was
-        32 us per call, more than the GPU's time.  Only what changes from call to call is set: the index list, the Philox
+        (``cache`` = the list ``cd_train_step(..., cache_out=)`` filled): for small layers, whose step is two short launches,
+        the host side -- building two ctypes structs of ~70 fields, resolving scratch, statistics and workspace buffers --
+        was 32 us per call, more than the GPU's time.  Only what changes from call to call is set: the index list, the Philox
         step, lr / momentum and the cost slot.  Returns None when the cache does not apply (the caller takes the full path)."""
-        a, u, a_ref, u_ref, key, sc, keep = cache[:7]
-        W, W_speed, W0 = keep[2], keep[3], keep[4]
+        (c,) = cache
+        a, u, sc, W = c.args, c.update, c.scratch, c.W
         # the structs were captured for a W WITHOUT bf16 planes: if another consumer of the same W has created some since
         # (another batch size of the same RBM, planes_min_work = 0), these steps must not go on updating W behind them
         if getattr(W, "_mdbn_planes", None) is not None:
             return None
-        if key != (data.data_ptr(), data.shape[0], data.stride(0), idx.dtype, idx.numel(),
-                   self._workspace.data_ptr() if self._workspace is not None else 0, self.keep_f32, self.trace_chain,
-                   self._options_epoch, a.rng.seed, a.rng.stream_id, torch._C._cuda_getCurrentRawStream(self.device.index),
-                   W.data_ptr(), W_speed.data_ptr(), W0.data_ptr() if W0 is not None else 0):
+        if c.key != self._step_cache_key(data, idx, params, batch_size, n_rows):
             return None
         a.indexes = idx.data_ptr()
         a.rng.step = rng_step & 0xFFFFFFFF
@@ -881,11 +901,11 @@ class HipEngine(object):
                 nxt = self.index_tensor(next_indexes, data.shape[0])
                 if nxt.numel() == idx.numel() and nxt.dtype == idx.dtype:
                     a.next_indexes = nxt.data_ptr()
-                    announce = (data, data._version, nxt, 0, nxt._version)
-        _lib.check(self.lib.mdbn_cd_train_step(self.ctx, self._stream(), a_ref, u_ref), "mdbn_cd_train_step")
+                    announce = Ahead(data, data._version, nxt, 0, nxt._version, None)
+        _lib.check(self.lib.mdbn_cd_train_step(self.ctx, self._stream(), c.args_ref, c.update_ref), "mdbn_cd_train_step")
         self._w_serial += 1
-        if announce is not None and a.ahead_done and a.ahead_done[0]:
-            sc.ahead = self._ahead_record(announce, W)
+        if announce is not None:
+            self._gathered_ahead(sc, announce, a.ahead_done and a.ahead_done[0], W, True)
         return cost
 
     def cd_train_step(self, data, indexes, W, W_speed, W0, hbias, hbias_speed, vbias, vbias_speed, gauss, k,
@@ -896,9 +916,9 @@ class HipEngine(object):
         monitoring cost (0-d device tensor).  ``cache_out``: a list that receives the argument structs of this call when
         the next call of the same step function may reuse them (``cd_train_step_cached``): index list given, no plane
         buffers (the plane path's arguments change from step to step: gather-ahead), no chain taps."""
-        a, stats, sc, _keep = self._cd_args(data, indexes, W, hbias, vbias, gauss, k, rng, None, False, 0,
-                                            sample_stats, next_indexes=next_indexes)
-        sc._announce, announce = None, getattr(sc, "_announce", None)
+        call = self._cd_args(data, indexes, W, hbias, vbias, gauss, k, rng, None, False, 0,
+                             sample_stats, next_indexes=next_indexes)
+        a, stats, sc = call.args, call.stats, call.scratch
         u, cost = self._update_args(W, W_speed, W0, hbias, hbias_speed, vbias, vbias_speed, stats, lr,
                                     lambda_1, lambda_2, weightcost, momentum, batch_size, n_rows, cost_scale,
                                     0, a.ldv)
@@ -906,22 +926,18 @@ class HipEngine(object):
                    "mdbn_cd_train_step")
         self._w_planes_written(W)
         self._w_serial += 1
-        if announce is not None and a.ahead_done and self._ahead_flag.value:
-            sc.ahead = self._ahead_record(announce, W)              # the next call finds its rows ready
+        self._gathered_ahead(sc, call.announce, a.ahead_done and self._ahead_flag.value, W, call.thin)
         if cache_out is not None:
             del cache_out[:]
-            idx = _keep[1]
+            dm, idx = call.data, call.indexes
             if idx is not None and sc.planes is None and not a.W_planes and not self.trace_chain and not sample_stats:
-                dm = _keep[0]
                 if a.B <= 32 and a.ldh <= 512 and not self.keep_f32:
                     # thin-batch candidates: the cached calls hand the next minibatch to the update kernel (their own flag)
                     flag = C.c_int32(0)
                     a.planes_alt, a.x_buffer, a.ahead_done = sc.alt_planes(self, a.ldv).data_ptr(), 0, C.pointer(flag)
-                key = (dm.data_ptr(), dm.shape[0], dm.stride(0), idx.dtype, idx.numel(), self._workspace.data_ptr(), self.keep_f32,
-                       self.trace_chain, self._options_epoch, a.rng.seed, a.rng.stream_id,
-                       torch._C._cuda_getCurrentRawStream(self.device.index), W.data_ptr(), W_speed.data_ptr(),
-                       W0.data_ptr() if W0 is not None else 0)
-                cache_out.extend([a, u, C.byref(a), C.byref(u), key, sc, (dm, stats, W, W_speed, W0, hbias, hbias_speed, vbias, vbias_speed)])
+                params = (W, W_speed, W0, hbias, hbias_speed, vbias, vbias_speed)
+                cache_out.append(StepCache(a, u, C.byref(a), C.byref(u), self._step_cache_key(dm, idx, params, batch_size, n_rows),
+                                           sc, W, (dm, stats) + params))
         return cost
 
     def apply_update(self, W, W_speed, W0, hbias, hbias_speed, vbias, vbias_speed, stats,

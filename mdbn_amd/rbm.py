@@ -12,7 +12,9 @@ sampling call and every step-function call consumes one ``step`` (see csrc/philo
 """
 from __future__ import print_function
 
+import os
 import timeit
+from collections import deque, namedtuple
 
 import numpy
 import torch
@@ -75,6 +77,106 @@ class LazyCost(object):
         return float(self)
 
 
+# The rows one call trains on: the matrix and the index tensor of THIS rank's rows (None: all of ``data``), the size of the whole
+# minibatch, the rank's rows [lo, hi) of it, and whether ``data`` is a buffer of a HostFeed (to be handed back).
+Minibatch = namedtuple("Minibatch", "data idx n_global lo hi staged")
+Hyper = namedtuple("Hyper", "lr momentum batch_size n_rows cost_scale ldv")     # of one step's update, beside the plan's constants
+Pending = namedtuple("Pending", "work stats hyper lazy")    # deferred half of an overlapped step: all-reduce in flight, ..., LazyCost
+
+
+class HostFeed(object):
+    """Feed of a host-resident training table (shared.HostTable) into the steps of one step function, through a RowFeeder
+    (engine.row_feeder, mdbn_feeder_*): CPU threads gather an ANNOUNCED minibatch's rows into pinned staging, one SDMA copy
+    moves them, three slots deep -- no kernel runs beside the step (a PCIe gather kernel there costs it 60 us).  Unannounced
+    minibatches are gathered on the spot by the PCIe gather kernel, in stream order.  ``shard(n)``: this rank's rows of an
+    n-row minibatch."""
+
+    def __init__(self, engine, shard):
+        self.engine, self.shard = engine, shard
+        self.feeder, self.queue = None, deque()     # RowFeeder; announced and submitted: (key, ticket, n_global, lo, hi, key version)
+        self.held, self.now = None, None            # ticket of the fed buffer the current step reads; buffer of unannounced rows
+
+    @staticmethod
+    def _same_indexes(a, b):
+        if a is b:
+            return True
+        if isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor):
+            # the prefetched view is kept alive, so its storage cannot have been reused: equal address, length and
+            # type mean the same (never mutated) index list
+            return a.data_ptr() == b.data_ptr() and a.numel() == b.numel() and a.dtype == b.dtype and a.device == b.device
+        if isinstance(a, torch.Tensor) or isinstance(b, torch.Tensor):
+            return False
+        a, b = numpy.asarray(a), numpy.asarray(b)
+        return a.shape == b.shape and bool((a == b).all())
+
+    def announce(self, table, batches, host_indexes):
+        """``batches`` (non-empty list) are the next calls' ``indexes``, ``host_indexes`` the same values on the host:
+        whatever was announced before is void, their rows start moving now."""
+        self.drop()
+        shards = []
+        for key, h in zip(batches, host_indexes):
+            h = h if isinstance(h, torch.Tensor) else torch.from_numpy(numpy.ascontiguousarray(numpy.asarray(h), dtype=numpy.int64))
+            h = h.to(torch.int64).reshape(-1)
+            if len(h):      # as engine.index_tensor: numpy fancy indexing (negative values count from the end)
+                lo_i, hi_i = int(h.min()), int(h.max())
+                if lo_i < -len(table) or hi_i >= len(table):
+                    raise IndexError("minibatch index out of range for %d rows: [%d, %d]" % (len(table), lo_i, hi_i))
+                if lo_i < 0:
+                    h = torch.where(h < 0, h + len(table), h)
+            lo, hi = self.shard(len(h))
+            shards.append((key, h[lo:hi].contiguous(), len(h), lo, hi))
+        need = max(hi - lo for _, _, _, lo, hi in shards)
+        fd = self.feeder
+        if need > 0 and (fd is None or fd.max_rows < need or fd.host is not table.host):     # (set_value replaces .host)
+            if fd is not None:
+                fd.close()
+            fd = self.feeder = self.engine.row_feeder(table.host, table.cols, need)
+        for key, h, n_global, lo, hi in shards:
+            ticket = fd.submit(h) if hi > lo else None
+            # (the version counter of an announced index TENSOR: a buffer refilled in place afterwards is not the announced list)
+            self.queue.append((key, ticket, n_global, lo, hi, getattr(key, "_version", None)))
+
+    def drop(self):
+        """Void every announcement (and hand back a buffer still held)."""
+        self.consumed()
+        if self.queue:
+            self.queue.clear()
+            if self.feeder is not None:
+                self.feeder.cancel()
+
+    def take(self, table, indexes):
+        """The Minibatch of this step: this rank's rows in a device buffer -- the fed one if ``indexes`` is what was announced
+        next, else gathered now by the PCIe kernel -- to be read with the identity index."""
+        eng = self.engine
+        self.consumed()                            # (a step that raised before handing its rows back)
+        if self.queue:
+            key, ticket, n_global, lo, hi, key_version = self.queue[0]
+            if self._same_indexes(key, indexes) and key_version == getattr(indexes, "_version", None):
+                self.queue.popleft()
+                if ticket is None:
+                    return Minibatch(eng.alloc_matrix(0, table.cols, table.host.stride(0)), None, n_global, lo, hi, True)
+                buf = self.feeder.acquire(ticket, hi - lo)
+                self.held = ticket
+                return Minibatch(buf, None, n_global, lo, hi, True)
+            self.drop()                            # not what was announced: the remaining announcements are void
+        n_global = len(table) if indexes is None else len(indexes)
+        lo, hi = self.shard(n_global)
+        buf = self.now
+        if buf is None or buf.shape[0] != hi - lo:
+            buf = self.now = eng.alloc_matrix(hi - lo, table.cols, table.host.stride(0))
+        if hi > lo:
+            idx = torch.arange(lo, hi, dtype=torch.int64, device=eng.device) if indexes is None else \
+                eng.index_tensor(indexes, len(table))[lo:hi]
+            table.rows(idx, out=buf)               # same stream as the steps: the previous reader of `buf` is ahead of it
+        return Minibatch(buf, None, n_global, lo, hi, True)
+
+    def consumed(self):
+        """The step that reads the fed rows has been enqueued: their slot may be refilled after it."""
+        if self.held is not None:
+            self.feeder.release(self.held)
+            self.held = None
+
+
 class StepFunction(object):
     """One compiled training step: ``fn(indexes=, momentum=, lr=)`` -> monitoring cost
     (0-d device tensor; ``float(cost)`` synchronises).
@@ -106,14 +208,17 @@ class StepFunction(object):
         self.overlap = bool(overlap and self.group is not None and self.group.world_size > 1
                             and p.persistent is None and p.lambda_1 == 0.0
                             and (p.weightcost == 0.0 or p.W0 is not None))
-        self._pending = None                # (work, stats, hyper-parameters, LazyCost) of the last step
-        self._staging = None                # feed of a host-resident table (RowFeeder, announced minibatches)
+        self._pending = None                # Pending: the deferred half of the last overlapped step
+        self._feed = None                   # HostFeed of a host-resident table, made by its first announcement or step
         self._n_calls = 0
+        eng = self.engine                   # what the engine offers (the checker engine lacks most of it)
+        self._has_feeder, self._has_cache = hasattr(eng, "row_feeder"), hasattr(eng, "cd_train_step_cached")
+        self._has_forward, self._has_count = getattr(eng, "cd_forward", None) is not None, hasattr(eng, "count_nonfinite")
         # statistics buffers of the data-parallel path are OWNED by this step function: a deferred
         # update reads them a whole call later, so another step function of the same shape (two
         # equal-sized modalities, alternating layers) must not share them
         self._stats_slots = [None, None]
-        self._fast = []                     # argument structs of the previous single-device call (engine.cd_train_step_cached)
+        self._fast = []                     # warm: [engine.StepCache] of the previous single-device call (cd_train_step_cached)
         # nan_guard: check cost and parameters for NaN / Inf after every call (synchronises; what the
         # reference's commented-out NanGuardMode would do, rbm.py:542-543, dbn.py:311)
         self.nan_guard = bool(getattr(self.engine, "nan_guard", False))
@@ -125,9 +230,8 @@ class StepFunction(object):
         # from it and lose the longer cover (185.0 vs 187.8 us alone, 216 vs 203 beside a 120-us stand-in): only with
         # MDBN_DP_FUSED_UPDATE=2 / fn.fuse_deferred = 2.  0 restores the update launch after the step everywhere;
         # bench.py --gpus N measures all of them.
-        import os as _os
-        self.fuse_deferred = int(_os.environ.get("MDBN_DP_FUSED_UPDATE", "1"))      # 0 | 1 | 2 (2: balanced launches too)
-        if self.group is not None and self.group.world_size > 1 and hasattr(self.engine, "set_option"):
+        self.fuse_deferred = int(os.environ.get("MDBN_DP_FUSED_UPDATE", "1"))       # 0 | 1 | 2 (2: balanced launches too)
+        if self.group is not None and self.group.world_size > 1 and hasattr(eng, "set_option"):
             # The collective's kernels run beside the next step's GEMMs and take whole CUs (RCCL's gfx950 all-reduce
             # kernel: 248-256 VGPRs per wave, 37.6 KB LDS -- nothing of ours fits next to it), and a one-workgroup-per-
             # CU GEMM grid on fewer CUs needs a second round: measured 163 -> 219 us per step with EIGHT CUs taken.
@@ -140,41 +244,24 @@ class StepFunction(object):
             for arr in self.rbm.params_speed:
                 arr._sync_hook = self.flush
 
+    # -- where the minibatch comes from
     def _data(self):
         if self.input_fn is not None:
             return self.input_fn()
         return self.engine.as_matrix(self.train_set_x)
 
-    # -- host-resident training table (shared.HostTable): the minibatch rows are gathered over PCIe into one of two
-    #    device staging buffers, on a side stream, ONE MINIBATCH AHEAD of the step that consumes them
     def _host_table(self):
         return self.train_set_x if (self.input_fn is None and isinstance(self.train_set_x, HostTable)) else None
 
-    @staticmethod
-    def _same_indexes(a, b):
-        if a is b:
-            return True
-        if isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor):
-            # the prefetched view is kept alive, so its storage cannot have been reused: equal address, length and
-            # type mean the same (never mutated) index list
-            return a.data_ptr() == b.data_ptr() and a.numel() == b.numel() and a.dtype == b.dtype and a.device == b.device
-        if isinstance(a, torch.Tensor) or isinstance(b, torch.Tensor):
-            return False
-        a, b = numpy.asarray(a), numpy.asarray(b)
-        return a.shape == b.shape and bool((a == b).all())
-
-    # A host-resident table feeds the step through a RowFeeder (engine.row_feeder, mdbn_feeder_*): CPU threads gather an
-    # ANNOUNCED minibatch's rows into pinned staging, one SDMA copy moves them, three slots deep -- no kernel runs beside
-    # the step (a PCIe gather kernel there costs it 60 us).  Unannounced minibatches are gathered on the spot by the PCIe
-    # gather kernel, in stream order.
-    def _feed_state(self):
-        if self._staging is None:
-            from collections import deque
-            self._staging = {"feeder": None, "queue": deque(), "held": None, "now": None}
-        return self._staging
-
     def _shard(self, n_global):
         return (0, n_global) if self.group is None else self.group.shard(n_global)
+
+    def _host_feed(self):
+        if self._feed is None:
+            self._feed = HostFeed(self.engine, self._shard)
+        return self._feed
+
+    _staging = property(lambda self: None if self._feed is None else vars(self._feed))     # the feed's state as a mapping
 
     def announce(self, batches, host_indexes=None):
         """Tell the step function which minibatches come next, in order (the trainers know the epoch's order up front):
@@ -183,7 +270,7 @@ class StepFunction(object):
         values as host arrays, when the caller has them (saves one device-to-host copy of the list).  A pure hint: a call
         whose ``indexes`` are not the announced ones drops the remaining announcements.  No-op for device-resident data."""
         table = self._host_table()
-        if table is None or not torch.cuda.is_available() or not hasattr(self.engine, "row_feeder"):
+        if table is None or not torch.cuda.is_available() or not self._has_feeder:
             return
         batches = list(batches)
         if not batches:
@@ -194,277 +281,214 @@ class StepFunction(object):
                 host_indexes = list(torch.split(flat, [len(b) for b in batches]))
             else:
                 host_indexes = batches
-        st = self._feed_state()
-        self._drop_feed()                          # "these are the next calls": whatever was announced before is void
-        shards = []
-        for key, h in zip(batches, host_indexes):
-            h = h if isinstance(h, torch.Tensor) else torch.from_numpy(numpy.ascontiguousarray(numpy.asarray(h), dtype=numpy.int64))
-            h = h.to(torch.int64).reshape(-1)
-            if len(h):      # as engine.index_tensor: numpy fancy indexing (negative values count from the end)
-                lo_i, hi_i = int(h.min()), int(h.max())
-                if lo_i < -len(table) or hi_i >= len(table):
-                    raise IndexError("minibatch index out of range for %d rows: [%d, %d]" % (len(table), lo_i, hi_i))
-                if lo_i < 0:
-                    h = torch.where(h < 0, h + len(table), h)
-            lo, hi = self._shard(len(h))
-            shards.append((key, h[lo:hi].contiguous(), len(h), lo, hi))
-        need = max(hi - lo for _, _, _, lo, hi in shards)
-        fd = st["feeder"]
-        if need > 0 and (fd is None or fd.max_rows < need or fd.host is not table.host):     # (set_value replaces .host)
-            if fd is not None:
-                fd.close()
-            fd = st["feeder"] = self.engine.row_feeder(table.host, table.cols, need)
-        for key, h, n_global, lo, hi in shards:
-            ticket = fd.submit(h) if hi > lo else None
-            # (the version counter of an announced index TENSOR: a buffer refilled in place afterwards is not the announced list)
-            st["queue"].append((key, ticket, n_global, lo, hi, getattr(key, "_version", None)))
+        self._host_feed().announce(table, batches, host_indexes)
 
     def prefetch(self, indexes):
         """``announce([indexes])``: the next minibatch only."""
         self.announce([indexes])
 
-    def _drop_feed(self):
-        st = self._staging
-        if st is None:
-            return
-        if st["held"] is not None:
-            st["feeder"].release(st["held"])
-            st["held"] = None
-        if st["queue"]:
-            st["queue"].clear()
-            if st["feeder"] is not None:
-                st["feeder"].cancel()
+    def _minibatch(self, indexes):
+        """The Minibatch of this call, from either source."""
+        table = self._host_table()
+        if table is not None and torch.cuda.is_available():
+            # the shard's rows arrive in a device buffer (fed ahead of the step when announced), read with the identity index
+            return self._host_feed().take(table, indexes)
+        data = self._data()
+        n_global = data.shape[0] if indexes is None else len(indexes)
+        lo, hi = self._shard(n_global)      # data-parallel shard of the minibatch: contiguous rows [lo, hi) of `indexes`
+        if indexes is None:
+            idx = None if (lo == 0 and hi == data.shape[0]) else torch.arange(lo, hi, dtype=torch.int64, device=data.device)
+        else:
+            idx = self.engine.index_tensor(indexes, data.shape[0])
+            if lo != 0 or hi != n_global:   # (a view of everything would be the same list: as much host time as the record costs)
+                idx = idx[lo:hi]
+        return Minibatch(data, idx, n_global, lo, hi, False)
 
-    def _staged(self, table, indexes):
-        """Device rows of this step's minibatch shard: the fed buffer if ``indexes`` is what was announced next, else
-        gathered now by the PCIe kernel."""
-        st = self._feed_state()
-        eng = self.engine
-        if st["held"] is not None:                 # a step that raised before handing its rows back
-            self._fed()
-        if st["queue"]:
-            key, ticket, n_global, lo, hi, key_version = st["queue"][0]
-            if self._same_indexes(key, indexes) and key_version == getattr(indexes, "_version", None):
-                st["queue"].popleft()
-                if ticket is None:
-                    return eng.alloc_matrix(0, table.cols, table.host.stride(0)), n_global, lo, hi
-                buf = st["feeder"].acquire(ticket, hi - lo)
-                st["held"] = ticket
-                return buf, n_global, lo, hi
-            self._drop_feed()                      # not what was announced: the remaining announcements are void
-        n_global = len(table) if indexes is None else len(indexes)
-        lo, hi = self._shard(n_global)
-        buf = st["now"]
-        if buf is None or buf.shape[0] != hi - lo:
-            buf = st["now"] = eng.alloc_matrix(hi - lo, table.cols, table.host.stride(0))
-        if hi > lo:
-            idx = torch.arange(lo, hi, dtype=torch.int64, device=eng.device) if indexes is None else \
-                eng.index_tensor(indexes, len(table))[lo:hi]
-            table.rows(idx, out=buf)               # same stream as the steps: the previous reader of `buf` is ahead of it
-        return buf, n_global, lo, hi
+    def _rows_consumed(self, mb, next_indexes):
+        """The step reading ``mb`` has been enqueued: fed rows go back, and the next shard of a host table starts moving."""
+        if mb.staged:
+            self._feed.consumed()
+            if next_indexes is not None and not self._feed.queue:
+                self.announce([next_indexes])
 
-    def _fed(self):
-        """The step that reads the fed rows has been enqueued: their slot may be refilled after it."""
-        st = self._staging
-        if st is not None and st["held"] is not None:
-            st["feeder"].release(st["held"])
-            st["held"] = None
+    # -- the one statement of what every path passes to the engine
+    def _params(self):
+        """(W, W_speed, W0, hbias, hbias_speed, vbias, vbias_speed), as cd_train_step and apply_update take them."""
+        rbm, W0 = self.rbm, self.plan.W0
+        return (rbm.W.tensor, rbm.W_speed.tensor, W0.tensor if W0 is not None else None,
+                rbm.hbias.tensor, rbm.hbias_speed.tensor, rbm.vbias.tensor, rbm.vbias_speed.tensor)
+
+    def _update_args(self, stats, hp, phase):
+        """The 18 arguments of ``apply_update`` (and of ``cd_statistics(deferred=)``)."""
+        p = self.plan
+        return self._params() + (stats, hp.lr, p.lambda_1, p.lambda_2, p.weightcost, hp.momentum, hp.batch_size, hp.n_rows,
+                                 hp.cost_scale, phase, hp.ldv)
+
+    def _rng_addr(self, step, lo):
+        return RngAddr(self.rbm.theano_rng.seed, self.rbm.stream_id, step, 0, lo)
+
+    def _cost_scale(self, n_global):
+        # rbm.py:480 (sum over units, mean over rows) / rbm.py:697 (mean over everything)
+        return 1.0 / (n_global * self.rbm.n_visible) if self.rbm.gauss else 1.0 / n_global
 
     # -- deferred half of an overlapped step: speeds (and cost) from the reduced statistics
-    def _complete_pending(self):
-        if self._pending is None:
-            return
-        work, stats, hp, lazy = self._pending
-        self._pending = None
-        work.wait()
-        rbm, p = self.rbm, self.plan
-        cost = self.engine.apply_update(
-            rbm.W.tensor, rbm.W_speed.tensor, p.W0.tensor if p.W0 is not None else None,
-            rbm.hbias.tensor, rbm.hbias_speed.tensor, rbm.vbias.tensor, rbm.vbias_speed.tensor, stats,
-            hp["lr"], p.lambda_1, p.lambda_2, p.weightcost, hp["momentum"], hp["batch_size"],
-            hp["n_rows"], hp["cost_scale"], phase=1, ldv=hp["ldv"])
-        lazy._value = cost
+    def _take_pending(self):                        # the pending step, its all-reduce awaited (on the stream)
+        pend, self._pending = self._pending, None
+        pend.work.wait()
+        return pend
 
-    def _resolve_cost(self, lazy):
-        if self._pending is not None and self._pending[3] is lazy:
-            self._complete_pending()
-        if lazy._value is None:
-            raise RuntimeError("cost of a step that was never completed")
+    def _deferred_args(self, pend, lr):
+        """Speeds from the reduced statistics of step t-1, then theta(t+1) from those speeds: phases 1 and 2 touch the same
+        arrays, so they run as ONE pass (phase 3; the speed half keeps step t-1's momentum and divisors, the other this lr)."""
+        return self._update_args(pend.stats, pend.hyper._replace(lr=lr), 3)
 
     def flush(self):
         """Complete the deferred speed update of the last overlapped step (no-op otherwise)."""
-        self._complete_pending()
+        if self._pending is not None:
+            pend = self._take_pending()
+            pend.lazy._value = self.engine.apply_update(*self._update_args(pend.stats, pend.hyper, 1))
+
+    def _resolve_cost(self, lazy):
+        if self._pending is not None and self._pending.lazy is lazy:
+            self.flush()
+        if lazy._value is None:
+            raise RuntimeError("cost of a step that was never completed")
 
     def __call__(self, indexes=None, momentum=0.0, lr=None, next_indexes=None):
         """``next_indexes``: the minibatch of the NEXT call, when the caller knows it (the trainers do: the epoch's order
         is drawn up front, dbn.py:446-458) -- a pure hint: the single-device plane path then gathers those rows inside
         this step's statistics kernel, a host-resident table starts moving them over PCIe; results never change."""
-        p, rbm, eng = self.plan, self.rbm, self.engine
+        p = self.plan
         if lr is None:
             lr = p.lr
         if isinstance(lr, Scalar):
             raise TypeError("step function needs lr= (learning rate is a symbolic input)")
-        table = self._host_table()
+        mb = self._minibatch(indexes)
+        batch_size = p.batch_size if (p.batch_size is not None and not p.symbolic_grad) else mb.n_global
+        step = self.rbm._take_step()
         distributed = self.group is not None and self.group.world_size > 1
-        staged_slot = None
-        if table is not None and torch.cuda.is_available():
-            # host-resident table: the shard's rows arrive in a device buffer (fed ahead of the step when the trainer
-            # announced them); the step then runs on that buffer with the identity index
-            data, n_global, lo, hi = self._staged(table, indexes)
-            staged_slot = True
-            idx = None
-        else:
-            data = self._data()
-            n_global = data.shape[0] if indexes is None else len(indexes)
-            # data-parallel shard of the minibatch: contiguous rows [lo, hi) of `indexes`
-            lo, hi = 0, n_global
-            if self.group is not None:
-                lo, hi = self.group.shard(n_global)
-            if indexes is None:
-                idx = None if (lo == 0 and hi == data.shape[0]) else \
-                    torch.arange(lo, hi, dtype=torch.int64, device=data.device)
-            else:
-                idx = eng.index_tensor(indexes, data.shape[0])[lo:hi]
-        batch_size = p.batch_size if (p.batch_size is not None and not p.symbolic_grad) else n_global
-        step = rbm._take_step()
+        if not distributed and p.persistent is None and mb.hi > mb.lo:
+            return self._single_device_step(mb, step, lr, momentum, batch_size, next_indexes)
+        return self._group_step(mb, step, lr, momentum, batch_size, next_indexes, distributed)
+
+    def _single_device_step(self, mb, step, lr, momentum, batch_size, next_indexes):
+        """The whole step function in one library call (mdbn_cd_train_step)."""
+        p, rbm, eng = self.plan, self.rbm, self.engine
+        params = self._params()
+        if self._fast and mb.idx is not None and not mb.staged and not self.nan_guard:
+            # the argument structs of the previous call (small layers are host-bound: engine.cd_train_step_cached)
+            out = eng.cd_train_step_cached(self._fast, mb.data, mb.idx, params, batch_size, mb.n_global, step, lr, momentum, next_indexes)
+            if out is not None:
+                rbm._n_updates += 1
+                return out
+        extra = {"cache_out": self._fast} if self._has_cache else {}
+        if next_indexes is not None and mb.idx is not None and not mb.staged:
+            extra["next_indexes"] = next_indexes        # the train-step hint: as it came, whenever the step has an index list
+        out = eng.cd_train_step(mb.data, mb.idx, *params, rbm.gauss, p.k, self._rng_addr(step, mb.lo), lr, p.lambda_1,
+                                p.lambda_2, p.weightcost, momentum, batch_size, mb.n_global, self._cost_scale(mb.n_global),
+                                sample_stats=p.symbolic_grad, **extra)
+        rbm._n_updates += 1
+        self._rows_consumed(mb, next_indexes)
+        if self.nan_guard:
+            self._check_finite(out)
+        return out
+
+    def _group_step(self, mb, step, lr, momentum, batch_size, next_indexes, distributed):
+        """The step in pieces -- statistics of this rank's rows, (all-reduce,) update: data parallel, and PCD anywhere."""
+        p, rbm, eng = self.plan, self.rbm, self.engine
+        data = mb.data
         persistent = None
         if p.persistent is not None:
             persistent = p.persistent.tensor
-            if persistent.shape[0] != n_global:
-                raise ValueError("persistent chain has %d rows but the minibatch has %d "
-                                 "(the reference fails the same way, rbm.py:416)"
-                                 % (persistent.shape[0], n_global))
+            if persistent.shape[0] != mb.n_global:
+                raise ValueError("persistent chain has %d rows but the minibatch has %d (the reference fails the same way, "
+                                 "rbm.py:416)" % (persistent.shape[0], mb.n_global))
             if distributed:
                 # PCD under data parallelism: chain row g belongs to the rank that owns minibatch row g
                 # (rbm.py:308-311,369); a rank only ever reads and writes its own rows of the chain
-                persistent = persistent[lo:hi]
-        if not distributed and p.persistent is None and hi > lo:
-            # single device: the whole step function in one library call (mdbn_cd_train_step)
-            if len(self._fast) == 8 and idx is not None and staged_slot is None and not self.nan_guard and self._fast[7] == \
-                    (batch_size, n_global, rbm.W.tensor.data_ptr(), rbm.hbias.tensor.data_ptr(), rbm.vbias.tensor.data_ptr()):
-                # the argument structs of the previous call (small layers are host-bound: engine.cd_train_step_cached)
-                out = eng.cd_train_step_cached(self._fast, data, idx, step, lr, momentum, next_indexes)
-                if out is not None:
-                    rbm._n_updates += 1
-                    return out
-            cost_scale = 1.0 / (n_global * rbm.n_visible) if rbm.gauss else 1.0 / n_global
-            out = eng.cd_train_step(data, idx, rbm.W.tensor, rbm.W_speed.tensor,
-                                    p.W0.tensor if p.W0 is not None else None,
-                                    rbm.hbias.tensor, rbm.hbias_speed.tensor, rbm.vbias.tensor,
-                                    rbm.vbias_speed.tensor, rbm.gauss, p.k,
-                                    RngAddr(rbm.theano_rng.seed, rbm.stream_id, step, 0, lo),
-                                    lr, p.lambda_1, p.lambda_2, p.weightcost, momentum, batch_size,
-                                    n_global, cost_scale, sample_stats=p.symbolic_grad,
-                                    **dict({"next_indexes": next_indexes} if (next_indexes is not None and idx is not None
-                                                                              and staged_slot is None) else {},
-                                           **({"cache_out": self._fast} if hasattr(eng, "cd_train_step_cached") else {})))
-            if self._fast:        # (what else must stay as it was for the structs to be reused)
-                self._fast.append((batch_size, n_global, rbm.W.tensor.data_ptr(), rbm.hbias.tensor.data_ptr(), rbm.vbias.tensor.data_ptr()))
-            rbm._n_updates += 1
-            if staged_slot is not None:
-                self._fed()
-                if next_indexes is not None and not self._staging["queue"]:
-                    self.announce([next_indexes])
-            if self.nan_guard:
-                self._check_finite(out)
-            return out
+                persistent = persistent[mb.lo:mb.hi]
         slot = self._n_calls & 1 if self.overlap else 0     # the other buffer may still be reducing
         self._n_calls += 1
         if self._stats_slots[slot] is None:
-            self._stats_slots[slot] = eng.new_stats_buffer(rbm.n_visible, rbm.n_hidden, data.stride(0),
-                                                           rbm.W.tensor.stride(0))
+            self._stats_slots[slot] = eng.new_stats_buffer(rbm.n_visible, rbm.n_hidden, data.stride(0), rbm.W.tensor.stride(0))
         stats = self._stats_slots[slot]
-        args = (rbm.W.tensor, rbm.W_speed.tensor, p.W0.tensor if p.W0 is not None else None,
-                rbm.hbias.tensor, rbm.hbias_speed.tensor, rbm.vbias.tensor, rbm.vbias_speed.tensor)
         deferred_done = False
-        if hi > lo:
+        if mb.hi > mb.lo:
             extra = {"comm_cus": self.comm_cus} if self.comm_cus else {}
-            if self.overlap and self._pending is not None and int(self.fuse_deferred) >= (2 if self.comm_cus else 1) and \
-                    getattr(eng, "cd_forward", None) is not None:
-                # Overlapped order with the update INSIDE the statistics GEMM: the forward half of step t (everything that
-                # reads theta(t)), then wait for the all-reduce of step t-1, then the statistics half, whose kernel applies
-                # the deferred update of step t-1 (speeds from its reduced statistics, theta(t+1) from those speeds) beside
-                # its own main loop -- bitwise what apply_update(phase=3) after cd_step does, one launch fewer.
-                token = eng.cd_forward(data, idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, rbm.gauss, p.k,
-                                       RngAddr(rbm.theano_rng.seed, rbm.stream_id, step, 0, lo),
-                                       sample_stats=p.symbolic_grad, stats=stats,
-                                       next_indexes=(eng.index_tensor(next_indexes, data.shape[0])[lo:hi]
-                                                     if (next_indexes is not None and idx is not None and staged_slot is None
-                                                         and len(next_indexes) == n_global) else None), **extra)
-                pwork, pstats, hp, plazy = self._pending
-                self._pending = None
-                pwork.wait()
-                _, _, pcost = eng.cd_statistics(token, deferred=args + (pstats, lr, p.lambda_1, p.lambda_2, p.weightcost,
-                                                                        hp["momentum"], hp["batch_size"], hp["n_rows"],
-                                                                        hp["cost_scale"], 3, hp["ldv"]))
-                plazy._value = pcost
+            if self.overlap and self._pending is not None and self._has_forward and \
+                    int(self.fuse_deferred) >= (2 if self.comm_cus else 1):
+                self._forward_then_statistics(mb, step, lr, stats, next_indexes, extra)
                 deferred_done = True
             else:
-                eng.cd_step(data, idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, rbm.gauss, p.k,
-                            RngAddr(rbm.theano_rng.seed, rbm.stream_id, step, 0, lo),
-                            persistent=persistent, sample_stats=p.symbolic_grad, stats=stats, **extra)
+                eng.cd_step(data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, rbm.gauss, p.k,
+                            self._rng_addr(step, mb.lo), persistent=persistent, sample_stats=p.symbolic_grad, stats=stats, **extra)
         else:                                  # this rank holds no row of a short minibatch
             stats.zero_()
-
-        if p.persistent is not None:
-            # PCD monitors the pseudo-likelihood (rbm.py:371) with pre-update parameters
-            if hi > lo:
-                cost = rbm._pseudo_likelihood_value(eng.gather_rows(data, idx) if idx is not None else data)
-            else:
-                cost = None
-                rbm.bit_i_idx = (rbm.bit_i_idx + 1) % rbm.n_visible
-            cost_scale = 0.0
-            if distributed:
-                # a mean over rows: every rank contributes (its mean * its rows) through the cost slot of the
-                # statistics buffer, the update kernel divides the all-reduced sum by the global row count
-                slot_idx = rbm.n_visible * rbm.W.tensor.stride(0) + rbm.W.tensor.stride(0) + data.stride(0)
-                stats[slot_idx] = cost * float(hi - lo) if cost is not None else 0.0
-                cost, cost_scale = None, 1.0 / n_global
-        else:
-            cost = None
-            # rbm.py:480 (sum over units, mean over rows) / rbm.py:697 (mean over everything)
-            cost_scale = 1.0 / (n_global * rbm.n_visible) if rbm.gauss else 1.0 / n_global
-        if staged_slot is not None:
-            self._fed()
-            if next_indexes is not None and not self._staging["queue"]:
-                self.announce([next_indexes])        # host-resident table: the next shard starts moving now
+        cost, cost_scale = self._pcd_monitor(mb, stats, distributed) if p.persistent is not None else \
+            (None, self._cost_scale(mb.n_global))
+        self._rows_consumed(mb, next_indexes)        # host-resident table: the next shard starts moving now
+        hp = Hyper(lr, momentum, batch_size, mb.n_global, cost_scale, data.stride(0))
         if self.overlap:
-            work = self.group.all_reduce_sum_async(stats, self.engine)
-            if deferred_done:
-                pass                                   # (step t-1's update went into this step's statistics GEMM)
-            elif self._pending is not None:
-                # speeds from the reduced statistics of step t-1, then theta(t+1) from those speeds:
-                # phases 1 and 2 back to back touch the same arrays, so they run as ONE pass (phase 3;
-                # the speed half keeps step t-1's momentum and divisors, the parameter half this lr)
-                pwork, pstats, hp, plazy = self._pending
-                self._pending = None
-                pwork.wait()
-                plazy._value = eng.apply_update(*args, pstats, lr, p.lambda_1, p.lambda_2, p.weightcost,
-                                                hp["momentum"], hp["batch_size"], hp["n_rows"],
-                                                hp["cost_scale"], phase=3, ldv=hp["ldv"])
-            else:
-                eng.apply_update(*args, stats, lr, p.lambda_1, p.lambda_2, p.weightcost, momentum,
-                                 batch_size, n_global, cost_scale, phase=2, ldv=data.stride(0))   # theta(t+1)
-            lazy = LazyCost(self, self._n_calls)
-            self._pending = (work, stats, dict(lr=lr, momentum=momentum, batch_size=batch_size,
-                                               n_rows=n_global, cost_scale=cost_scale, ldv=data.stride(0)), lazy)
-            rbm._n_updates += 1
-            return lazy
-
+            return self._overlapped_tail(stats, hp, deferred_done)
         if distributed:
-            self.group.all_reduce_sum(stats, self.engine)
-        out = eng.apply_update(*args, stats, lr, p.lambda_1, p.lambda_2, p.weightcost, momentum,
-                               batch_size, n_global, cost_scale, ldv=data.stride(0))
+            self.group.all_reduce_sum(stats, eng)
+        out = eng.apply_update(*self._update_args(stats, hp, 0))
         rbm._n_updates += 1
         if self.nan_guard:
             self._check_finite(cost if cost is not None else out)
         return cost if cost is not None else out
 
+    def _forward_then_statistics(self, mb, step, lr, stats, next_indexes, extra):
+        """Overlapped order with the update INSIDE the statistics GEMM: the forward half of step t (everything that reads
+        theta(t)), then wait for the all-reduce of step t-1, then the statistics half, whose kernel applies the deferred
+        update of step t-1 (speeds from its reduced statistics, theta(t+1) from those speeds) beside its own main loop --
+        bitwise what apply_update(phase=3) after cd_step does, one launch fewer."""
+        p, rbm, eng = self.plan, self.rbm, self.engine
+        forward_hint = None                         # the forward hint: this rank's rows of a hint as long as the minibatch
+        if next_indexes is not None and mb.idx is not None and not mb.staged and len(next_indexes) == mb.n_global:
+            forward_hint = eng.index_tensor(next_indexes, mb.data.shape[0])[mb.lo:mb.hi]
+        token = eng.cd_forward(mb.data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, rbm.gauss, p.k,
+                               self._rng_addr(step, mb.lo), sample_stats=p.symbolic_grad, stats=stats,
+                               next_indexes=forward_hint, **extra)
+        pend = self._take_pending()
+        _, _, pend.lazy._value = eng.cd_statistics(token, deferred=self._deferred_args(pend, lr))
+
+    def _pcd_monitor(self, mb, stats, distributed):
+        """PCD monitors the pseudo-likelihood (rbm.py:371) with pre-update parameters: -> (cost or None, cost_scale)."""
+        rbm = self.rbm
+        if mb.hi > mb.lo:
+            cost = rbm._pseudo_likelihood_value(self.engine.gather_rows(mb.data, mb.idx) if mb.idx is not None else mb.data)
+        else:
+            cost = None
+            rbm.bit_i_idx = (rbm.bit_i_idx + 1) % rbm.n_visible
+        if not distributed:
+            return cost, 0.0
+        # a mean over rows: every rank contributes (its mean * its rows) through the cost slot of the
+        # statistics buffer, the update kernel divides the all-reduced sum by the global row count
+        ldh = rbm.W.tensor.stride(0)
+        stats[rbm.n_visible * ldh + ldh + mb.data.stride(0)] = cost * float(mb.hi - mb.lo) if cost is not None else 0.0
+        return None, 1.0 / mb.n_global
+
+    def _overlapped_tail(self, stats, hp, deferred_done):
+        """Start this step's all-reduce, apply what does not wait for it, leave the rest pending: -> LazyCost."""
+        work = self.group.all_reduce_sum_async(stats, self.engine)
+        if deferred_done:
+            pass                                   # (step t-1's update went into this step's statistics GEMM)
+        elif self._pending is not None:
+            pend = self._take_pending()
+            pend.lazy._value = self.engine.apply_update(*self._deferred_args(pend, hp.lr))
+        else:
+            self.engine.apply_update(*self._update_args(stats, hp, 2))     # theta(t+1)
+        lazy = LazyCost(self, self._n_calls)
+        self._pending = Pending(work, stats, hp, lazy)
+        self.rbm._n_updates += 1
+        return lazy
+
     def _check_finite(self, cost):
         rbm = self.rbm
         c = float(cost)
         bad = self.engine.count_nonfinite(rbm.W.tensor, rbm.W_speed.tensor, rbm.hbias.tensor, rbm.vbias.tensor) \
-            if hasattr(self.engine, "count_nonfinite") else 0
+            if self._has_count else 0
         if bad or not numpy.isfinite(c):
             raise FloatingPointError("step %d of %s: cost = %r, %d non-finite parameter / speed values (learning rate "
                                      "too large for this data?)" % (rbm._n_updates, self.name or "step function", c, bad))

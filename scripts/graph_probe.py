@@ -34,7 +34,8 @@ for (V, H, B, gauss) in [(400, 40, 20, True), (1000, 400, 20, True), (16384, 400
     idx = perm[:B].contiguous()
     Wd, hb, vb = rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor
     Ws, hs, vs = rbm.W_speed.tensor, rbm.hbias_speed.tensor, rbm.vbias_speed.tensor
-    a, stats, sc, keep = eng._cd_args(shared.tensor, idx, Wd, hb, vb, gauss, 1, RngAddr(1, 0, 5, 0), None, False, 0, False)
+    call = eng._cd_args(shared.tensor, idx, Wd, hb, vb, gauss, 1, RngAddr(1, 0, 5, 0), None, False, 0, False)
+    a, stats = call.args, call.stats
     u, cost = eng._update_args(Wd, Ws, None, hb, hs, vb, vs, stats, 0.0, 0.0, 0.1, 0.0, 0.5, B, B, 1.0, 0, a.ldv)
     def run_c(n):
         for _ in range(n):
