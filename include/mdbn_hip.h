@@ -563,6 +563,36 @@ int  mdbn_pt_run_z(mdbn_ctx *ctx, void *stream, const float *W, int64_t V, int64
                    float *trace_v, float *trace_h, int32_t *trace_swaps, int path, int64_t steps_per_launch,
                    const mdbn_rng *rng, void *workspace, int64_t workspace_bytes, double *zacc, double *trace_work);
 
+/* Pieces of the variational lower bound on log p(data) of a DBN (Salakhutdinov & Murray 2008, section 4.2;
+ * DBN.log_likelihood_bound): with the recognition model q(x_l | x_{l-1}) = Bernoulli(sigmoid(x_{l-1} W_l + hbias_l)),
+ *   B(x_0) = E_q[ sum_{l < L} ( log p(x_{l-1} | x_l) + H[q(. | x_{l-1})] ) - F_L(x_{L-1}) ] - log Z_L  <=  log p(x_0).
+ *
+ * mdbn_propdown_rowll: the directed term of every replica row, the propdown GEMM fused with its row reduction -- the
+ * [R, V] pre-activations exist in accumulators only.  h [R, ldh] holds 0 / 1 SAMPLES (precondition: any other value is
+ * outside the contract; h enters the matrix pipe as one bf16 piece), W [V, ldh], vbias [V], target [T, ldv] with
+ * T = ceil(R / target_div): replica row r is scored against target row r / target_div (target_div >= 1; S replicas of one
+ * data row share that row).  With pre_i = h[r] . W[i, :] + vbias_i over the H live columns,
+ *   gauss = 0:  out[r] = sum_{i < V} ( t_i pre_i - softplus(pre_i) ),   softplus(x) = max(x, 0) + log1p(exp(-|x|))
+ *   gauss = 1:  out[r] = -1/2 sum_{i < V} (t_i - pre_i)^2 - V / 2 log 2 pi        (unit variance, as mdbn_free_energy)
+ * float32 [R].  The padding of h and W beyond H and of target beyond V is never used (it may hold anything).  Products as the
+ * plane propdown's for 0 / 1 operands (W split exactly into three bf16 pieces, f32 accumulation); a row's terms are summed per
+ * 128-column tile and the tiles in ascending order by a second small launch: no atomics, two runs agree bit for bit.
+ * workspace: >= mdbn_rowll_workspace_bytes(R, V, H) (the tile sums).  ldh % 4 == 0, h and W 16-byte aligned.
+ *
+ * mdbn_sample_replicas: S samples of every row of mean [N, ldh] (H live columns):
+ *   sample[n S + s, j] = (u[n S + s, j] < mean[n, j]),   sample [N S, ldh] (pad columns written as 0),
+ * u being the matrix mdbn_rng_uniform(rows = N S, cols = H) yields for the same mdbn_rng, row_offset included -- a caller
+ * that walks its data rows in chunks (row_offset = first row x S) draws what one call over all rows draws.  entropy
+ * (nullable) [N]: entropy[n] = -sum_{j < H} ( m log m + (1 - m) log(1 - m) ), 0 log 0 = 0, of the factorial Bernoulli
+ * distribution with the means of row n.  S = 1 samples a matrix of means row by row.  The caller advances its step counter
+ * by one. */
+int  mdbn_rowll_workspace_bytes(mdbn_ctx *ctx, int64_t R, int64_t V, int64_t H, int64_t *bytes);
+int  mdbn_propdown_rowll(mdbn_ctx *ctx, void *stream, const float *h, int64_t R, int64_t ldh, const float *W,
+                         int64_t V, int64_t H, const float *vbias, const float *target, int64_t ldv,
+                         int64_t target_div, int gauss, float *out, void *workspace, int64_t workspace_bytes);
+int  mdbn_sample_replicas(mdbn_ctx *ctx, void *stream, const float *mean, int64_t N, int64_t H, int64_t ldh,
+                          int64_t S, float *sample, float *entropy, const mdbn_rng *rng);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)). */

@@ -143,6 +143,28 @@ def impute_modalities(nets, joint, inputs, n_steps=1000, burn_in=200, n_chains=8
                                                            for i, lo, w in missing}
 
 
+def log_likelihood_bound(nets, joint, inputs, n_samples=64, **kw):
+    """Variational lower bound on log p of the raw data of every modality under the whole multimodal model, in nats per row
+    (``DBN.log_likelihood_bound`` for the forest of networks; ``bound.stack_bound``).
+
+    ``nets`` / ``joint`` as ``impute_modalities``; ``inputs``: one data matrix per modality, a list in the order of ``nets`` or
+    a dict {modality index: matrix} with exactly the keys 0 .. len(nets) - 1.  Every modality DBN is sampled up through ALL
+    its layers -- each contributes a directed term log p(x_{l-1} | x_l) and the entropy of its recognition distribution --,
+    the sampled tops are concatenated in the column order of the joint layer (the order ``train_top`` is given the outputs
+    in), and the joint DBN continues up to its top RBM, whose free energy and log Z close the bound.  Keywords: ``log_z``,
+    ``chunk_rows``, ``trace`` and those of ``RBM.log_partition``.  Returns a ``bound.StackBound``: the fields of ``bound.Bound``
+    plus ``modality_rows`` [M, N] (the terms each modality's layers add) and ``joint_rows`` [N]; ``rows`` is their sum.  Every
+    sampled layer consumes one RNG step of its own RBM."""
+    from .bound import stack_bound
+    if isinstance(inputs, dict):
+        if set(inputs) != set(range(len(nets))):
+            raise ValueError("inputs must have exactly the keys 0 .. %d, got %r" % (len(nets) - 1, sorted(inputs, key=repr)))
+        inputs = [inputs[i] for i in range(len(nets))]
+    if len(inputs) != len(nets) or any(x is None for x in inputs):
+        raise ValueError("one input per modality: every modality is given")
+    return stack_bound(list(zip(nets, inputs)), joint, n_samples=n_samples, **kw)
+
+
 def modality_log_likelihood(nets, joint, inputs, target, n_chains=64, n_betas=1000, path=0, base_data=None):
     """How well the joint layer predicts modality ``target`` from the others, in nats per row (Srivastava & Salakhutdinov
     2012): log p(block_target | the other blocks) under the joint DBN's first RBM.

@@ -15,8 +15,8 @@ from .rbm import RBM, GRBM, Scalar, ais_estimate, function
 from .dbn import DBN
 from .temper import TemperedChains
 from . import MDBN, checkpoint, dist, utils
-from .MDBN import modality_log_likelihood
+from .MDBN import log_likelihood_bound, modality_log_likelihood
 
-__all__ = ["modality_log_likelihood","MdbnError", "HipEngine", "RngAddr", "get_engine", "set_engine", "RandomStreams",
+__all__ = ["modality_log_likelihood", "log_likelihood_bound", "MdbnError", "HipEngine", "RngAddr", "get_engine", "set_engine", "RandomStreams",
            "SharedArray", "HostTable", "shared", "get_minibatches_idx", "HiddenLayer", "RBM", "GRBM",
            "Scalar", "function", "ais_estimate", "DBN", "TemperedChains", "MDBN", "dist", "checkpoint", "utils"]

@@ -1,0 +1,41 @@
+// Pieces of the variational lower bound of a DBN (mdbn_bound.hip): the fused propdown + row log-likelihood and the replica
+// sampler.  Arguments and launchers.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "philox.h"
+
+namespace mdbn {
+
+constexpr int ROWLL_BM = 128;               // replica rows of a tile
+constexpr int ROWLL_BN = 128;               // visible columns of a tile
+constexpr int ROWLL_BK = 32;                // hidden units of a K stage
+constexpr int ROWLL_NT = 256;               // threads: four waves, 64 x 64 of the tile each
+
+// out[r] = log p(target[r / target_div] | h[r]) under sigmoid / unit-variance Gaussian visibles.
+// PRECONDITION: h holds 0 / 1 only (it enters the matrix pipe as ONE bf16 piece: any other value is truncated to its upper
+// 16 bits).  The padding of h and W beyond H, and of target beyond V, is never used.
+struct RowllArgs {
+    int R, V, H, gauss;
+    int target_div;                          // >= 1: replica row r is scored against target row r / target_div
+    int tiles_m, tiles_n;                    // ceil(R / ROWLL_BM), ceil(V / ROWLL_BN)
+    int64_t ldh, ldv;                        // leading dimensions of h and W (ldh), of target (ldv)
+    const float* h; const float* W;          // [R][ldh] 0 / 1 samples; [V][ldh]
+    const float* vbias; const float* target; // [V]; [ceil(R / target_div)][ldv]
+    float* partial;                          // [tiles_n][R]: the row sums of one column tile each
+    float* out;                              // [R]
+};
+
+struct ReplicaArgs {
+    int64_t N, S, H, ldh;                    // data rows, replicas per row, live / stored columns
+    const float* mean;                       // [N][ldh]
+    float* sample;                           // [N S][ldh]: row n S + s = (u[n S + s] < mean[n]); pad columns 0
+    float* entropy;                          // [N] or NULL: -sum_j m log m + (1 - m) log(1 - m), 0 log 0 = 0
+    PhiloxKey rng;                           // the addressing of mdbn_rng_uniform(rows = N S, cols = H)
+};
+
+inline int64_t rowll_partial_floats(int64_t R, int64_t V) { return ((V + ROWLL_BN - 1) / ROWLL_BN) * R; }
+hipError_t launch_rowll(const RowllArgs& a, hipStream_t s);
+hipError_t launch_sample_replicas(const ReplicaArgs& a, hipStream_t s);
+
+}  // namespace mdbn

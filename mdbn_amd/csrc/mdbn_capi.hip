@@ -28,6 +28,7 @@
 #include "mdbn_ais.h"
 #include "mdbn_clamp.h"
 #include "mdbn_temper.h"
+#include "mdbn_bound.h"
 
 using namespace mdbn;
 
@@ -2867,6 +2868,50 @@ int mdbn_rng_normal(mdbn_ctx* ctx, void* stream, float* out, int64_t rows, int64
     CtxScope ctx_scope(ctx);
     REQUIRE(ctx && out && rng && rows >= 0 && cols >= 0 && ld >= cols, "bad arguments");
     HIP_OK(launch_rng_fill(out, rows, cols, ld, make_key(*rng, rng->draw), 1, (hipStream_t)stream));
+    return MDBN_OK;
+}
+
+// ---------------------------------------------------------------------------------- variational bound (mdbn_bound.hip)
+int mdbn_rowll_workspace_bytes(mdbn_ctx* ctx, int64_t R, int64_t V, int64_t H, int64_t* bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(ctx && bytes && R > 0 && V > 0 && H > 0, "bad arguments");
+    *bytes = rowll_partial_floats(R, V) * (int64_t)sizeof(float);
+    return MDBN_OK;
+}
+
+int mdbn_propdown_rowll(mdbn_ctx* ctx, void* stream, const float* h, int64_t R, int64_t ldh, const float* W, int64_t V, int64_t H,
+                        const float* vbias, const float* target, int64_t ldv, int64_t target_div, int gauss, float* out,
+                        void* workspace, int64_t workspace_bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(ctx && h && W && vbias && target && out && R > 0 && V > 0 && H > 0, "bad arguments");
+    REQUIRE(R <= (1 << 30) && V <= (1 << 30) && H <= (1 << 30), "shape too large");
+    REQUIRE(target_div >= 1 && target_div <= (1 << 30), "target_div must be >= 1");
+    REQUIRE(ldh >= H && ldv >= V && ldh % 4 == 0, "leading dimensions: ldh >= H, ldh %% 4 == 0, ldv >= V");
+    REQUIRE(aligned16(h) && aligned16(W), "h and W must be 16-byte aligned");
+    RowllArgs a;
+    a.R = (int)R; a.V = (int)V; a.H = (int)H; a.gauss = gauss != 0; a.target_div = (int)target_div;
+    a.tiles_m = (int)((R + ROWLL_BM - 1) / ROWLL_BM); a.tiles_n = (int)((V + ROWLL_BN - 1) / ROWLL_BN);
+    REQUIRE((int64_t)a.tiles_m * a.tiles_n <= 0x7fffffff, "shape too large");
+    REQUIRE(workspace != nullptr && workspace_bytes >= rowll_partial_floats(R, V) * (int64_t)sizeof(float),
+            "workspace of mdbn_rowll_workspace_bytes needed");
+    a.ldh = ldh; a.ldv = ldv; a.h = h; a.W = W; a.vbias = vbias; a.target = target;
+    a.partial = reinterpret_cast<float*>(workspace); a.out = out;
+    HIP_OK(launch_rowll(a, (hipStream_t)stream));
+    return MDBN_OK;
+}
+
+int mdbn_sample_replicas(mdbn_ctx* ctx, void* stream, const float* mean, int64_t N, int64_t H, int64_t ldh, int64_t S,
+                         float* sample, float* entropy, const mdbn_rng* rng)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(ctx && mean && sample && rng && N > 0 && H > 0 && S > 0 && ldh >= H, "bad arguments");
+    REQUIRE(N <= ((int64_t)1 << 40) / S && rng->row_offset <= ((uint64_t)1 << 40), "shape too large");
+    ReplicaArgs a;
+    a.N = N; a.S = S; a.H = H; a.ldh = ldh; a.mean = mean; a.sample = sample; a.entropy = entropy;
+    a.rng = make_key(*rng, rng->draw);
+    HIP_OK(launch_sample_replicas(a, (hipStream_t)stream));
     return MDBN_OK;
 }
 

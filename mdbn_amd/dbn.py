@@ -170,6 +170,19 @@ class DBN(object):
         below = getattr(data, "tensor", data) if i == 0 else self._forward(data, i - 1)
         return self.rbm_layers[i].log_likelihood(self.engine.to_numpy(self.engine.as_matrix(below)), **ais)
 
+    def log_likelihood_bound(self, data, n_samples=64, log_z=None, chunk_rows=16384, trace=False, **ais):
+        """Variational lower bound on log p(data) under the WHOLE stack (Salakhutdinov & Murray 2008, section 4.2), in nats
+        per row: the layers below the top RBM are sampled upwards, ``n_samples`` configurations per data row, and
+        B(x_0) = E_q[sum_l (log p(x_{l-1} | x_l) + H[q(. | x_{l-1})]) - F_L(x_{L-1})] - log Z_L  <=  log p(x_0)  (``bound.py``).
+        Returns a ``bound.Bound``: ``bound`` (mean over the rows), ``stderr`` (its sampling error; that of log Z is NOT in it),
+        ``log_z`` / ``log_z_stderr`` (``rbm_layers[-1].log_partition(**ais)`` -- ``method="tempering"`` and every other keyword
+        pass through; base rate: the data seen through the layers below, as ``layer_log_likelihood`` -- unless ``log_z`` is
+        given), ``rows`` / ``row_stderr`` [N] and, with ``trace``, what was sampled.  Data rows are walked in chunks of
+        ``chunk_rows // n_samples`` (a host-resident table is streamed); the chunking changes no draw.  Every sampled layer
+        consumes ONE RNG step of its own RBM.  A one-layer network draws nothing and gives ``log_likelihood``."""
+        from .bound import stack_bound
+        return stack_bound([(self, data)], None, n_samples=n_samples, log_z=log_z, chunk_rows=chunk_rows, trace=trace, **ais)
+
     def _layer_input_fn(self, i, train_set_x):
         """Input matrix of RBM i: the data for i == 0, else the activations of layer i-1
         (dbn.py:146).  Lower layers are frozen while layer i trains (dbn.py:426-458), so

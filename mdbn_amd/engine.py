@@ -526,6 +526,53 @@ class HipEngine(object):
             self._p(ws), ws.numel() * 4), "mdbn_free_energy")
         return out
 
+    def propdown_row_loglik(self, h, W, vbias, target, gauss, target_div=1):
+        """``log p(target[r // target_div] | h[r])`` of every row of the 0 / 1 sample matrix ``h`` [R, H] under the layer's
+        visible conditional (sigmoid(h W^T + vbias); N(h W^T + vbias, I) with ``gauss``) as a float32 device vector [R]
+        (mdbn_propdown_rowll: the propdown GEMM reduced against the target in its epilogue, no [R, V] matrix is written).
+        ``target``: [ceil(R / target_div), V].  ``h`` must hold 0 / 1 only."""
+        h, target = self.as_matrix(h), self.as_matrix(target)
+        R, H = (int(x) for x in h.shape)
+        V = int(W.shape[0])
+        target_div = int(target_div)
+        if W.shape[1] != H or target.shape[1] != V:
+            raise ValueError("h [%d, %d], W %r and target %r do not fit" % (R, H, tuple(W.shape), tuple(target.shape)))
+        if target_div < 1 or target.shape[0] != (R + target_div - 1) // target_div:
+            raise ValueError("target has %d rows; %d rows of h at target_div = %d need %d"
+                             % (target.shape[0], R, target_div, (R + max(target_div, 1) - 1) // max(target_div, 1)))
+        h = self._padded(h, R, H, W.stride(0))          # the C-ABI reads h with W's ld
+        out = self.alloc_vector(R)
+        if R == 0:
+            return out
+        n = C.c_int64()
+        _lib.check(self.lib.mdbn_rowll_workspace_bytes(self.ctx, R, V, H, C.byref(n)), "mdbn_rowll_workspace_bytes")
+        ws = getattr(self, "_rowll_ws", None)
+        if ws is None or ws.numel() * 4 < n.value:
+            ws = self._rowll_ws = torch.empty(n.value // 4 + 64, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.mdbn_propdown_rowll(
+            self.ctx, self._stream(), self._p(h), R, h.stride(0), self._p(W), V, H, self._p(vbias), self._p(target),
+            target.stride(0), target_div, int(bool(gauss)), self._p(out), self._p(ws), ws.numel() * 4), "mdbn_propdown_rowll")
+        return out
+
+    def sample_replicas(self, mean, n_samples, rng):
+        """``n_samples`` Bernoulli samples of every row of ``mean`` [N, H] (mdbn_sample_replicas): ``(sample, entropy)``,
+        device tensors -- ``sample`` [N n_samples, H] on the leading dimension of ``mean``, row n n_samples + s =
+        (u[n n_samples + s] < mean[n]) with u the uniforms ``rng_uniform(N n_samples, H, rng)`` yields; ``entropy`` [N] the
+        entropy of the factorial Bernoulli distribution of each row.  Consumes one RNG step."""
+        mean = self.as_matrix(mean)
+        N, H = (int(x) for x in mean.shape)
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError("n_samples must be >= 1, got %r" % (n_samples,))
+        sample = self.alloc_matrix(N * S, H, mean.stride(0))
+        entropy = self.alloc_vector(N)
+        if N == 0:
+            return sample, entropy
+        r = rng.c()
+        _lib.check(self.lib.mdbn_sample_replicas(self.ctx, self._stream(), self._p(mean), N, H, mean.stride(0), S,
+                                                 self._p(sample), self._p(entropy), C.byref(r)), "mdbn_sample_replicas")
+        return sample, entropy
+
     def _padded(self, x, rows, V, ldv):
         """``x`` as a [rows, V] device matrix on the leading dimension ``ldv`` (copied where it is on another)."""
         x = self.as_matrix(x)
