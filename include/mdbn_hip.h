@@ -277,7 +277,11 @@ int  mdbn_split_planes(mdbn_ctx *ctx, void *stream, const float *x, int64_t rows
 /* floats in the packed statistics buffer [S (V*ldh) | s_h (ldh) | s_v (ldv) | 4] */
 int  mdbn_stats_floats(int64_t V, int64_t ldv, int64_t ldh, int64_t *n);
 
-/* minibatch gather: train_set_x[indexes]  (src/dbn.py:307, src/rbm.py:538) */
+/* minibatch gather: train_set_x[indexes]  (src/dbn.py:307, src/rbm.py:538): dst[r] = src[indexes[r]] for r < n_idx, the
+ * round_up4(cols) leading floats of each row (the source's zero pad up to a multiple of 4 travels with it; columns of dst
+ * beyond that are not written).  indexes: int32, or int64 with index_is_64; NULL = the first n_idx rows.  A negative index
+ * counts from the end as in numpy: i in [-n_rows, 0) names row i + n_rows, so the valid range is [-n_rows, n_rows).
+ * Duplicates are allowed.  ld_src and ld_dst are independent. */
 int  mdbn_gather_rows(mdbn_ctx *ctx, void *stream, const float *src, int64_t n_rows,
                       int64_t cols, int64_t ld_src, const void *indexes, int index_is_64,
                       int64_t n_idx, float *dst, int64_t ld_dst);
@@ -595,7 +599,10 @@ int  mdbn_sample_replicas(mdbn_ctx *ctx, void *stream, const float *mean, int64_
 
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
- * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)). */
+ * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)) (the float32 softplus terms summed in
+ * float64, rounded once).  The rounding is exact for every float32 (0.49999997 -> 0, 8388609 stays; the sign of x is
+ * kept on a zero result, NaN stays NaN); the pad columns cols..ld-1 of `out` are WRITTEN, as zero -- x's own pad columns
+ * are not read. */
 int  mdbn_round_flip(mdbn_ctx *ctx, void *stream, const float *x, int64_t rows, int64_t cols, int64_t ld,
                      int64_t flip_col, float *out);
 int  mdbn_pl_cost(mdbn_ctx *ctx, void *stream, const float *fe, const float *fe_flip, int64_t rows,
@@ -613,7 +620,9 @@ int  mdbn_count_nonfinite(mdbn_ctx *ctx, void *stream, const float *x, int64_t n
 
 /* bfloat16 wire format of the data-parallel statistics (opt-in reporting mode MDBN_WIRE_BF16=1, never a
  * parity path): dst[i] = bfloat16(src[i]) with round-to-nearest-even, and the exact widening back.  n elements; both
- * buffers 16-byte aligned. */
+ * buffers 16-byte aligned (MDBN_EINVAL otherwise, without a launch).  FLT_MAX rounds to inf; a NaN stays a NaN of its sign,
+ * also one whose payload lies in the dropped half.  Subnormal float32 inputs are rounded to nearest even as well, not
+ * flushed to zero (measured on the MI355X: 0x00018000 -> 0x0002, 0x007FFFFF -> 0x0080, 0x00008000 and 0x00000001 -> 0). */
 int  mdbn_f32_to_bf16(mdbn_ctx *ctx, void *stream, const float *src, void *dst, int64_t n);
 int  mdbn_bf16_to_f32(mdbn_ctx *ctx, void *stream, const void *src, float *dst, int64_t n);
 

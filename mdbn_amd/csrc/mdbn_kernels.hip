@@ -1747,7 +1747,9 @@ hipError_t launch_rng_fill(float* out, int64_t rows, int64_t cols, int64_t ld, c
 // arrays (rbm.py:449-482, :690-699), tanh for HiddenLayer (mlp.py:103-107), finite check (the role of
 // NanGuardMode, rbm.py:542-543).
 // ----------------------------------------------------------------------------------
-// xi = tensor.round(x) (round half away from zero); flip_col >= 0: that column becomes 1 - xi
+// xi = tensor.round(x) (round half away from zero); flip_col >= 0: that column becomes 1 - xi; the pad columns
+// of out are written as zero.  roundf, not floorf(|x| + 0.5f): that addition rounds by itself (0.49999997f + 0.5f is a tie
+// that becomes 1, and from 2^23 upwards an odd integer becomes the next even one).
 __global__ __launch_bounds__(256) void round_flip_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t rows,
                                                          int64_t cols, int64_t ld, int64_t flip_col)
 {
@@ -1757,7 +1759,7 @@ __global__ __launch_bounds__(256) void round_flip_kernel(const float* __restrict
     float v = 0.f;
     if (c < cols) {
         const float a = x[i];
-        v = copysignf(floorf(fabsf(a) + 0.5f), a);
+        v = roundf(a);
         if (c == flip_col) v = 1.0f - v;
     }
     out[i] = v;
@@ -1771,15 +1773,20 @@ hipError_t launch_round_flip(const float* x, float* out, int64_t rows, int64_t c
     return hipGetLastError();
 }
 
-// out[0] = -mean_r( n_visible * softplus(F(xi)_r - F(xi_flip)_r) )   (rbm.py:442); one block, fixed order
+// out[0] = -mean_r( n_visible * softplus(F(xi)_r - F(xi_flip)_r) )   (rbm.py:442); one block, fixed order.  The float32
+// softplus terms (up to 121 each on a saturated layer) are summed and scaled in f64 and rounded once, as free_energy_kernel
+// does: float32 partials and a float32 n_visible * tot / rows left the cost a whole ulp (2.4e-4 at 3558) off at 63 rows.
 __global__ __launch_bounds__(256) void pl_cost_kernel(const float* __restrict__ fe, const float* __restrict__ fe_flip,
                                                       int64_t rows, float n_visible, float* __restrict__ out)
 {
-    __shared__ float red[8];
-    float a = 0.f;
-    for (int64_t r = threadIdx.x; r < rows; r += blockDim.x) a += softplusf_(fe[r] - fe_flip[r]);
-    const float tot = block_sum(a, red);
-    if (threadIdx.x == 0) out[0] = -(n_visible * tot) / (float)rows;
+    __shared__ double red[4];
+    double a = 0.0;
+    for (int64_t r = threadIdx.x; r < rows; r += blockDim.x) a += (double)softplusf_(fe[r] - fe_flip[r]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = (float)(-((double)n_visible * (red[0] + red[1] + red[2] + red[3])) / (double)rows);
 }
 
 hipError_t launch_pl_cost(const float* fe, const float* fe_flip, int64_t rows, float n_visible, float* out, hipStream_t s)

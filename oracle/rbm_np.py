@@ -154,10 +154,22 @@ def reconstruction_cost(s, pre_sigmoid_nv, v0):
     return bce.sum(axis=1).mean()
 
 
+def round_half_away(x):
+    """tensor.round: round half away from zero, exact in the dtype of ``x``.  ``floor(|x| + 0.5)`` is not: the
+    addition itself rounds (float32: 0.49999997 + 0.5 is a tie that goes to 1, and from 2^23 upwards odd integers move to
+    the next even one).  x - trunc(x) is exact in every binary format, so the comparison with 0.5 decides on the true
+    fraction.  The sign of x is kept on a zero result (-0.3 -> -0); NaN and the infinities pass through."""
+    x = np.asarray(x)
+    with np.errstate(invalid="ignore"):
+        t = np.trunc(x)
+        r = t + np.sign(x) * (np.abs(x - t) >= 0.5)
+    return np.copysign(np.where(np.isfinite(x), r, x), x).astype(x.dtype)
+
+
 def pseudo_likelihood_cost(s, v0):
     """rbm.py:421-447 (reads bit_i_idx; caller advances it as part of the updates).
     tensor.round is round-half-away-from-zero."""
-    xi = np.sign(v0) * np.floor(np.abs(v0) + 0.5)
+    xi = round_half_away(v0)
     fe_xi = free_energy(s, xi)
     xi_flip = xi.copy()
     xi_flip[:, s.bit_i_idx] = 1 - xi[:, s.bit_i_idx]

@@ -176,7 +176,7 @@ class OracleEngine(object):
 
     def round_flip(self, x, flip_col=-1):
         x = self.as_matrix(x).numpy()
-        xi = np.sign(x) * np.floor(np.abs(x) + 0.5)
+        xi = rbm_np.round_half_away(x)
         if flip_col >= 0:
             xi[:, flip_col] = 1 - xi[:, flip_col]
         return self._t(xi)
