@@ -201,7 +201,9 @@ int  mdbn_ctx_destroy(mdbn_ctx *ctx);
  *   no epilogue launch; another fp32 summation grouping (one K-long chain instead of two halves).
  * "slab_tail" (default 1): the split-K propup of the plane path (16x16x32 shape) walks its last stages quarter by
  *   quarter of a wave's tile and stores each quarter's split-K partials, 16 bytes per lane, while the other quarters'
- *   MFMAs still run; 0 = all partials stored behind the last MFMA.  Bitwise the same outputs.
+ *   MFMAs still run; 0 = all partials stored behind the last MFMA.  Bitwise the same outputs.  1 also gives the
+ *   fused-update statistics launch of the single-device step (early parameter half) the same tail: the first half of the
+ *   new weight speed is stored while the second half's MFMAs still run; 0 = the whole speed behind the last MFMA.
  * "feed_copy_streams" (default 1): a host-resident row feeder created afterwards moves each minibatch as 1 or 2 copies
  *   on as many streams.
  * "gather_ahead" (default 1): honour mdbn_cd_args.next_indexes (the next minibatch gathered inside the statistics

@@ -312,7 +312,8 @@ bool prefer_skinny(int64_t M, int64_t N, int64_t K)
 #define g_opt_narrow_tiles (t_opt->narrow_tiles)
 // mdbn_set_option("slab_tail"): the split-K propup on planes (16x16x32 shape) walks its last stages quarter by quarter and
 // stores each quarter's partials, 16 bytes per lane, while the other quarters' MFMAs run (gemm_planes_slabtail_kernel);
-// 0 = every slab store behind the last MFMA.  Same bits either way.
+// 0 = every slab store behind the last MFMA.  Same bits either way.  1 also routes the fused-update statistics launch with the
+// early parameter half to gemm_planes_statstail_kernel (half of the new speed stored under the last stages' MFMAs).
 #define g_opt_slab_tail (t_opt->slab_tail)
 // mdbn_set_option("feed_copy_streams"): a row feeder created afterwards moves each minibatch as 1 or 2 copies on as many
 // streams (two SDMA engines side by side)
@@ -1016,6 +1017,9 @@ int planes_statistics(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const
         // conditions of the update (no lambda_1; weight cost off or on a frozen snapshot) and >= 12 stages to spread over
         g.upd.early = g_opt_early_w && upd->lambda_1 == 0.f && (upd->weightcost == 0.f || upd->W0 != nullptr) &&
                       2 * B / 32 >= 12 && g_opt_planes_mfma == 16 && !g_opt_bf16_inputs;
+        // "slab_tail" also asks for the statistics kernel that stores the new speed under its last stages, wherever the early
+        // parameter half runs (its 16-byte stores take 32-bit offsets inside a tile of W_speed: a bound on the row pitch)
+        g.stats_tail = g_opt_slab_tail && g.upd.early == 1 && ldh < ((int64_t)1 << 21);
         set_gather_ahead();
         HIP_OK(timed_gemm_planes(LAY_MN, LAY_MN, g, s));
         return MDBN_OK;

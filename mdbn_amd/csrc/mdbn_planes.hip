@@ -39,9 +39,17 @@ typedef short ps16x8 __attribute__((ext_vector_type(8)));
 typedef float pf32x16 __attribute__((ext_vector_type(16)));
 typedef float pf32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int pu32x4b __attribute__((ext_vector_type(4)));
+typedef unsigned int pu32x2b __attribute__((ext_vector_type(2)));
 
 #ifndef PL_ARGS_EARLY
 #define PL_ARGS_EARLY 1
+#endif
+// PL_SIDE_WT = 1 (experiment, default off): the side work of the statistics loader with the early parameter half -- the new W,
+// its three planes, the planes of the gathered-ahead minibatch -- leaves through write-through stores (sc1, buffer form) at the
+// same positions and in the same number as the plain ones, so the counted waits of the ring hold.  Measured, not kept:
+// docs/LABNOTES.md "Statistics tail".
+#ifndef PL_SIDE_WT
+#define PL_SIDE_WT 0
 #endif
 constexpr int PL_PLANE = 8192, PL_STAGE = 6 * PL_PLANE, PL_NSTAGE = 3, PL_LW = 4;
 
@@ -265,14 +273,37 @@ __device__ __forceinline__ void pl_loader(const PlaneGemmArgs& g, char* smem, in
         } else if (g.upd.early) {
             const float decay = upd_decay(g.upd.lr, g.upd.l2);
             const int64_t lane_off = (int64_t)(m0 + (lt >> 5)) * g.upd.ld + n0 + 4 * (lt & 31);
+            // PL_SIDE_WT: descriptors of this tile of W and of its three planes (32-bit offsets inside the tile)
+            const int64_t tile_off = (int64_t)m0 * g.upd.ld + n0;
+            const int tile_elems = 127 * (int)g.upd.ld + 128;
+            // (unused and dropped by the compiler in a default build; without planes the plane descriptors are never stored through)
+            const __amdgpu_buffer_rsrc_t side_w = __builtin_amdgcn_make_buffer_rsrc(g.upd.W + tile_off, 0, tile_elems * 4, 0x00020000);
+            __amdgpu_buffer_rsrc_t side_p[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+                side_p[p] = __builtin_amdgcn_make_buffer_rsrc(g.upd.Wp + p * g.upd.wp_stride + tile_off, 0, g.upd.Wp ? tile_elems * 2 : 0, 0x00020000);
+            (void)side_w; (void)side_p;
 #define CW_STORE(WV, SV, CH)                                                                  \
     do {                                                                                      \
         const int64_t off_ = lane_off + (int64_t)8 * (CH) * g.upd.ld;                         \
         const float4 w4_ = make_float4(WV[0], WV[1], WV[2], WV[3]), s4_ = make_float4(SV[0], SV[1], SV[2], SV[3]); \
         float4 wn_;                                                                           \
         _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) setc(wn_, j_, upd_param(comp(w4_, j_), decay, comp(s4_, j_), g.upd.lr)); \
-        *reinterpret_cast<float4*>(g.upd.W + off_) = wn_;                                     \
-        if (g.upd.Wp) store_planes4(g.upd.Wp, g.upd.wp_stride, off_, wn_);                    \
+        if (PL_SIDE_WT) {                                                                     \
+            const int o_ = (int)(off_ - tile_off) * 4;                                        \
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pu32x4b, wn_), side_w, o_, 0, 16); \
+            if (g.upd.Wp) {                                                                   \
+                unsigned short q_[3][4];                                                      \
+                _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) split3(comp(wn_, j_), q_[0][j_], q_[1][j_], q_[2][j_]); \
+                _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) {                            \
+                    const pu32x2b v_ = {q_[p_][0] | ((unsigned)q_[p_][1] << 16), q_[p_][2] | ((unsigned)q_[p_][3] << 16)}; \
+                    __builtin_amdgcn_raw_buffer_store_b64(v_, side_p[p_], o_ >> 1, 0, 16);    \
+                }                                                                             \
+            }                                                                                 \
+        } else {                                                                              \
+            *reinterpret_cast<float4*>(g.upd.W + off_) = wn_;                                 \
+            if (g.upd.Wp) store_planes4(g.upd.Wp, g.upd.wp_stride, off_, wn_);                \
+        }                                                                                     \
     } while (0)
             if (nt >= 20) {                          // one chunk per stage: 16 items
                 pf32x4 cw[17], cs[17];
@@ -322,6 +353,11 @@ __device__ __forceinline__ void pl_loader(const PlaneGemmArgs& g, char* smem, in
                 const int64_t ld8 = g.ga.ld >> 3;
                 const int nunits = g.ga.rpw * g.ga.passes;
                 pf32x4 ga[4], gb[4];
+                __amdgpu_buffer_rsrc_t side_g[3];            // PL_SIDE_WT: the three destination planes
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+                    side_g[p] = __builtin_amdgcn_make_buffer_rsrc(g.ga.P + p * g.ga.plane_stride, 0, g.ga.B * (int)g.ga.ld * 2, 0x00020000);
+                (void)side_g;
 #define GU_ADDR(U)                                                                            \
     const int i_r0 = (U) / g.ga.passes, pass_ = (U) - i_r0 * g.ga.passes, i_r = i_r0 < 4 ? i_r0 : 3;   \
     const int64_t c_ = (int64_t)pass_ * 256 + lt, cc_ = c_ < ld8 ? c_ : ld8 - 1;              \
@@ -341,6 +377,9 @@ __device__ __forceinline__ void pl_loader(const PlaneGemmArgs& g, char* smem, in
                 uint4 wv_;                                                                    \
                 wv_.x = q_[p_][0] | ((unsigned)q_[p_][1] << 16); wv_.y = q_[p_][2] | ((unsigned)q_[p_][3] << 16); \
                 wv_.z = q_[p_][4] | ((unsigned)q_[p_][5] << 16); wv_.w = q_[p_][6] | ((unsigned)q_[p_][7] << 16); \
+                if (PL_SIDE_WT)                                                               \
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pu32x4b, wv_), side_g[p_], (r_ * (int)g.ga.ld + 8 * (int)c_) * 2, 0, 16); \
+                else                                                                          \
                 *reinterpret_cast<uint4*>(g.ga.P + p_ * g.ga.plane_stride + (int64_t)r_ * g.ga.ld + 8 * c_) = wv_; \
             }                                                                                 \
         }                                                                                     \
@@ -952,17 +991,35 @@ static hipError_t launch_planes_t(const PlaneGemmArgs& g, hipStream_t s)
 #ifndef PL_TAIL_WT
 #define PL_TAIL_WT 1
 #endif
+// Where a finished quarter of the tail goes (pl_tail16's OUT).  final_quarter(q, ah, bh) is called once per quarter, behind
+// the last MFMA chain of quarter q = (A half ah, B half bh); HANDOVER = the sink writes into the ring, so the tail meets one
+// more barrier ahead of its last item's MFMAs, behind which no wave reads the ring any more.
 struct PlSlabOut {
+    static constexpr bool HANDOVER = false;
     __amdgpu_buffer_rsrc_t rsrc;     // this workgroup's slab
     int lane_off, ldc4;              // bytes: the lane's row / column share of the wave's tile; one slab row
+    // 16 bytes per lane and 16-row block, straight from the accumulators
+    template <int WT>
+    __device__ __forceinline__ void final_quarter(char*, int q, int ah, int bh, const pf32x4a (&acc)[4][4]) const
+    {
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const pu32x4b v = __builtin_bit_cast(pu32x4b, acc[2 * ah + a][2 * bh + b]);
+                const int off = 16 * (2 * ah + a) * ldc4 + 64 * (2 * bh + b);
+                if (WT == 2 || (WT == 1 && q < 3)) __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, lane_off, off, 16);
+                else __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, lane_off, off, 0);
+            }
+    }
 };
 
 // The tail: TC stages from stage nb on, quarter-major.  Enters holding the first quarter's fragments of stage nb in
 // (A0, B0) -- (Alo, Blo) behind an even body, (Alo, Bhi) behind an odd one (PAR) -- and double-buffers (A0, B0) / (A1, B1).
-template <int LA, int LB, int AP, int TC, int PAR, int WT>
+template <int LA, int LB, int AP, int TC, int PAR, int WT, class OUT>
 __device__ __forceinline__ void pl_tail16(const char* smem, int nb, const int (&offA)[4][2], const int (&offB)[4][2],
                                           pf32x4a (&acc)[4][4], pbf16x8 (&A0)[3][2], pbf16x8 (&B0)[3][2], pbf16x8 (&A1)[3][2],
-                                          pbf16x8 (&B1)[3][2], const PlSlabOut& so)
+                                          pbf16x8 (&B1)[3][2], const OUT& so)
 {
     constexpr int NBH = 2;
     PL_CONSUME_CONSTS_SW(true);
@@ -976,6 +1033,10 @@ __device__ __forceinline__ void pl_tail16(const char* smem, int nb, const int (&
         const int ah_ = q_ >> 1, bh_ = (((q_ + 1) >> 1) & 1) ^ PAR;                           \
         const int ah1_ = q1_ >> 1, bh1_ = (((q1_ + 1) >> 1) & 1) ^ PAR;                       \
         if (q_ == 0) PL_RAW_BARRIER();            /* stage nb + s_ + 1 landed (s_ + 1 < TC) */ \
+        if (OUT::HANDOVER && (I) == 4 * TC - 1) { /* this item's fragments were the last reads of the ring: returned, meet */ \
+            PIN(CA, NA); PINB(CB, NB);                                                        \
+            PL_RAW_BARRIER();                                                                 \
+        }                                                                                     \
         /* (the slot offset is made opaque per item: hipcc otherwise keeps the fragment addresses of every tail stage */ \
         /* live across the quarters, 12 VGPRs per stage, and spills) */                       \
         int o1_ = sb[s1_];                                                                    \
@@ -983,15 +1044,7 @@ __device__ __forceinline__ void pl_tail16(const char* smem, int nb, const int (&
         if ((I) + 1 < 4 * TC) { RD_A(NXA, smem + o1_, ah1_); RD_B(NXB, smem + o1_, bh1_); }   \
         MMQ(CA, CB, ah_, bh_);                                                                \
         if ((I) + 1 < 4 * TC) { ORD(RA + RB); }                                               \
-        if (s_ == TC - 1) {                       /* the quarter is final: 16 bytes per lane and 16-row block */ \
-            _Pragma("unroll") for (int a = 0; a < 2; ++a)                                     \
-                _Pragma("unroll") for (int b = 0; b < 2; ++b) {                               \
-                    const pu32x4b v_ = __builtin_bit_cast(pu32x4b, acc[2 * ah_ + a][2 * bh_ + b]); \
-                    const int off_ = 16 * (2 * ah_ + a) * so.ldc4 + 64 * (2 * bh_ + b);       \
-                    if (WT == 2 || (WT == 1 && q_ < 3)) __builtin_amdgcn_raw_buffer_store_b128(v_, so.rsrc, so.lane_off, off_, 16); \
-                    else __builtin_amdgcn_raw_buffer_store_b128(v_, so.rsrc, so.lane_off, off_, 0); \
-                }                                                                             \
-        }                                                                                     \
+        if (s_ == TC - 1) so.template final_quarter<WT>(const_cast<char*>(smem), q_, ah_, bh_, acc);   /* the quarter is final */ \
         __builtin_amdgcn_sched_barrier(0);        /* an item is one scheduling region, as a half stage of the body is */ \
     } while (0)
 #pragma unroll
@@ -1002,9 +1055,10 @@ __device__ __forceinline__ void pl_tail16(const char* smem, int nb, const int (&
 #undef PL_TAIL_ITEM
 }
 
-// pl_consume16 with the tail: the body is pl_consume16's (serpentine, barriers, PINs) on stages [0, nt - tc)
-template <int LA, int LB, int AP, int T, int WT>
-__device__ __forceinline__ void pl_consume16_tail(char* smem, int nt, int lane, int wm, int wn, pf32x4a (&acc)[4][4], const PlSlabOut& so)
+// pl_consume16 with the tail: the body is pl_consume16's (serpentine, barriers, PINs) on stages [0, nt - tc).
+// EVEN = the caller guarantees nt >= T and nt - T even: only the even hand-over is instantiated.
+template <int LA, int LB, int AP, int T, int WT, bool EVEN = false, class OUT>
+__device__ __forceinline__ void pl_consume16_tail(char* smem, int nt, int lane, int wm, int wn, pf32x4a (&acc)[4][4], const OUT& so)
 {
     static_assert(T >= 1 && T <= PL_NSTAGE, "the tail stages must all be resident in the ring");
     long long bar_wait = 0;
@@ -1016,7 +1070,7 @@ __device__ __forceinline__ void pl_consume16_tail(char* smem, int nt, int lane, 
     pbf16x8 Alo[3][2], Ahi[3][2], Blo[3][2], Bhi[3][2];
     // T is clamped to the stages the workgroup has: one with fewer than T (nt = 1, 2; a plan's smallest chunks) takes a
     // one-stage tail, whose code is the smallest
-    const int tc = nt < T ? 1 : T, nb = nt - tc;
+    const int tc = (EVEN || nt >= T) ? T : 1, nb = nt - tc;
     RD_A(Alo, smem, 0);
     RD_B(Blo, smem, 0);
     for (int it = 0; it < nb; it += 2) {
@@ -1032,7 +1086,9 @@ __device__ __forceinline__ void pl_consume16_tail(char* smem, int nt, int lane, 
         }
     }
     // the hand-over: an even number of body stages leaves (Alo, Blo) of stage nb, an odd number (Alo, Bhi)
-    if (tc == T) {
+    if constexpr (EVEN) {
+        pl_tail16<LA, LB, AP, T, 0, WT>(smem, nb, offA, offB, acc, Alo, Blo, Ahi, Bhi, so);
+    } else if (tc == T) {
         if (nb & 1) pl_tail16<LA, LB, AP, T, 1, WT>(smem, nb, offA, offB, acc, Alo, Bhi, Ahi, Blo, so);
         else pl_tail16<LA, LB, AP, T, 0, WT>(smem, nb, offA, offB, acc, Alo, Blo, Ahi, Bhi, so);
     } else if constexpr (T > 1) {
@@ -1099,6 +1155,165 @@ static hipError_t launch_planes_slabtail(const PlaneGemmArgs& g, hipStream_t s)
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------- statistics GEMM, speed stores under the tail
+// The fused-update statistics launch of the single-device step (fused == 2, upd.early == 1, 16x16x32 shape) with the same
+// quarter-major tail: gemm_planes_kernel<LAY_MN, LAY_MN, 3, 2, 16> parks the finished tile behind its last MFMA and only
+// then lets the loader waves form and store the new speed -- 16.8 MB at the headline shape that leave the L2s after the last
+// wave has retired.  Here the tile is handed over in two HALVES, which is the granularity the loader's register layout has
+// (EarlySpeed: chunk j = rows 8 j + lt / 32; quarters 0 and 1 of the four MFMA waves complete rows [0, 32) u [64, 96) =
+// chunks 0-3 and 8-11 over all 128 columns), and the first half's speed goes out, write-through, under quarters 2 and 3.
+//   MFMA waves: body on stages [0, nt - 2), tail of T = 2 (nt = 2 B / 32 is a multiple of 8 on the plane path and
+//   early == 1 means nt >= 12: only the even hand-over exists).  Operands swapped (PL_SWP) as in the slab tail, so a lane
+//   parks four neighbouring columns of one row with one 16-byte LDS write per 16 x 16 block; same products, same order,
+//   same bits.  The loader waves keep es.sp / es.w0 and upd_speed(upd_grad(...)) exactly as gemm_planes_kernel has them.
+//   LDS: half 0 is parked in ring slot nt % 3 -- the slot of stage nt - 3, whose last reads returned ahead of the body's
+//   last barrier and which no DMA writes again (the last one issued is stage nt - 1) -- half 1 in slot (nt + 1) % 3 (tail
+//   stage nt - 2's) once no wave reads the ring any more.  64 rows x PL_HALF_LDT floats = 34.8 KB of a slot's 48 KB.
+//   Barriers, nt + 4 on every path:
+//     loader waves: opening + nt (LD_SYNC) in pl_loader; H1 (half 0 parked), H2, H3 (half 1 parked).  They arrive early
+//                   at each and wait; between H1 and H2 they store half 0's speed, behind H3 half 1's.
+//     MFMA waves:   opening + nt - 2 (body) + 2 (tail quarter 0, as the slab tail); H1 behind quarter 1's last chain and
+//                   its LDS writes; H2 ahead of the LAST item's MFMAs, when that item's fragments -- the tail's last reads
+//                   of the ring -- have returned (only the waves' skew is waited for, the item's MFMAs follow); H3 behind
+//                   the LDS writes of quarters 2 and 3.  lgkmcnt(0) ahead of each (PL_RAW_BARRIER).
+//   Stores: 16 bytes per lane through a buffer descriptor of the tile (32-bit offsets: host checks the row pitch); half 0
+//   write-through (sc1), half 1 by PL_STATS_TAIL_WT: 1 = plain, 2 = write-through too (default), 0 = both plain.
+// PL_STATS_TAIL = 0 compiles the launch site out: "slab_tail" then leaves the statistics launch on gemm_planes_kernel.
+// Same-box A/Bs on the headline step (profiles/r10a_stats_tail_ab.log; identical arms differ by 0.0 - 0.45 us): parent 131.45 -
+// 131.78 us, PL_STATS_TAIL = 0 131.6 - 132.6, halves with both stores plain 131.3 - 131.6 (the hand-over alone gains
+// nothing), first half write-through 130.1 - 130.3, both write-through 129.8 - 130.2; kernel trace of the launch 47.18 ->
+// 44.87 us.  The per-quarter hand-over (speed_old re-fetched in quarter layout) was not built: docs/LABNOTES.md.
+#ifndef PL_STATS_TAIL
+#define PL_STATS_TAIL 1
+#endif
+#ifndef PL_STATS_TAIL_WT
+#define PL_STATS_TAIL_WT 2
+#endif
+constexpr int PL_HALF_LDT = 128 + 8;
+static_assert(64 * PL_HALF_LDT * 4 <= PL_STAGE, "a parked half tile must fit one ring slot");
+
+struct PlStatsPark {
+    static constexpr bool HANDOVER = true;
+    int off0, off1;                  // LDS bytes: the lane's row / column share of the wave's 32 x 64 part of half 0 / half 1
+    __device__ __forceinline__ void park(char* base, int ah, int bh, const pf32x4a (&acc)[4][4]) const
+    {
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                *reinterpret_cast<pf32x4a*>(base + (16 * a * PL_HALF_LDT + 32 * bh + 16 * b) * 4) = acc[2 * ah + a][2 * bh + b];
+    }
+    template <int WT>
+    __device__ __forceinline__ void final_quarter(char* smem, int q, int ah, int bh, const pf32x4a (&acc)[4][4]) const
+    {
+        if (ah == 0) park(smem + off0, 0, bh, acc);                    // quarters 0, 1: nobody reads slot nt % 3
+        if (q == 1) PL_RAW_BARRIER();                                  // H1
+        if (q == 3) {                                                  // behind H2: the whole ring is free
+            park(smem + off1, 1, 1, acc);
+            park(smem + off1, 1, 0, acc);
+            PL_RAW_BARRIER();                                          // H3
+        }
+    }
+};
+
+// a loader lane's share of one parked half: chunks 4 HALF + {0..3, 8..11}
+template <int HALF, int AUX>
+__device__ __forceinline__ void pl_stats_speed_half(const UpdEpi& u, const char* half, int lt, const EarlySpeed& es,
+                                                    __amdgpu_buffer_rsrc_t rsrc)
+{
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) {
+        const int j = 4 * HALF + (jj & 3) + 8 * (jj >> 2);
+        const int row = 8 * j + (lt >> 5), c4 = lt & 31;
+        const int lr = (row & 31) + 32 * (row >> 6);
+        const float4 st = *reinterpret_cast<const float4*>(half + (lr * PL_HALF_LDT + 4 * c4) * 4);
+        pf32x4 sn;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            sn[c] = upd_speed(upd_grad(comp(st, c), u.inv_bs, u.wc, comp(es.w0[j], c)), comp(es.sp[j], c), u.mu);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pu32x4b, sn), rsrc, (row * (int)u.ld + 4 * c4) * 4, 0, AUX);
+    }
+}
+
+template <int WT>
+__global__ __launch_bounds__(64 * (4 + PL_LW)) void gemm_planes_statstail_kernel(PlaneGemmArgs g)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+#if PL_ARGS_EARLY
+    asm volatile("" :: "s"(g.A), "s"(g.lda), "s"(g.pa), "s"(g.B), "s"(g.ldb), "s"(g.pb), "s"(g.kchunk), "s"(g.tiles_m),
+                 "s"(g.tiles_n), "s"((int)gridDim.x));
+#endif
+    // tile order and wave roles as gemm_planes_kernel (one workgroup per tile: the launch is unsplit)
+    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int xcd = bid & 7, slot = bid >> 3;
+    const int qq = nwg >> 3, rem = nwg & 7;
+    const int t = (xcd < rem ? xcd * (qq + 1) : rem * (qq + 1) + (xcd - rem) * qq) + slot;
+    int tm, tn;
+    if (g.tiles_m <= g.tiles_n) { tn = t / g.tiles_m; tm = t - tn * g.tiles_m; }
+    else { tm = t / g.tiles_n; tn = t - tm * g.tiles_n; }
+    const int m0 = tm * 128, n0 = tn * 128;
+    const int nt = g.kchunk / 32;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int half0 = (nt % PL_NSTAGE) * PL_STAGE, half1 = ((nt + 1) % PL_NSTAGE) * PL_STAGE;
+    if (wave >= 4) {
+        EarlySpeed es;
+        pl_loader<LAY_MN, LAY_MN, 3, 16, true, 128>(g, smem, wave - 4, lane, m0, n0, 0, nt, &es);
+        const int lt = (wave - 4) * 64 + lane;
+        // this tile of W_speed: offsets inside it are 32-bit and the descriptor bounds every store to it
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+            g.upd.Ws + (int64_t)m0 * g.upd.ld + n0, 0, (127 * (int)g.upd.ld + 128) * 4, 0x00020000);
+        asm volatile("s_barrier" ::: "memory");                        // H1: half 0 is parked
+        pl_stats_speed_half<0, (WT != 0 ? 16 : 0)>(g.upd, smem + half0, lt, es, rsrc);
+        asm volatile("s_barrier" ::: "memory");                        // H2 (the MFMA waves' last reads of the ring)
+        asm volatile("s_barrier" ::: "memory");                        // H3: half 1 is parked
+        pl_stats_speed_half<1, (WT == 2 ? 16 : 0)>(g.upd, smem + half1, lt, es, rsrc);
+        return;
+    }
+    if (g.fin_enabled) {            // finalize units while the first stages are in flight
+        const int nu = fin_units(g.fin);
+        for (int unit = wave * (int)gridDim.x + (int)blockIdx.x; unit <= nu; unit += 4 * (int)gridDim.x)
+            finalize_unit(g.fin, unit, lane);
+    }
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    pf32x4a acc[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = pf32x4a{0.f, 0.f, 0.f, 0.f};
+    // transposed accumulator blocks (PL_SWP): row = lane & 15, columns 4 * (lane >> 4) .. + 3
+    PlStatsPark pk;
+    const int lane_share = (((wm >> 6) * 32 + (lane & 15)) * PL_HALF_LDT + wn + 4 * (lane >> 4)) * 4;
+    pk.off0 = half0 + lane_share;
+    pk.off1 = half1 + lane_share;
+    __syncthreads();                                 // stage 0 landed
+    pl_consume16_tail<LAY_MN, LAY_MN, 3, 2, 0, true>(smem, nt, lane, wm, wn, acc, pk);
+}
+
+[[maybe_unused]] static hipError_t launch_planes_statstail(const PlaneGemmArgs& g, hipStream_t s)
+{
+    auto kern = gemm_planes_statstail_kernel<PL_STATS_TAIL_WT>;
+    static bool attr_set = false;
+    constexpr int lds = PL_NSTAGE * PL_STAGE;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(64 * (4 + PL_LW)), lds, s, g);
+    return hipGetLastError();
+}
+
+// may this launch set g.stats_tail?  The fused-update statistics launch with the early parameter half on the 16x16x32
+// shape, a whole number of stage pairs, and a speed tile whose 16-byte stores take 32-bit offsets
+bool stats_tail_ok(const PlaneGemmArgs& g, int la, int lb)
+{
+    const int nt = g.kchunk / 32;
+    return la == LAY_MN && lb == LAY_MN && g.ap == 3 && g.fused == 2 && g.upd.early == 1 && g.ms == 16 && g.bn != 64 && !g.bal &&
+           g.splitk == 1 && nt >= 12 && (nt & 1) == 0 && (g.upd.ld & 3) == 0 && g.upd.ld < ((int64_t)1 << 21) &&
+           (reinterpret_cast<uintptr_t>(g.upd.Ws) & 15) == 0;
+}
+
 // what a slab_tail launch needs beyond launch_gemm_planes' own checks: 16-byte stores into 32-bit-addressable slabs
 bool slab_tail_ok(const PlaneGemmArgs& g, int la, int lb)
 {
@@ -1122,6 +1337,12 @@ hipError_t launch_gemm_planes(int la, int lb, const PlaneGemmArgs& g, hipStream_
     if (g.slab_tail) {      // split-K propup with the slab stores under its last stages (the caller checked slab_tail_ok)
         if (!slab_tail_ok(g, la, lb)) return hipErrorInvalidValue;
         return g.ap == 1 ? launch_planes_slabtail<1>(g, s) : launch_planes_slabtail<3>(g, s);
+    }
+    if (g.stats_tail) {     // fused-update statistics launch with the speed stores under its last stages (stats_tail_ok)
+        if (!stats_tail_ok(g, la, lb)) return hipErrorInvalidValue;
+#if PL_STATS_TAIL
+        return launch_planes_statstail(g, s);
+#endif
     }
 #define PL_CASE(LAV, LBV, APV, FV) \
     if (la == LAV && lb == LBV && g.ap == APV && g.fused == FV) return launch_planes_t<LAV, LBV, APV, FV>(g, s)

@@ -40,7 +40,8 @@ out["gemm_avg_bytes_per_launch"] = gemm_bytes / max(gemm_n, 1)
 # steps each launch the statistics GEMM once; kernels launched less than once per two steps (one-off splits, the free-energy
 # check) are not part of the step
 # (one statistics GEMM per step; with the gather-ahead the gather kernel itself is launched once per run)
-steps = max([v["launches"] for k, v in out["per_launch_bytes"].items() if k.startswith("mdbn::gemm_planes_kernel<1, 1")] or
+steps = max([v["launches"] for k, v in out["per_launch_bytes"].items()
+             if k.startswith("mdbn::gemm_planes_kernel<1, 1") or k.startswith("mdbn::gemm_planes_statstail_kernel")] or
             [out["per_launch_bytes"].get("mdbn::gather_planes_kernel", {}).get("launches", 0)])
 if steps:
     out["steps_profiled"] = steps
