@@ -599,6 +599,40 @@ int  mdbn_propdown_rowll(mdbn_ctx *ctx, void *stream, const float *h, int64_t R,
 int  mdbn_sample_replicas(mdbn_ctx *ctx, void *stream, const float *mean, int64_t N, int64_t H, int64_t ldh,
                           int64_t S, float *sample, float *entropy, const mdbn_rng *rng);
 
+/* Centred CD training (Montavon & Mueller 2012; Cho et al. 2011, the "enhanced gradient"; Melchior, Fischer & Wiskott 2016,
+ * Algorithm 1) of a layer kept in its ordinary parameters (W, vbias, hbias): visible and hidden units are referred to running
+ * means mu [V] / lam [H] before the statistics are formed, and for such a layer the centred gradient is a transform of the
+ * packed statistics [S | s_h | s_v | cost] of mdbn_cd_step, applied before mdbn_apply_update.  With all sums over the rows
+ * of the minibatch,
+ *   sum_r [(v0 - mu)(ph - lam)' - (vk - mu)(nh - lam)']  =  S - mu s_h' - s_v lam'  =:  S'
+ * and, the update dividing S by batch_size and the bias sums by n_rows (src/rbm.py:411-417), rho = n_rows / batch_size,
+ *   s_v' = s_v - rho S' lam,     s_h' = s_h - rho S'^T mu.
+ * The unchanged update rule then runs on (S', s_h', s_v'); its weight-cost and lambda_1 / lambda_2 terms take no part.
+ *
+ * mdbn_center_offsets: v0 [B, ldv] and ph [B, ldh] are the data half of the step's scratch (rows 0..B-1 of
+ * mdbn_cd_args.V2 / P2: a step run with keep_f32 = 1 on the plane and one-launch paths).  m_v[i] = (sum_{r < B} v0[r, i]) / B
+ * and m_h[j] likewise from ph, rows added in ascending order in float32 with a compensation term (Kahan: the error of a mean
+ * enters s_h' multiplied by mu . s_v, so a plain running sum of a few hundred rows is not good enough); then mu_i = fmaf(nu, m_v[i] - mu_i, mu_i),
+ * lam_j = fmaf(nu, m_h[j] - lam_j, lam_j), and with nu = 1 exactly mu = m_v, lam = m_h (how a first centred step starts
+ * them).  nu in (0, 1].  ld % 4 == 0, v0 and ph 16-byte aligned; the pad columns are not read.
+ *
+ * mdbn_center_stats: in place on stats (packed as mdbn_cd_args.stats, 16-byte aligned), per element
+ *   t = fmaf(-mu_i, s_h[j], S_ij);   S'_ij = fmaf(-s_v[i], lam_j, t)
+ * by workgroups that own blocks of whole rows of S; s_v'[i] = fmaf(-rho, sum_j S'_ij lam_j, s_v[i]) with the row's sum
+ * reduced inside its workgroup, and s_h'[j] = fmaf(-rho, sum_i mu_i S'_ij, s_h[j]) from the workgroups' partial column
+ * sums (workspace: [row blocks][round_up(H, 4)] floats, >= mdbn_center_workspace_bytes(V, H), 16-byte aligned) by a
+ * second small launch -- every sum in a fixed order, no atomics: two runs agree bit for bit.  row_scale = rho > 0.  Pad
+ * columns H..ldh-1 of S and s_h and V..ldv-1 of s_v are neither read nor written, the four cost floats are untouched; with
+ * mu = 0 and lam = 0 the buffer comes back bit for bit.  H <= 4096.
+ *
+ * Bad arguments (a size < 1, a null pointer, a misaligned buffer or a leading dimension that is no multiple of 4, nu outside
+ * (0, 1], row_scale <= 0, a short workspace) return MDBN_EINVAL without a launch. */
+int  mdbn_center_workspace_bytes(mdbn_ctx *ctx, int64_t V, int64_t H, int64_t *bytes);
+int  mdbn_center_offsets(mdbn_ctx *ctx, void *stream, const float *v0, int64_t ldv, const float *ph, int64_t ldh,
+                         int64_t B, int64_t V, int64_t H, float nu, float *mu, float *lam);
+int  mdbn_center_stats(mdbn_ctx *ctx, void *stream, float *stats, int64_t V, int64_t H, int64_t ldv, int64_t ldh,
+                       const float *mu, const float *lam, float row_scale, void *workspace, int64_t workspace_bytes);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)) (the float32 softplus terms summed in

@@ -15,11 +15,12 @@ def _fit(net, data, held_out, batch_size, graph_output, **schedule):
     return net
 
 
-def train_top(batch_size, graph_output, joint_train_set, joint_val_set, rng):
-    """Joint DBN over the concatenated top-layer activations of the modalities (MDBN.py:31-42)."""
+def train_top(batch_size, graph_output, joint_train_set, joint_val_set, rng, centered=False, offset_rate=0.01):
+    """Joint DBN over the concatenated top-layer activations of the modalities (MDBN.py:31-42).  ``centered`` /
+    ``offset_rate``: the centred gradient (``RBM.get_cost_updates``)."""
     joint = shared(joint_train_set)
     net = DBN(numpy_rng=rng, n_ins=joint.shape[1], **TOP_SHAPE)
-    return _fit(net, joint, joint_val_set, batch_size, graph_output, **TOP_SCHEDULE)
+    return _fit(net, joint, joint_val_set, batch_size, graph_output, centered=centered, offset_rate=offset_rate, **TOP_SCHEDULE)
 
 
 def build_bottom_layer(n_visible, layers_sizes, rng):
@@ -85,9 +86,10 @@ def train_modalities(modalities, rng, group="auto", shuffle_seed=None, graph_out
 
 def train_bottom_layer(train_set, validation_set, batch_size=20, k=1, layers_sizes=[40],
                        pretraining_epochs=[800], pretrain_lr=[0.005], lambda_1=0.0, lambda_2=0.1,
-                       rng=None, graph_output=False):
+                       rng=None, graph_output=False, centered=False, offset_rate=0.01):
     """DBN of one modality, Gaussian first layer (MDBN.py:45-76).  Returns the network and its
-    outputs for the training and the validation rows (None without validation rows)."""
+    outputs for the training and the validation rows (None without validation rows).  ``centered`` / ``offset_rate``: the
+    centred gradient (``RBM.get_cost_updates``)."""
     rows = shared(train_set)
     held_out = None if validation_set is None else shared(validation_set)
     n_visible, n_top = rows.shape[1], layers_sizes[-1]
@@ -96,7 +98,7 @@ def train_bottom_layer(train_set, validation_set, batch_size=20, k=1, layers_siz
         print('Output nodes: %i' % n_top)
     net = _fit(build_bottom_layer(n_visible, layers_sizes, rng),
                rows, held_out, batch_size, graph_output, k=k, pretraining_epochs=pretraining_epochs,
-               pretrain_lr=pretrain_lr, lambda_1=lambda_1, lambda_2=lambda_2)
+               pretrain_lr=pretrain_lr, lambda_1=lambda_1, lambda_2=lambda_2, centered=centered, offset_rate=offset_rate)
     return net, net.get_output(rows), net.get_output(held_out)
 
 

@@ -126,6 +126,9 @@ SIGNATURES = {
     "mdbn_rowll_workspace_bytes": [_vp, _i64, _i64, _i64, C.POINTER(_i64)],
     "mdbn_propdown_rowll": [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64],
     "mdbn_sample_replicas": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _rngp],
+    "mdbn_center_workspace_bytes": [_vp, _i64, _i64, C.POINTER(_i64)],
+    "mdbn_center_offsets": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp],
+    "mdbn_center_stats": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _i64],
     "mdbn_round_flip": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
     "mdbn_pl_cost": [_vp, _vp, _vp, _vp, _i64, _i64, _vp],
     "mdbn_recon_cost": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64],

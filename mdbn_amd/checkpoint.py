@@ -8,8 +8,9 @@ The reference saves only W and b at the end of a run (vbias, momentum speeds, RN
 epoch are lost, so it cannot resume).  ``save_network(..., resume=True)`` adds
 ``<name>_resume``: visible biases, the three speeds, RNG seed / stream / step, the update count and
 -- where a step function with a weight cost was built -- the frozen weight-cost constant W0
-(rbm.py:415) of every RBM layer; ``load_network`` restores them when present, and the next
-``get_cost_updates`` of a restored layer reuses that W0 instead of snapshotting the resumed W.
+(rbm.py:415) of every RBM layer, and the offsets of a layer trained by the centred gradient (``v_offset`` / ``h_offset``);
+``load_network`` restores them when present, and the next ``get_cost_updates`` of a restored layer reuses that W0 instead of
+snapshotting the resumed W.
 
 Trainer-loop resume (round 4): while ``DBN.training(..., on_step=)`` runs, ``dbn.trainer_state`` holds where its loop
 stands -- layer index, epoch, next minibatch, the early-stopping state (patience limit, best cost), the state of the
@@ -22,6 +23,7 @@ import numpy
 
 from .dbn import DBN
 from .rbm import GRBM
+from .shared import shared
 
 
 def _resume_state(dbn):
@@ -33,6 +35,8 @@ def _resume_state(dbn):
                     'hbias_speed': r.hbias_speed.get_value(), 'vbias_speed': r.vbias_speed.get_value(),
                     'rng_seed': r.theano_rng.seed, 'rng_stream': r.stream_id, 'rng_step': r._rng_step,
                     'n_updates': r._n_updates, 'bit_i_idx': r.bit_i_idx})
+        if r.v_offset is not None:              # centred gradient: optimiser state, like the speeds
+            out[-1].update(v_offset=r.v_offset.get_value(), h_offset=r.h_offset.get_value())
     return out
 
 
@@ -88,6 +92,9 @@ def load_network(input_file, names=None, engine=None):
                 r._rng_step, r._n_updates, r.bit_i_idx = int(st['rng_step']), int(st['n_updates']), int(st['bit_i_idx'])
                 if st.get('W0') is not None:
                     r._resume_W0 = st['W0']
+                if st.get('v_offset') is not None:
+                    r.v_offset = shared(numpy.asarray(st['v_offset'], dtype=numpy.float32), name='v_offset', engine=r.engine)
+                    r.h_offset = shared(numpy.asarray(st['h_offset'], dtype=numpy.float32), name='h_offset', engine=r.engine)
         if name + '_trainer' in npz.files:
             dbn.trainer_state = npz[name + '_trainer'][0]
         out[name] = dbn

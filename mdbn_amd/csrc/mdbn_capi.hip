@@ -29,6 +29,7 @@
 #include "mdbn_clamp.h"
 #include "mdbn_temper.h"
 #include "mdbn_bound.h"
+#include "mdbn_center.h"
 
 using namespace mdbn;
 
@@ -2916,6 +2917,51 @@ int mdbn_sample_replicas(mdbn_ctx* ctx, void* stream, const float* mean, int64_t
     a.N = N; a.S = S; a.H = H; a.ldh = ldh; a.mean = mean; a.sample = sample; a.entropy = entropy;
     a.rng = make_key(*rng, rng->draw);
     HIP_OK(launch_sample_replicas(a, (hipStream_t)stream));
+    return MDBN_OK;
+}
+
+// ---------------------------------------------------------------------------------- centred CD (mdbn_center.hip)
+int mdbn_center_workspace_bytes(mdbn_ctx* ctx, int64_t V, int64_t H, int64_t* bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(ctx && bytes && V > 0 && H > 0 && V <= (1 << 30) && H <= CENTER_MAX_H, "bad arguments (0 < V <= 2^30, 0 < H <= %d)", CENTER_MAX_H);
+    *bytes = center_partial_floats(V, H) * (int64_t)sizeof(float);
+    return MDBN_OK;
+}
+
+int mdbn_center_offsets(mdbn_ctx* ctx, void* stream, const float* v0, int64_t ldv, const float* ph, int64_t ldh, int64_t B,
+                        int64_t V, int64_t H, float nu, float* mu, float* lam)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(ctx && v0 && ph && mu && lam, "null pointer");
+    REQUIRE(B > 0 && V > 0 && H > 0 && B <= (1 << 30) && V <= (1 << 30) && H <= (1 << 30), "sizes must be positive (and <= 2^30)");
+    REQUIRE(ldv >= V && ldh >= H && ldv % 4 == 0 && ldh % 4 == 0, "leading dimensions: ld >= cols, ld %% 4 == 0");
+    REQUIRE(aligned16(v0) && aligned16(ph), "v0 and ph must be 16-byte aligned");
+    REQUIRE((reinterpret_cast<uintptr_t>(mu) & 3u) == 0 && (reinterpret_cast<uintptr_t>(lam) & 3u) == 0, "mu / lam not aligned");
+    REQUIRE(nu > 0.f && nu <= 1.f, "nu must lie in (0, 1]");
+    CenterOffsetsArgs a;
+    a.v0 = v0; a.ph = ph; a.ldv = ldv; a.ldh = ldh; a.B = (int)B; a.V = (int)V; a.H = (int)H; a.nu = nu; a.mu = mu; a.lam = lam;
+    HIP_OK(launch_center_offsets(a, (hipStream_t)stream));
+    return MDBN_OK;
+}
+
+int mdbn_center_stats(mdbn_ctx* ctx, void* stream, float* stats, int64_t V, int64_t H, int64_t ldv, int64_t ldh, const float* mu,
+                      const float* lam, float row_scale, void* workspace, int64_t workspace_bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(ctx && stats && mu && lam && workspace, "null pointer");
+    REQUIRE(V > 0 && H > 0 && V <= (1 << 30), "sizes must be positive (and V <= 2^30)");
+    REQUIRE(H <= CENTER_MAX_H, "H = %lld: at most %d hidden units", (long long)H, CENTER_MAX_H);
+    REQUIRE(ldv >= V && ldh >= H && ldv % 4 == 0 && ldh % 4 == 0, "leading dimensions: ld >= cols, ld %% 4 == 0");
+    REQUIRE(aligned16(stats) && aligned16(workspace), "stats and workspace must be 16-byte aligned");
+    REQUIRE((reinterpret_cast<uintptr_t>(mu) & 3u) == 0 && (reinterpret_cast<uintptr_t>(lam) & 3u) == 0, "mu / lam not aligned");
+    REQUIRE(row_scale > 0.f && row_scale <= 3.0e38f, "row_scale must be positive and finite");
+    REQUIRE(workspace_bytes >= center_partial_floats(V, H) * (int64_t)sizeof(float), "workspace of mdbn_center_workspace_bytes needed");
+    CenterStatsArgs a;
+    a.stats = stats; a.ldv = ldv; a.ldh = ldh; a.V = (int)V; a.H = (int)H;
+    a.rows = center_rows_per_block(V); a.blocks = (int)center_blocks(V); a.ldp = (int)ru4(H);
+    a.rho = row_scale; a.mu = mu; a.lam = lam; a.partial = reinterpret_cast<float*>(workspace);
+    HIP_OK(launch_center_stats(a, (hipStream_t)stream));
     return MDBN_OK;
 }
 

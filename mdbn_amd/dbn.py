@@ -205,9 +205,11 @@ class DBN(object):
         return provider
 
     def training_functions(self, train_set_x, batch_size, k, lambda_1=0.0, lambda_2=0.1,
-                           monitor=False):
+                           monitor=False, centered=False, offset_rate=0.01):
         '''Per-layer step functions ``fn(indexes=, momentum=, lr=)`` and free-energy functions
-        ``fn(train_sample, test_sample)`` (dbn.py:238-332).'''
+        ``fn(train_sample, test_sample)`` (dbn.py:238-332).  ``centered`` / ``offset_rate``: every layer trains by the
+        centred gradient (``RBM.get_cost_updates``).'''
+        center = dict(centered=centered, offset_rate=offset_rate) if centered else {}
         learning_rate = Scalar('lr')
         assert batch_size > 1                                          # dbn.py:276
         train_set_x = shared(train_set_x, engine=self.engine)
@@ -216,10 +218,10 @@ class DBN(object):
             if isinstance(rbm, GRBM):
                 cost, updates = rbm.get_cost_updates(learning_rate, lambda_1=lambda_1,
                                                      lambda_2=lambda_2, batch_size=batch_size,
-                                                     persistent=None, k=k)
+                                                     persistent=None, k=k, **center)
             else:
                 cost, updates = rbm.get_cost_updates(learning_rate, weightcost=0.0002,
-                                                     batch_size=batch_size, persistent=None, k=k)
+                                                     batch_size=batch_size, persistent=None, k=k, **center)
             train_fns.append(function(updates, train_set_x, input_fn=self._layer_input_fn(i, train_set_x),
                                       data_parallel=self.data_parallel))
             free_energy_gap_fns.append(rbm.free_energies)
@@ -227,7 +229,7 @@ class DBN(object):
 
     def training(self, train_set_x, batch_size, k, pretraining_epochs, pretrain_lr,
                  lambda_1=0.0, lambda_2=0.1, validation_set_x=None, monitor=False,
-                 graph_output=False, resume=None, on_step=None):
+                 graph_output=False, resume=None, on_step=None, centered=False, offset_rate=0.01):
         '''Greedy layer-wise pre-training (dbn.py:334-517).  Returns, per layer, the list of
         (iteration, cost, free_energy_gap) records taken at the validation points.
 
@@ -235,7 +237,9 @@ class DBN(object):
         describes where the loop stands -- layer, epoch, next minibatch, early-stopping state, the shuffle generator's state
         at the start of the epoch, the records so far -- and ``on_step(self)`` is called (e.g. to write a checkpoint:
         ``checkpoint.save_network(..., resume=True)`` stores the trainer state with the layers' own).  ``resume=state``
-        continues such a run: same minibatch order, same validation points, same parameters bit for bit.'''
+        continues such a run: same minibatch order, same validation points, same parameters bit for bit.
+        ``centered`` / ``offset_rate``: every layer trains by the centred gradient (``RBM.get_cost_updates``); the layers'
+        offsets are part of the resume state.'''
         data = shared(train_set_x, engine=self.engine)
         held_out = None if validation_set_x is None else shared(validation_set_x, engine=self.engine)
         self._print('... getting the pretraining functions')
@@ -243,7 +247,8 @@ class DBN(object):
         if held_out is not None:
             self._print('Validation set sample size %i' % held_out.shape[0])
         step_fns, energy_fns = self.training_functions(train_set_x=data, batch_size=batch_size, k=k,
-                                                       lambda_1=lambda_1, lambda_2=lambda_2, monitor=monitor)
+                                                       lambda_1=lambda_1, lambda_2=lambda_2, monitor=monitor,
+                                                       centered=centered, offset_rate=offset_rate)
         self._print('... pre-training the model')
         t_start = timeit.default_timer()
         if resume is None:

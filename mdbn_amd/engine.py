@@ -761,8 +761,9 @@ class HipEngine(object):
             sc.ahead = announce._replace(params=params)
 
     def _cd_args(self, data, indexes, W, hbias, vbias, gauss, k, rng, persistent, add_noise, stats_slot,
-                 sample_stats=False, stats=None, comm_cus=0, next_indexes=None):
+                 sample_stats=False, stats=None, comm_cus=0, next_indexes=None, keep_f32=None):
         data = self.as_matrix(data)
+        keep_f32 = self.keep_f32 if keep_f32 is None else bool(keep_f32)      # (of this call only: cd_step(keep_f32=))
         V, H = W.shape
         assert data.shape[1] == V, "data has %d columns, RBM has %d visibles" % (data.shape[1], V)
         idx = self.index_tensor(indexes, data.shape[0]) if indexes is not None else None
@@ -781,7 +782,7 @@ class HipEngine(object):
         a.index_is_64 = int(idx is not None and idx.dtype == torch.int64)
         a.gauss, a.add_noise, a.k = int(bool(gauss)), int(bool(add_noise)), int(k)
         a.sample_stats = int(bool(sample_stats))
-        a.keep_f32 = int(bool(self.keep_f32))
+        a.keep_f32 = int(bool(keep_f32))
         a.B, a.V, a.H = B, V, H
         a.ldv, a.ldh = ldv, ldh
         a.W, a.hbias, a.vbias = W.data_ptr(), hbias.data_ptr(), vbias.data_ptr()
@@ -808,7 +809,7 @@ class HipEngine(object):
         # (the step variants thin_eligible refuses never take part: nothing would honour the hand-over)
         thin = sc.planes is None and B <= 32 and ldh <= 512 and persistent is None and not sample_stats and \
             not (gauss and add_noise)
-        if (sc.planes is not None or thin) and idx is not None and not self.keep_f32 and not self.trace_chain:
+        if (sc.planes is not None or thin) and idx is not None and not keep_f32 and not self.trace_chain:
             # (the announcing step keeps the matrix and the index tensor alive, so an equal address is the same object)
             # ... and unchanged: an index buffer refilled IN PLACE between the announcing call and this one has another
             # version counter, and the rows are gathered afresh
@@ -835,13 +836,15 @@ class HipEngine(object):
         return CdCall(a, stats, sc, data, idx, keep, announce, thin)
 
     def cd_step(self, data, indexes, W, hbias, vbias, gauss, k, rng, persistent=None, add_noise=False,
-                stats_slot=0, sample_stats=False, stats=None, comm_cus=0):
+                stats_slot=0, sample_stats=False, stats=None, comm_cus=0, keep_f32=None):
         """gather + positive phase + k Gibbs steps + statistics (rbm.py:303-345,374).
         Returns (stats, scratch): the packed [S | s_h | s_v | cost_sum] buffer and the
         CDScratch holding ph_mean / nv_mean / nh_mean for inspection.  ``comm_cus`` > 0 (data-parallel
-        mode): CUs left to the collective that runs beside this step (mdbn_cd_args.comm_cus)."""
+        mode): CUs left to the collective that runs beside this step (mdbn_cd_args.comm_cus).  ``keep_f32``: the engine's
+        attribute of that name for this one call (None: the attribute) -- a caller that reads v0 / ph_mean in the scratch
+        (the centred step) asks for the float32 copies without changing what other steps of the engine do."""
         call = self._cd_args(data, indexes, W, hbias, vbias, gauss, k, rng, persistent,
-                             add_noise, stats_slot, sample_stats, stats, comm_cus)
+                             add_noise, stats_slot, sample_stats, stats, comm_cus, keep_f32=keep_f32)
         _lib.check(self.lib.mdbn_cd_step(self.ctx, self._stream(), C.byref(call.args)), "mdbn_cd_step")
         if call.args.W_planes:
             self._w_planes_written(W)            # (split on entry if they were stale)
@@ -1000,6 +1003,29 @@ class HipEngine(object):
         if phase != 1:
             self._w_planes_written(W)
         return cost
+
+    # ------------------------------------------------------------------ centred gradient (mdbn_center_*)
+    def center_offsets(self, scratch, B, mu, lam, nu):
+        """Slide the offsets ``mu`` [V] / ``lam`` [H] (device vectors, updated IN PLACE) towards the column means of v0 and
+        ph_mean of the step that filled ``scratch`` (rows 0..B-1 of its V2 / P2: a ``cd_step(keep_f32=True)``) by ``nu`` in
+        (0, 1]; 1 sets them to those means (mdbn_center_offsets)."""
+        V2, P2 = scratch.V2, scratch.P2
+        _lib.check(self.lib.mdbn_center_offsets(self.ctx, self._stream(), self._p(V2), V2.stride(0), self._p(P2), P2.stride(0),
+                                                int(B), V2.shape[1], P2.shape[1], float(nu), self._p(mu), self._p(lam)),
+                   "mdbn_center_offsets")
+
+    def center_stats(self, stats, V, H, ldv, ldh, mu, lam, row_scale):
+        """The offset correction of the packed statistics, IN PLACE (mdbn_center_stats): S' = S - mu s_h' - s_v lam',
+        s_v' = s_v - row_scale S' lam, s_h' = s_h - row_scale S'^T mu; ``row_scale`` = n_rows / batch_size."""
+        n = C.c_int64()
+        _lib.check(self.lib.mdbn_center_workspace_bytes(self.ctx, int(V), int(H), C.byref(n)), "mdbn_center_workspace_bytes")
+        ws = getattr(self, "_center_ws", None)
+        if ws is None or ws.numel() * 4 < n.value:
+            ws = self._center_ws = torch.empty(n.value // 4 + 64, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.mdbn_center_stats(self.ctx, self._stream(), self._p(stats), int(V), int(H), int(ldv), int(ldh),
+                                              self._p(mu), self._p(lam), float(row_scale), self._p(ws), ws.numel() * 4),
+                   "mdbn_center_stats")
+        return stats
 
     # ------------------------------------------------------------------ monitoring helpers (all HIP)
     def round_flip(self, x, flip_col=-1):

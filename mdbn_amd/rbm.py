@@ -46,13 +46,16 @@ class UpdatePlan(object):
     CD-k / PCD-k step needs, bound when ``get_cost_updates`` is called."""
 
     def __init__(self, rbm, lr, k, lambda_1, lambda_2, weightcost, batch_size, persistent, W0,
-                 symbolic_grad=False):
+                 symbolic_grad=False, centered=False, offset_rate=0.01):
         self.rbm, self.lr, self.k = rbm, lr, int(k)
         self.lambda_1, self.lambda_2, self.weightcost = lambda_1, lambda_2, weightcost
         self.batch_size, self.persistent, self.W0 = batch_size, persistent, W0
         # compute_symbolic_grad (rbm.py:378-390): negative data = nv_samples[-1], no weight-cost
         # term, true means (the batch_size argument is not used)
         self.symbolic_grad = bool(symbolic_grad)
+        # centred gradient (StepFunction._centered_step): the statistics are referred to the layer's running offsets
+        # rbm.v_offset / rbm.h_offset, which slide towards the batch means by offset_rate per step
+        self.centered, self.offset_rate = bool(centered), float(offset_rate)
 
 
 class LazyCost(object):
@@ -208,6 +211,9 @@ class StepFunction(object):
         self.overlap = bool(overlap and self.group is not None and self.group.world_size > 1
                             and p.persistent is None and p.lambda_1 == 0.0
                             and (p.weightcost == 0.0 or p.W0 is not None))
+        if p.centered and self.group is not None and self.group.world_size > 1:
+            raise NotImplementedError("centered=True on a data-parallel group of %d ranks: the offsets need the means of the "
+                                      "whole minibatch in the all-reduce, which is not built yet" % self.group.world_size)
         self._pending = None                # Pending: the deferred half of the last overlapped step
         self._feed = None                   # HostFeed of a host-resident table, made by its first announcement or step
         self._n_calls = 0
@@ -367,6 +373,8 @@ class StepFunction(object):
         batch_size = p.batch_size if (p.batch_size is not None and not p.symbolic_grad) else mb.n_global
         step = self.rbm._take_step()
         distributed = self.group is not None and self.group.world_size > 1
+        if p.centered:
+            return self._centered_step(mb, step, lr, momentum, batch_size, next_indexes)
         if not distributed and p.persistent is None and mb.hi > mb.lo:
             return self._single_device_step(mb, step, lr, momentum, batch_size, next_indexes)
         return self._group_step(mb, step, lr, momentum, batch_size, next_indexes, distributed)
@@ -432,6 +440,43 @@ class StepFunction(object):
             return self._overlapped_tail(stats, hp, deferred_done)
         if distributed:
             self.group.all_reduce_sum(stats, eng)
+        out = eng.apply_update(*self._update_args(stats, hp, 0))
+        rbm._n_updates += 1
+        if self.nan_guard:
+            self._check_finite(cost if cost is not None else out)
+        return cost if cost is not None else out
+
+    def _centered_step(self, mb, step, lr, momentum, batch_size, next_indexes):
+        """The step with the centred gradient (Melchior et al. 2016, Algorithm 1), CD or PCD on one device: the statistics
+        are materialised, the offsets slide towards the means of v0 and ph_mean of this minibatch (the first step of a layer
+        sets them to those means), the statistics are corrected for the offsets in place -- S' = S - mu s_h' - s_v lam',
+        s_v' = s_v - rho S' lam, s_h' = s_h - rho S'^T mu, rho = n_rows / batch_size -- and the unchanged update rule runs
+        on them."""
+        p, rbm, eng = self.plan, self.rbm, self.engine
+        data = mb.data
+        persistent = None
+        if p.persistent is not None:
+            persistent = p.persistent.tensor
+            if persistent.shape[0] != mb.n_global:
+                raise ValueError("persistent chain has %d rows but the minibatch has %d (the reference fails the same way, "
+                                 "rbm.py:416)" % (persistent.shape[0], mb.n_global))
+        V, H, ldv, ldh = rbm.n_visible, rbm.n_hidden, data.stride(0), rbm.W.tensor.stride(0)
+        if self._stats_slots[0] is None:
+            self._stats_slots[0] = eng.new_stats_buffer(V, H, ldv, ldh)
+        stats = self._stats_slots[0]
+        self._n_calls += 1
+        _, scratch = eng.cd_step(data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, rbm.gauss, p.k,
+                                 self._rng_addr(step, mb.lo), persistent=persistent, stats=stats, keep_f32=True)
+        first = rbm.v_offset is None
+        if first:
+            rbm.v_offset = SharedArray(None, engine=eng, _tensor=eng.alloc_vector(V))
+            rbm.h_offset = SharedArray(None, engine=eng, _tensor=eng.alloc_vector(H))
+        eng.center_offsets(scratch, mb.n_global, rbm.v_offset.tensor, rbm.h_offset.tensor, 1.0 if first else p.offset_rate)
+        eng.center_stats(stats, V, H, ldv, ldh, rbm.v_offset.tensor, rbm.h_offset.tensor, float(mb.n_global) / float(batch_size))
+        cost, cost_scale = self._pcd_monitor(mb, stats, False) if p.persistent is not None else \
+            (None, self._cost_scale(mb.n_global))
+        self._rows_consumed(mb, next_indexes)
+        hp = Hyper(lr, momentum, batch_size, mb.n_global, cost_scale, ldv)
         out = eng.apply_update(*self._update_args(stats, hp, 0))
         rbm._n_updates += 1
         if self.nan_guard:
@@ -586,6 +631,8 @@ class RBM(object):
         self.strict_reference = True
         self._W0_snapshot = None               # the frozen weight-cost constant of the last get_cost_updates
         self._resume_W0 = None                 # ... restored from a checkpoint, consumed by the next one
+        self.v_offset = self.h_offset = None   # running means of the centred gradient (SharedArray [V] / [H]; optimiser state,
+                                               # like the speeds: None until the first centred step)
         self.bit_i_idx = 0                     # rbm.py:425
         self._rng_step = 0
         self._n_updates = 0
@@ -927,12 +974,20 @@ class RBM(object):
 
     # ------------------------------------------------------------------ CD-k / PCD-k
     def get_cost_updates(self, lr=0.1, k=1, lambda_1=0.0, lambda_2=0.0, weightcost=0.0,
-                         batch_size=None, persistent=None, symbolic_grad=False):
+                         batch_size=None, persistent=None, symbolic_grad=False, centered=False, offset_rate=0.01):
         """One step of CD-k or PCD-k (rbm.py:258-376).  Returns ``(cost, updates)``; pass
         ``updates`` to ``mdbn_amd.function`` to obtain the step function.
 
         ``lr`` may be a float or a ``Scalar`` (then the step function takes ``lr=``).
-        ``persistent``: None for CD, a SharedArray [batch_size, n_hidden] for PCD."""
+        ``persistent``: None for CD, a SharedArray [batch_size, n_hidden] for PCD.
+        ``centered``: the centred gradient (Montavon & Mueller 2012; Melchior et al. 2016) -- visible and hidden units are
+        referred to the running means ``self.v_offset`` / ``self.h_offset`` of the data and of ph_mean before the statistics
+        are formed; the offsets slide by ``offset_rate`` per step (the first centred step sets them to its batch means).
+        The model and its parameters (W, vbias, hbias) keep their meaning; the offsets are optimiser state."""
+        if centered and symbolic_grad:
+            raise NotImplementedError("centered=True with symbolic_grad=True is not supported")
+        if centered and not 0.0 < float(offset_rate) <= 1.0:
+            raise ValueError("offset_rate must lie in (0, 1], got %r" % (offset_rate,))
         if symbolic_grad and self.gauss and not getattr(self, "error_free", True):
             raise NotImplementedError("symbolic_grad with a noisy GRBM (error_free=False) is not supported")
         if symbolic_grad:
@@ -956,7 +1011,7 @@ class RBM(object):
                 t.copy_(persistent.tensor)
                 persistent.tensor = t
         updates = UpdatePlan(self, lr, k, lambda_1, lambda_2, weightcost, batch_size, persistent, W0,
-                             symbolic_grad=symbolic_grad)
+                             symbolic_grad=symbolic_grad, centered=centered, offset_rate=offset_rate)
         cost = CostHandle('pseudo_likelihood' if persistent is not None else 'reconstruction')
         return cost, updates
 
@@ -984,20 +1039,22 @@ class RBM(object):
     # ------------------------------------------------------------------ stand-alone trainer
     def training(self, train_set_x, validation_set_x, training_epochs, batch_size=10,
                  learning_rate=0.1, k=1, initial_momentum=0.0, final_momentum=0.0,
-                 weightcost=0.0, lambda_2=0.0, persistent=True, display_fn=None, graph_output=False, tempering=None):
+                 weightcost=0.0, lambda_2=0.0, persistent=True, display_fn=None, graph_output=False, tempering=None,
+                 centered=False, offset_rate=0.01):
         """rbm.py:484-520 (note: like the reference, ``lambda_2`` is accepted but not used).
 
         ``tempering=R`` (with ``persistent``): PCD whose negative chains are the beta = 1 replicas of ``batch_size``
         parallel-tempering ladders of R temperatures (Desjardins et al. 2010) -- every step is ``chains.run(1)``,
         ``chains.to_persistent``, the unchanged PCD step, ``chains.from_persistent``; the ladders stay in ``self.tempered``.
-        None: nothing changes."""
+        None: nothing changes.  ``centered`` / ``offset_rate``: the centred gradient (``get_cost_updates``)."""
         if persistent:
             persistent_chain = shared(numpy.zeros((batch_size, self.n_hidden), dtype=numpy.float32),
                                       engine=self.engine)               # rbm.py:496-498
         else:
             persistent_chain = None
         cost, updates = self.get_cost_updates(lr=learning_rate, k=k, weightcost=weightcost,
-                                              batch_size=batch_size, persistent=persistent_chain)
+                                              batch_size=batch_size, persistent=persistent_chain,
+                                              centered=centered, offset_rate=offset_rate)
         step_hooks = None
         if tempering is not None:
             if not persistent:
@@ -1105,11 +1162,12 @@ class GRBM(RBM):
     def training(self, train_set_x, validation_set_x, training_epochs, batch_size=10,
                  learning_rate=0.01, k=1, initial_momentum=0.0, final_momentum=0.0,
                  weightcost=0.0, lambda_1=0.0, lambda_2=0.1, persistent=False,
-                 display_fn=None, graph_output=False):
-        """rbm.py:701-728: always CD (``persistent`` is ignored, as in the reference)."""
+                 display_fn=None, graph_output=False, centered=False, offset_rate=0.01):
+        """rbm.py:701-728: always CD (``persistent`` is ignored, as in the reference).  ``centered`` / ``offset_rate``: the
+        centred gradient (``get_cost_updates``)."""
         cost, updates = self.get_cost_updates(lr=learning_rate, k=k, lambda_1=lambda_1,
                                               lambda_2=lambda_2, weightcost=weightcost,
-                                              batch_size=batch_size)
+                                              batch_size=batch_size, centered=centered, offset_rate=offset_rate)
         return self.learn_model(train_set_x=train_set_x, validation_set_x=validation_set_x,
                                 training_epochs=training_epochs, batch_size=batch_size,
                                 initial_momentum=initial_momentum, final_momentum=final_momentum,
