@@ -633,6 +633,39 @@ int  mdbn_center_offsets(mdbn_ctx *ctx, void *stream, const float *v0, int64_t l
 int  mdbn_center_stats(mdbn_ctx *ctx, void *stream, float *stats, int64_t V, int64_t H, int64_t ldv, int64_t ldh,
                        const float *mu, const float *lam, float row_scale, void *workspace, int64_t workspace_bytes);
 
+/* Sparsity target for the hidden units (Lee, Ekanadham & Ng 2008; Nair & Hinton 2009; Hinton's practical guide, section 11):
+ * a penalty that drives the mean activation q_j of every hidden unit towards `target`, as a second transform of the packed
+ * statistics [S | s_h | s_v | cost] of mdbn_cd_step, applied before mdbn_apply_update (and before mdbn_center_stats when the
+ * step is centred as well: the sparsity part of the weight gradient is then taken through the centred input).  With
+ * m_h[j] = mean_r ph[r, j], m_v[i] = mean_r v0[r, i] over the n rows of the minibatch and t_j = target - q_j,
+ *   s_h[j] += b_scale t_j,    S_ij += w_scale m_v[i] t_j,    b_scale = cost n,  w_scale = cost batch_size,
+ * so that the unchanged update rule (S / batch_size, s_h / n_rows; src/rbm.py:411-417) adds cost t_j to the hidden-bias
+ * gradient and cost t_j m_v[i] to the weight gradient: the derivative of the cross-entropy between target and q_j with
+ * respect to the unit's total input, through the bias and through the batch-mean input.  w_scale = 0 is the bias-only form
+ * of Lee et al.  The update's weight-cost and lambda_1 / lambda_2 terms take no part.
+ *
+ * mdbn_sparsity_activity: ph [B, ldh] and v0 [B, ldv] are the data half of the step's scratch, as for mdbn_center_offsets.
+ * The rows of a column are added in ascending order in float32 with a compensation term; then
+ * q_j = fmaf(rate, m_h[j] - q_j, q_j), exactly m_h[j] at rate = 1 (how a first sparse step starts the estimate; afterwards
+ * rate = 1 - decay, Nair & Hinton's running estimate), and v_mean[i] = m_v[i].  v0 and v_mean are both given or both null;
+ * null: the hidden half alone, V and ldv are ignored.  rate in (0, 1].  ld % 4 == 0, ph and v0 16-byte aligned; the pad
+ * columns are not read.
+ *
+ * mdbn_sparsity_stats: in place on stats (packed as mdbn_cd_args.stats, 16-byte aligned), per element
+ *   t_j = target - q_j;   a_i = w_scale * v_mean[i];   S_ij = fmaf(a_i, t_j, S_ij)
+ * by workgroups that own blocks of whole rows of S, one of which also does s_h[j] = fmaf(b_scale, t_j, s_h[j]).  No sum is
+ * formed: two runs agree bit for bit, and H has no limit.  Pad columns H..ldh-1 of S and s_h are neither read nor written;
+ * s_v, the four cost floats, q and v_mean are untouched.  w_scale = 0 does the s_h half only and never touches S (v_mean
+ * may then be null); both scales 0 return MDBN_OK without a launch.  target in (0, 1); the scales finite and >= 0.
+ *
+ * Bad arguments (a size < 1, a null required pointer, v0 without v_mean or the reverse, w_scale > 0 without v_mean, a
+ * misaligned buffer, a leading dimension below its width or no multiple of 4, rate, target or a scale out of range or NaN)
+ * return MDBN_EINVAL without a launch. */
+int  mdbn_sparsity_activity(mdbn_ctx *ctx, void *stream, const float *ph, int64_t ldh, const float *v0, int64_t ldv,
+                            int64_t B, int64_t V, int64_t H, float rate, float *q, float *v_mean);
+int  mdbn_sparsity_stats(mdbn_ctx *ctx, void *stream, float *stats, int64_t V, int64_t H, int64_t ldv, int64_t ldh,
+                         const float *q, const float *v_mean, float target, float w_scale, float b_scale);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)) (the float32 softplus terms summed in

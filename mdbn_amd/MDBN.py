@@ -8,6 +8,7 @@ from .shared import shared
 # the joint network of MDBN.py:31-42: Bernoulli 24 -> 3 on the concatenated modality outputs, CD-1
 TOP_SHAPE = dict(gauss=False, hidden_layers_sizes=[24], n_outs=3)
 TOP_SCHEDULE = dict(k=1, pretraining_epochs=[800, 800], pretrain_lr=[0.1, 0.1])
+SPARSITY_KEYS = ("sparsity_target", "sparsity_cost", "sparsity_decay", "sparsity_weights")     # of RBM.get_cost_updates
 
 
 def _fit(net, data, held_out, batch_size, graph_output, **schedule):
@@ -15,12 +16,15 @@ def _fit(net, data, held_out, batch_size, graph_output, **schedule):
     return net
 
 
-def train_top(batch_size, graph_output, joint_train_set, joint_val_set, rng, centered=False, offset_rate=0.01):
-    """Joint DBN over the concatenated top-layer activations of the modalities (MDBN.py:31-42).  ``centered`` /
-    ``offset_rate``: the centred gradient (``RBM.get_cost_updates``)."""
+def train_top(batch_size, graph_output, joint_train_set, joint_val_set, rng, sparsity_target=None, sparsity_cost=0.0,
+              sparsity_decay=0.9, sparsity_weights=True, centered=False, offset_rate=0.01):
+    """Joint DBN over the concatenated top-layer activations of the modalities (MDBN.py:31-42).  ``sparsity_*``: the sparsity
+    target, ``centered`` / ``offset_rate``: the centred gradient (``RBM.get_cost_updates``)."""
     joint = shared(joint_train_set)
     net = DBN(numpy_rng=rng, n_ins=joint.shape[1], **TOP_SHAPE)
-    return _fit(net, joint, joint_val_set, batch_size, graph_output, centered=centered, offset_rate=offset_rate, **TOP_SCHEDULE)
+    return _fit(net, joint, joint_val_set, batch_size, graph_output, centered=centered, offset_rate=offset_rate,
+                sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
+                sparsity_weights=sparsity_weights, **TOP_SCHEDULE)
 
 
 def build_bottom_layer(n_visible, layers_sizes, rng):
@@ -38,7 +42,7 @@ def train_modalities(modalities, rng, group="auto", shuffle_seed=None, graph_out
 
     ``modalities``: ordered list of dicts with ``train_set``, optional ``validation_set``, and the keyword
     arguments of ``train_bottom_layer`` (batch_size, k, layers_sizes, pretraining_epochs, pretrain_lr, lambda_1,
-    lambda_2).  Returns ``[(net, out_train, out_val), ...]`` in the same order, identical on every rank.
+    lambda_2, sparsity_target, sparsity_cost, sparsity_decay, sparsity_weights).  Returns ``[(net, out_train, out_val), ...]`` in the same order, identical on every rank.
 
     Every rank CONSTRUCTS all networks in order -- construction is all that consumes ``rng``, so the initial weights
     and the state ``rng`` is left in (for ``train_top``) are those of the sequential reference on every rank.  The
@@ -65,7 +69,8 @@ def train_modalities(modalities, rng, group="auto", shuffle_seed=None, graph_out
         if i % world == rank:
             _fit(net, rows, held_out, m.get("batch_size", 20), graph_output, k=m.get("k", 1),
                  pretraining_epochs=m.get("pretraining_epochs", [800]), pretrain_lr=m.get("pretrain_lr", [0.005]),
-                 lambda_1=m.get("lambda_1", 0.0), lambda_2=m.get("lambda_2", 0.1))
+                 lambda_1=m.get("lambda_1", 0.0), lambda_2=m.get("lambda_2", 0.1),
+                 **{key: m[key] for key in SPARSITY_KEYS if key in m})
     if world > 1:
         import torch.distributed as td
         for i, (net, _, _) in enumerate(nets):       # one broadcast per array, once per modality
@@ -86,10 +91,11 @@ def train_modalities(modalities, rng, group="auto", shuffle_seed=None, graph_out
 
 def train_bottom_layer(train_set, validation_set, batch_size=20, k=1, layers_sizes=[40],
                        pretraining_epochs=[800], pretrain_lr=[0.005], lambda_1=0.0, lambda_2=0.1,
-                       rng=None, graph_output=False, centered=False, offset_rate=0.01):
+                       rng=None, graph_output=False, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9,
+                       sparsity_weights=True, centered=False, offset_rate=0.01):
     """DBN of one modality, Gaussian first layer (MDBN.py:45-76).  Returns the network and its
-    outputs for the training and the validation rows (None without validation rows).  ``centered`` / ``offset_rate``: the
-    centred gradient (``RBM.get_cost_updates``)."""
+    outputs for the training and the validation rows (None without validation rows).  ``sparsity_*``: the sparsity target,
+    ``centered`` / ``offset_rate``: the centred gradient (``RBM.get_cost_updates``)."""
     rows = shared(train_set)
     held_out = None if validation_set is None else shared(validation_set)
     n_visible, n_top = rows.shape[1], layers_sizes[-1]
@@ -98,7 +104,9 @@ def train_bottom_layer(train_set, validation_set, batch_size=20, k=1, layers_siz
         print('Output nodes: %i' % n_top)
     net = _fit(build_bottom_layer(n_visible, layers_sizes, rng),
                rows, held_out, batch_size, graph_output, k=k, pretraining_epochs=pretraining_epochs,
-               pretrain_lr=pretrain_lr, lambda_1=lambda_1, lambda_2=lambda_2, centered=centered, offset_rate=offset_rate)
+               pretrain_lr=pretrain_lr, lambda_1=lambda_1, lambda_2=lambda_2, centered=centered, offset_rate=offset_rate,
+               sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
+               sparsity_weights=sparsity_weights)
     return net, net.get_output(rows), net.get_output(held_out)
 
 

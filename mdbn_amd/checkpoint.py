@@ -8,7 +8,8 @@ The reference saves only W and b at the end of a run (vbias, momentum speeds, RN
 epoch are lost, so it cannot resume).  ``save_network(..., resume=True)`` adds
 ``<name>_resume``: visible biases, the three speeds, RNG seed / stream / step, the update count and
 -- where a step function with a weight cost was built -- the frozen weight-cost constant W0
-(rbm.py:415) of every RBM layer, and the offsets of a layer trained by the centred gradient (``v_offset`` / ``h_offset``);
+(rbm.py:415) of every RBM layer, the offsets of a layer trained by the centred gradient (``v_offset`` / ``h_offset``) and the
+activity estimate of a layer trained with a sparsity target (``h_activity``);
 ``load_network`` restores them when present, and the next ``get_cost_updates`` of a restored layer reuses that W0 instead of
 snapshotting the resumed W.
 
@@ -37,6 +38,8 @@ def _resume_state(dbn):
                     'n_updates': r._n_updates, 'bit_i_idx': r.bit_i_idx})
         if r.v_offset is not None:              # centred gradient: optimiser state, like the speeds
             out[-1].update(v_offset=r.v_offset.get_value(), h_offset=r.h_offset.get_value())
+        if r.h_activity is not None:            # sparsity target: the running activity estimate
+            out[-1].update(h_activity=r.h_activity.get_value())
     return out
 
 
@@ -95,6 +98,8 @@ def load_network(input_file, names=None, engine=None):
                 if st.get('v_offset') is not None:
                     r.v_offset = shared(numpy.asarray(st['v_offset'], dtype=numpy.float32), name='v_offset', engine=r.engine)
                     r.h_offset = shared(numpy.asarray(st['h_offset'], dtype=numpy.float32), name='h_offset', engine=r.engine)
+                if st.get('h_activity') is not None:
+                    r.h_activity = shared(numpy.asarray(st['h_activity'], dtype=numpy.float32), name='h_activity', engine=r.engine)
         if name + '_trainer' in npz.files:
             dbn.trainer_state = npz[name + '_trainer'][0]
         out[name] = dbn

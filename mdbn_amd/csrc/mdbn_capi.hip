@@ -30,6 +30,7 @@
 #include "mdbn_temper.h"
 #include "mdbn_bound.h"
 #include "mdbn_center.h"
+#include "mdbn_sparsity.h"
 
 using namespace mdbn;
 
@@ -2962,6 +2963,48 @@ int mdbn_center_stats(mdbn_ctx* ctx, void* stream, float* stats, int64_t V, int6
     a.rows = center_rows_per_block(V); a.blocks = (int)center_blocks(V); a.ldp = (int)ru4(H);
     a.rho = row_scale; a.mu = mu; a.lam = lam; a.partial = reinterpret_cast<float*>(workspace);
     HIP_OK(launch_center_stats(a, (hipStream_t)stream));
+    return MDBN_OK;
+}
+
+// ---------------------------------------------------------------------------------- sparsity target (mdbn_sparsity.hip)
+int mdbn_sparsity_activity(mdbn_ctx* ctx, void* stream, const float* ph, int64_t ldh, const float* v0, int64_t ldv, int64_t B,
+                           int64_t V, int64_t H, float rate, float* q, float* v_mean)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(ctx && ph && q, "null pointer");
+    REQUIRE((v0 != nullptr) == (v_mean != nullptr), "v0 and v_mean: both or neither");
+    REQUIRE(B > 0 && H > 0 && B <= (1 << 30) && H <= (1 << 30), "sizes must be positive (and <= 2^30)");
+    REQUIRE(ldh >= H && ldh % 4 == 0, "leading dimensions: ld >= cols, ld %% 4 == 0");
+    REQUIRE(aligned16(ph) && (reinterpret_cast<uintptr_t>(q) & 3u) == 0, "ph must be 16-byte aligned, q float-aligned");
+    if (v0) {
+        REQUIRE(V > 0 && V <= (1 << 30), "sizes must be positive (and <= 2^30)");
+        REQUIRE(ldv >= V && ldv % 4 == 0, "leading dimensions: ld >= cols, ld %% 4 == 0");
+        REQUIRE(aligned16(v0) && (reinterpret_cast<uintptr_t>(v_mean) & 3u) == 0, "v0 must be 16-byte aligned, v_mean float-aligned");
+    }
+    REQUIRE(rate > 0.f && rate <= 1.f, "rate must lie in (0, 1]");
+    SparsityActivityArgs a;
+    a.ph = ph; a.v0 = v0; a.ldh = ldh; a.ldv = v0 ? ldv : 0; a.B = (int)B; a.V = v0 ? (int)V : 0; a.H = (int)H;
+    a.rate = rate; a.q = q; a.v_mean = v_mean;
+    HIP_OK(launch_sparsity_activity(a, (hipStream_t)stream));
+    return MDBN_OK;
+}
+
+int mdbn_sparsity_stats(mdbn_ctx* ctx, void* stream, float* stats, int64_t V, int64_t H, int64_t ldv, int64_t ldh, const float* q,
+                        const float* v_mean, float target, float w_scale, float b_scale)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(ctx && stats && q, "null pointer");
+    REQUIRE(V > 0 && H > 0 && V <= (1 << 30) && H <= (1 << 30), "sizes must be positive (and <= 2^30)");
+    REQUIRE(ldv >= V && ldh >= H && ldv % 4 == 0 && ldh % 4 == 0, "leading dimensions: ld >= cols, ld %% 4 == 0");
+    REQUIRE(aligned16(stats), "stats must be 16-byte aligned");
+    REQUIRE((reinterpret_cast<uintptr_t>(q) & 3u) == 0 && (reinterpret_cast<uintptr_t>(v_mean) & 3u) == 0, "q / v_mean not aligned");
+    REQUIRE(target > 0.f && target < 1.f, "target must lie in (0, 1)");
+    REQUIRE(w_scale >= 0.f && w_scale <= 3.0e38f && b_scale >= 0.f && b_scale <= 3.0e38f, "scales must be finite and not negative");
+    REQUIRE(w_scale == 0.f || v_mean, "w_scale > 0 needs v_mean");
+    SparsityStatsArgs a;
+    a.stats = stats; a.ldh = ldh; a.V = (int)V; a.H = (int)H; a.rows = center_rows_per_block(V);
+    a.q = q; a.v_mean = v_mean; a.target = target; a.w_scale = w_scale; a.b_scale = b_scale;
+    HIP_OK(launch_sparsity_stats(a, (hipStream_t)stream));
     return MDBN_OK;
 }
 

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mdbn_center.h"
+#include "mdbn_packed_walk.h"
 
 namespace mdbn {
 namespace {
@@ -30,57 +31,9 @@ __global__ __launch_bounds__(CENTER_OFF_NT) void center_offsets_kernel(CenterOff
     const bool vis = (int)blockIdx.x < blocks_v;
     const int c = ((int)blockIdx.x - (vis ? 0 : blocks_v)) * CENTER_OFF_NT + (int)threadIdx.x;
     if (c >= (vis ? a.V : a.H)) return;
-    const float* x = (vis ? a.v0 : a.ph) + c;
-    const int64_t ld = vis ? a.ldv : a.ldh;
-    // compensated (Kahan) float32 sum: a plain running sum of 512 means in (0, 1) is off by 5e-7 of the mean, and the
-    // correction of s_h multiplies an error of lam by mu . s_v, thousands for sparse 0 / 1 data
-    float s = 0.f, comp = 0.f;
-    auto add = [&](float v) {
-        const float y = v - comp, t = s + y;
-        comp = (t - s) - y;
-        s = t;
-    };
-    int r = 0;
-    for (; r + 32 <= a.B; r += 32) {         // 32 rows in flight (the walk is latency-bound: one wave per 64 columns), added in ascending order
-        float t[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) t[u] = x[(int64_t)(r + u) * ld];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) add(t[u]);
-    }
-    for (; r < a.B; ++r) add(x[(int64_t)r * ld]);
-    const float m = s / (float)a.B;
+    const float m = column_mean((vis ? a.v0 : a.ph) + c, vis ? a.ldv : a.ldh, a.B);
     float* off = (vis ? a.mu : a.lam) + c;
     *off = a.nu == 1.0f ? m : fmaf(a.nu, m - *off, *off);
-}
-
-// the floats 0 .. n-1 of a 16-byte group, the others as exact zeros (n = 4: one 16-byte access)
-__device__ __forceinline__ float4 load_live(const float* p, int n)
-{
-    if (n == 4) return *reinterpret_cast<const float4*>(p);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (n > 0) v.x = p[0];
-    if (n > 1) v.y = p[1];
-    if (n > 2) v.z = p[2];
-    return v;
-}
-
-__device__ __forceinline__ float4 load_live_scalar(const float* p, int n)     // a base that need not be 16-byte aligned
-{
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (n > 0) v.x = p[0];
-    if (n > 1) v.y = p[1];
-    if (n > 2) v.z = p[2];
-    if (n > 3) v.w = p[3];
-    return v;
-}
-
-__device__ __forceinline__ void store_live(float* p, int n, float4 v)
-{
-    if (n == 4) { *reinterpret_cast<float4*>(p) = v; return; }
-    if (n > 0) p[0] = v.x;
-    if (n > 1) p[1] = v.y;
-    if (n > 2) p[2] = v.z;
 }
 
 // CT threads side by side on a row (a multiple of the wave), CENTER_NT / CT rows side by side, NCH 16-byte groups of a row

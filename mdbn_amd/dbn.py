@@ -147,6 +147,12 @@ class DBN(object):
             return None
         return self.engine.to_numpy(self._forward(input, layer))
 
+    def hidden_activity(self, data):
+        """``RBM.hidden_activity`` of every layer, each fed the means of the layer below for the rows ``data``: a list of
+        float32 [n_hidden] arrays, bottom layer first."""
+        x = getattr(data, "tensor", data)
+        return [r.hidden_activity(x if i == 0 else self._forward(x, i - 1)) for i, r in enumerate(self.rbm_layers)]
+
     def down_pass(self, h, layer=-1):
         """Mean-field top-down pass, the inverse direction of ``get_output``: ``h`` (activations of ``sigmoid_layers[layer]``,
         host or device matrix) is taken down through ``rbm_layers[layer] .. rbm_layers[0]`` by the layers' conditional means
@@ -205,11 +211,15 @@ class DBN(object):
         return provider
 
     def training_functions(self, train_set_x, batch_size, k, lambda_1=0.0, lambda_2=0.1,
-                           monitor=False, centered=False, offset_rate=0.01):
+                           monitor=False, centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0,
+                           sparsity_decay=0.9, sparsity_weights=True):
         '''Per-layer step functions ``fn(indexes=, momentum=, lr=)`` and free-energy functions
         ``fn(train_sample, test_sample)`` (dbn.py:238-332).  ``centered`` / ``offset_rate``: every layer trains by the
-        centred gradient (``RBM.get_cost_updates``).'''
+        centred gradient; ``sparsity_*``: every layer trains with the sparsity target (``RBM.get_cost_updates``).'''
         center = dict(centered=centered, offset_rate=offset_rate) if centered else {}
+        if sparsity_target is not None:
+            center.update(sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
+                          sparsity_weights=sparsity_weights)
         learning_rate = Scalar('lr')
         assert batch_size > 1                                          # dbn.py:276
         train_set_x = shared(train_set_x, engine=self.engine)
@@ -229,7 +239,8 @@ class DBN(object):
 
     def training(self, train_set_x, batch_size, k, pretraining_epochs, pretrain_lr,
                  lambda_1=0.0, lambda_2=0.1, validation_set_x=None, monitor=False,
-                 graph_output=False, resume=None, on_step=None, centered=False, offset_rate=0.01):
+                 graph_output=False, resume=None, on_step=None, centered=False, offset_rate=0.01, sparsity_target=None,
+                 sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         '''Greedy layer-wise pre-training (dbn.py:334-517).  Returns, per layer, the list of
         (iteration, cost, free_energy_gap) records taken at the validation points.
 
@@ -239,7 +250,9 @@ class DBN(object):
         ``checkpoint.save_network(..., resume=True)`` stores the trainer state with the layers' own).  ``resume=state``
         continues such a run: same minibatch order, same validation points, same parameters bit for bit.
         ``centered`` / ``offset_rate``: every layer trains by the centred gradient (``RBM.get_cost_updates``); the layers'
-        offsets are part of the resume state.'''
+        offsets are part of the resume state.  ``sparsity_target`` / ``sparsity_cost`` / ``sparsity_decay`` /
+        ``sparsity_weights``: every layer trains with the sparsity target; the layers' activity estimates are part of the
+        resume state.'''
         data = shared(train_set_x, engine=self.engine)
         held_out = None if validation_set_x is None else shared(validation_set_x, engine=self.engine)
         self._print('... getting the pretraining functions')
@@ -248,7 +261,9 @@ class DBN(object):
             self._print('Validation set sample size %i' % held_out.shape[0])
         step_fns, energy_fns = self.training_functions(train_set_x=data, batch_size=batch_size, k=k,
                                                        lambda_1=lambda_1, lambda_2=lambda_2, monitor=monitor,
-                                                       centered=centered, offset_rate=offset_rate)
+                                                       centered=centered, offset_rate=offset_rate,
+                                                       sparsity_target=sparsity_target, sparsity_cost=sparsity_cost,
+                                                       sparsity_decay=sparsity_decay, sparsity_weights=sparsity_weights)
         self._print('... pre-training the model')
         t_start = timeit.default_timer()
         if resume is None:

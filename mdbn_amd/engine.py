@@ -1027,6 +1027,28 @@ class HipEngine(object):
                    "mdbn_center_stats")
         return stats
 
+    # ------------------------------------------------------------------ sparsity target (mdbn_sparsity_*)
+    def sparsity_activity(self, scratch, B, q, v_mean, rate):
+        """Slide the activity estimate ``q`` [H] (device vector, updated IN PLACE) towards the column means of ph_mean of the
+        step that filled ``scratch`` (rows 0..B-1 of its P2: a ``cd_step(keep_f32=True)``) by ``rate`` in (0, 1]; 1 sets it
+        to those means.  ``v_mean`` [V]: receives the column means of v0 (rows 0..B-1 of V2); None: the hidden half alone,
+        ``scratch.V2`` is not looked at (mdbn_sparsity_activity)."""
+        P2 = scratch.P2
+        V2 = scratch.V2 if v_mean is not None else None
+        _lib.check(self.lib.mdbn_sparsity_activity(self.ctx, self._stream(), self._p(P2), P2.stride(0), self._p(V2),
+                                                   V2.stride(0) if V2 is not None else 0, int(B),
+                                                   V2.shape[1] if V2 is not None else 0, P2.shape[1], float(rate),
+                                                   self._p(q), self._p(v_mean)), "mdbn_sparsity_activity")
+
+    def sparsity_stats(self, stats, V, H, ldv, ldh, q, v_mean, target, w_scale, b_scale):
+        """The sparsity penalty's additions to the packed statistics, IN PLACE (mdbn_sparsity_stats): with t = target - q,
+        S += w_scale v_mean t', s_h += b_scale t; ``w_scale`` = cost * batch_size (0: S is not touched, ``v_mean`` may be
+        None), ``b_scale`` = cost * n_rows."""
+        _lib.check(self.lib.mdbn_sparsity_stats(self.ctx, self._stream(), self._p(stats), int(V), int(H), int(ldv), int(ldh),
+                                                self._p(q), self._p(v_mean), float(target), float(w_scale), float(b_scale)),
+                   "mdbn_sparsity_stats")
+        return stats
+
     # ------------------------------------------------------------------ monitoring helpers (all HIP)
     def round_flip(self, x, flip_col=-1):
         """tensor.round(x) with column ``flip_col`` replaced by 1 - round(x) (rbm.py:428-436)."""

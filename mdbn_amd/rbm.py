@@ -46,16 +46,24 @@ class UpdatePlan(object):
     CD-k / PCD-k step needs, bound when ``get_cost_updates`` is called."""
 
     def __init__(self, rbm, lr, k, lambda_1, lambda_2, weightcost, batch_size, persistent, W0,
-                 symbolic_grad=False, centered=False, offset_rate=0.01):
+                 symbolic_grad=False, centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0,
+                 sparsity_decay=0.9, sparsity_weights=True):
         self.rbm, self.lr, self.k = rbm, lr, int(k)
         self.lambda_1, self.lambda_2, self.weightcost = lambda_1, lambda_2, weightcost
         self.batch_size, self.persistent, self.W0 = batch_size, persistent, W0
         # compute_symbolic_grad (rbm.py:378-390): negative data = nv_samples[-1], no weight-cost
         # term, true means (the batch_size argument is not used)
         self.symbolic_grad = bool(symbolic_grad)
-        # centred gradient (StepFunction._centered_step): the statistics are referred to the layer's running offsets
+        # centred gradient (StepFunction._statistics_step): the statistics are referred to the layer's running offsets
         # rbm.v_offset / rbm.h_offset, which slide towards the batch means by offset_rate per step
         self.centered, self.offset_rate = bool(centered), float(offset_rate)
+        # sparsity target (StepFunction._statistics_step): a penalty of sparsity_cost drives the layer's running estimate
+        # rbm.h_activity of every hidden unit's mean activation towards sparsity_target; sparsity_weights=False: through the
+        # hidden biases only
+        self.sparse = sparsity_target is not None and float(sparsity_cost) > 0.0
+        self.sparsity_target = None if sparsity_target is None else float(sparsity_target)
+        self.sparsity_cost, self.sparsity_decay = float(sparsity_cost), float(sparsity_decay)
+        self.sparsity_weights = bool(sparsity_weights)
 
 
 class LazyCost(object):
@@ -79,6 +87,9 @@ class LazyCost(object):
     def item(self):
         return float(self)
 
+
+# What engine.sparsity_activity reads of a CD step's scratch, for hidden means that no CD step made (RBM.hidden_activity)
+ActivityRows = namedtuple("ActivityRows", "P2")
 
 # The rows one call trains on: the matrix and the index tensor of THIS rank's rows (None: all of ``data``), the size of the whole
 # minibatch, the rank's rows [lo, hi) of it, and whether ``data`` is a buffer of a HostFeed (to be handed back).
@@ -214,6 +225,10 @@ class StepFunction(object):
         if p.centered and self.group is not None and self.group.world_size > 1:
             raise NotImplementedError("centered=True on a data-parallel group of %d ranks: the offsets need the means of the "
                                       "whole minibatch in the all-reduce, which is not built yet" % self.group.world_size)
+        if p.sparse and self.group is not None and self.group.world_size > 1:
+            raise NotImplementedError("a sparsity target on a data-parallel group of %d ranks: the activity estimate needs "
+                                      "the means of the whole minibatch in the all-reduce, which is not built yet"
+                                      % self.group.world_size)
         self._pending = None                # Pending: the deferred half of the last overlapped step
         self._feed = None                   # HostFeed of a host-resident table, made by its first announcement or step
         self._n_calls = 0
@@ -224,6 +239,7 @@ class StepFunction(object):
         # update reads them a whole call later, so another step function of the same shape (two
         # equal-sized modalities, alternating layers) must not share them
         self._stats_slots = [None, None]
+        self._v_mean = None                 # [V] means of v0 of the current minibatch (a sparse step with sparsity_weights)
         self._fast = []                     # warm: [engine.StepCache] of the previous single-device call (cd_train_step_cached)
         # nan_guard: check cost and parameters for NaN / Inf after every call (synchronises; what the
         # reference's commented-out NanGuardMode would do, rbm.py:542-543, dbn.py:311)
@@ -373,8 +389,8 @@ class StepFunction(object):
         batch_size = p.batch_size if (p.batch_size is not None and not p.symbolic_grad) else mb.n_global
         step = self.rbm._take_step()
         distributed = self.group is not None and self.group.world_size > 1
-        if p.centered:
-            return self._centered_step(mb, step, lr, momentum, batch_size, next_indexes)
+        if p.centered or p.sparse:
+            return self._statistics_step(mb, step, lr, momentum, batch_size, next_indexes)
         if not distributed and p.persistent is None and mb.hi > mb.lo:
             return self._single_device_step(mb, step, lr, momentum, batch_size, next_indexes)
         return self._group_step(mb, step, lr, momentum, batch_size, next_indexes, distributed)
@@ -446,12 +462,19 @@ class StepFunction(object):
             self._check_finite(cost if cost is not None else out)
         return cost if cost is not None else out
 
-    def _centered_step(self, mb, step, lr, momentum, batch_size, next_indexes):
-        """The step with the centred gradient (Melchior et al. 2016, Algorithm 1), CD or PCD on one device: the statistics
-        are materialised, the offsets slide towards the means of v0 and ph_mean of this minibatch (the first step of a layer
-        sets them to those means), the statistics are corrected for the offsets in place -- S' = S - mu s_h' - s_v lam',
-        s_v' = s_v - rho S' lam, s_h' = s_h - rho S'^T mu, rho = n_rows / batch_size -- and the unchanged update rule runs
-        on them."""
+    def _statistics_step(self, mb, step, lr, momentum, batch_size, next_indexes):
+        """The step in the order statistics, transforms, update -- CD or PCD on one device: the statistics are materialised
+        (with the float32 copies of v0 / ph_mean in the scratch), transformed in place, and the unchanged update rule runs on
+        them.
+
+        Sparsity target (Hinton's guide, section 11): the layer's activity estimate q slides towards the means of ph_mean
+        of this minibatch (the first sparse step of a layer sets it to those means), then with t = target - q,
+        s_h += cost n_rows t and, unless sparsity_weights is off, S += cost batch_size <v0> t'.
+
+        Centred gradient (Melchior et al. 2016, Algorithm 1), after the sparsity transform: the offsets slide towards the
+        means of v0 and ph_mean of this minibatch (the first step of a layer sets them to those means), the statistics are
+        corrected for the offsets -- S' = S - mu s_h' - s_v lam', s_v' = s_v - rho S' lam, s_h' = s_h - rho S'^T mu,
+        rho = n_rows / batch_size."""
         p, rbm, eng = self.plan, self.rbm, self.engine
         data = mb.data
         persistent = None
@@ -467,12 +490,26 @@ class StepFunction(object):
         self._n_calls += 1
         _, scratch = eng.cd_step(data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, rbm.gauss, p.k,
                                  self._rng_addr(step, mb.lo), persistent=persistent, stats=stats, keep_f32=True)
-        first = rbm.v_offset is None
-        if first:
-            rbm.v_offset = SharedArray(None, engine=eng, _tensor=eng.alloc_vector(V))
-            rbm.h_offset = SharedArray(None, engine=eng, _tensor=eng.alloc_vector(H))
-        eng.center_offsets(scratch, mb.n_global, rbm.v_offset.tensor, rbm.h_offset.tensor, 1.0 if first else p.offset_rate)
-        eng.center_stats(stats, V, H, ldv, ldh, rbm.v_offset.tensor, rbm.h_offset.tensor, float(mb.n_global) / float(batch_size))
+        if p.sparse:
+            first = rbm.h_activity is None
+            if first:
+                rbm.h_activity = SharedArray(None, engine=eng, _tensor=eng.alloc_vector(H))
+            v_mean = None
+            if p.sparsity_weights:
+                if self._v_mean is None:
+                    self._v_mean = eng.alloc_vector(V)
+                v_mean = self._v_mean
+            eng.sparsity_activity(scratch, mb.n_global, rbm.h_activity.tensor, v_mean, 1.0 if first else 1.0 - p.sparsity_decay)
+            eng.sparsity_stats(stats, V, H, ldv, ldh, rbm.h_activity.tensor, v_mean, p.sparsity_target,
+                               p.sparsity_cost * float(batch_size) if p.sparsity_weights else 0.0,
+                               p.sparsity_cost * float(mb.n_global))
+        if p.centered:
+            first = rbm.v_offset is None
+            if first:
+                rbm.v_offset = SharedArray(None, engine=eng, _tensor=eng.alloc_vector(V))
+                rbm.h_offset = SharedArray(None, engine=eng, _tensor=eng.alloc_vector(H))
+            eng.center_offsets(scratch, mb.n_global, rbm.v_offset.tensor, rbm.h_offset.tensor, 1.0 if first else p.offset_rate)
+            eng.center_stats(stats, V, H, ldv, ldh, rbm.v_offset.tensor, rbm.h_offset.tensor, float(mb.n_global) / float(batch_size))
         cost, cost_scale = self._pcd_monitor(mb, stats, False) if p.persistent is not None else \
             (None, self._cost_scale(mb.n_global))
         self._rows_consumed(mb, next_indexes)
@@ -633,6 +670,8 @@ class RBM(object):
         self._resume_W0 = None                 # ... restored from a checkpoint, consumed by the next one
         self.v_offset = self.h_offset = None   # running means of the centred gradient (SharedArray [V] / [H]; optimiser state,
                                                # like the speeds: None until the first centred step)
+        self.h_activity = None                 # running mean activation of the hidden units under a sparsity target
+                                               # (SharedArray [H]; optimiser state: None until the first sparse step)
         self.bit_i_idx = 0                     # rbm.py:425
         self._rng_step = 0
         self._n_updates = 0
@@ -751,6 +790,24 @@ class RBM(object):
         pre, mean, _ = self.engine.propup(as_tensor(vis, self.engine), self.W.tensor, self.hbias.tensor,
                                           want_sample=False)
         return [self._wrap(pre), self._wrap(mean)]
+
+    def hidden_activity(self, data, chunk_rows=4096):
+        """Mean of p(h = 1 | v) over all rows of ``data`` for every hidden unit: float32 [n_hidden], computed on the device
+        -- what a sparsity target (``get_cost_updates``) steers.  ``data`` goes up ``chunk_rows`` rows at a time; each chunk's
+        column means are folded into one accumulator at rate n_chunk / n_seen (``engine.sparsity_activity``), which is the
+        exact running mean.  No random number is consumed."""
+        eng = self.engine
+        x = as_tensor(data, eng)
+        if x.shape[0] < 1:
+            raise ValueError("hidden_activity needs at least one row")
+        q = eng.alloc_vector(self.n_hidden)
+        seen, step = 0, max(1, int(chunk_rows))
+        for lo in range(0, x.shape[0], step):
+            rows = x[lo:lo + step]
+            mean = eng.propup(rows, self.W.tensor, self.hbias.tensor, want_pre=False, want_sample=False)[1]
+            seen += rows.shape[0]
+            eng.sparsity_activity(ActivityRows(mean), rows.shape[0], q, None, float(rows.shape[0]) / float(seen))
+        return numpy.asarray(eng.to_numpy(q), dtype=numpy.float32)
 
     def sample_h_given_v(self, v0_sample):
         ''' [pre_sigmoid_h1, h1_mean, h1_sample] (rbm.py:201-213) '''
@@ -974,7 +1031,8 @@ class RBM(object):
 
     # ------------------------------------------------------------------ CD-k / PCD-k
     def get_cost_updates(self, lr=0.1, k=1, lambda_1=0.0, lambda_2=0.0, weightcost=0.0,
-                         batch_size=None, persistent=None, symbolic_grad=False, centered=False, offset_rate=0.01):
+                         batch_size=None, persistent=None, symbolic_grad=False, centered=False, offset_rate=0.01,
+                         sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         """One step of CD-k or PCD-k (rbm.py:258-376).  Returns ``(cost, updates)``; pass
         ``updates`` to ``mdbn_amd.function`` to obtain the step function.
 
@@ -983,7 +1041,22 @@ class RBM(object):
         ``centered``: the centred gradient (Montavon & Mueller 2012; Melchior et al. 2016) -- visible and hidden units are
         referred to the running means ``self.v_offset`` / ``self.h_offset`` of the data and of ph_mean before the statistics
         are formed; the offsets slide by ``offset_rate`` per step (the first centred step sets them to its batch means).
-        The model and its parameters (W, vbias, hbias) keep their meaning; the offsets are optimiser state."""
+        The model and its parameters (W, vbias, hbias) keep their meaning; the offsets are optimiser state.
+        ``sparsity_target`` p in (0, 1) with ``sparsity_cost`` c > 0: a penalty that drives every hidden unit's mean
+        activation towards p (Lee et al. 2008; Nair & Hinton 2009; Hinton's guide, section 11).  ``self.h_activity`` q is the
+        running estimate of those means -- the first sparse step sets it to the means of ph_mean over its minibatch,
+        afterwards q += (1 - ``sparsity_decay``) (mean - q) -- and the step adds c (p - q_j) to the hidden-bias gradient and,
+        with ``sparsity_weights`` (False: the bias-only form of Lee et al.), c (p - q_j) <v_i> to the weight gradient.  q is
+        optimiser state; without a target, or at cost 0, the step is the plain one.  Composes with ``centered``."""
+        sparse = sparsity_target is not None and float(sparsity_cost) > 0.0
+        if sparsity_target is not None and not 0.0 < float(sparsity_target) < 1.0:
+            raise ValueError("sparsity_target must lie in (0, 1), got %r" % (sparsity_target,))
+        if not float(sparsity_cost) >= 0.0:
+            raise ValueError("sparsity_cost must not be negative, got %r" % (sparsity_cost,))
+        if not 0.0 <= float(sparsity_decay) < 1.0:
+            raise ValueError("sparsity_decay must lie in [0, 1), got %r" % (sparsity_decay,))
+        if sparse and symbolic_grad:
+            raise NotImplementedError("a sparsity target with symbolic_grad=True is not supported")
         if centered and symbolic_grad:
             raise NotImplementedError("centered=True with symbolic_grad=True is not supported")
         if centered and not 0.0 < float(offset_rate) <= 1.0:
@@ -1011,7 +1084,9 @@ class RBM(object):
                 t.copy_(persistent.tensor)
                 persistent.tensor = t
         updates = UpdatePlan(self, lr, k, lambda_1, lambda_2, weightcost, batch_size, persistent, W0,
-                             symbolic_grad=symbolic_grad, centered=centered, offset_rate=offset_rate)
+                             symbolic_grad=symbolic_grad, centered=centered, offset_rate=offset_rate,
+                             sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
+                             sparsity_weights=sparsity_weights)
         cost = CostHandle('pseudo_likelihood' if persistent is not None else 'reconstruction')
         return cost, updates
 
@@ -1040,13 +1115,15 @@ class RBM(object):
     def training(self, train_set_x, validation_set_x, training_epochs, batch_size=10,
                  learning_rate=0.1, k=1, initial_momentum=0.0, final_momentum=0.0,
                  weightcost=0.0, lambda_2=0.0, persistent=True, display_fn=None, graph_output=False, tempering=None,
-                 centered=False, offset_rate=0.01):
+                 centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9,
+                 sparsity_weights=True):
         """rbm.py:484-520 (note: like the reference, ``lambda_2`` is accepted but not used).
 
         ``tempering=R`` (with ``persistent``): PCD whose negative chains are the beta = 1 replicas of ``batch_size``
         parallel-tempering ladders of R temperatures (Desjardins et al. 2010) -- every step is ``chains.run(1)``,
         ``chains.to_persistent``, the unchanged PCD step, ``chains.from_persistent``; the ladders stay in ``self.tempered``.
-        None: nothing changes.  ``centered`` / ``offset_rate``: the centred gradient (``get_cost_updates``)."""
+        None: nothing changes.  ``centered`` / ``offset_rate``: the centred gradient, ``sparsity_*``: the sparsity target
+        (``get_cost_updates``)."""
         if persistent:
             persistent_chain = shared(numpy.zeros((batch_size, self.n_hidden), dtype=numpy.float32),
                                       engine=self.engine)               # rbm.py:496-498
@@ -1054,7 +1131,9 @@ class RBM(object):
             persistent_chain = None
         cost, updates = self.get_cost_updates(lr=learning_rate, k=k, weightcost=weightcost,
                                               batch_size=batch_size, persistent=persistent_chain,
-                                              centered=centered, offset_rate=offset_rate)
+                                              centered=centered, offset_rate=offset_rate, sparsity_target=sparsity_target,
+                                              sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
+                                              sparsity_weights=sparsity_weights)
         step_hooks = None
         if tempering is not None:
             if not persistent:
@@ -1162,12 +1241,15 @@ class GRBM(RBM):
     def training(self, train_set_x, validation_set_x, training_epochs, batch_size=10,
                  learning_rate=0.01, k=1, initial_momentum=0.0, final_momentum=0.0,
                  weightcost=0.0, lambda_1=0.0, lambda_2=0.1, persistent=False,
-                 display_fn=None, graph_output=False, centered=False, offset_rate=0.01):
+                 display_fn=None, graph_output=False, centered=False, offset_rate=0.01, sparsity_target=None,
+                 sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         """rbm.py:701-728: always CD (``persistent`` is ignored, as in the reference).  ``centered`` / ``offset_rate``: the
-        centred gradient (``get_cost_updates``)."""
+        centred gradient, ``sparsity_*``: the sparsity target (``get_cost_updates``)."""
         cost, updates = self.get_cost_updates(lr=learning_rate, k=k, lambda_1=lambda_1,
                                               lambda_2=lambda_2, weightcost=weightcost,
-                                              batch_size=batch_size, centered=centered, offset_rate=offset_rate)
+                                              batch_size=batch_size, centered=centered, offset_rate=offset_rate,
+                                              sparsity_target=sparsity_target, sparsity_cost=sparsity_cost,
+                                              sparsity_decay=sparsity_decay, sparsity_weights=sparsity_weights)
         return self.learn_model(train_set_x=train_set_x, validation_set_x=validation_set_x,
                                 training_epochs=training_epochs, batch_size=batch_size,
                                 initial_momentum=initial_momentum, final_momentum=final_momentum,
