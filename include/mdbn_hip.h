@@ -666,6 +666,44 @@ int  mdbn_sparsity_activity(mdbn_ctx *ctx, void *stream, const float *ph, int64_
 int  mdbn_sparsity_stats(mdbn_ctx *ctx, void *stream, float *stats, int64_t V, int64_t H, int64_t ldv, int64_t ldh,
                          const float *q, const float *v_mean, float target, float w_scale, float b_scale);
 
+/* Up-down fine-tuning of a DBN (Hinton, Osindero & Teh 2006, contrastive wake-sleep): the delta rules of a directed layer
+ * whose recognition weights W (upwards) and generative weights G (downwards) have been untied.  Both rules are CD statistics
+ * with chosen operands, applied by the unchanged update rule (src/rbm.py:347-365) that `upd` describes: upd->stats and
+ * upd->cost_out are ignored, upd->phase must be 0, and the bias half that a rule does not own must be NULL.
+ *
+ * mdbn_updown_gen_step (upd->W = G [V, ldh], upd->W_speed its speed, upd->vbias / vbias_speed the generative bias;
+ * upd->hbias = upd->hbias_speed = NULL): with x_lo [n, ldv] the layer's input and x_hi [n, ldh] the state inferred above it,
+ *   g = act(x_hi G^T + vbias)   (sigmoid; gauss = 1: the linear mean),   S = (x_lo - g)^T x_hi,   s_v = sum_r (x_lo - g),
+ * the gradient of sum_r log p(x_lo | x_hi) (Bernoulli and unit-variance Gaussian alike); S is divided by upd->batch_size and
+ * s_v by upd->n_rows.  g is formed from the parameters as they are on entry.  cost_out (nullable, device):
+ * upd->cost_scale * sum_r -log p(x_lo | x_hi), the cross-entropy x softplus(-pre) + (1 - x) softplus(pre) summed over the
+ * units, or with gauss half the squared error.
+ * mdbn_updown_rec_step (upd->W = W, upd->hbias / hbias_speed the recognition bias; upd->vbias = upd->vbias_speed = NULL): with
+ * y_lo [n, ldv], y_hi [n, ldh] a dreamt pair of states and r = sigmoid(y_lo W + hbias) [n, ldh] (mdbn_propup_sample),
+ *   S = y_lo^T (y_hi - r),   s_h = sum_r (y_hi - r).
+ *
+ * path: 0 = by shape, 2 = composed from the launchers of the CD step on any shape -- the operands stacked as
+ * V2 = [x_lo; g], P2 = [x_hi; -x_hi] (V2 = [y_lo; y_lo], P2 = [y_hi; -r]), mdbn_propdown_sample for g, mdbn_cd_stats,
+ * mdbn_apply_update with a throw-away vector in place of the bias half that must not move --, 1 = one pass over the matrix:
+ * n <= 32 rows and ldh <= 512 (MDBN_EINVAL elsewhere; path 0 then takes the composed path).  The one-pass generative kernel
+ * holds whole rows of G per workgroup, forms its slice of g completely (float32 fmaf chains, never bf16), the error, the rows
+ * of S in registers and applies the rule at once: G and its speed are read and written once, S is never stored; it neither
+ * reads nor writes the pad columns H..ldh-1 of G, of the speed and of x_hi.  The one-pass recognition update is the rank-2n
+ * update kernel of the thin-batch CD step on the stacked operands.  upd->W_planes, where given, are rewritten with the split
+ * of the new matrix on every path.  No atomics, every sum in a fixed order: two runs agree bit for bit.
+ *
+ * Bad arguments (a size < 1 or > 2^24, a null or misaligned matrix, a leading dimension below its width or no multiple of 4,
+ * a bias half that should be NULL or is missing, divisors <= 0, phase != 0, path 1 on a shape it does not serve, a short
+ * workspace) return MDBN_EINVAL without a launch: no output is touched. */
+int  mdbn_updown_gen_workspace_bytes(mdbn_ctx *ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int path,
+                                     int64_t *bytes);
+int  mdbn_updown_gen_step(mdbn_ctx *ctx, void *stream, const float *x_lo, const float *x_hi, int64_t n, int gauss,
+                          const mdbn_update_args *upd, float *cost_out, int path, void *workspace, int64_t workspace_bytes);
+int  mdbn_updown_rec_workspace_bytes(mdbn_ctx *ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int path,
+                                     int64_t *bytes);
+int  mdbn_updown_rec_step(mdbn_ctx *ctx, void *stream, const float *y_lo, const float *y_hi, const float *r, int64_t n,
+                          const mdbn_update_args *upd, int path, void *workspace, int64_t workspace_bytes);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)) (the float32 softplus terms summed in

@@ -175,6 +175,24 @@ def log_likelihood_bound(nets, joint, inputs, n_samples=64, **kw):
     return stack_bound(list(zip(nets, inputs)), joint, n_samples=n_samples, **kw)
 
 
+def fine_tune(nets, joint, inputs, epochs, batch_size=20, *, lr, k=1, momentum=0.0, weightcost=0.0, lambda_1=0.0, lambda_2=0.0,
+              top_lr=None, on_epoch=None, path="auto"):
+    """Up-down fine-tuning of the whole multimodal model (``DBN.fine_tune`` over the structure ``log_likelihood_bound`` walks;
+    ``updown.py``): every layer of every modality DBN and the joint DBN's lower layers are directed and get generative weights
+    of their own, the joint DBN's last RBM is the top.  The wake pass concatenates the sampled modality tops in the order of
+    ``nets``, the sleep pass splits the dream back by the same column blocks.  ``inputs``: one data matrix per modality, a list
+    or a dict {modality index: matrix}.  The epoch order comes from ``joint.shuffle_rng``.  Returns the per-epoch record
+    ``[(sum over the modalities of the mean -log p(x_0 | x_1) per row, the top RBM's mean monitoring cost), ...]``."""
+    from . import updown
+    if isinstance(inputs, dict):
+        if set(inputs) != set(range(len(nets))):
+            raise ValueError("inputs must have exactly the keys 0 .. %d, got %r" % (len(nets) - 1, sorted(inputs, key=repr)))
+        inputs = [inputs[i] for i in range(len(nets))]
+    return updown.fine_tune(list(nets), joint, list(inputs), epochs, batch_size, lr=lr, k=k, momentum=momentum,
+                            weightcost=weightcost, lambda_1=lambda_1, lambda_2=lambda_2, top_lr=top_lr, on_epoch=on_epoch,
+                            path=path)
+
+
 def modality_log_likelihood(nets, joint, inputs, target, n_chains=64, n_betas=1000, path=0, base_data=None):
     """How well the joint layer predicts modality ``target`` from the others, in nats per row (Srivastava & Salakhutdinov
     2012): log p(block_target | the other blocks) under the joint DBN's first RBM.

@@ -14,7 +14,7 @@ from .mlp import HiddenLayer
 from .rbm import RBM, GRBM, Scalar, ais_estimate, function
 from .dbn import DBN
 from .temper import TemperedChains
-from . import MDBN, checkpoint, dist, utils
+from . import MDBN, checkpoint, dist, updown, utils
 from .MDBN import log_likelihood_bound, modality_log_likelihood
 
 __all__ = ["modality_log_likelihood", "log_likelihood_bound", "MdbnError", "HipEngine", "RngAddr", "get_engine", "set_engine", "RandomStreams",

@@ -131,6 +131,10 @@ SIGNATURES = {
     "mdbn_center_stats": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _i64],
     "mdbn_sparsity_activity": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp],
     "mdbn_sparsity_stats": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _f32],
+    "mdbn_updown_gen_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
+    "mdbn_updown_gen_step": [_vp, _vp, _vp, _vp, _i64, _i32, C.POINTER(UpdateArgs), _vp, _i32, _vp, _i64],
+    "mdbn_updown_rec_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
+    "mdbn_updown_rec_step": [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(UpdateArgs), _i32, _vp, _i64],
     "mdbn_round_flip": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
     "mdbn_pl_cost": [_vp, _vp, _vp, _vp, _i64, _i64, _vp],
     "mdbn_recon_cost": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64],

@@ -58,7 +58,8 @@ def _climb(net, x, n_sampled, div, row_offset, steps, keep):
         r = net.rbm_layers[l]
         mean = eng.propup(x, r.W.tensor, r.hbias.tensor, want_pre=False, want_sample=False)[1]
         sample, entropy = eng.sample_replicas(mean, div, RngAddr(r.theano_rng.seed, r.stream_id, steps[id(r)], 0, row_offset))
-        directed = _host64(eng.propdown_row_loglik(sample, r.W.tensor, r.vbias.tensor, x, r.gauss, target_div=div))
+        # (the directed term is the generative model's: the generative weights of a layer untied by fine-tuning)
+        directed = _host64(eng.propdown_row_loglik(sample, r.down_W, r.vbias.tensor, x, r.gauss, target_div=div))
         entropy = _host64(entropy)
         term = directed + numpy.repeat(entropy, div)
         total = term if total is None else total + term

@@ -40,6 +40,8 @@ def _resume_state(dbn):
             out[-1].update(v_offset=r.v_offset.get_value(), h_offset=r.h_offset.get_value())
         if r.h_activity is not None:            # sparsity target: the running activity estimate
             out[-1].update(h_activity=r.h_activity.get_value())
+        if r.W_gen is not None:                 # up-down fine-tuning: the untied generative weights and their speed
+            out[-1].update(W_gen=r.W_gen.get_value(), W_gen_speed=r.W_gen_speed.get_value())
     return out
 
 
@@ -100,6 +102,11 @@ def load_network(input_file, names=None, engine=None):
                     r.h_offset = shared(numpy.asarray(st['h_offset'], dtype=numpy.float32), name='h_offset', engine=r.engine)
                 if st.get('h_activity') is not None:
                     r.h_activity = shared(numpy.asarray(st['h_activity'], dtype=numpy.float32), name='h_activity', engine=r.engine)
+                if st.get('W_gen') is not None:
+                    ld = r.W.tensor.stride(0)       # (the layout of W: the delta rules walk both)
+                    r.W_gen = shared(numpy.asarray(st['W_gen'], dtype=numpy.float32), name='W_gen', engine=r.engine, ld=ld)
+                    r.W_gen_speed = shared(numpy.asarray(st['W_gen_speed'], dtype=numpy.float32), name='W_gen_speed',
+                                           engine=r.engine, ld=ld)
         if name + '_trainer' in npz.files:
             dbn.trainer_state = npz[name + '_trainer'][0]
         out[name] = dbn

@@ -166,7 +166,8 @@ class DBN(object):
         for i in range(top, -1, -1):
             r = self.rbm_layers[i]
             # (the propagation call wants an address for the sample it also offers; the mean does not depend on it)
-            x = self.engine.propdown(x, r.W.tensor, r.vbias.tensor, gauss=r.gauss, add_noise=False,
+            # (a layer untied by fine_tune goes down through its generative weights)
+            x = self.engine.propdown(x, r.down_W, r.vbias.tensor, gauss=r.gauss, add_noise=False,
                                      rng=RngAddr(r.theano_rng.seed, r.stream_id, 0, 0, 0))[1]
         return self.engine.to_numpy(x)
 
@@ -188,6 +189,25 @@ class DBN(object):
         consumes ONE RNG step of its own RBM.  A one-layer network draws nothing and gives ``log_likelihood``."""
         from .bound import stack_bound
         return stack_bound([(self, data)], None, n_samples=n_samples, log_z=log_z, chunk_rows=chunk_rows, trace=trace, **ais)
+
+    def fine_tune(self, train_set_x, epochs, batch_size=20, *, lr, k=1, momentum=0.0, weightcost=0.0, lambda_1=0.0,
+                  lambda_2=0.0, top_lr=None, on_epoch=None, path="auto"):
+        """Up-down fine-tuning of the whole stack after ``training`` (Hinton, Osindero & Teh 2006, contrastive wake-sleep;
+        ``updown.py``): the layers below the top RBM are untied -- ``rbm.W_gen``, the generative weights, start as a copy of W
+        --, every minibatch is sampled upwards (wake), the top RBM takes a CD-``k`` step on what arrives and dreams downwards
+        from its last visible sample (sleep), and local delta rules train the generative weights on the wake states and the
+        recognition weights (W, shared with ``sigmoid_layers``) on the dream, all by the engine's update rule (``lr``,
+        ``momentum``, ``weightcost``, ``lambda_1``, ``lambda_2``; ``top_lr``: the top RBM's rate, default ``lr``).  Needs
+        ``n_layers >= 2`` (ValueError) and one device (NotImplementedError under a process group of several ranks).  The epoch
+        order comes from ``shuffle_rng``.  Returns ``[(mean -log p(x_0 | x_1) per row under the wake pass, the top RBM's mean
+        monitoring cost), ...]`` per epoch; ``on_epoch(epoch, record)`` is called after each.  ``path``: "auto", or "composed" /
+        "fused" to force how the delta rules run (``HipEngine.updown_gen_step``).  Afterwards ``down_pass``, the directed terms
+        of ``log_likelihood_bound`` and ``MDBN.impute_modalities`` go through ``W_gen``; ``get_output`` and the RBM-level
+        methods keep to W, so a lower layer's own free energy and AIS then describe its recognition RBM, not the model."""
+        from . import updown
+        return updown.fine_tune([self], None, [train_set_x], epochs, batch_size, lr=lr, k=k, momentum=momentum,
+                                weightcost=weightcost, lambda_1=lambda_1, lambda_2=lambda_2, top_lr=top_lr, on_epoch=on_epoch,
+                                path=path)
 
     def _layer_input_fn(self, i, train_set_x):
         """Input matrix of RBM i: the data for i == 0, else the activations of layer i-1

@@ -1049,6 +1049,80 @@ class HipEngine(object):
                    "mdbn_sparsity_stats")
         return stats
 
+    # ------------------------------------------------------------------ up-down fine-tuning (mdbn_updown_*)
+    UPDOWN_PATHS = {"auto": 0, "fused": 1, "composed": 2}
+
+    def _updown_call(self, kind, n, W, W_speed, bias, bias_speed, ldv, rule, cost_scale, path):
+        """What the two delta-rule calls share: the update struct with the half that must not move left NULL, the workspace
+        the library asks for under ``path``, the planes of the matrix written.  Returns ``(u, workspace, path number)``."""
+        lr, lambda_1, lambda_2, weightcost, momentum, batch_size, n_rows = rule
+        V, H = W.shape
+        if W_speed.stride(0) != W.stride(0):
+            raise _lib.MdbnError("a weight matrix and its speed must share the leading dimension")
+        p = self.UPDOWN_PATHS[path]
+        u = _lib.UpdateArgs()
+        u.W, u.W_speed = W.data_ptr(), W_speed.data_ptr()
+        if kind == "gen":
+            u.vbias, u.vbias_speed = bias.data_ptr(), bias_speed.data_ptr()
+        else:
+            u.hbias, u.hbias_speed = bias.data_ptr(), bias_speed.data_ptr()
+        u.V, u.H, u.ldv, u.ldh = V, H, int(ldv), W.stride(0)
+        u.lr, u.lambda_1, u.lambda_2 = float(lr), float(lambda_1), float(lambda_2)
+        u.weightcost, u.momentum = float(weightcost), float(momentum)
+        u.batch_size, u.n_rows, u.cost_scale = float(batch_size), float(n_rows), float(cost_scale)
+        wp, _ = self.w_planes(W)
+        u.W_planes = wp.data_ptr() if wp is not None else None    # kept in step with the matrix by every path that writes it
+        nbytes = C.c_int64()
+        if kind == "gen":
+            _lib.check(self.lib.mdbn_updown_gen_workspace_bytes(self.ctx, int(n), V, H, int(ldv), W.stride(0), p, C.byref(nbytes)),
+                       "mdbn_updown_gen_workspace_bytes")
+        else:
+            _lib.check(self.lib.mdbn_updown_rec_workspace_bytes(self.ctx, int(n), V, H, int(ldv), W.stride(0), p, C.byref(nbytes)),
+                       "mdbn_updown_rec_workspace_bytes")
+        ws = getattr(self, "_updown_ws", None)
+        if ws is None or ws.numel() * 4 < nbytes.value:
+            ws = self._updown_ws = torch.empty(nbytes.value // 4 + 64, dtype=torch.float32, device=self.device)
+        return u, ws, p
+
+    def updown_gen_step(self, x_lo, x_hi, G, G_speed, vbias, vbias_speed, gauss, lr, lambda_1, lambda_2, weightcost, momentum,
+                        batch_size, n_rows, cost_scale=1.0, path="auto"):
+        """The generative delta rule of an untied layer (mdbn_updown_gen_step): g = act(x_hi G^T + vbias) from the parameters as
+        they are, S = (x_lo - g)^T x_hi, s_v = sum_r (x_lo - g), and the update rule on G / G_speed / vbias / vbias_speed.
+        Returns ``cost_scale`` * sum_r -log p(x_lo | x_hi) (up to the Gaussian constant) as a 0-d device tensor.  ``path``:
+        "auto", "fused" (one pass over G: n <= 32, ld <= 512; refused elsewhere) or "composed"."""
+        x_lo = self.as_matrix(x_lo)
+        n, V = (int(v) for v in x_lo.shape)
+        if tuple(G.shape) != (V, x_hi.shape[1]) or x_hi.shape[0] != n:
+            raise ValueError("x_lo %r, x_hi %r and G %r do not fit" % (tuple(x_lo.shape), tuple(x_hi.shape), tuple(G.shape)))
+        x_hi = self._padded(x_hi, n, G.shape[1], G.stride(0))      # the C-ABI reads x_hi with G's ld
+        u, ws, p = self._updown_call("gen", n, G, G_speed, vbias, vbias_speed, x_lo.stride(0),
+                                     (lr, lambda_1, lambda_2, weightcost, momentum, batch_size, n_rows), cost_scale, path)
+        cost = self._next_cost_slot()
+        _lib.check(self.lib.mdbn_updown_gen_step(self.ctx, self._stream(), self._p(x_lo), self._p(x_hi), n, int(bool(gauss)),
+                                                 C.byref(u), self._p(cost), p, self._p(ws), ws.numel() * 4), "mdbn_updown_gen_step")
+        self._w_serial += 1
+        self._w_planes_written(G)
+        return cost
+
+    def updown_rec_step(self, y_lo, y_hi, r, W, W_speed, hbias, hbias_speed, lr, lambda_1, lambda_2, weightcost, momentum,
+                        batch_size, n_rows, path="auto"):
+        """The recognition delta rule of an untied layer (mdbn_updown_rec_step): S = y_lo^T (y_hi - r), s_h = sum_r (y_hi - r)
+        with r = sigmoid(y_lo W + hbias) given, and the update rule on W / W_speed / hbias / hbias_speed.  ``path`` as
+        ``updown_gen_step`` ("fused": the thin-batch step's one-pass update on the stacked operands)."""
+        y_lo = self.as_matrix(y_lo)
+        n, V = (int(v) for v in y_lo.shape)
+        H, ldh = int(W.shape[1]), W.stride(0)
+        if W.shape[0] != V or tuple(y_hi.shape) != (n, H) or tuple(r.shape) != (n, H):
+            raise ValueError("y_lo %r, y_hi %r, r %r and W %r do not fit" % (tuple(y_lo.shape), tuple(y_hi.shape), tuple(r.shape), tuple(W.shape)))
+        y_hi, r = self._padded(y_hi, n, H, ldh), self._padded(r, n, H, ldh)
+        u, ws, p = self._updown_call("rec", n, W, W_speed, hbias, hbias_speed, y_lo.stride(0),
+                                     (lr, lambda_1, lambda_2, weightcost, momentum, batch_size, n_rows), 1.0, path)
+        _lib.check(self.lib.mdbn_updown_rec_step(self.ctx, self._stream(), self._p(y_lo), self._p(y_hi), self._p(r), n, C.byref(u), p,
+                                                 self._p(ws), ws.numel() * 4), "mdbn_updown_rec_step")
+        self._w_serial += 1
+        self._w_planes_written(W)
+        return None
+
     # ------------------------------------------------------------------ monitoring helpers (all HIP)
     def round_flip(self, x, flip_col=-1):
         """tensor.round(x) with column ``flip_col`` replaced by 1 - round(x) (rbm.py:428-436)."""

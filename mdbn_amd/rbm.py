@@ -672,9 +672,17 @@ class RBM(object):
                                                # like the speeds: None until the first centred step)
         self.h_activity = None                 # running mean activation of the hidden units under a sparsity target
                                                # (SharedArray [H]; optimiser state: None until the first sparse step)
+        self.W_gen = self.W_gen_speed = None   # generative (top-down) weights of a layer untied by up-down fine-tuning
+                                               # (SharedArray [V, H] on W's leading dimension; None: tied, W serves both ways)
         self.bit_i_idx = 0                     # rbm.py:425
         self._rng_step = 0
         self._n_updates = 0
+
+    @property
+    def down_W(self):
+        """The matrix a directed top-down pass through this layer uses: ``W_gen`` once ``updown`` has untied the layer, else W.
+        The RBM's own methods (propdown, Gibbs chains, free energy, AIS) keep to W: they describe the recognition RBM."""
+        return self.W.tensor if self.W_gen is None else self.W_gen.tensor
 
     @property
     def Wt(self):
