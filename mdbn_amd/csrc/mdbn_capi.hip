@@ -2,161 +2,48 @@
 // planning, workspace carving and the launch sequence of one CD-k step.  No allocation,
 // no synchronisation: every entry point only enqueues kernels on the caller's stream.
 #include <hip/hip_runtime.h>
-#include "row_pool.h"
-#include <dlfcn.h>
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
 #include <cstdint>
-#include <deque>
 #include <initializer_list>
-#include <map>
-#include <mutex>
-#include <set>
-#include <thread>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
+#include "mdbn_capi_internal.h"
 #include "mdbn_kernels.h"
 #include "mdbn_small.h"
 #include "mdbn_thin.h"
 #include "mdbn_gchain.h"
-#include "mdbn_ais.h"
-#include "mdbn_clamp.h"
-#include "mdbn_temper.h"
-#include "mdbn_bound.h"
-#include "mdbn_center.h"
-#include "mdbn_sparsity.h"
-#include "mdbn_updown.h"
 
 using namespace mdbn;
+using namespace mdbn::capi;
 
-// Tuning knobs of ONE context (mdbn_set_option(ctx, ...) writes ctx->opt; a knob set on one context never changes what
-// another context of the process launches).  The option comments sit beside the g_opt_* names below, which read the
-// options of the context whose call is running on this thread (CtxScope).
-struct Options {
-    int gemm_bk = 0;
-    int x6_min_jobs = 48;
-    int x6_pw = 4;
-    int gemm_cw = 0;
-    int update_overlap = 0;
-    int fused_epilogue = 1;
-    int fused_update = 1;
-    int fused_finalize = 1;
-    int skinny_gemm = 1;
-    int skinny_fused_max_k = 1024;
-    int64_t skinny_max_macs = 32ll << 20;
-    int stream_x6 = 2;
-    int64_t stream_max_macs = (int64_t)1 << 30;
-    int stream_mi = 0;
-    int stream_ni = 0;
-    int gemm_bf16x6 = 3;
-    int small_fused = 1;
-    int thin_fused = 1;
-    int gchain = 0;
-    int gemm_planes = 1;
-    int planes_mfma = 16;
-    int early_w = 1;
-    int narrow_tiles = 1;
-    int slab_tail = 1;
-    int feed_copy_streams = 1;
-    int gather_ahead = 1;
-    int bf16_inputs = 0;
-    int64_t planes_min_work = (int64_t)1 << 30;
-    int comm_cus = 0;
-    int bal_blocks = 0;
-    int min_splitk = 128;
-    int epilogue_cw = 0;
-    int epilogue_threads = 0;
-    int small_fin_lanes = 0;
-};
-
-// Optional HIP-event timing of the GEMM launches (the dominant kernel), used by bench.py to
-// quote the roofline from the kernel's own average duration on the stream it runs on.
-struct GemmTiming {
-    bool enabled = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-    // per recorded launch: which GEMM it was and the work it issued (mdbn_kernel_timing_detail)
-    struct Meta { int kind; double alg_flop, pipe_flop; };
-    std::vector<Meta> meta;
-    size_t used = 0;
-};
-
-struct mdbn_ctx {
-    int device;
-    int num_cu;
-    Options opt;
-    GemmTiming timing;                  // mdbn_kernel_timing: per context
-    // mdbn_cd_forward -> mdbn_cd_statistics hand-over (host side only): the cost partials the chain's last visible pass left
-    int pending_n_cost = -1;
-    const void* pending_stats = nullptr;
-    void* comm = nullptr;      // ncclComm_t of mdbn_comm_init_rank (RCCL), or NULL
-    int comm_ranks = 0;
-    // side stream + events for mdbn_cd_train_step (memory-bound update work overlapped with the
-    // compute-bound statistics GEMM); created on first use
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // group-chain step (mdbn_gchain.hip): the flag words of its in-launch exchange ([GC_MAX_FLAGS] + one error word; made
-    // and zeroed on first use, written by that protocol only) and the sequence number of the next launch's first exchange
-    unsigned* gc_flags = nullptr;
-    unsigned gc_seq = 1;
-};
-
-
-// The options / timing records a library call reads are those of the context it was made on: every entry point that takes
-// a context opens a CtxScope; context-free entry points (mdbn_workspace_bytes, mdbn_planes_eligible, ...) see the defaults
-// of a fresh context.
+// The records behind CtxScope (mdbn_capi_internal.h): those of the context whose call is running on this thread
 static const Options g_default_options;
 static GemmTiming g_no_timing;                          // calls outside any context record nothing
 static thread_local const Options* t_opt = &g_default_options;
 static thread_local GemmTiming* t_timing = &g_no_timing;
 #define g_timing (*t_timing)
-struct CtxScope {
-    const Options* prev_opt; GemmTiming* prev_timing;
-    explicit CtxScope(mdbn_ctx* c) : prev_opt(t_opt), prev_timing(t_timing)
-    {
-        if (c) {
-            t_opt = &c->opt; t_timing = &c->timing;
-            set_epilogue_cw(c->opt.epilogue_cw); set_epilogue_threads(c->opt.epilogue_threads);
-            g_small_fin_lanes = c->opt.small_fin_lanes;
-        }
+
+namespace mdbn {
+namespace capi {
+CtxScope::CtxScope(mdbn_ctx* c) : prev_opt(t_opt), prev_timing(t_timing)
+{
+    if (c) {
+        t_opt = &c->opt; t_timing = &c->timing;
+        set_epilogue_cw(c->opt.epilogue_cw); set_epilogue_threads(c->opt.epilogue_threads);
+        g_small_fin_lanes = c->opt.small_fin_lanes;
     }
-    ~CtxScope() { t_opt = prev_opt; t_timing = prev_timing; }
-    CtxScope(const CtxScope&) = delete;
-    CtxScope& operator=(const CtxScope&) = delete;
-};
+}
+CtxScope::~CtxScope() { t_opt = prev_opt; t_timing = prev_timing; }
+}  // namespace capi
+}  // namespace mdbn
 
 namespace {
 
 thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIP_OK(expr)                                                                    \
-    do {                                                                                \
-        hipError_t _e = (expr);                                                         \
-        if (_e != hipSuccess)                                                           \
-            return fail(MDBN_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                        __FILE__, __LINE__);                                            \
-    } while (0)
-
-#define REQUIRE(cond, ...)                                 \
-    do {                                                   \
-        if (!(cond)) return fail(MDBN_EINVAL, __VA_ARGS__); \
-    } while (0)
 
 #define g_opt_gemm_bk (t_opt->gemm_bk)          // mdbn_set_option("gemm_bk"): 0 = auto, 32, 64
 #define g_opt_x6_min_jobs (t_opt->x6_min_jobs)     // mdbn_set_option("x6_min_jobs"): fewer 128x128-tile jobs than this keep the exact kernel (192 -> 48: 1024->256 and 512^3 at B = 512 -6%)
@@ -175,19 +62,7 @@ int fail(int code, const char* fmt, ...)
 #define g_opt_fused_update (t_opt->fused_update)
 // mdbn_set_option("fused_finalize"): ... and runs the bias statistics / cost / bias update inside that GEMM too
 #define g_opt_fused_finalize (t_opt->fused_finalize)
-constexpr int kTargetJobs = 256;       // one 8-wave tile job per CU (MI355X: 256 CUs)
 #define kMinSplitK (t_opt->min_splitk)     // >= 4 slices of BK = 32 per split (mdbn_set_option "gemm_min_splitk")
-
-inline int64_t ru4(int64_t x) { return (x + 3) & ~int64_t(3); }
-// Leading-dimension policy (mdbn_padded_ld).  Padding 1-KiB-multiple rows by 64 floats (to spread
-// a GEMM slice's rows over the L2 channels) gained ~10% in the isolated GEMM microbenchmark
-// (scripts/gemm_ldpad.py) but LOST 2% on the whole CD step (K1 42.3 vs 40.6 us, update 17.0 vs
-// 13.5 us, profiles r01e vs r01d), and does nothing for the streaming kernel of the mid-size layers either
-// (profiles/r05zc_ldpad.log), so the policy is plain round_up(cols, 4); every entry point
-// accepts any ld % 4 == 0, ld >= cols.
-inline int64_t padded_ld(int64_t cols) { return ru4(cols); }
-inline int64_t ru64(int64_t x) { return (x + 63) & ~int64_t(63); }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 struct Plan {
     int tiles_m, tiles_n, splitk, kchunk, bn, bk;
@@ -468,28 +343,6 @@ hipError_t timed_gemm(int la, int lb, const GemmArgs& g_in, hipStream_t s)
                         [&]() { return launch_gemm(la, lb, g, s); });
 }
 
-PhiloxKey make_key(const mdbn_rng& r, uint32_t draw)
-{
-    PhiloxKey k;
-    k.k0 = (uint32_t)r.seed;
-    k.k1 = (uint32_t)(r.seed >> 32) ^ r.stream_id;
-    k.step = r.step;
-    k.draw = draw;
-    k.row_offset = r.row_offset;
-    return k;
-}
-
-// carve-up of the caller's workspace
-struct Workspace {
-    float* slabs;
-    int64_t slab_floats;
-    float* cost_partials;
-    int64_t cost_floats;
-    float* colPpos;   // [row_groups][ldh]  4-row partial column sums of  ph_mean
-    float* colPneg;   // [row_groups][ldh]                                -nh_mean
-    float* colV;      // [row_groups][ldv]                                 v0 - nv_mean
-};
-
 struct WsSizes {
     int64_t slab, cost, colP, colV;
     int64_t total_bytes() const { return 4 * (ru64(slab) + ru64(cost) + ru64(colP) + ru64(colV)); }
@@ -563,138 +416,6 @@ WsSizes ws_sizes(int64_t B, int64_t V, int64_t H)
     }
     return s;
 }
-
-int carve(void* ws, int64_t bytes, int64_t B, int64_t V, int64_t H, Workspace& out, bool need_stats)
-{
-    REQUIRE(ws != nullptr && aligned16(ws), "workspace must be a 16-byte aligned device pointer");
-    const WsSizes s = ws_sizes(B, V, H);
-    float* p = reinterpret_cast<float*>(ws);
-    if (need_stats) {
-        if (bytes < s.total_bytes())
-            return fail(MDBN_ENOSPC, "workspace %lld bytes < %lld needed for B=%lld V=%lld H=%lld",
-                        (long long)bytes, (long long)s.total_bytes(), (long long)B, (long long)V, (long long)H);
-        out.slabs = p;            out.slab_floats = s.slab;  p += ru64(s.slab);
-        out.cost_partials = p;    out.cost_floats = s.cost;  p += ru64(s.cost);
-        out.colPpos = p;          out.colPneg = p + s.colP / 2;  p += ru64(s.colP);
-        out.colV = p;
-    } else {
-        // propagation only: a fixed cost region at the end, everything else is slabs
-        const int64_t floats = bytes / 4;
-        const int64_t cost = 1 << 16;
-        if (floats < cost + 4096)
-            return fail(MDBN_ENOSPC, "workspace %lld bytes is too small", (long long)bytes);
-        out.slabs = p;
-        out.slab_floats = (floats - cost) & ~int64_t(63);
-        out.cost_partials = p + out.slab_floats;
-        out.cost_floats = cost;
-        out.colPpos = out.colPneg = out.colV = nullptr;
-    }
-    return MDBN_OK;
-}
-
-// One affine map + activation over `rows` rows, chunked so the split-K slabs fit.
-//   up   (dir 0): x[rows, V] * W        -> [rows, H]   (bias = hbias)
-//   down (dir 1): x[rows, H] * W^T      -> [rows, V]   (bias = vbias)
-// The constructors take the operands of a pass; its outputs and options are assigned by name at the call site.
-struct Affine {
-    const float* x = nullptr; int64_t rows = 0, ldx = 0;
-    const float* W = nullptr; int64_t V = 0, H = 0, ldw = 0;
-    int dir = 0;
-    const float* bias = nullptr;
-    float* pre = nullptr; float* mean = nullptr; float* sample = nullptr; int64_t ldo = 0;
-    float mean_scale = 1.0f; int gauss = 0;
-    const float* target = nullptr; int64_t ld_target = 0;
-    bool want_cost = false;
-    const mdbn_rng* rng = nullptr; uint32_t draw = 0u;
-    float* colsum = nullptr; int colsum_kind = 0;
-    // x holds 0/1 samples written by our own epilogues (a Gibbs chain state): exactly representable
-    // in bf16, so the bf16x6 kernel needs one piece of it and three products instead of six
-    bool x_binary = false;
-    // up pass: the output rides on W's leading dimension
-    Affine(const float* x, int64_t rows, int64_t ldx, const float* W, int64_t V, int64_t H, int64_t ldw, const float* hbias)
-        : x(x), rows(rows), ldx(ldx), W(W), V(V), H(H), ldw(ldw), dir(0), bias(hbias), ldo(ldw) {}
-    // down pass
-    Affine(const float* x, int64_t rows, int64_t ldx, const float* W, int64_t V, int64_t H, int64_t ldw, const float* vbias,
-           int64_t ldo, int gauss) : x(x), rows(rows), ldx(ldx), W(W), V(V), H(H), ldw(ldw), dir(1), bias(vbias), ldo(ldo), gauss(gauss) {}
-};
-
-int run_affine(const Affine& a, const Workspace& ws, hipStream_t s, int* n_cost_out)
-{
-    const int64_t Kdim = a.dir == 0 ? a.V : a.H;
-    const int64_t Ndim = a.dir == 0 ? a.H : a.V;
-    int n_cost = 0;
-    int64_t r0 = 0;
-    while (r0 < a.rows) {
-        int64_t R = a.rows - r0;
-        Plan p = plan_forward(R, Ndim, Kdim, a.ldo);
-        bool fuse = false;
-        for (;;) {      // shrink the chunk until its slabs (unfused) and cost partials fit
-            fuse = g_opt_fused_epilogue && p.splitk == 1;
-            const bool slabs_fit = fuse || p.slab_floats(R, a.ldo) <= ws.slab_floats;
-            const int64_t need_cost = !a.want_cost ? 0 : fuse ? (int64_t)p.tiles_m * p.tiles_n : epilogue_blocks(R, a.ldo);
-            if (slabs_fit && n_cost + need_cost <= ws.cost_floats) break;
-            if (R <= 4) return fail(MDBN_ENOSPC, "workspace cannot hold one 4-row chunk");
-            R = std::max<int64_t>(4, (R / 2 + 3) & ~int64_t(3));
-            p = plan_forward(R, Ndim, Kdim, a.ldo);
-        }
-        GemmArgs g{};
-        g.A = a.x + r0 * a.ldx;  g.lda = a.ldx;
-        g.B = a.W;               g.ldb = a.ldw;
-        g.C = ws.slabs;          g.ldc = a.ldo;
-        g.slab_stride = R * a.ldo;
-        g.M = (int)R; g.N = (int)Ndim; g.K = (int)Kdim; g.Nst = (int)a.ldo;
-        p.fill(g);
-        if (p.x6 && a.x_binary) g.x6 = 2;
-
-        EpiArgs e{};
-        e.slabs = ws.slabs; e.slab_stride = g.slab_stride; e.nsplit = p.splitk;
-        e.rows = (int)R; e.cols = (int)Ndim; e.ld = a.ldo;
-        e.bias = a.bias;
-        e.pre = a.pre ? a.pre + r0 * a.ldo : nullptr;
-        e.mean = a.mean ? a.mean + r0 * a.ldo : nullptr;
-        e.sample = a.sample ? a.sample + r0 * a.ldo : nullptr;
-        e.mean_scale = a.mean_scale; e.gauss = a.gauss;
-        e.target = a.target ? a.target + r0 * a.ld_target : nullptr;
-        e.ld_target = a.ld_target;
-        e.colsum = a.colsum ? a.colsum + (r0 / 4) * a.ldo : nullptr;
-        e.colsum_kind = a.colsum_kind;
-        const int nb = fuse ? p.tiles_m * p.tiles_n : epilogue_blocks(R, a.ldo);
-        e.cost_partials = nullptr;
-        if (a.want_cost) {
-            if (n_cost + nb > ws.cost_floats) return fail(MDBN_ENOSPC, "cost scratch exhausted");
-            e.cost_partials = ws.cost_partials + n_cost;
-            n_cost += nb;
-        }
-        mdbn_rng zero;
-        memset(&zero, 0, sizeof zero);
-        const mdbn_rng& rr = a.rng ? *a.rng : zero;
-        e.rng = make_key(rr, a.draw);
-        e.rng.row_offset = rr.row_offset + (uint64_t)r0;
-        if (fuse) {                 // activation on the accumulators: no slabs, one launch
-            g.fused = 1;
-            g.epi = e;
-            HIP_OK(timed_gemm(LAY_K, a.dir == 0 ? LAY_MN : LAY_K, g, s));
-        } else {
-            HIP_OK(timed_gemm(LAY_K, a.dir == 0 ? LAY_MN : LAY_K, g, s));
-            HIP_OK(launch_act_epilogue(e, s));
-        }
-        r0 += R;
-    }
-    if (n_cost_out) *n_cost_out = n_cost;
-    return MDBN_OK;
-}
-
-int check_mat(const void* p, int64_t ld, int64_t cols, const char* name)
-{
-    REQUIRE(p != nullptr, "%s is NULL", name);
-    REQUIRE(aligned16(p), "%s is not 16-byte aligned", name);
-    REQUIRE(ld % 4 == 0 && ld >= cols, "%s: leading dimension %lld must be a multiple of 4 and >= %lld",
-            name, (long long)ld, (long long)cols);
-    return MDBN_OK;
-}
-
-#define CHECK(expr) do { int _rc = (expr); if (_rc != MDBN_OK) return _rc; } while (0)
-
 
 // ---------------------------------------------------------------------------------- bf16 plane path
 hipError_t timed_gemm_planes(int la, int lb, const PlaneGemmArgs& g_in, hipStream_t s)
@@ -864,23 +585,6 @@ struct StatsView {
 bool plain_cd(const mdbn_cd_args* a) { return !a->persistent && !a->sample_stats && !(a->gauss && a->add_noise); }
 // float32 inspection copies of v0 / nv / ph / -nh / samples that nothing on the one-launch, thin and plane paths reads
 bool keeps_f32(const mdbn_cd_args* a) { return a->keep_f32 != 0 || a->trace_h != nullptr || a->trace_v != nullptr; }
-
-// the weight half of an update rule as a kernel applies it to its own tile of S (Wp: planes of the new W, or NULL)
-void fill_upd(UpdEpi& e, const mdbn_update_args& u, int64_t V, int64_t ldh, unsigned short* Wp)
-{
-    e.W = u.W; e.Ws = u.W_speed; e.W0 = u.W0; e.ld = ldh; e.rows = (int)V;
-    e.lr = u.lr; e.l1 = u.lambda_1; e.l2 = u.lambda_2; e.wc = u.weightcost;
-    e.mu = u.momentum; e.inv_bs = 1.0f / u.batch_size;
-    e.Wp = Wp; e.wp_stride = V * ldh;
-}
-
-// ... and its bias / monitoring-cost half (H: the live hidden width)
-void fill_bias_upd(BiasUpd& b, const mdbn_update_args& u, int64_t H)
-{
-    b.hb = u.hbias; b.hbs = u.hbias_speed; b.vb = u.vbias; b.vbs = u.vbias_speed;
-    b.H = H; b.V = u.V; b.lr = u.lr; b.mu = u.momentum; b.inv_rows = 1.0f / u.n_rows;
-    b.cost_scale = u.cost_scale; b.cost_out = u.cost_out;
-}
 
 // an update as a launch of its own, W's planes rewritten with it; the whole rule of a step's own update
 hipError_t launch_whole_update(const mdbn_update_args& u, hipStream_t s)
@@ -1088,6 +792,159 @@ int planes_statistics(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a, const
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------- what mdbn_capi_internal.h declares
+// The part of the core the feature drivers in the other files may call (CtxScope: at the top of this file).
+namespace mdbn {
+namespace capi {
+
+int fail(int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+PhiloxKey make_key(const mdbn_rng& r, uint32_t draw)
+{
+    PhiloxKey k;
+    k.k0 = (uint32_t)r.seed;
+    k.k1 = (uint32_t)(r.seed >> 32) ^ r.stream_id;
+    k.step = r.step;
+    k.draw = draw;
+    k.row_offset = r.row_offset;
+    return k;
+}
+
+int64_t dense_workspace_bytes(int64_t B, int64_t V, int64_t H) { return ws_sizes(B, V, H).total_bytes(); }
+
+int carve(void* ws, int64_t bytes, int64_t B, int64_t V, int64_t H, Workspace& out, bool need_stats)
+{
+    REQUIRE(ws != nullptr && aligned16(ws), "workspace must be a 16-byte aligned device pointer");
+    const WsSizes s = ws_sizes(B, V, H);
+    float* p = reinterpret_cast<float*>(ws);
+    if (need_stats) {
+        if (bytes < s.total_bytes())
+            return fail(MDBN_ENOSPC, "workspace %lld bytes < %lld needed for B=%lld V=%lld H=%lld",
+                        (long long)bytes, (long long)s.total_bytes(), (long long)B, (long long)V, (long long)H);
+        out.slabs = p;            out.slab_floats = s.slab;  p += ru64(s.slab);
+        out.cost_partials = p;    out.cost_floats = s.cost;  p += ru64(s.cost);
+        out.colPpos = p;          out.colPneg = p + s.colP / 2;  p += ru64(s.colP);
+        out.colV = p;
+    } else {
+        // propagation only: a fixed cost region at the end, everything else is slabs
+        const int64_t floats = bytes / 4;
+        const int64_t cost = 1 << 16;
+        if (floats < cost + 4096)
+            return fail(MDBN_ENOSPC, "workspace %lld bytes is too small", (long long)bytes);
+        out.slabs = p;
+        out.slab_floats = (floats - cost) & ~int64_t(63);
+        out.cost_partials = p + out.slab_floats;
+        out.cost_floats = cost;
+        out.colPpos = out.colPneg = out.colV = nullptr;
+    }
+    return MDBN_OK;
+}
+
+// (struct Affine: mdbn_capi_internal.h)
+int run_affine(const Affine& a, const Workspace& ws, hipStream_t s, int* n_cost_out)
+{
+    const int64_t Kdim = a.dir == 0 ? a.V : a.H;
+    const int64_t Ndim = a.dir == 0 ? a.H : a.V;
+    int n_cost = 0;
+    int64_t r0 = 0;
+    while (r0 < a.rows) {
+        int64_t R = a.rows - r0;
+        Plan p = plan_forward(R, Ndim, Kdim, a.ldo);
+        bool fuse = false;
+        for (;;) {      // shrink the chunk until its slabs (unfused) and cost partials fit
+            fuse = g_opt_fused_epilogue && p.splitk == 1;
+            const bool slabs_fit = fuse || p.slab_floats(R, a.ldo) <= ws.slab_floats;
+            const int64_t need_cost = !a.want_cost ? 0 : fuse ? (int64_t)p.tiles_m * p.tiles_n : epilogue_blocks(R, a.ldo);
+            if (slabs_fit && n_cost + need_cost <= ws.cost_floats) break;
+            if (R <= 4) return fail(MDBN_ENOSPC, "workspace cannot hold one 4-row chunk");
+            R = std::max<int64_t>(4, (R / 2 + 3) & ~int64_t(3));
+            p = plan_forward(R, Ndim, Kdim, a.ldo);
+        }
+        GemmArgs g{};
+        g.A = a.x + r0 * a.ldx;  g.lda = a.ldx;
+        g.B = a.W;               g.ldb = a.ldw;
+        g.C = ws.slabs;          g.ldc = a.ldo;
+        g.slab_stride = R * a.ldo;
+        g.M = (int)R; g.N = (int)Ndim; g.K = (int)Kdim; g.Nst = (int)a.ldo;
+        p.fill(g);
+        if (p.x6 && a.x_binary) g.x6 = 2;
+
+        EpiArgs e{};
+        e.slabs = ws.slabs; e.slab_stride = g.slab_stride; e.nsplit = p.splitk;
+        e.rows = (int)R; e.cols = (int)Ndim; e.ld = a.ldo;
+        e.bias = a.bias;
+        e.pre = a.pre ? a.pre + r0 * a.ldo : nullptr;
+        e.mean = a.mean ? a.mean + r0 * a.ldo : nullptr;
+        e.sample = a.sample ? a.sample + r0 * a.ldo : nullptr;
+        e.mean_scale = a.mean_scale; e.gauss = a.gauss;
+        e.target = a.target ? a.target + r0 * a.ld_target : nullptr;
+        e.ld_target = a.ld_target;
+        e.colsum = a.colsum ? a.colsum + (r0 / 4) * a.ldo : nullptr;
+        e.colsum_kind = a.colsum_kind;
+        const int nb = fuse ? p.tiles_m * p.tiles_n : epilogue_blocks(R, a.ldo);
+        e.cost_partials = nullptr;
+        if (a.want_cost) {
+            if (n_cost + nb > ws.cost_floats) return fail(MDBN_ENOSPC, "cost scratch exhausted");
+            e.cost_partials = ws.cost_partials + n_cost;
+            n_cost += nb;
+        }
+        mdbn_rng zero;
+        memset(&zero, 0, sizeof zero);
+        const mdbn_rng& rr = a.rng ? *a.rng : zero;
+        e.rng = make_key(rr, a.draw);
+        e.rng.row_offset = rr.row_offset + (uint64_t)r0;
+        if (fuse) {                 // activation on the accumulators: no slabs, one launch
+            g.fused = 1;
+            g.epi = e;
+            HIP_OK(timed_gemm(LAY_K, a.dir == 0 ? LAY_MN : LAY_K, g, s));
+        } else {
+            HIP_OK(timed_gemm(LAY_K, a.dir == 0 ? LAY_MN : LAY_K, g, s));
+            HIP_OK(launch_act_epilogue(e, s));
+        }
+        r0 += R;
+    }
+    if (n_cost_out) *n_cost_out = n_cost;
+    return MDBN_OK;
+}
+
+int check_mat(const void* p, int64_t ld, int64_t cols, const char* name)
+{
+    REQUIRE(p != nullptr, "%s is NULL", name);
+    REQUIRE(aligned16(p), "%s is not 16-byte aligned", name);
+    REQUIRE(ld % 4 == 0 && ld >= cols, "%s: leading dimension %lld must be a multiple of 4 and >= %lld",
+            name, (long long)ld, (long long)cols);
+    return MDBN_OK;
+}
+
+// the weight half of an update rule as a kernel applies it to its own tile of S (Wp: planes of the new W, or NULL)
+void fill_upd(UpdEpi& e, const mdbn_update_args& u, int64_t V, int64_t ldh, unsigned short* Wp)
+{
+    e.W = u.W; e.Ws = u.W_speed; e.W0 = u.W0; e.ld = ldh; e.rows = (int)V;
+    e.lr = u.lr; e.l1 = u.lambda_1; e.l2 = u.lambda_2; e.wc = u.weightcost;
+    e.mu = u.momentum; e.inv_bs = 1.0f / u.batch_size;
+    e.Wp = Wp; e.wp_stride = V * ldh;
+}
+
+// ... and its bias / monitoring-cost half (H: the live hidden width)
+void fill_bias_upd(BiasUpd& b, const mdbn_update_args& u, int64_t H)
+{
+    b.hb = u.hbias; b.hbs = u.hbias_speed; b.vb = u.vbias; b.vbs = u.vbias_speed;
+    b.H = H; b.V = u.V; b.lr = u.lr; b.mu = u.momentum; b.inv_rows = 1.0f / u.n_rows;
+    b.cost_scale = u.cost_scale; b.cost_out = u.cost_out;
+}
+
+}  // namespace capi
+}  // namespace mdbn
+
 extern "C" {
 
 int mdbn_version(void) { return MDBN_VERSION; }
@@ -1128,8 +985,6 @@ int mdbn_ctx_create(mdbn_ctx** out, int device)
     *out = c;
     return MDBN_OK;
 }
-
-int mdbn_comm_destroy(mdbn_ctx* ctx);
 
 int mdbn_ctx_destroy(mdbn_ctx* ctx)
 {
@@ -1540,89 +1395,6 @@ int mdbn_propdown_sample(mdbn_ctx* ctx, void* stream, const float* h, int64_t B,
     if (cost_sum)
         HIP_OK(launch_finalize_stats(nullptr, nullptr, nullptr, 0, 0, 0, ws.cost_partials, n_cost, nullptr,
                                      nullptr, cost_sum, nullptr, s));
-    return MDBN_OK;
-}
-
-// ---------------------------------------------------------------------------------- RCCL (data parallelism)
-// librccl is opened lazily: the library loads and every single-device entry point works without it.
-namespace {
-struct Rccl {
-    void* h = nullptr;
-    int (*GetUniqueId)(void*) = nullptr;
-    void* CommInitRank = nullptr;          // ncclCommInitRank(ncclComm_t*, int, ncclUniqueId BY VALUE, int)
-    int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    int (*CommDestroy)(void*) = nullptr;
-    const char* (*GetErrorString)(int) = nullptr;
-};
-Rccl g_rccl;
-struct NcclId { char internal[128]; };
-
-int rccl_load()
-{
-    if (g_rccl.h) return MDBN_OK;
-    void* h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) return fail(MDBN_EHIP, "cannot open librccl.so: %s", dlerror());
-    g_rccl.GetUniqueId = reinterpret_cast<int (*)(void*)>(dlsym(h, "ncclGetUniqueId"));
-    g_rccl.CommInitRank = dlsym(h, "ncclCommInitRank");
-    g_rccl.AllReduce = reinterpret_cast<int (*)(const void*, void*, size_t, int, int, void*, hipStream_t)>(dlsym(h, "ncclAllReduce"));
-    g_rccl.CommDestroy = reinterpret_cast<int (*)(void*)>(dlsym(h, "ncclCommDestroy"));
-    g_rccl.GetErrorString = reinterpret_cast<const char* (*)(int)>(dlsym(h, "ncclGetErrorString"));
-    if (!g_rccl.GetUniqueId || !g_rccl.CommInitRank || !g_rccl.AllReduce || !g_rccl.CommDestroy)
-        return fail(MDBN_EHIP, "librccl.so lacks an expected symbol");
-    g_rccl.h = h;
-    return MDBN_OK;
-}
-#define RCCL_OK(expr)                                                                          \
-    do {                                                                                       \
-        int _r = (expr);                                                                       \
-        if (_r != 0)                                                                           \
-            return fail(MDBN_EHIP, "%s failed: %s", #expr, g_rccl.GetErrorString ? g_rccl.GetErrorString(_r) : "?"); \
-    } while (0)
-}  // namespace
-
-int mdbn_comm_unique_id(char* id128)
-{
-    REQUIRE(id128 != nullptr, "id buffer is NULL");
-    CHECK(rccl_load());
-    RCCL_OK(g_rccl.GetUniqueId(id128));
-    return MDBN_OK;
-}
-
-int mdbn_comm_init_rank(mdbn_ctx* ctx, const char* id128, int nranks, int rank)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx != nullptr && id128 != nullptr && nranks >= 1 && rank >= 0 && rank < nranks, "bad arguments");
-    REQUIRE(ctx->comm == nullptr, "this context already has a communicator");
-    CHECK(rccl_load());
-    HIP_OK(hipSetDevice(ctx->device));
-    typedef int (*init_fn)(void**, int, NcclId, int);          // ncclUniqueId is passed BY VALUE
-    NcclId id;
-    memcpy(id.internal, id128, 128);
-    RCCL_OK(reinterpret_cast<init_fn>(g_rccl.CommInitRank)(&ctx->comm, nranks, id, rank));
-    ctx->comm_ranks = nranks;
-    return MDBN_OK;
-}
-
-int mdbn_allreduce_stats(mdbn_ctx* ctx, void* stream, float* stats, int64_t n)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx != nullptr && ctx->comm != nullptr, "no communicator: call mdbn_comm_init_rank first");
-    REQUIRE(stats != nullptr && n > 0, "bad arguments");
-    // in place, float32 (ncclFloat32 = 7), sum (ncclSum = 0): the packed [S | s_h | s_v | cost] buffer of one CD step
-    RCCL_OK(g_rccl.AllReduce(stats, stats, (size_t)n, 7, 0, ctx->comm, (hipStream_t)stream));
-    return MDBN_OK;
-}
-
-int mdbn_comm_destroy(mdbn_ctx* ctx)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx != nullptr, "ctx is NULL");
-    if (ctx->comm) {
-        RCCL_OK(g_rccl.CommDestroy(ctx->comm));
-        ctx->comm = nullptr;
-        ctx->comm_ranks = 0;
-    }
     return MDBN_OK;
 }
 
@@ -2230,570 +2002,7 @@ int mdbn_free_energy(mdbn_ctx* ctx, void* stream, const float* x, int64_t N, int
     return MDBN_OK;
 }
 
-// ---------------------------------------------------------------------------------- what the three sampler drivers share
-namespace {
-
-// Scratch of the propagation GEMMs of a general path (carve: slabs + a fixed cost region).  Any size serves (a pass is chunked
-// until its split-K slabs fit); what the plans of `rows` rows ask for is not monotone in the rows (fewer rows: more split-K), so
-// with cover_fewer_rows the answer is the largest over `rows` and the whole 32-row tilings below it -- a buffer sized for
-// `rows` rows serves any fewer
-int64_t gemm_scratch_bytes(int64_t rows, int64_t V, int64_t H, bool cover_fewer_rows)
-{
-    int64_t g = ws_sizes(rows, V, H).total_bytes();
-    if (cover_fewer_rows) {
-        const int64_t step = std::max<int64_t>(32, ((rows >> 12) + 31) & ~int64_t(31));
-        for (int64_t m = step; m < rows; m += step) g = std::max(g, ws_sizes(m, V, H).total_bytes());
-    }
-    return g + 4 * ((int64_t)(1 << 16) + 4096);
-}
-
-// The path a *_workspace_bytes call sizes for.  One buffer serves a layer whatever its visible type, so path 1 needs the layer
-// to fit for either type, and path 0 sizes for the one-launch path only where a run would take it for both.  -1: path 1 was
-// asked for and the layer fits for neither.
-int sizing_path(int path, bool fits_either, bool taken_both)
-{
-    if (path == 1) return fits_either ? 1 : -1;
-    return path == 0 && taken_both ? 1 : 2;
-}
-
-// The path a run takes: path = 0 chooses by shape
-int run_path(int path, bool one_launch) { return path == 0 ? (one_launch ? 1 : 2) : path; }
-
-// Two groups of argument rules the three run entry points share; an entry point checks its own rules before, between and after
-// them (the API tests assert which error a bad call reports, and that it comes without a device: the order stays).
-int sampler_workspace_rules(int64_t workspace_bytes, int64_t need, const char* sizer, const mdbn_ctx* ctx, const mdbn_rng* rng)
-{
-    REQUIRE(workspace_bytes >= need, "workspace %lld bytes < %lld needed (%s)", (long long)workspace_bytes, (long long)need, sizer);
-    REQUIRE(ctx != nullptr && rng != nullptr, "ctx / rng is NULL");
-    return MDBN_OK;
-}
-
-int sampler_pointer_rules(const void* workspace, std::initializer_list<const void*> optional_outputs)
-{
-    REQUIRE(workspace != nullptr && aligned16(workspace), "workspace must be a 16-byte aligned device pointer");
-    for (const void* q : optional_outputs) REQUIRE(q == nullptr || aligned16(q), "output not 16-byte aligned");
-    return MDBN_OK;
-}
-
-}  // namespace
-
-// ---------------------------------------------------------------------------------- annealed importance sampling
-namespace {
-
-// The clamp of mdbn_ais_cond_run: chain m of the N C chains keeps the columns where its data row's mask is 1 at obs.  A run
-// without one (mdbn_ais_run) is the same run with no held column: one data row per chain, nothing to read.
-struct AisClamp {
-    const float* obs; const float* mask;
-    int64_t mask_rows, N, C;
-};
-
-// The caller's workspace of an AIS run.  One-launch path: the visible state carried between launches.  General path: a
-// zero bias (the propdown product is taken without bias), the pre-activations of a pass, the hidden and the visible state,
-// s1 and d2 (mdbn_ais.hip: 64 floats, and under a clamp one sum per data row behind them), then the scratch of the
-// propagation GEMMs.
-struct AisWs {
-    int64_t zero, pre, h, v, s1, d2, gemm_bytes;
-    int64_t total_bytes() const { return 4 * (zero + pre + h + v + s1 + d2) + gemm_bytes; }
-};
-
-AisWs ais_ws(int path, int64_t M, int64_t clamp_rows, int64_t V, int64_t H, int64_t ldv, int64_t ldh)
-{
-    AisWs w{};
-    w.v = ru64(M * ldv);
-    w.d2 = 64;
-    if (path == 2) {
-        w.zero = ru64(std::max(ldv, ldh));
-        w.pre = ru64(M * std::max(ldv, ldh));
-        w.h = ru64(M * ldh);
-        w.s1 = ru64(M);
-        if (clamp_rows) w.d2 += ru64(clamp_rows);
-        w.gemm_bytes = gemm_scratch_bytes(M, V, H, true);
-    }
-    return w;
-}
-
-// N C chains as mdbn_ais_run counts them
-int cais_chain_rules(int64_t N, int64_t C, int64_t V, int64_t H)
-{
-    REQUIRE(N >= 1 && C >= 1 && V >= 1 && H >= 1, "bad shape N=%lld C=%lld V=%lld H=%lld", (long long)N, (long long)C, (long long)V, (long long)H);
-    REQUIRE(N < (1ll << 31) && C < (1ll << 31) && N * C < (1ll << 31), "N C = %lld x %lld chains: too many", (long long)N, (long long)C);
-    return MDBN_OK;
-}
-
-// What both sizers answer once their own shape rule holds: M chains, clamp_rows = the data rows of a clamp or 0
-int ais_workspace_bytes(int64_t M, int64_t clamp_rows, int64_t V, int64_t H, int64_t n_betas, int path, int64_t* bytes)
-{
-    REQUIRE(n_betas >= 2, "n_betas = %lld: a schedule has at least beta_0 = 0 and beta_K = 1", (long long)n_betas);
-    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
-    const int64_t ldv = padded_ld(V), ldh = padded_ld(H);
-    const bool f0 = ais_small_ok(M, V, H, 0, ldv, ldh), f1 = ais_small_ok(M, V, H, 1, ldv, ldh);
-    const int p = sizing_path(path, f0 || f1, f0 && f1);
-    REQUIRE(p > 0, "path 1: %lld -> %lld is not LDS-resident", (long long)V, (long long)H);
-    *bytes = ais_ws(p, M, clamp_rows, V, H, ldv, ldh).total_bytes();
-    return MDBN_OK;
-}
-
-// Both runs once their own shape rule holds (the rules that need no device still come first): M chains, free (clamp == NULL)
-// or clamped; `sizer` names the entry point's own *_workspace_bytes
-int ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias, const float* vbias,
-            const float* base_vbias, int gauss, const float* betas, int64_t n_betas, int64_t M, const AisClamp* clamp, int64_t ldv,
-            float* v_state, double* logw, float* trace_h, float* trace_v, int path, const mdbn_rng* rng, void* workspace,
-            int64_t workspace_bytes, const char* sizer)
-{
-    REQUIRE(n_betas >= 2, "n_betas = %lld: a schedule has at least beta_0 = 0 and beta_K = 1", (long long)n_betas);
-    if (clamp)
-        REQUIRE(clamp->mask_rows == 1 || clamp->mask_rows == clamp->N, "mask_rows = %lld is neither 1 nor N = %lld",
-                (long long)clamp->mask_rows, (long long)clamp->N);
-    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
-    REQUIRE(ldv % 4 == 0 && ldv >= V && ldh % 4 == 0 && ldh >= H, "leading dimensions must be multiples of 4, ldv >= V, ldh >= H");
-    const bool fits = ais_small_ok(M, V, H, gauss, ldv, ldh);
-    REQUIRE(path != 1 || fits, "path 1: %lld -> %lld (ldv %lld, ldh %lld) is not LDS-resident", (long long)V, (long long)H,
-            (long long)ldv, (long long)ldh);
-    const int p = run_path(path, fits);
-    const AisWs w = ais_ws(p, M, clamp ? clamp->N : 0, V, H, ldv, ldh);
-    CHECK(sampler_workspace_rules(workspace_bytes, w.total_bytes(), sizer, ctx, rng));
-    CHECK(check_mat(W, ldh, H, "W"));
-    if (clamp) {
-        CHECK(check_mat(clamp->obs, ldv, V, "obs"));
-        CHECK(check_mat(clamp->mask, ldv, V, "mask"));
-    }
-    REQUIRE(hbias && vbias && base_vbias && betas && logw, "NULL pointer");
-    CHECK(sampler_pointer_rules(workspace, {v_state, trace_h, trace_v}));
-    hipStream_t s = (hipStream_t)stream;
-    const int K = (int)n_betas - 1;
-    float* wsf = reinterpret_cast<float*>(workspace);
-    const float* obs = clamp ? clamp->obs : nullptr;
-    const float* mask = clamp ? clamp->mask : nullptr;
-    const int mask_rows = clamp ? (int)clamp->mask_rows : 1, C = clamp ? (int)clamp->C : 1;
-
-    if (p == 1) {
-        AisSmallArgs a{};
-        a.M = (int)M; a.V = (int)V; a.H = (int)H; a.gauss = gauss != 0;
-        a.ldv = ldv; a.ldh = ldh;
-        a.W = W; a.hbias = hbias; a.vbias = vbias; a.base_vbias = base_vbias; a.betas = betas;
-        a.K = K;
-        a.rng = make_key(*rng, 0u);
-        a.obs = obs; a.mask = mask; a.mask_rows = mask_rows; a.C = C;
-        a.v_state = v_state ? v_state : wsf;
-        a.logw = logw;
-        a.trace_h = trace_h; a.trace_v = trace_v;
-        for (int k0 = 0; k0 < K; k0 += AIS_CUT) {       // a launch stays short; the state travels in v_state / logw
-            a.k0 = k0; a.k1 = std::min(K, k0 + AIS_CUT);
-            HIP_OK(launch_ais_small(a, s));
-        }
-        return MDBN_OK;
-    }
-
-    float* zero = wsf;
-    float* pre = zero + w.zero;
-    float* h = pre + w.pre;
-    float* v = h + w.h;
-    float* s1 = v + w.v;
-    float* d2 = s1 + w.s1;
-    void* gemm_ws = d2 + w.d2;
-    if (v_state) v = v_state;
-    Workspace ws;
-    CHECK(carve(gemm_ws, w.gemm_bytes, M, V, H, ws, false));
-    HIP_OK(hipMemsetAsync(zero, 0, sizeof(float) * w.zero, s));
-    AisStepArgs st{};
-    st.M = (int)M; st.V = (int)V; st.H = (int)H; st.gauss = gauss != 0; st.K = K;
-    st.ldv = ldv; st.ldh = ldh;
-    st.betas = betas; st.vbias = vbias; st.base_vbias = base_vbias;
-    st.rng = make_key(*rng, 0u);
-    st.obs = obs; st.mask = mask; st.mask_rows = mask_rows; st.C = C;
-    st.pre = pre; st.h = h; st.v = v; st.s1 = s1; st.d2 = d2; st.logw = logw;
-    if (gauss) HIP_OK(launch_ais_d2(st, d2, s));         // (read under gauss only)
-    st.k = 0; st.trace = trace_v;
-    HIP_OK(launch_ais_visible(st, s));
-    for (int k = 1; k <= K; ++k) {
-        st.k = k;
-        Affine up(v, M, ldv, W, V, H, ldh, hbias);
-        up.pre = pre;
-        // A held column may hold any real value: never the 0/1 operand hint on the way up under a clamp (where the state is 0/1
-        // the six-product kernel adds exact zeros to the three products of the hinted one: the same bits)
-        up.x_binary = !gauss && !clamp;
-        CHECK(run_affine(up, ws, s, nullptr));
-        st.trace = trace_h && k < K ? trace_h + (int64_t)(k - 1) * M * ldh : nullptr;
-        HIP_OK(launch_ais_hidden(st, s));
-        if (k == K) break;
-        Affine down(h, M, ldh, W, V, H, ldh, zero, ldv, 1);
-        down.pre = pre;
-        down.x_binary = true;                            // our own 0/1 hidden samples
-        CHECK(run_affine(down, ws, s, nullptr));
-        st.trace = trace_v ? trace_v + (int64_t)k * M * ldv : nullptr;
-        HIP_OK(launch_ais_visible(st, s));
-    }
-    return MDBN_OK;
-}
-
-}  // namespace
-
-int mdbn_ais_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t V, int64_t H, int64_t n_betas, int path, int64_t* bytes)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(bytes != nullptr, "bytes is NULL");
-    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
-    return ais_workspace_bytes(M, 0, V, H, n_betas, path, bytes);
-}
-
-int mdbn_ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
-                 const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t n_betas, int64_t M,
-                 int64_t ldv, float* v_state, double* logw, float* trace_h, float* trace_v, int path, const mdbn_rng* rng,
-                 void* workspace, int64_t workspace_bytes)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
-    REQUIRE(M < (1ll << 31) && n_betas < (1ll << 30), "M / n_betas too large");
-    return ais_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, gauss, betas, n_betas, M, nullptr, ldv, v_state, logw, trace_h,
-                   trace_v, path, rng, workspace, workspace_bytes, "mdbn_ais_workspace_bytes");
-}
-
-int mdbn_ais_cond_workspace_bytes(mdbn_ctx* ctx, int64_t N, int64_t C, int64_t V, int64_t H, int64_t n_betas, int path, int64_t* bytes)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(bytes != nullptr, "bytes is NULL");
-    CHECK(cais_chain_rules(N, C, V, H));
-    return ais_workspace_bytes(N * C, N, V, H, n_betas, path, bytes);
-}
-
-int mdbn_ais_cond_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
-                      const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t n_betas,
-                      const float* obs, const float* mask, int64_t mask_rows, int64_t N, int64_t C, int64_t ldv, float* v_state,
-                      double* logw, float* trace_h, float* trace_v, int path, const mdbn_rng* rng, void* workspace,
-                      int64_t workspace_bytes)
-{
-    CtxScope ctx_scope(ctx);
-    CHECK(cais_chain_rules(N, C, V, H));
-    REQUIRE(n_betas < (1ll << 30), "n_betas too large");
-    const AisClamp clamp{obs, mask, mask_rows, N, C};
-    return ais_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, gauss, betas, n_betas, N * C, &clamp, ldv, v_state, logw,
-                   trace_h, trace_v, path, rng, workspace, workspace_bytes, "mdbn_ais_cond_workspace_bytes");
-}
-
-// ---------------------------------------------------------------------------------- clamped Gibbs sampling
-namespace {
-
-// The caller's workspace of mdbn_gibbs_clamped: the two accumulators (one-launch path: what a cut run carries from launch to
-// launch), then -- general path -- the scratch of the propagation GEMMs.
-struct ClampWs {
-    int64_t acc_v, acc_h, gemm_bytes;
-    int64_t total_bytes() const { return 4 * (acc_v + acc_h) + gemm_bytes; }
-};
-
-ClampWs clamp_ws(int path, int64_t B, int64_t V, int64_t H, int64_t ldv, int64_t ldh)
-{
-    ClampWs w{};
-    w.acc_v = ru64(B * ldv);
-    w.acc_h = ru64(B * ldh);
-    if (path == 2) w.gemm_bytes = gemm_scratch_bytes(B, V, H, false);
-    return w;
-}
-
-}  // namespace
-
-int mdbn_gibbs_clamped_workspace_bytes(mdbn_ctx* ctx, int64_t B, int64_t V, int64_t H, int path, int64_t* bytes)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(bytes != nullptr, "bytes is NULL");
-    REQUIRE(B >= 1 && V >= 1 && H >= 1, "bad shape B=%lld V=%lld H=%lld", (long long)B, (long long)V, (long long)H);
-    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
-    const int64_t ldv = padded_ld(V), ldh = padded_ld(H);
-    const bool f0 = clamp_small_ok(B, V, H, 0, ldv, ldh), f1 = clamp_small_ok(B, V, H, 1, ldv, ldh);
-    const int p = sizing_path(path, f0 || f1, f0 && f1);
-    REQUIRE(p > 0, "path 1: %lld -> %lld is not LDS-resident", (long long)V, (long long)H);
-    *bytes = clamp_ws(p, B, V, H, ldv, ldh).total_bytes();
-    return MDBN_OK;
-}
-
-int mdbn_gibbs_clamped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, const float* mask, int64_t mask_rows,
-                       int64_t B, int64_t ldv, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
-                       const float* vbias, int gauss, int add_noise, int64_t n_steps, int64_t burn_in, float* h_mean,
-                       float* h_sample, float* v_mean, float* v_avg, float* h_avg, float* trace_h, float* trace_v,
-                       int path, int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes)
-{
-    CtxScope ctx_scope(ctx);
-    // (the argument rules first: they need no device)
-    REQUIRE(B >= 1 && V >= 1 && H >= 1, "bad shape B=%lld V=%lld H=%lld", (long long)B, (long long)V, (long long)H);
-    REQUIRE(B < (1ll << 31), "B too large");
-    REQUIRE(n_steps >= 1 && n_steps < (1ll << 30), "n_steps = %lld must be in [1, 2^30)", (long long)n_steps);
-    REQUIRE(burn_in >= 0 && burn_in < n_steps, "burn_in = %lld must be in [0, n_steps = %lld)", (long long)burn_in, (long long)n_steps);
-    REQUIRE(mask_rows == 1 || mask_rows == B, "mask_rows = %lld is neither 1 nor B = %lld", (long long)mask_rows, (long long)B);
-    REQUIRE(gauss >= 0 && gauss <= 2, "gauss = %d is not 0 (Bernoulli), 1 (Gaussian, hidden mean down) or 2 (Gaussian, Gibbs sampler)", gauss);
-    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
-    REQUIRE(steps_per_launch >= 0, "steps_per_launch = %lld is negative (0 = default)", (long long)steps_per_launch);
-    REQUIRE(ldv % 4 == 0 && ldv >= V && ldh % 4 == 0 && ldh >= H, "leading dimensions must be multiples of 4, ldv >= V, ldh >= H");
-    const bool fits = clamp_small_ok(B, V, H, gauss, ldv, ldh);
-    REQUIRE(path != 1 || fits, "path 1: %lld -> %lld (ldv %lld, ldh %lld) is not LDS-resident", (long long)V, (long long)H,
-            (long long)ldv, (long long)ldh);
-    const int p = run_path(path, fits);
-    const ClampWs w = clamp_ws(p, B, V, H, ldv, ldh);
-    CHECK(sampler_workspace_rules(workspace_bytes, w.total_bytes(), "mdbn_gibbs_clamped_workspace_bytes", ctx, rng));
-    CHECK(check_mat(v, ldv, V, "v"));
-    CHECK(check_mat(obs, ldv, V, "obs"));
-    CHECK(check_mat(mask, ldv, V, "mask"));
-    CHECK(check_mat(W, ldh, H, "W"));
-    CHECK(check_mat(h_mean, ldh, H, "h_mean"));
-    CHECK(check_mat(h_sample, ldh, H, "h_sample"));
-    CHECK(check_mat(v_mean, ldv, V, "v_mean"));
-    REQUIRE(hbias && vbias, "bias pointers are NULL");
-    CHECK(sampler_pointer_rules(workspace, {v_avg, h_avg, trace_h, trace_v}));
-    hipStream_t s = (hipStream_t)stream;
-    float* acc_v = reinterpret_cast<float*>(workspace);
-    float* acc_h = acc_v + w.acc_v;
-    const bool noisy = gauss && (add_noise || gauss == 2);
-    const bool feed_sample = gauss != 1;            // gauss = 1: the hidden MEAN goes down (mdbn_gibbs_chain); 2: the sample
-
-    if (p == 1) {
-        ClampSmallArgs a{};
-        a.B = (int)B; a.V = (int)V; a.H = (int)H; a.gauss = gauss; a.add_noise = add_noise != 0;
-        a.ldv = ldv; a.ldh = ldh;
-        a.W = W; a.hbias = hbias; a.vbias = vbias;
-        a.v = v; a.obs = obs; a.mask = mask; a.mask_rows = (int)mask_rows;
-        a.n_steps = (int)n_steps; a.burn_in = (int)burn_in;
-        a.rng = make_key(*rng, 0u);
-        a.h_mean = h_mean; a.h_sample = h_sample; a.v_mean = v_mean; a.v_avg = v_avg; a.h_avg = h_avg;
-        a.acc_v = acc_v; a.acc_h = acc_h;
-        a.trace_h = trace_h; a.trace_v = trace_v;
-        const int64_t cut = steps_per_launch ? steps_per_launch : CLAMP_CUT;
-        for (int64_t t0 = 0; t0 < n_steps; t0 += cut) {       // a launch stays short; the state travels in v / acc_v / acc_h
-            a.t0 = (int)t0; a.t1 = (int)std::min(n_steps, t0 + cut);
-            HIP_OK(launch_clamp_small(a, s));
-        }
-        return MDBN_OK;
-    }
-
-    Workspace ws;
-    CHECK(carve(acc_h + w.acc_h, w.gemm_bytes, B, V, H, ws, false));
-    HIP_OK(hipMemsetAsync(acc_v, 0, sizeof(float) * (w.acc_v + w.acc_h), s));
-    ClampStepArgs c{};
-    c.B = (int)B; c.V = (int)V; c.H = (int)H;
-    c.ldv = ldv; c.ldh = ldh;
-    c.v = v; c.v_mean = v_mean; c.obs = obs; c.mask = mask; c.mask_rows = (int)mask_rows;
-    c.h_mean = h_mean; c.h_sample = h_sample;
-    c.n_avg = (float)(n_steps - burn_in);
-    c.acc_v = acc_v; c.acc_h = acc_h; c.v_avg = v_avg; c.h_avg = h_avg;
-    c.entry = 1; c.v_new = v;
-    HIP_OK(launch_clamp_step(c, s));
-    c.entry = 0;
-    for (int64_t t = 0; t < n_steps; ++t) {
-        const bool last = t + 1 == n_steps;
-        mdbn_rng rh = *rng, rv = *rng;
-        rh.step = rng->step + (uint32_t)(2 * t);     rh.draw = 0;
-        rv.step = rng->step + (uint32_t)(2 * t + 1); rv.draw = 0;
-        // the passes of mdbn_gibbs_chain.  The visible state may hold real observed values: never the 0/1 operand hint there
-        Affine up(v, B, ldv, W, V, H, ldh, hbias);
-        up.mean = h_mean; up.sample = (feed_sample || last || trace_h) ? h_sample : nullptr; up.rng = &rh;
-        CHECK(run_affine(up, ws, s, nullptr));
-        Affine down(feed_sample ? h_sample : h_mean, B, ldh, W, V, H, ldh, vbias, ldv, gauss != 0);
-        down.mean = v_mean; down.sample = (!gauss || noisy) ? v : nullptr; down.rng = &rv;
-        down.x_binary = feed_sample;                     // our own 0/1 hidden samples
-        CHECK(run_affine(down, ws, s, nullptr));
-        c.v_new = (!gauss || noisy) ? v : v_mean;
-        c.accumulate = t >= burn_in; c.last = last;
-        c.trace_h = trace_h ? trace_h + t * B * ldh : nullptr;
-        c.trace_v = trace_v ? trace_v + t * B * ldv : nullptr;
-        HIP_OK(launch_clamp_step(c, s));
-    }
-    return MDBN_OK;
-}
-
-// ---------------------------------------------------------------------------------- parallel tempering
-namespace {
-
-// The caller's workspace of mdbn_pt_run: the betas on the device, the per-ladder swap counts and the two running sums (what a
-// cut run carries from launch to launch), then -- general path -- a zero bias, the pre-activations of a pass, s1
-// (mdbn_temper.hip) and the scratch of the propagation GEMMs over M R rows.  mdbn_pt_run_z (`z`): on the general path also
-// g = |b - b_A|^2, a double, behind the running sums.
-struct PtWs {
-    int64_t betas, counts, v_sum, h_sum, g, zero, pre, s1, gemm_bytes;
-    int64_t total_bytes() const { return 4 * (betas + counts + v_sum + h_sum + g + zero + pre + s1) + gemm_bytes; }
-};
-
-PtWs pt_ws(int path, int64_t M, int64_t R, int64_t V, int64_t H, int64_t ldv, int64_t ldh, bool z = false)
-{
-    PtWs w{};
-    w.betas = ru64(R);
-    w.counts = ru64(M * (R - 1));
-    w.v_sum = ru64(M * ldv);
-    w.h_sum = ru64(M * ldh);
-    if (path == 2 && z) w.g = ru64(2);
-    if (path == 2) {
-        const int64_t rows = M * R;
-        w.zero = ru64(std::max(ldv, ldh));
-        w.pre = ru64(rows * std::max(ldv, ldh));
-        w.s1 = ru64(rows);
-        w.gemm_bytes = gemm_scratch_bytes(rows, V, H, true);
-    }
-    return w;
-}
-
-}  // namespace
-
-namespace {
-
-int pt_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t R, int64_t V, int64_t H, int path, int64_t* bytes, bool z)
-{
-    REQUIRE(bytes != nullptr, "bytes is NULL");
-    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
-    REQUIRE(R >= 2 && R <= PT_MAX_R_GENERAL, "R = %lld: a ladder has 2 to %d temperatures", (long long)R, PT_MAX_R_GENERAL);
-    REQUIRE(M * R < (1ll << 31), "M * R too large");
-    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
-    const int64_t ldv = padded_ld(V), ldh = padded_ld(H);
-    const int p = sizing_path(path, pt_small_ok(M, R, V, H, 0, ldv, ldh) || pt_small_ok(M, R, V, H, 1, ldv, ldh),
-                              pt_small_preferred(M, R, V, H, 0, ldv, ldh) && pt_small_preferred(M, R, V, H, 1, ldv, ldh));
-    REQUIRE(p > 0, "path 1: %lld -> %lld with R = %lld is not LDS-resident (or R is no multiple of 4)", (long long)V, (long long)H,
-            (long long)R);
-    *bytes = pt_ws(p, M, R, V, H, ldv, ldh, z).total_bytes();
-    return MDBN_OK;
-}
-
-// mdbn_pt_run (z = false: zacc and trace_work NULL) and mdbn_pt_run_z: one statement of the rules and of the run
-int pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
-           const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t R, int64_t M, int64_t ldv,
-           float* v, float* h, int32_t* rank, int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t* accepted,
-           float* v_avg, float* h_avg, float* trace_v, float* trace_h, int32_t* trace_swaps, int path,
-           int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes, bool z, double* zacc,
-           double* trace_work)
-{
-    // (the argument rules first: they need no device)
-    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
-    REQUIRE(R >= 2 && R <= PT_MAX_R_GENERAL, "R = %lld: a ladder has 2 to %d temperatures", (long long)R, PT_MAX_R_GENERAL);
-    REQUIRE(M * R < (1ll << 31), "M * R too large");
-    REQUIRE(betas != nullptr, "betas is NULL (a host array of R values)");
-    REQUIRE(betas[0] >= 0.0f, "betas[0] = %g is negative", (double)betas[0]);
-    for (int64_t r = 1; r < R; ++r)
-        REQUIRE(betas[r] > betas[r - 1], "betas must rise strictly: betas[%lld] = %g after %g", (long long)r, (double)betas[r],
-                (double)betas[r - 1]);
-    REQUIRE(betas[R - 1] == 1.0f, "betas must end at exactly 1, not %.9g", (double)betas[R - 1]);
-    REQUIRE(n_sweeps >= 1 && n_sweeps < (1ll << 29), "n_sweeps = %lld must be in [1, 2^29)", (long long)n_sweeps);
-    REQUIRE(burn_in >= 0 && burn_in < n_sweeps, "burn_in = %lld must be in [0, n_sweeps = %lld)", (long long)burn_in, (long long)n_sweeps);
-    REQUIRE(sweep0 >= 0, "sweep0 = %lld is negative", (long long)sweep0);
-    REQUIRE(gauss == 0 || gauss == 1, "gauss = %d is not 0 (Bernoulli) or 1 (Gaussian visibles)", gauss);
-    REQUIRE(path >= 0 && path <= 2, "path %d is not 0 (by shape), 1 (one launch) or 2 (general)", path);
-    REQUIRE(steps_per_launch >= 0, "steps_per_launch = %lld is negative (0 = default)", (long long)steps_per_launch);
-    REQUIRE(ldv % 4 == 0 && ldv >= V && ldh % 4 == 0 && ldh >= H, "leading dimensions must be multiples of 4, ldv >= V, ldh >= H");
-    const bool fits = pt_small_ok(M, R, V, H, gauss, ldv, ldh);
-    REQUIRE(path != 1 || fits, "path 1: %lld -> %lld (ldv %lld, ldh %lld) with R = %lld is not LDS-resident (or R is no multiple of 4)",
-            (long long)V, (long long)H, (long long)ldv, (long long)ldh, (long long)R);
-    // (path = 0: the one-launch kernel only where it was measured to win: pt_small_preferred)
-    const int p = run_path(path, pt_small_preferred(M, R, V, H, gauss, ldv, ldh));
-    const PtWs w = pt_ws(p, M, R, V, H, ldv, ldh, z);
-    CHECK(sampler_workspace_rules(workspace_bytes, w.total_bytes(), z ? "mdbn_pt_run_z_workspace_bytes" : "mdbn_pt_workspace_bytes", ctx, rng));
-    CHECK(check_mat(W, ldh, H, "W"));
-    CHECK(check_mat(v, ldv, V, "v"));
-    CHECK(check_mat(h, ldh, H, "h"));
-    REQUIRE(hbias && vbias && base_vbias && rank && accepted, "NULL pointer");
-    CHECK(sampler_pointer_rules(workspace, {v_avg, h_avg, trace_h, trace_v, zacc, trace_work}));
-    hipStream_t s = (hipStream_t)stream;
-    float* wsf = reinterpret_cast<float*>(workspace);
-    float* d_betas = wsf;
-    int* counts = reinterpret_cast<int*>(d_betas + w.betas);
-    float* v_sum = reinterpret_cast<float*>(counts) + w.counts;
-    float* h_sum = v_sum + w.v_sum;
-    HIP_OK(hipMemcpyAsync(d_betas, betas, sizeof(float) * R, hipMemcpyHostToDevice, s));
-
-    if (p == 1) {
-        PtSmallArgs a{};
-        a.M = (int)M; a.R = (int)R; a.V = (int)V; a.H = (int)H; a.gauss = gauss;
-        a.ldv = ldv; a.ldh = ldh;
-        a.W = W; a.hbias = hbias; a.vbias = vbias; a.base_vbias = base_vbias; a.betas = d_betas;
-        a.v = v; a.h = h; a.rank = rank; a.counts = counts;
-        a.v_sum = v_sum; a.h_sum = h_sum; a.v_avg = v_avg; a.h_avg = h_avg;
-        a.n = (int)n_sweeps; a.burn_in = (int)burn_in; a.sweep0 = sweep0;
-        a.rng = make_key(*rng, 0u);
-        a.trace_v = trace_v; a.trace_h = trace_h; a.trace_swaps = trace_swaps;
-        a.zacc = zacc; a.trace_work = trace_work;
-        const int64_t cut = steps_per_launch ? steps_per_launch : pt_default_cut(R);
-        for (int64_t t0 = 0; t0 < n_sweeps; t0 += cut) {      // a launch stays short; the state travels in h / rank / counts / sums
-            a.t0 = (int)t0; a.t1 = (int)std::min(n_sweeps, t0 + cut);
-            HIP_OK(launch_pt_small(a, s));
-        }
-        HIP_OK(launch_pt_counts(counts, (int)M, (int)R, accepted, s));
-        return MDBN_OK;
-    }
-
-    const int64_t rows = M * R;
-    double* g = reinterpret_cast<double*>(h_sum + w.h_sum);
-    float* zero = h_sum + w.h_sum + w.g;
-    float* pre = zero + w.zero;
-    float* s1 = pre + w.pre;
-    void* gemm_ws = s1 + w.s1;
-    Workspace ws;
-    CHECK(carve(gemm_ws, w.gemm_bytes, rows, V, H, ws, false));
-    HIP_OK(hipMemsetAsync(counts, 0, sizeof(float) * (w.counts + w.v_sum + w.h_sum + w.g + w.zero), s));
-    PtStepArgs st{};
-    st.M = (int)M; st.R = (int)R; st.V = (int)V; st.H = (int)H; st.gauss = gauss;
-    st.ldv = ldv; st.ldh = ldh;
-    st.vbias = vbias; st.base_vbias = base_vbias; st.betas = d_betas;
-    st.pre = pre; st.v = v; st.h = h; st.rank = rank; st.counts = counts; st.s1 = s1;
-    st.v_sum = v_sum; st.h_sum = h_sum; st.v_avg = v_avg; st.h_avg = h_avg;
-    st.n_avg = (float)(n_sweeps - burn_in); st.sweep0 = sweep0;
-    st.rng = make_key(*rng, 0u);
-    st.zacc = zacc;
-    if (zacc || trace_work) {
-        st.g = g;
-        if (gauss) HIP_OK(launch_pt_gnorm(vbias, base_vbias, (int)V, g, s));
-    }
-    for (int64_t t = 0; t < n_sweeps; ++t) {
-        st.t = (int)t; st.accumulate = t >= burn_in; st.last = t + 1 == n_sweeps;
-        st.trace_work = trace_work ? trace_work + t * M * (R - 1) * 2 : nullptr;
-        st.trace_v = trace_v ? trace_v + t * rows * ldv : nullptr;
-        st.trace_h = trace_h ? trace_h + t * rows * ldh : nullptr;
-        st.trace_swaps = trace_swaps ? trace_swaps + t * M * 2 * R : nullptr;
-        Affine down(h, rows, ldh, W, V, H, ldh, zero, ldv, 1);
-        down.pre = pre;
-        down.x_binary = true;                            // our own 0/1 hidden samples
-        CHECK(run_affine(down, ws, s, nullptr));
-        HIP_OK(launch_pt_visible(st, s));
-        Affine up(v, rows, ldv, W, V, H, ldh, hbias);
-        up.pre = pre;
-        up.x_binary = !gauss;
-        CHECK(run_affine(up, ws, s, nullptr));
-        HIP_OK(launch_pt_swap_hidden(st, s));
-    }
-    HIP_OK(launch_pt_counts(counts, (int)M, (int)R, accepted, s));
-    return MDBN_OK;
-}
-
-}  // namespace
-
-int mdbn_pt_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t R, int64_t V, int64_t H, int path, int64_t* bytes)
-{
-    CtxScope ctx_scope(ctx);
-    return pt_workspace_bytes(ctx, M, R, V, H, path, bytes, false);
-}
-
-int mdbn_pt_run_z_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t R, int64_t V, int64_t H, int path, int64_t* bytes)
-{
-    CtxScope ctx_scope(ctx);
-    return pt_workspace_bytes(ctx, M, R, V, H, path, bytes, true);
-}
-
-int mdbn_pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
-                const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t R, int64_t M, int64_t ldv,
-                float* v, float* h, int32_t* rank, int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t* accepted,
-                float* v_avg, float* h_avg, float* trace_v, float* trace_h, int32_t* trace_swaps, int path,
-                int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes)
-{
-    CtxScope ctx_scope(ctx);
-    return pt_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, gauss, betas, R, M, ldv, v, h, rank, n_sweeps, burn_in, sweep0,
-                  accepted, v_avg, h_avg, trace_v, trace_h, trace_swaps, path, steps_per_launch, rng, workspace, workspace_bytes, false,
-                  nullptr, nullptr);
-}
-
-int mdbn_pt_run_z(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
-                  const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t R, int64_t M, int64_t ldv,
-                  float* v, float* h, int32_t* rank, int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t* accepted,
-                  float* v_avg, float* h_avg, float* trace_v, float* trace_h, int32_t* trace_swaps, int path,
-                  int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes, double* zacc,
-                  double* trace_work)
-{
-    CtxScope ctx_scope(ctx);
-    return pt_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, gauss, betas, R, M, ldv, v, h, rank, n_sweeps, burn_in, sweep0,
-                  accepted, v_avg, h_avg, trace_v, trace_h, trace_swaps, path, steps_per_launch, rng, workspace, workspace_bytes, true,
-                  zacc, trace_work);
-}
-
+// ---------------------------------------------------------------------------------- one-kernel helpers
 int mdbn_round_flip(mdbn_ctx* ctx, void* stream, const float* x, int64_t rows, int64_t cols, int64_t ld, int64_t flip_col,
                     float* out)
 {
@@ -2875,691 +2084,6 @@ int mdbn_rng_normal(mdbn_ctx* ctx, void* stream, float* out, int64_t rows, int64
     CtxScope ctx_scope(ctx);
     REQUIRE(ctx && out && rng && rows >= 0 && cols >= 0 && ld >= cols, "bad arguments");
     HIP_OK(launch_rng_fill(out, rows, cols, ld, make_key(*rng, rng->draw), 1, (hipStream_t)stream));
-    return MDBN_OK;
-}
-
-// ---------------------------------------------------------------------------------- variational bound (mdbn_bound.hip)
-int mdbn_rowll_workspace_bytes(mdbn_ctx* ctx, int64_t R, int64_t V, int64_t H, int64_t* bytes)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx && bytes && R > 0 && V > 0 && H > 0, "bad arguments");
-    *bytes = rowll_partial_floats(R, V) * (int64_t)sizeof(float);
-    return MDBN_OK;
-}
-
-int mdbn_propdown_rowll(mdbn_ctx* ctx, void* stream, const float* h, int64_t R, int64_t ldh, const float* W, int64_t V, int64_t H,
-                        const float* vbias, const float* target, int64_t ldv, int64_t target_div, int gauss, float* out,
-                        void* workspace, int64_t workspace_bytes)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx && h && W && vbias && target && out && R > 0 && V > 0 && H > 0, "bad arguments");
-    REQUIRE(R <= (1 << 30) && V <= (1 << 30) && H <= (1 << 30), "shape too large");
-    REQUIRE(target_div >= 1 && target_div <= (1 << 30), "target_div must be >= 1");
-    REQUIRE(ldh >= H && ldv >= V && ldh % 4 == 0, "leading dimensions: ldh >= H, ldh %% 4 == 0, ldv >= V");
-    REQUIRE(aligned16(h) && aligned16(W), "h and W must be 16-byte aligned");
-    RowllArgs a;
-    a.R = (int)R; a.V = (int)V; a.H = (int)H; a.gauss = gauss != 0; a.target_div = (int)target_div;
-    a.tiles_m = (int)((R + ROWLL_BM - 1) / ROWLL_BM); a.tiles_n = (int)((V + ROWLL_BN - 1) / ROWLL_BN);
-    REQUIRE((int64_t)a.tiles_m * a.tiles_n <= 0x7fffffff, "shape too large");
-    REQUIRE(workspace != nullptr && workspace_bytes >= rowll_partial_floats(R, V) * (int64_t)sizeof(float),
-            "workspace of mdbn_rowll_workspace_bytes needed");
-    a.ldh = ldh; a.ldv = ldv; a.h = h; a.W = W; a.vbias = vbias; a.target = target;
-    a.partial = reinterpret_cast<float*>(workspace); a.out = out;
-    HIP_OK(launch_rowll(a, (hipStream_t)stream));
-    return MDBN_OK;
-}
-
-int mdbn_sample_replicas(mdbn_ctx* ctx, void* stream, const float* mean, int64_t N, int64_t H, int64_t ldh, int64_t S,
-                         float* sample, float* entropy, const mdbn_rng* rng)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx && mean && sample && rng && N > 0 && H > 0 && S > 0 && ldh >= H, "bad arguments");
-    REQUIRE(N <= ((int64_t)1 << 40) / S && rng->row_offset <= ((uint64_t)1 << 40), "shape too large");
-    ReplicaArgs a;
-    a.N = N; a.S = S; a.H = H; a.ldh = ldh; a.mean = mean; a.sample = sample; a.entropy = entropy;
-    a.rng = make_key(*rng, rng->draw);
-    HIP_OK(launch_sample_replicas(a, (hipStream_t)stream));
-    return MDBN_OK;
-}
-
-// ---------------------------------------------------------------------------------- centred CD (mdbn_center.hip)
-int mdbn_center_workspace_bytes(mdbn_ctx* ctx, int64_t V, int64_t H, int64_t* bytes)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx && bytes && V > 0 && H > 0 && V <= (1 << 30) && H <= CENTER_MAX_H, "bad arguments (0 < V <= 2^30, 0 < H <= %d)", CENTER_MAX_H);
-    *bytes = center_partial_floats(V, H) * (int64_t)sizeof(float);
-    return MDBN_OK;
-}
-
-int mdbn_center_offsets(mdbn_ctx* ctx, void* stream, const float* v0, int64_t ldv, const float* ph, int64_t ldh, int64_t B,
-                        int64_t V, int64_t H, float nu, float* mu, float* lam)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx && v0 && ph && mu && lam, "null pointer");
-    REQUIRE(B > 0 && V > 0 && H > 0 && B <= (1 << 30) && V <= (1 << 30) && H <= (1 << 30), "sizes must be positive (and <= 2^30)");
-    REQUIRE(ldv >= V && ldh >= H && ldv % 4 == 0 && ldh % 4 == 0, "leading dimensions: ld >= cols, ld %% 4 == 0");
-    REQUIRE(aligned16(v0) && aligned16(ph), "v0 and ph must be 16-byte aligned");
-    REQUIRE((reinterpret_cast<uintptr_t>(mu) & 3u) == 0 && (reinterpret_cast<uintptr_t>(lam) & 3u) == 0, "mu / lam not aligned");
-    REQUIRE(nu > 0.f && nu <= 1.f, "nu must lie in (0, 1]");
-    CenterOffsetsArgs a;
-    a.v0 = v0; a.ph = ph; a.ldv = ldv; a.ldh = ldh; a.B = (int)B; a.V = (int)V; a.H = (int)H; a.nu = nu; a.mu = mu; a.lam = lam;
-    HIP_OK(launch_center_offsets(a, (hipStream_t)stream));
-    return MDBN_OK;
-}
-
-int mdbn_center_stats(mdbn_ctx* ctx, void* stream, float* stats, int64_t V, int64_t H, int64_t ldv, int64_t ldh, const float* mu,
-                      const float* lam, float row_scale, void* workspace, int64_t workspace_bytes)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx && stats && mu && lam && workspace, "null pointer");
-    REQUIRE(V > 0 && H > 0 && V <= (1 << 30), "sizes must be positive (and V <= 2^30)");
-    REQUIRE(H <= CENTER_MAX_H, "H = %lld: at most %d hidden units", (long long)H, CENTER_MAX_H);
-    REQUIRE(ldv >= V && ldh >= H && ldv % 4 == 0 && ldh % 4 == 0, "leading dimensions: ld >= cols, ld %% 4 == 0");
-    REQUIRE(aligned16(stats) && aligned16(workspace), "stats and workspace must be 16-byte aligned");
-    REQUIRE((reinterpret_cast<uintptr_t>(mu) & 3u) == 0 && (reinterpret_cast<uintptr_t>(lam) & 3u) == 0, "mu / lam not aligned");
-    REQUIRE(row_scale > 0.f && row_scale <= 3.0e38f, "row_scale must be positive and finite");
-    REQUIRE(workspace_bytes >= center_partial_floats(V, H) * (int64_t)sizeof(float), "workspace of mdbn_center_workspace_bytes needed");
-    CenterStatsArgs a;
-    a.stats = stats; a.ldv = ldv; a.ldh = ldh; a.V = (int)V; a.H = (int)H;
-    a.rows = center_rows_per_block(V); a.blocks = (int)center_blocks(V); a.ldp = (int)ru4(H);
-    a.rho = row_scale; a.mu = mu; a.lam = lam; a.partial = reinterpret_cast<float*>(workspace);
-    HIP_OK(launch_center_stats(a, (hipStream_t)stream));
-    return MDBN_OK;
-}
-
-// ---------------------------------------------------------------------------------- sparsity target (mdbn_sparsity.hip)
-int mdbn_sparsity_activity(mdbn_ctx* ctx, void* stream, const float* ph, int64_t ldh, const float* v0, int64_t ldv, int64_t B,
-                           int64_t V, int64_t H, float rate, float* q, float* v_mean)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx && ph && q, "null pointer");
-    REQUIRE((v0 != nullptr) == (v_mean != nullptr), "v0 and v_mean: both or neither");
-    REQUIRE(B > 0 && H > 0 && B <= (1 << 30) && H <= (1 << 30), "sizes must be positive (and <= 2^30)");
-    REQUIRE(ldh >= H && ldh % 4 == 0, "leading dimensions: ld >= cols, ld %% 4 == 0");
-    REQUIRE(aligned16(ph) && (reinterpret_cast<uintptr_t>(q) & 3u) == 0, "ph must be 16-byte aligned, q float-aligned");
-    if (v0) {
-        REQUIRE(V > 0 && V <= (1 << 30), "sizes must be positive (and <= 2^30)");
-        REQUIRE(ldv >= V && ldv % 4 == 0, "leading dimensions: ld >= cols, ld %% 4 == 0");
-        REQUIRE(aligned16(v0) && (reinterpret_cast<uintptr_t>(v_mean) & 3u) == 0, "v0 must be 16-byte aligned, v_mean float-aligned");
-    }
-    REQUIRE(rate > 0.f && rate <= 1.f, "rate must lie in (0, 1]");
-    SparsityActivityArgs a;
-    a.ph = ph; a.v0 = v0; a.ldh = ldh; a.ldv = v0 ? ldv : 0; a.B = (int)B; a.V = v0 ? (int)V : 0; a.H = (int)H;
-    a.rate = rate; a.q = q; a.v_mean = v_mean;
-    HIP_OK(launch_sparsity_activity(a, (hipStream_t)stream));
-    return MDBN_OK;
-}
-
-int mdbn_sparsity_stats(mdbn_ctx* ctx, void* stream, float* stats, int64_t V, int64_t H, int64_t ldv, int64_t ldh, const float* q,
-                        const float* v_mean, float target, float w_scale, float b_scale)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx && stats && q, "null pointer");
-    REQUIRE(V > 0 && H > 0 && V <= (1 << 30) && H <= (1 << 30), "sizes must be positive (and <= 2^30)");
-    REQUIRE(ldv >= V && ldh >= H && ldv % 4 == 0 && ldh % 4 == 0, "leading dimensions: ld >= cols, ld %% 4 == 0");
-    REQUIRE(aligned16(stats), "stats must be 16-byte aligned");
-    REQUIRE((reinterpret_cast<uintptr_t>(q) & 3u) == 0 && (reinterpret_cast<uintptr_t>(v_mean) & 3u) == 0, "q / v_mean not aligned");
-    REQUIRE(target > 0.f && target < 1.f, "target must lie in (0, 1)");
-    REQUIRE(w_scale >= 0.f && w_scale <= 3.0e38f && b_scale >= 0.f && b_scale <= 3.0e38f, "scales must be finite and not negative");
-    REQUIRE(w_scale == 0.f || v_mean, "w_scale > 0 needs v_mean");
-    SparsityStatsArgs a;
-    a.stats = stats; a.ldh = ldh; a.V = (int)V; a.H = (int)H; a.rows = center_rows_per_block(V);
-    a.q = q; a.v_mean = v_mean; a.target = target; a.w_scale = w_scale; a.b_scale = b_scale;
-    HIP_OK(launch_sparsity_stats(a, (hipStream_t)stream));
-    return MDBN_OK;
-}
-
-// ---------------------------------------------------------------------------------- up-down fine-tuning (mdbn_updown.hip)
-namespace {
-
-// Workspace of the two delta-rule steps, in floats (every piece a multiple of 64 floats: 16-byte aligned)
-struct UpdownWs {
-    int64_t V2, P2, pre, mean, stats, junk, partials, inner;
-    int64_t total() const { return V2 + P2 + pre + mean + stats + junk + partials + inner; }
-};
-
-bool updown_gen_fused_ok(const mdbn_ctx* ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, UpdownGeom& ug)
-{
-    return updown_geom(n, V, H, ldv, ldh, std::min(ctx->num_cu, kTargetJobs), ug);
-}
-
-bool updown_rec_fused_ok(const mdbn_ctx* ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, ThinGeom& tg)
-{
-    return thin_geom(n, V, H, ldv, ldh, std::min(ctx->num_cu, kTargetJobs), tg);
-}
-
-int updown_inner_floats(int64_t n, int64_t V, int64_t H, int64_t* out)
-{
-    int64_t bytes = 0;
-    CHECK(mdbn_workspace_bytes(n, V, H, &bytes));
-    // (a propagation carves a fixed cost region off the end and chunks its rows over what is left: the 8 MB floor of
-    //  HipEngine.workspace)
-    *out = ru64(std::max<int64_t>((bytes + 3) / 4, int64_t(2) << 20));
-    return MDBN_OK;
-}
-
-// gen: fused = the cost partials only; composed = stacked operands, prediction, packed statistics, a throw-away hidden bias
-// and speed, cost partials, and the workspace of the launchers it strings together
-int updown_gen_ws(bool fused, const UpdownGeom& ug, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, UpdownWs& w)
-{
-    w = UpdownWs{};
-    if (fused) { w.partials = ru64(ug.G); return MDBN_OK; }
-    w.V2 = ru64(2 * n * ldv); w.P2 = ru64(2 * n * ldh); w.pre = ru64(n * ldv); w.mean = ru64(n * ldv);
-    w.stats = ru64(V * ldh + ldh + ldv + 4); w.junk = ru64(2 * ldh); w.partials = ru64(UD_COST_MAXG);
-    return updown_inner_floats(n, V, H, &w.inner);
-}
-
-// rec: stacked operands, then fused = [s_h | s_v | cost] of the one-pass update, a throw-away visible bias and speed;
-// composed = the packed statistics, the same throw-away vectors and the launchers' workspace
-int updown_rec_ws(bool fused, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, UpdownWs& w)
-{
-    w = UpdownWs{};
-    w.V2 = ru64(2 * n * ldv); w.P2 = ru64(2 * n * ldh); w.junk = ru64(2 * ldv); w.partials = 64;
-    if (fused) { w.stats = ru64(ldh + ldv + 4); return MDBN_OK; }
-    w.stats = ru64(V * ldh + ldh + ldv + 4);
-    return updown_inner_floats(n, V, H, &w.inner);
-}
-
-int updown_check_shape(const mdbn_ctx* ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int path)
-{
-    REQUIRE(ctx != nullptr, "ctx is NULL");
-    REQUIRE(n > 0 && V > 0 && H > 0 && n <= (1 << 24) && V <= (1 << 24) && H <= (1 << 24), "sizes must be positive (and <= 2^24)");
-    REQUIRE(ldv >= V && ldh >= H && ldv % 4 == 0 && ldh % 4 == 0, "leading dimensions: ld >= cols, ld %% 4 == 0");
-    REQUIRE(path >= 0 && path <= 2, "path must be 0 (by shape), 1 (one-pass kernel) or 2 (composed)");
-    return MDBN_OK;
-}
-
-// the rule's own arguments: one statement for both halves (stats is ignored; `gen`: the visible half is updated, else the hidden)
-int updown_check_update(const mdbn_update_args* u, bool gen)
-{
-    REQUIRE(u != nullptr, "upd is NULL");
-    REQUIRE(u->struct_size == sizeof(mdbn_update_args), "mdbn_update_args.struct_size is %llu, this library's struct has %llu bytes",
-            (unsigned long long)u->struct_size, (unsigned long long)sizeof(mdbn_update_args));
-    REQUIRE(u->V > 0 && u->H > 0 && u->ldh >= u->H && u->ldv >= u->V && u->ldh % 4 == 0 && u->ldv % 4 == 0, "bad shape / leading dims");
-    CHECK(check_mat(u->W, u->ldh, u->H, "W"));
-    CHECK(check_mat(u->W_speed, u->ldh, u->H, "W_speed"));
-    REQUIRE(u->W0 == nullptr || aligned16(u->W0), "W0 not aligned");
-    REQUIRE(u->W_planes == nullptr || aligned16(u->W_planes), "W_planes not aligned");
-    if (gen) REQUIRE(u->vbias && u->vbias_speed && !u->hbias && !u->hbias_speed, "generative half: vbias and its speed, hbias NULL");
-    else REQUIRE(u->hbias && u->hbias_speed && !u->vbias && !u->vbias_speed, "recognition half: hbias and its speed, vbias NULL");
-    REQUIRE(u->batch_size > 0.f && u->n_rows > 0.f, "bad divisors");
-    REQUIRE(u->phase == 0, "the delta rules apply the whole rule (phase 0)");
-    return MDBN_OK;
-}
-
-float* updown_take(float*& p, int64_t floats) { float* r = p; p += floats; return r; }
-
-}  // namespace
-
-int mdbn_updown_gen_workspace_bytes(mdbn_ctx* ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int path, int64_t* bytes)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(bytes != nullptr, "bytes is NULL");
-    CHECK(updown_check_shape(ctx, n, V, H, ldv, ldh, path));
-    UpdownGeom ug{};
-    const bool ok = updown_gen_fused_ok(ctx, n, V, H, ldv, ldh, ug);
-    REQUIRE(path != 1 || ok, "the one-pass generative kernel serves n <= %d rows on ldh <= %d", UD_MAXB, UD_MAX_LDH);
-    UpdownWs w;
-    CHECK(updown_gen_ws(path != 2 && ok, ug, n, V, H, ldv, ldh, w));
-    *bytes = w.total() * (int64_t)sizeof(float);
-    return MDBN_OK;
-}
-
-int mdbn_updown_gen_step(mdbn_ctx* ctx, void* stream, const float* x_lo, const float* x_hi, int64_t n, int gauss,
-                         const mdbn_update_args* upd, float* cost_out, int path, void* workspace, int64_t workspace_bytes)
-{
-    CtxScope ctx_scope(ctx);
-    CHECK(updown_check_update(upd, true));
-    const int64_t V = upd->V, H = upd->H, ldv = upd->ldv, ldh = upd->ldh;
-    CHECK(updown_check_shape(ctx, n, V, H, ldv, ldh, path));
-    CHECK(check_mat(x_lo, ldv, V, "x_lo"));
-    CHECK(check_mat(x_hi, ldh, H, "x_hi"));
-    REQUIRE(gauss == 0 || gauss == 1, "gauss must be 0 or 1");
-    REQUIRE(cost_out == nullptr || (reinterpret_cast<uintptr_t>(cost_out) & 3u) == 0, "cost_out not aligned");
-    REQUIRE(workspace != nullptr && aligned16(workspace), "workspace must be a 16-byte aligned device pointer");
-    UpdownGeom ug{};
-    const bool ok = updown_gen_fused_ok(ctx, n, V, H, ldv, ldh, ug);
-    REQUIRE(path != 1 || ok, "the one-pass generative kernel serves n <= %d rows on ldh <= %d", UD_MAXB, UD_MAX_LDH);
-    const bool fused = path != 2 && ok;
-    UpdownWs w;
-    CHECK(updown_gen_ws(fused, ug, n, V, H, ldv, ldh, w));
-    REQUIRE(workspace_bytes >= w.total() * (int64_t)sizeof(float), "workspace of mdbn_updown_gen_workspace_bytes needed");
-    hipStream_t s = (hipStream_t)stream;
-    float* p = reinterpret_cast<float*>(workspace);
-    const float scale = upd->cost_scale;
-
-    if (fused) {
-        UpdownGenArgs a{};
-        a.n = (int)n; a.Bq = ug.Bq; a.V = (int)V; a.H = (int)H; a.ldv = ldv; a.ldh = ldh; a.rpw = ug.rpw; a.G = ug.G;
-        a.x_lo = x_lo; a.x_hi = x_hi; a.gauss = gauss;
-        fill_upd(a.upd, *upd, V, ldh, reinterpret_cast<unsigned short*>(upd->W_planes));
-        a.vb = upd->vbias; a.vbs = upd->vbias_speed; a.inv_rows = 1.0f / upd->n_rows;
-        a.cost_partials = p;
-        HIP_OK(launch_updown_gen(a, ug, s));
-        if (cost_out) HIP_OK(launch_updown_cost_finish(p, ug.G, scale, cost_out, s));
-        return MDBN_OK;
-    }
-
-    float* V2 = updown_take(p, w.V2); float* P2 = updown_take(p, w.P2);
-    float* pre = updown_take(p, w.pre); float* mean = updown_take(p, w.mean);
-    float* stats = updown_take(p, w.stats); float* junk = updown_take(p, w.junk);
-    float* partials = updown_take(p, w.partials);
-    void* inner = p;
-    const int64_t inner_bytes = w.inner * (int64_t)sizeof(float);
-    // g = act(x_hi G^T + c) with the pre-step parameters
-    CHECK(mdbn_propdown_sample(ctx, stream, x_hi, n, ldh, upd->W, V, H, ldv, upd->vbias, gauss, 0, gauss ? nullptr : pre, mean,
-                               nullptr, nullptr, nullptr, nullptr, inner, inner_bytes));
-    if (cost_out) {
-        UpdownCostArgs c{};
-        c.n = (int)n; c.V = (int)V; c.gauss = gauss; c.ldv = ldv; c.x = x_lo; c.pre = gauss ? mean : pre;
-        c.G = (int)std::min<int64_t>(UD_COST_MAXG, (n * V + UD_COST_NT - 1) / UD_COST_NT);
-        c.cost_partials = partials;
-        HIP_OK(launch_updown_cost(c, s));
-        HIP_OK(launch_updown_cost_finish(partials, c.G, scale, cost_out, s));
-    }
-    // V2 = [x_lo; g], P2 = [x_hi; -x_hi]: S = (x_lo - g)^T x_hi, s_v = sum (x_lo - g)
-    UpdownStackArgs k{};
-    k.n = (int)n; k.V = (int)V; k.H = (int)H; k.ldv = ldv; k.ldh = ldh;
-    k.lo = x_lo; k.second = mean; k.hi = x_hi; k.neg = x_hi; k.V2 = V2; k.P2 = P2;
-    HIP_OK(launch_updown_stack(k, s));
-    CHECK(mdbn_cd_stats(ctx, stream, V2, P2, n, V, H, ldv, ldh, stats, inner, inner_bytes));
-    mdbn_update_args u = *upd;
-    u.stats = stats; u.hbias = junk; u.hbias_speed = junk + ldh; u.cost_out = nullptr;      // the hidden half must not move
-    CHECK(mdbn_apply_update(ctx, stream, &u));
-    return MDBN_OK;
-}
-
-int mdbn_updown_rec_workspace_bytes(mdbn_ctx* ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int path, int64_t* bytes)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(bytes != nullptr, "bytes is NULL");
-    CHECK(updown_check_shape(ctx, n, V, H, ldv, ldh, path));
-    ThinGeom tg{};
-    const bool ok = updown_rec_fused_ok(ctx, n, V, H, ldv, ldh, tg);
-    REQUIRE(path != 1 || ok, "the one-pass update serves n <= %d rows on ldh <= 512", TH_MAXB);
-    UpdownWs w;
-    CHECK(updown_rec_ws(path != 2 && ok, n, V, H, ldv, ldh, w));
-    *bytes = w.total() * (int64_t)sizeof(float);
-    return MDBN_OK;
-}
-
-int mdbn_updown_rec_step(mdbn_ctx* ctx, void* stream, const float* y_lo, const float* y_hi, const float* r, int64_t n,
-                         const mdbn_update_args* upd, int path, void* workspace, int64_t workspace_bytes)
-{
-    CtxScope ctx_scope(ctx);
-    CHECK(updown_check_update(upd, false));
-    const int64_t V = upd->V, H = upd->H, ldv = upd->ldv, ldh = upd->ldh;
-    CHECK(updown_check_shape(ctx, n, V, H, ldv, ldh, path));
-    CHECK(check_mat(y_lo, ldv, V, "y_lo"));
-    CHECK(check_mat(y_hi, ldh, H, "y_hi"));
-    CHECK(check_mat(r, ldh, H, "r"));
-    REQUIRE(workspace != nullptr && aligned16(workspace), "workspace must be a 16-byte aligned device pointer");
-    ThinGeom tg{};
-    const bool ok = updown_rec_fused_ok(ctx, n, V, H, ldv, ldh, tg);
-    REQUIRE(path != 1 || ok, "the one-pass update serves n <= %d rows on ldh <= 512", TH_MAXB);
-    const bool fused = path != 2 && ok;
-    UpdownWs w;
-    CHECK(updown_rec_ws(fused, n, V, H, ldv, ldh, w));
-    REQUIRE(workspace_bytes >= w.total() * (int64_t)sizeof(float), "workspace of mdbn_updown_rec_workspace_bytes needed");
-    hipStream_t s = (hipStream_t)stream;
-    float* p = reinterpret_cast<float*>(workspace);
-    float* V2 = updown_take(p, w.V2); float* P2 = updown_take(p, w.P2);
-    float* stats = updown_take(p, w.stats); float* junk = updown_take(p, w.junk);
-    float* partials = updown_take(p, w.partials);
-    // V2 = [y_lo; y_lo], P2 = [y_hi; -r]: S = y_lo^T (y_hi - r), s_h = sum (y_hi - r)
-    UpdownStackArgs k{};
-    k.n = (int)n; k.V = (int)V; k.H = (int)H; k.ldv = ldv; k.ldh = ldh;
-    k.lo = y_lo; k.second = y_lo; k.hi = y_hi; k.neg = r; k.V2 = V2; k.P2 = P2;
-    HIP_OK(launch_updown_stack(k, s));
-    mdbn_update_args u = *upd;
-    u.vbias = junk; u.vbias_speed = junk + ldv; u.cost_out = nullptr;                       // the visible half must not move
-    if (fused) {
-        // the rank-2n update of thin_update_kernel on the stacked operands: W and its speed read and written once
-        ThinUpdArgs t{};
-        t.B = (int)n; t.Bq = tg.Bq; t.V = (int)V; t.H = (int)H; t.ldv = ldv; t.ldh = ldh; t.G = tg.Gu; t.rpw = tg.rpu;
-        t.V2 = V2; t.P2 = P2;
-        t.S = nullptr; t.s_h = stats; t.s_v = stats + ldh; t.cost = stats + ldh + ldv;
-        t.cost_partials = partials; t.n_cost = 0;
-        t.do_upd = 1;
-        fill_upd(t.upd, u, V, ldh, reinterpret_cast<unsigned short*>(u.W_planes));
-        fill_bias_upd(t.bu, u, H);
-        HIP_OK(launch_thin_update(t, tg, s));
-        return MDBN_OK;
-    }
-    void* inner = p;
-    const int64_t inner_bytes = w.inner * (int64_t)sizeof(float);
-    CHECK(mdbn_cd_stats(ctx, stream, V2, P2, n, V, H, ldv, ldh, stats, inner, inner_bytes));
-    u.stats = stats;
-    CHECK(mdbn_apply_update(ctx, stream, &u));
-    return MDBN_OK;
-}
-
-int mdbn_philox_host(float* out, int64_t rows, int64_t cols, int64_t ld, const mdbn_rng* rng)
-{
-    REQUIRE(out && rng && rows >= 0 && cols >= 0 && ld >= cols, "bad arguments");
-    const PhiloxKey k = make_key(*rng, rng->draw);
-    for (int64_t r = 0; r < rows; ++r) {
-        const uint64_t g = k.row_offset + (uint64_t)r;
-        for (int64_t c = 0; c < cols; ++c) {
-            uint32_t w[4];
-            philox4x32_10((uint32_t)c, (uint32_t)(g >> 2), k.draw, k.step, k.k0, k.k1, w);
-            out[r * ld + c] = philox_u01(w[g & 3]);
-        }
-    }
-    return MDBN_OK;
-}
-
-// ---------------------------------------------------------------------------------- row feeder (host-resident table)
-// Minibatch rows of a table that stays in host memory reach the device WITHOUT a kernel on the CUs: worker threads
-// gather the rows into a pinned staging slot, one hipMemcpyAsync per minibatch moves the slot on the feeder's own copy
-// stream (SDMA), the consuming stream waits for the copy's event.  A kernel reading the pinned table over PCIe beside the
-// step slows every GEMM of the step (one-workgroup-per-CU grids: step 145 -> 215 us); an SDMA copy
-// does not (145.7 -> 147.3 us).  The ring is `slots` deep so the copy of minibatch t + 2 runs beside step t.
-using mdbn_host::RowPool;
-
-struct mdbn_feeder {
-    int device = 0;
-    const float* table = nullptr; int64_t n_rows = 0, cols = 0, ld = 0, max_rows = 0, ld_dev = 0;
-    int slots = 0;
-    std::vector<float*> dev, staging;
-    std::vector<hipEvent_t> copied, consumed;
-    std::vector<char> copied_set, consumed_set, busy;
-    hipStream_t copy_stream = nullptr, copy_stream2 = nullptr;     // the second one only with feed_copy_streams = 2
-    hipEvent_t half_done = nullptr, half_go = nullptr;
-    RowPool* pool = nullptr;
-    std::thread dispatcher;
-    std::mutex m;
-    std::condition_variable cv;
-    struct Job { int64_t ticket; std::vector<int64_t> idx; bool identity; int64_t n; };
-    struct Done { int slot; int rc; int64_t n; };
-    struct Staged { int64_t ticket; int slot; int rc; int64_t n; };
-    std::deque<Job> queue;                        // submitted
-    std::deque<Staged> staged;                    // gathered into pinned staging, copy not yet enqueued
-    std::set<int64_t> inflight;                   // taken off `queue`, not yet in `ready`
-    std::map<int64_t, Done> ready;                // copy enqueued, not yet acquired
-    std::map<int64_t, int> held;                  // acquired, not yet released: ticket -> slot
-    std::thread copier;
-    int64_t next_ticket = 0;
-    int next_slot = 0;
-    bool stop = false;
-    // host-side time spent per stage (mdbn_feeder_stats), seconds
-    double t_gather = 0, t_copy_call = 0, t_acquire_wait = 0;
-    int64_t n_fed = 0, n_acquired = 0;
-    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-    // stage 1 (dispatcher + pool): rows -> pinned staging slot
-    void run()
-    {
-        for (;;) {
-            Job job;
-            int slot;
-            {
-                std::unique_lock<std::mutex> l(m);
-                cv.wait(l, [&] { return stop || (!queue.empty() && !busy[next_slot]); });
-                if (stop) return;
-                job = std::move(queue.front());
-                queue.pop_front();
-                slot = next_slot;
-                next_slot = (next_slot + 1) % slots;
-                busy[slot] = 1;
-                inflight.insert(job.ticket);
-            }
-            int rc = MDBN_OK;
-            // the staging slot is free once the copy that last read it has finished (long ago in steady state)
-            if (copied_set[slot] && hipEventSynchronize(copied[slot]) != hipSuccess) rc = MDBN_EHIP;
-            const double t0 = now();
-            if (rc == MDBN_OK && !pool->gather(table, n_rows, cols, ld, job.identity ? nullptr : job.idx.data(), job.n,
-                                               staging[slot], ld_dev))
-                rc = MDBN_EINVAL;
-            {
-                std::lock_guard<std::mutex> l(m);
-                t_gather += now() - t0;
-                staged.push_back(Staged{job.ticket, slot, rc, job.n});
-            }
-            cv.notify_all();
-        }
-    }
-    // stage 2 (copier): staging slot -> device slot, one copy on the copy stream.  Its own thread: enqueueing an 8-MB
-    // hipMemcpyAsync takes the host ~100 us, during which stage 1 gathers the next minibatch.
-    void copy_loop()
-    {
-        (void)hipSetDevice(device);
-        for (;;) {
-            Staged st;
-            {
-                std::unique_lock<std::mutex> l(m);
-                cv.wait(l, [&] { return stop || !staged.empty(); });
-                if (stop) return;
-                st = staged.front();
-                staged.pop_front();
-            }
-            int rc = st.rc;
-            const double t0 = now();
-            if (rc == MDBN_OK) {
-                // the device slot is free once the step that last read it has finished: stream order, no host wait
-                hipError_t e = consumed_set[st.slot] ? hipStreamWaitEvent(copy_stream, consumed[st.slot], 0) : hipSuccess;
-                const int64_t n1 = copy_stream2 ? (st.n + 1) / 2 : st.n;       // rows of the first copy
-                if (e == hipSuccess && copy_stream2 && st.n > n1) {
-                    // second half on the second stream, ordered after the same "slot is free" point
-                    e = hipEventRecord(half_go, copy_stream);
-                    if (e == hipSuccess) e = hipStreamWaitEvent(copy_stream2, half_go, 0);
-                    if (e == hipSuccess)
-                        e = hipMemcpyAsync(dev[st.slot] + n1 * ld_dev, staging[st.slot] + n1 * ld_dev,
-                                           (size_t)(st.n - n1) * ld_dev * sizeof(float), hipMemcpyHostToDevice, copy_stream2);
-                    if (e == hipSuccess) e = hipEventRecord(half_done, copy_stream2);
-                }
-                if (e == hipSuccess)
-                    e = hipMemcpyAsync(dev[st.slot], staging[st.slot], (size_t)n1 * ld_dev * sizeof(float), hipMemcpyHostToDevice,
-                                       copy_stream);
-                if (e == hipSuccess && copy_stream2 && st.n > n1) e = hipStreamWaitEvent(copy_stream, half_done, 0);
-                if (e == hipSuccess) e = hipEventRecord(copied[st.slot], copy_stream);
-                if (e != hipSuccess) rc = MDBN_EHIP;
-                else copied_set[st.slot] = 1;
-            }
-            {
-                std::lock_guard<std::mutex> l(m);
-                ready[st.ticket] = Done{st.slot, rc, st.n};
-                inflight.erase(st.ticket);
-                t_copy_call += now() - t0;
-                ++n_fed;
-            }
-            cv.notify_all();
-        }
-    }
-};
-
-int mdbn_host_gather_rows(const float* table, int64_t n_rows, int64_t cols, int64_t ld, const int64_t* indexes, int64_t n,
-                          float* out, int64_t ld_out, int threads)
-{
-    REQUIRE(table && out && n_rows > 0 && cols > 0 && ld >= cols && ld_out >= cols && n >= 0, "bad arguments");
-    REQUIRE(threads >= 1 && threads <= 64, "threads must be in [1, 64]");
-    REQUIRE(indexes != nullptr || n <= n_rows, "identity gather longer than the table");
-    RowPool pool(threads - 1);
-    if (!pool.gather(table, n_rows, cols, ld, indexes, n, out, ld_out)) return fail(MDBN_EINVAL, "row index out of range");
-    return MDBN_OK;
-}
-
-int mdbn_feeder_create(mdbn_ctx* ctx, const float* table, int64_t n_rows, int64_t cols, int64_t ld, int64_t max_rows,
-                       int slots, float* const* device_slots, int64_t ld_device, int threads, mdbn_feeder** out)
-{
-    CtxScope ctx_scope(ctx);
-    REQUIRE(ctx != nullptr && out != nullptr, "ctx / out is NULL");
-    REQUIRE(table && n_rows > 0 && cols > 0 && ld >= cols && max_rows > 0, "bad table");
-    REQUIRE(slots >= 2 && slots <= 16 && device_slots != nullptr, "slots must be in [2, 16]");
-    REQUIRE(ld_device >= cols && ld_device % 4 == 0, "bad device leading dimension");
-    REQUIRE(threads >= 1 && threads <= 64, "threads must be in [1, 64]");
-    for (int i = 0; i < slots; ++i) REQUIRE(device_slots[i] && aligned16(device_slots[i]), "device slot NULL / not 16-byte aligned");
-    HIP_OK(hipSetDevice(ctx->device));
-    mdbn_feeder* f = new mdbn_feeder;
-    f->device = ctx->device;
-    f->table = table; f->n_rows = n_rows; f->cols = cols; f->ld = ld; f->max_rows = max_rows; f->ld_dev = ld_device;
-    f->slots = slots;
-    f->copied_set.assign(slots, 0); f->consumed_set.assign(slots, 0); f->busy.assign(slots, 0);
-    hipError_t e = hipStreamCreateWithFlags(&f->copy_stream, hipStreamNonBlocking);
-    if (e == hipSuccess && g_opt_feed_copy_streams == 2) {
-        e = hipStreamCreateWithFlags(&f->copy_stream2, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&f->half_done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&f->half_go, hipEventDisableTiming);
-    }
-    for (int i = 0; i < slots && e == hipSuccess; ++i) {
-        float* st = nullptr;
-        hipEvent_t a = nullptr, b = nullptr;
-        e = hipHostMalloc(reinterpret_cast<void**>(&st), (size_t)max_rows * ld_device * sizeof(float), hipHostMallocDefault);
-        if (e == hipSuccess) { memset(st, 0, (size_t)max_rows * ld_device * sizeof(float)); f->staging.push_back(st); }   // pad columns stay zero
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&a, hipEventDisableTiming);
-        if (e == hipSuccess) { f->copied.push_back(a); e = hipEventCreateWithFlags(&b, hipEventDisableTiming); }
-        if (e == hipSuccess) f->consumed.push_back(b);
-        f->dev.push_back(device_slots[i]);
-    }
-    if (e != hipSuccess) {
-        for (float* st : f->staging) (void)hipHostFree(st);
-        for (hipEvent_t ev : f->copied) (void)hipEventDestroy(ev);
-        for (hipEvent_t ev : f->consumed) (void)hipEventDestroy(ev);
-        if (f->half_done) (void)hipEventDestroy(f->half_done);
-        if (f->half_go) (void)hipEventDestroy(f->half_go);
-        if (f->copy_stream2) (void)hipStreamDestroy(f->copy_stream2);
-        if (f->copy_stream) (void)hipStreamDestroy(f->copy_stream);
-        delete f;
-        return fail(MDBN_EHIP, "row feeder: %s", hipGetErrorString(e));
-    }
-    f->pool = new RowPool(threads - 1);           // the dispatcher thread is the pool's last worker
-    f->dispatcher = std::thread([f] { f->run(); });
-    f->copier = std::thread([f] { f->copy_loop(); });
-    *out = f;
-    return MDBN_OK;
-}
-
-int mdbn_feeder_submit(mdbn_feeder* f, const int64_t* indexes, int64_t n, int64_t* ticket)
-{
-    REQUIRE(f != nullptr && ticket != nullptr, "feeder / ticket is NULL");
-    REQUIRE(n > 0 && n <= f->max_rows, "row count outside (0, max_rows]");
-    REQUIRE(indexes != nullptr || n <= f->n_rows, "identity gather longer than the table");
-    mdbn_feeder::Job job;
-    job.identity = indexes == nullptr;
-    job.n = n;
-    if (indexes) job.idx.assign(indexes, indexes + n);          // the caller's array may go away
-    {
-        std::lock_guard<std::mutex> l(f->m);
-        job.ticket = *ticket = f->next_ticket++;
-        f->queue.push_back(std::move(job));
-    }
-    f->cv.notify_all();
-    return MDBN_OK;
-}
-
-int mdbn_feeder_acquire(mdbn_feeder* f, int64_t ticket, void* stream, int* slot)
-{
-    REQUIRE(f != nullptr && slot != nullptr, "feeder / slot is NULL");
-    mdbn_feeder::Done d;
-    {
-        std::unique_lock<std::mutex> l(f->m);
-        bool pending = f->ready.count(ticket) != 0 || f->inflight.count(ticket) != 0;
-        if (!pending)
-            for (const auto& j : f->queue) pending = pending || j.ticket == ticket;
-        if (!pending) return fail(MDBN_EINVAL, "row feeder: ticket %lld is not pending", (long long)ticket);
-        // tickets are served in submission order on a ring of `slots`: with every slot held by the caller the ring cannot
-        // reach this ticket
-        if (!f->ready.count(ticket) && (int)f->held.size() >= f->slots)
-            return fail(MDBN_EINVAL, "row feeder: all %d slots are held; release one before acquiring ticket %lld", f->slots,
-                        (long long)ticket);
-        // ... and with every slot taken by EARLIER tickets that only this caller can free (ready or about to be, or held),
-        // a ticket that has not been started yet never will be: refuse instead of blocking for ever (slots = 3, tickets
-        // 0..3 submitted, acquire(3))
-        if (!f->ready.count(ticket) && !f->inflight.count(ticket) &&
-            (int)(f->ready.size() + f->held.size() + f->inflight.size()) >= f->slots)
-            return fail(MDBN_EINVAL, "row feeder: ticket %lld cannot start while %d earlier tickets occupy all %d slots; "
-                        "acquire and release them first (tickets are served in submission order)", (long long)ticket,
-                        (int)(f->ready.size() + f->held.size() + f->inflight.size()), f->slots);
-        const double t0 = mdbn_feeder::now();
-        f->cv.wait(l, [&] { return f->ready.count(ticket) != 0 || f->stop; });
-        f->t_acquire_wait += mdbn_feeder::now() - t0;
-        ++f->n_acquired;
-        if (!f->ready.count(ticket)) return fail(MDBN_EINVAL, "row feeder: shut down");
-        d = f->ready[ticket];
-        f->ready.erase(ticket);
-        if (d.rc != MDBN_OK) {
-            f->busy[d.slot] = 0;
-            l.unlock();
-            f->cv.notify_all();
-            return fail(d.rc, d.rc == MDBN_EINVAL ? "row feeder: row index out of range" : "row feeder: a HIP call failed");
-        }
-        f->held[ticket] = d.slot;
-    }
-    HIP_OK(hipStreamWaitEvent((hipStream_t)stream, f->copied[d.slot], 0));
-    *slot = d.slot;
-    return MDBN_OK;
-}
-
-int mdbn_feeder_release(mdbn_feeder* f, int64_t ticket, void* stream)
-{
-    REQUIRE(f != nullptr, "feeder is NULL");
-    int slot;
-    {
-        std::lock_guard<std::mutex> l(f->m);
-        auto it = f->held.find(ticket);
-        if (it == f->held.end()) return fail(MDBN_EINVAL, "row feeder: ticket %lld is not held", (long long)ticket);
-        slot = it->second;
-        f->held.erase(it);
-    }
-    HIP_OK(hipEventRecord(f->consumed[slot], (hipStream_t)stream));
-    {
-        std::lock_guard<std::mutex> l(f->m);
-        f->consumed_set[slot] = 1;
-        f->busy[slot] = 0;
-    }
-    f->cv.notify_all();
-    return MDBN_OK;
-}
-
-int mdbn_feeder_stats(mdbn_feeder* f, double* out5)
-{
-    REQUIRE(f != nullptr && out5 != nullptr, "feeder / out is NULL");
-    std::lock_guard<std::mutex> l(f->m);
-    out5[0] = (double)f->n_fed;
-    out5[1] = f->n_fed ? 1e6 * f->t_gather / f->n_fed : 0.0;
-    out5[2] = f->n_fed ? 1e6 * f->t_copy_call / f->n_fed : 0.0;
-    out5[3] = (double)f->n_acquired;
-    out5[4] = f->n_acquired ? 1e6 * f->t_acquire_wait / f->n_acquired : 0.0;
-    f->t_gather = f->t_copy_call = f->t_acquire_wait = 0;
-    f->n_fed = f->n_acquired = 0;
-    return MDBN_OK;
-}
-
-int mdbn_feeder_cancel(mdbn_feeder* f)
-{
-    REQUIRE(f != nullptr, "feeder is NULL");
-    std::unique_lock<std::mutex> l(f->m);
-    f->queue.clear();
-    f->cv.wait(l, [&] { return f->inflight.empty(); });
-    for (auto& kv : f->ready) f->busy[kv.second.slot] = 0;     // uploaded (or failed) and never read
-    f->ready.clear();
-    l.unlock();
-    f->cv.notify_all();
-    return MDBN_OK;
-}
-
-int mdbn_feeder_destroy(mdbn_feeder* f)
-{
-    if (!f) return MDBN_OK;
-    {
-        std::lock_guard<std::mutex> l(f->m);
-        f->stop = true;
-    }
-    f->cv.notify_all();
-    if (f->dispatcher.joinable()) f->dispatcher.join();
-    if (f->copier.joinable()) f->copier.join();
-    delete f->pool;
-    (void)hipSetDevice(f->device);
-    if (f->copy_stream) (void)hipStreamSynchronize(f->copy_stream);
-    if (f->copy_stream2) (void)hipStreamSynchronize(f->copy_stream2);
-    if (f->half_done) (void)hipEventDestroy(f->half_done);
-    if (f->half_go) (void)hipEventDestroy(f->half_go);
-    if (f->copy_stream2) (void)hipStreamDestroy(f->copy_stream2);
-    for (float* st : f->staging) (void)hipHostFree(st);
-    for (hipEvent_t ev : f->copied) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : f->consumed) (void)hipEventDestroy(ev);
-    if (f->copy_stream) (void)hipStreamDestroy(f->copy_stream);
-    delete f;
     return MDBN_OK;
 }
 

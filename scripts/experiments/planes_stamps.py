@@ -8,7 +8,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 out = os.path.join(ROOT, "gpurun_out"); os.makedirs(out, exist_ok=True)
 so = os.path.join(out, "libmdbn_planes_stamp.so")
-src = [os.path.join(ROOT, "mdbn_amd", "csrc", f) for f in ("mdbn_kernels.hip", "mdbn_planes.hip", "mdbn_small.hip", "mdbn_capi.hip")]
+from mdbn_amd import build
+src = [os.path.join(build.CSRC, f) for f in build.SOURCES]
 subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-DMDBN_STAMP"] + src + ["-o", so])
 import numpy as np, torch
 from mdbn_amd import _lib

@@ -12,6 +12,7 @@ from _knobs import KNOBS
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TESTS = os.path.join(ROOT, "tests")
 CAPI = os.path.join(ROOT, "mdbn_amd", "csrc", "mdbn_capi.hip")
+CAPI_INTERNAL = os.path.join(ROOT, "mdbn_amd", "csrc", "mdbn_capi_internal.h")
 HEADER = os.path.join(ROOT, "include", "mdbn_hip.h")
 
 
@@ -32,8 +33,8 @@ def _library_knobs():
 
 
 def _options_defaults():
-    """{Options field: default} parsed from struct Options of mdbn_capi.hip."""
-    src = open(CAPI).read()
+    """{Options field: default} parsed from struct Options of mdbn_capi_internal.h."""
+    src = open(CAPI_INTERNAL).read()
     body = src[src.index("struct Options {"):]
     body = body[:body.index("};")]
     out = {}

@@ -6,6 +6,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAPI = os.path.join(ROOT, "mdbn_amd", "csrc", "mdbn_capi.hip")
+CAPI_INTERNAL = os.path.join(ROOT, "mdbn_amd", "csrc", "mdbn_capi_internal.h")
 HEADER = os.path.join(ROOT, "include", "mdbn_hip.h")
 
 
@@ -26,7 +27,7 @@ def test_the_option_is_a_flag_of_the_context_and_set_option_reaches_it():
 
 
 def test_a_fresh_context_has_it_on():
-    src = open(CAPI).read()
+    src = open(CAPI_INTERNAL).read()
     body = src[src.index("struct Options {"):]
     assert re.search(r"^\s+int slab_tail = 1;", body[:body.index("};")], re.M)
 
