@@ -704,6 +704,70 @@ int  mdbn_updown_rec_workspace_bytes(mdbn_ctx *ctx, int64_t n, int64_t V, int64_
 int  mdbn_updown_rec_step(mdbn_ctx *ctx, void *stream, const float *y_lo, const float *y_hi, const float *r, int64_t n,
                           const mdbn_update_args *upd, int path, void *workspace, int64_t workspace_bytes);
 
+/* Categorical visible units: K-ary softmax groups (Salakhutdinov, Mnih & Hinton 2007) inside a Bernoulli visible layer.
+ * group_start[0 .. n_groups] (int32) are column offsets, strictly ascending, 0 <= group_start[0], group_start[n_groups] <= V;
+ * group g is columns group_start[g] .. group_start[g + 1] - 1, of 2 .. MDBN_GROUP_MAX columns, exactly one of which is on.
+ * The groups are adjacent (one contiguous span); the columns before and after the span are ordinary Bernoulli units;
+ * n_groups = 0 (no table read, both pointers may be NULL) is a plain Bernoulli layer.  The caller passes BOTH copies of the
+ * table: `group_start` in device memory, which the kernel reads, and `group_start_host`, the same values in host memory,
+ * which the library checks before anything is launched -- no call synchronises or copies to find out.  That the two agree is
+ * the caller's contract (the kernel clamps what the device copy says to the span the host copy gives, so a stale device copy
+ * gives wrong groups, never an access outside the row).
+ *
+ * mdbn_group_softmax_sample: p(v | h) from the visible pre-activations pre [B, ldv] = h W^T + vbias (what
+ * mdbn_propdown_sample(gauss = 1) stores as its mean).  Per row and group, with m = max_c x_c:  e_c = exp(x_c - m) (the
+ * hardware exponential),  Z = sum_c e_c in ascending c in float32,  mean_c = e_c / Z (correctly rounded).  One uniform per
+ * (row, group), addressed at the group's FIRST column -- counter (col, global_row >> 2, rng->draw, rng->step), word
+ * global_row & 3, rng->row_offset honoured (philox.h) --; the category is the first c with u < C_c, C_c the running float32
+ * sum of the stored means in ascending c, and the LAST one when none qualifies (C_{K-1} may fall short of the largest
+ * uniform, 1 - 2^-25).  sample is 0 / 1 floats with exactly one 1 per group.  A Bernoulli column is the arithmetic and the
+ * addressing of mdbn_propdown_sample(gauss = 0): mean = sigmoid(x), sample = (u < mean) with the column's own uniform, so
+ * n_groups = 0 reproduces that call's mean and sample bit for bit.  mean, sample and tap (a second copy of the sample, for a
+ * chain tap) may each be NULL; mean may be `pre` itself (in place).  With v0 [B, ldv] the cost
+ *   sum over groups of sum_c v0_c (log Z - (x_c - m))  +  sum over Bernoulli columns of v0 softplus(-x) + (1 - v0) softplus(x)
+ * -- the categorical cross-entropy from the log-sum-exp, finite where a probability underflows -- is written to cost_sum[0]
+ * (cost_sum: 4 floats, 16-byte aligned; [1..3] are zeroed) through per-workgroup partials in `workspace`
+ * (mdbn_group_softmax_workspace_bytes; only needed with v0) summed in a fixed order.  No atomics: two runs agree bit for
+ * bit.  Pad columns V..ldv-1 are neither read nor written.
+ *
+ * mdbn_cd_step_grouped: mdbn_cd_step for a layer with groups, composed from the propagation passes, the kernel above and
+ * mdbn_cd_stats:  gather;  propup (ph_mean, hidden sample);  k x [propdown to the linear pre-activations -> the group kernel
+ * (means in place, visible sample) -> propup from the visible SAMPLE];  mdbn_cd_stats.  It leaves what
+ * mdbn_cd_step(keep_f32 = 1) leaves: V2 rows 0..B-1 = v0, rows B..2B-1 = the last step's visible means; P2 = ph_mean and
+ * -nh_mean; hs, vs; the packed [S | s_h | s_v | cost], the cost slot holding the cost above of the LAST step's
+ * pre-activations against v0.  PCD: the chain starts from a->persistent, which is overwritten with the last hidden sample.
+ * trace_h / trace_v as in mdbn_cd_args.  Draw numbering, that of mdbn_cd_step: 0 = the positive-phase hidden draw, 2t - 1 =
+ * the visible draw of Gibbs step t (one uniform per Bernoulli column, one per group at its first column), 2t = its hidden
+ * draw -- a layer with n_groups = 0 follows the chain of mdbn_cd_step on the f32-operand path.  a->vs is required; the
+ * plane, keep_f32 and gather-ahead fields of `a` are ignored (W planes handed in are neither read nor re-split).
+ * MDBN_EINVAL with a message, before any launch and with every output untouched: a->gauss, a->sample_stats, an invalid
+ * table (not ascending, a group of fewer than 2 or more than MDBN_GROUP_MAX columns, a boundary beyond V, a missing copy),
+ * and what mdbn_cd_step refuses; a short workspace (mdbn_workspace_bytes serves) is MDBN_ENOSPC, likewise before any launch.
+ *
+ * mdbn_center_hidden_rows: the hidden-bias statistic of the centred gradient, s_h' = s_h - row_scale S'^T mu (mdbn_center_stats),
+ * formed from the rows of the step's scratch instead of from S -- mathematically the same number:
+ *   d_r = mu . (x_r - mu) over the 2B rows of V2 = [v0; nv],   q = s_v . mu,
+ *   s_h_out[j] = s_h[j] - row_scale (sum_{r < 2B} d_r P2[r, j] - q lam[j])        (P2 = [ph_mean; -nh_mean])
+ * On one-hot rows mu . x_r hardly varies, d_r is small, and nothing of the size of (mu . mu) s_h is formed and cancelled; through
+ * S that cancellation multiplies the float32 error of S by sum_i mu_i.  Call it BEFORE mdbn_center_stats (it reads the raw s_h
+ * and s_v of `stats`) with the offsets mdbn_center_offsets left, and store s_h_out [H] over the s_h block afterwards.  When
+ * `stats` went through mdbn_sparsity_stats first (S += w_scale v_mean t', s_h += b_scale t, t = target - q), pass that call's q,
+ * v_mean, target, w_scale and b_scale: S'^T mu then also holds (w_scale (v_mean . mu) - b_scale (mu . mu)) t, which the rows do
+ * not know and the call adds; q = NULL: no such transform ran (the other four are ignored).  Fixed order, no atomics;
+ * workspace: 2B + 3 floats.  Bad arguments: MDBN_EINVAL without a launch. */
+#define MDBN_GROUP_MAX 64
+int  mdbn_center_hidden_rows(mdbn_ctx *ctx, void *stream, const float *V2, int64_t ldv, const float *P2, int64_t ldh,
+                             int64_t B, int64_t V, int64_t H, const float *stats, const float *mu, const float *lam,
+                             float row_scale, const float *q, const float *v_mean, float target, float w_scale,
+                             float b_scale, float *s_h_out, void *workspace, int64_t workspace_bytes);
+int  mdbn_group_softmax_workspace_bytes(mdbn_ctx *ctx, int64_t B, int64_t V, int64_t *bytes);
+int  mdbn_group_softmax_sample(mdbn_ctx *ctx, void *stream, const float *pre, int64_t B, int64_t ldv, int64_t V,
+                               const int32_t *group_start, const int32_t *group_start_host, int64_t n_groups,
+                               float *mean, float *sample, float *tap, const mdbn_rng *rng, const float *v0,
+                               float *cost_sum, void *workspace, int64_t workspace_bytes);
+int  mdbn_cd_step_grouped(mdbn_ctx *ctx, void *stream, const mdbn_cd_args *a, const int32_t *group_start,
+                          const int32_t *group_start_host, int64_t n_groups);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)) (the float32 softplus terms summed in

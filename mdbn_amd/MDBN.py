@@ -16,21 +16,26 @@ def _fit(net, data, held_out, batch_size, graph_output, **schedule):
     return net
 
 
-def train_top(batch_size, graph_output, joint_train_set, joint_val_set, rng, sparsity_target=None, sparsity_cost=0.0,
-              sparsity_decay=0.9, sparsity_weights=True, centered=False, offset_rate=0.01):
+def train_top(batch_size, graph_output, joint_train_set, joint_val_set, rng, visible_groups=None, sparsity_target=None,
+              sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True, centered=False, offset_rate=0.01):
     """Joint DBN over the concatenated top-layer activations of the modalities (MDBN.py:31-42).  ``sparsity_*``: the sparsity
-    target, ``centered`` / ``offset_rate``: the centred gradient (``RBM.get_cost_updates``)."""
+    target, ``centered`` / ``offset_rate``: the centred gradient (``RBM.get_cost_updates``).  ``visible_groups``: categorical
+    units in the joint layer (``RBM.__init__``) -- a one-hot label block appended to the activations makes it a
+    classification RBM, read out by ``RBM.group_posterior``."""
     joint = shared(joint_train_set)
-    net = DBN(numpy_rng=rng, n_ins=joint.shape[1], **TOP_SHAPE)
+    net = DBN(numpy_rng=rng, n_ins=joint.shape[1], visible_groups=visible_groups, **TOP_SHAPE)
     return _fit(net, joint, joint_val_set, batch_size, graph_output, centered=centered, offset_rate=offset_rate,
                 sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
                 sparsity_weights=sparsity_weights, **TOP_SCHEDULE)
 
 
-def build_bottom_layer(n_visible, layers_sizes, rng):
+def build_bottom_layer(n_visible, layers_sizes, rng, visible_groups=None):
     """The (untrained) DBN of one modality: Gaussian first layer, ``layers_sizes[-1]`` output nodes (MDBN.py:58-62).
-    Constructing it is the only thing that draws from ``rng`` (dbn.py:110-114,155-159)."""
-    return DBN(numpy_rng=rng, n_ins=n_visible, hidden_layers_sizes=layers_sizes[:-1], n_outs=layers_sizes[-1])
+    Constructing it is the only thing that draws from ``rng`` (dbn.py:110-114,155-159).  ``visible_groups``: a categorical
+    modality (copy-number calls, mutation classes: ``utils.one_hot_groups``) -- a Bernoulli first layer with those softmax
+    groups instead."""
+    return DBN(numpy_rng=rng, n_ins=n_visible, hidden_layers_sizes=layers_sizes[:-1], n_outs=layers_sizes[-1],
+               gauss=visible_groups is None, visible_groups=visible_groups)
 
 
 def train_modalities(modalities, rng, group="auto", shuffle_seed=None, graph_output=False):
@@ -91,18 +96,19 @@ def train_modalities(modalities, rng, group="auto", shuffle_seed=None, graph_out
 
 def train_bottom_layer(train_set, validation_set, batch_size=20, k=1, layers_sizes=[40],
                        pretraining_epochs=[800], pretrain_lr=[0.005], lambda_1=0.0, lambda_2=0.1,
-                       rng=None, graph_output=False, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9,
-                       sparsity_weights=True, centered=False, offset_rate=0.01):
+                       rng=None, graph_output=False, visible_groups=None, sparsity_target=None, sparsity_cost=0.0,
+                       sparsity_decay=0.9, sparsity_weights=True, centered=False, offset_rate=0.01):
     """DBN of one modality, Gaussian first layer (MDBN.py:45-76).  Returns the network and its
     outputs for the training and the validation rows (None without validation rows).  ``sparsity_*``: the sparsity target,
-    ``centered`` / ``offset_rate``: the centred gradient (``RBM.get_cost_updates``)."""
+    ``centered`` / ``offset_rate``: the centred gradient (``RBM.get_cost_updates``).  ``visible_groups``: a categorical
+    modality, on a Bernoulli first layer with those softmax groups (``build_bottom_layer``)."""
     rows = shared(train_set)
     held_out = None if validation_set is None else shared(validation_set)
     n_visible, n_top = rows.shape[1], layers_sizes[-1]
     if DBN.verbose:
         print('Visible nodes: %i' % n_visible)
         print('Output nodes: %i' % n_top)
-    net = _fit(build_bottom_layer(n_visible, layers_sizes, rng),
+    net = _fit(build_bottom_layer(n_visible, layers_sizes, rng, visible_groups),
                rows, held_out, batch_size, graph_output, k=k, pretraining_epochs=pretraining_epochs,
                pretrain_lr=pretrain_lr, lambda_1=lambda_1, lambda_2=lambda_2, centered=centered, offset_rate=offset_rate,
                sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,

@@ -2,7 +2,8 @@
 (src/AMLsm2.py:112-205): per network ``<name>_config`` (a dict with 'number_of_nodes', ...),
 ``<name>_params`` (list of ``{p.name: p.get_value()}`` in DBN.params order: W0, b0, W1, b1, ...),
 plus ``classes``, ``holdout``, ``repeats`` -- so files written here load in the reference's
-notebooks and vice versa.
+notebooks and vice versa.  A network whose input layer has categorical units keeps their table as ``visible_groups`` (the
+list of boundaries) in ``<name>_config``.
 
 The reference saves only W and b at the end of a run (vbias, momentum speeds, RNG position and
 epoch are lost, so it cannot resume).  ``save_network(..., resume=True)`` adds
@@ -57,6 +58,9 @@ def save_network(output_file, networks, classes=None, holdout=0.0, repeats=1, co
             continue
         cfg = {'number_of_nodes': dbn.number_of_nodes(),
                'gauss': isinstance(dbn.rbm_layers[0], GRBM)}
+        groups = dbn.rbm_layers[0].visible_groups
+        if groups is not None:                  # categorical input units: the table's boundaries
+            cfg['visible_groups'] = [int(b) for b in groups.host]
         cfg.update((configs or {}).get(name, {}))
         blob[name + '_config'] = cfg
         blob[name + '_params'] = numpy.array([{p.name: p.get_value()} for p in dbn.params], dtype=object)
@@ -86,7 +90,7 @@ def load_network(input_file, names=None, engine=None):
         b_list = [params[2 * i + 1]['b'] for i in range(n_layers)]
         gauss = config.get('gauss', name != 'top')
         dbn = DBN(n_ins=layer_sizes[0], hidden_layers_sizes=list(layer_sizes[1:-1]), n_outs=layer_sizes[-1],
-                  gauss=gauss, W_list=W_list, b_list=b_list, engine=engine)
+                  gauss=gauss, W_list=W_list, b_list=b_list, engine=engine, visible_groups=config.get('visible_groups'))
         if name + '_resume' in npz.files:
             for r, st in zip(dbn.rbm_layers, npz[name + '_resume']):
                 r.vbias.set_value(st['vbias'])

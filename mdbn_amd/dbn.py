@@ -62,8 +62,12 @@ class DBN(object):
                             # or None: this network trains in this process alone (modality-parallel placement, MDBN.py)
 
     def __init__(self, numpy_rng=None, theano_rng=None, n_ins=784, gauss=True,
-                 hidden_layers_sizes=[400], n_outs=40, W_list=None, b_list=None, engine=None):
+                 hidden_layers_sizes=[400], n_outs=40, W_list=None, b_list=None, engine=None, visible_groups=None):
+        """``visible_groups``: categorical units in the INPUT layer (``RBM.__init__``: an int K or ascending boundaries);
+        needs ``gauss=False``.  The layers above are unchanged."""
         self.engine = engine if engine is not None else get_engine()
+        if visible_groups is not None and gauss:
+            raise ValueError("visible_groups needs gauss=False: a Gaussian input layer has no categorical units")
         self.n_ins = n_ins
         self.sigmoid_layers = []
         self.rbm_layers = []
@@ -107,7 +111,8 @@ class DBN(object):
             cls = GRBM if (i == 0 and gauss) else RBM
             rbm_layer = cls(numpy_rng=numpy_rng, theano_rng=theano_rng, input=layer_input,
                             n_visible=input_size, n_hidden=n_out,
-                            W=sigmoid_layer.W, hbias=sigmoid_layer.b, engine=self.engine)
+                            W=sigmoid_layer.W, hbias=sigmoid_layer.b, engine=self.engine,
+                            **(dict(visible_groups=visible_groups) if (i == 0 and visible_groups is not None) else {}))
             self.rbm_layers.append(rbm_layer)
         self._lower_cache = {}
         self.trainer_state = None    # where DBN.training stands (set while it runs with on_step; see training())
@@ -157,7 +162,8 @@ class DBN(object):
         """Mean-field top-down pass, the inverse direction of ``get_output``: ``h`` (activations of ``sigmoid_layers[layer]``,
         host or device matrix) is taken down through ``rbm_layers[layer] .. rbm_layers[0]`` by the layers' conditional means
         (sigmoid(h W^T + vbias); the linear mean h W^T + vbias at a Gaussian bottom layer).  Returns a host array
-        [rows, n_ins].  No random number is consumed: no layer's RNG counter moves."""
+        [rows, n_ins].  No random number is consumed: no layer's RNG counter moves.  An input layer with
+        ``visible_groups`` returns its grouped means (softmax inside every group)."""
         if h is None:
             return None
         from .engine import RngAddr
@@ -165,6 +171,9 @@ class DBN(object):
         x = self.engine.as_matrix(getattr(h, "tensor", h))
         for i in range(top, -1, -1):
             r = self.rbm_layers[i]
+            if r.visible_groups is not None:
+                x = r._grouped_down(x, None, W=r.down_W)[1]
+                continue
             # (the propagation call wants an address for the sample it also offers; the mean does not depend on it)
             # (a layer untied by fine_tune goes down through its generative weights)
             x = self.engine.propdown(x, r.down_W, r.vbias.tensor, gauss=r.gauss, add_noise=False,
@@ -188,6 +197,7 @@ class DBN(object):
         ``chunk_rows // n_samples`` (a host-resident table is streamed); the chunking changes no draw.  Every sampled layer
         consumes ONE RNG step of its own RBM.  A one-layer network draws nothing and gives ``log_likelihood``."""
         from .bound import stack_bound
+        self.rbm_layers[0]._no_groups("log_likelihood_bound")
         return stack_bound([(self, data)], None, n_samples=n_samples, log_z=log_z, chunk_rows=chunk_rows, trace=trace, **ais)
 
     def fine_tune(self, train_set_x, epochs, batch_size=20, *, lr, k=1, momentum=0.0, weightcost=0.0, lambda_1=0.0,
@@ -205,6 +215,7 @@ class DBN(object):
         of ``log_likelihood_bound`` and ``MDBN.impute_modalities`` go through ``W_gen``; ``get_output`` and the RBM-level
         methods keep to W, so a lower layer's own free energy and AIS then describe its recognition RBM, not the model."""
         from . import updown
+        self.rbm_layers[0]._no_groups("fine_tune")
         return updown.fine_tune([self], None, [train_set_x], epochs, batch_size, lr=lr, k=k, momentum=momentum,
                                 weightcost=weightcost, lambda_1=lambda_1, lambda_2=lambda_2, top_lr=top_lr, on_epoch=on_epoch,
                                 path=path)
@@ -259,8 +270,8 @@ class DBN(object):
 
     def training(self, train_set_x, batch_size, k, pretraining_epochs, pretrain_lr,
                  lambda_1=0.0, lambda_2=0.1, validation_set_x=None, monitor=False,
-                 graph_output=False, resume=None, on_step=None, centered=False, offset_rate=0.01, sparsity_target=None,
-                 sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
+                 graph_output=False, resume=None, on_step=None, visible_groups=None, centered=False, offset_rate=0.01,
+                 sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         '''Greedy layer-wise pre-training (dbn.py:334-517).  Returns, per layer, the list of
         (iteration, cost, free_energy_gap) records taken at the validation points.
 
@@ -272,7 +283,10 @@ class DBN(object):
         ``centered`` / ``offset_rate``: every layer trains by the centred gradient (``RBM.get_cost_updates``); the layers'
         offsets are part of the resume state.  ``sparsity_target`` / ``sparsity_cost`` / ``sparsity_decay`` /
         ``sparsity_weights``: every layer trains with the sparsity target; the layers' activity estimates are part of the
-        resume state.'''
+        resume state.  ``visible_groups`` (not None): the input layer's ``set_visible_groups`` first -- it trains with
+        categorical visible units (a Gaussian input layer refuses).'''
+        if visible_groups is not None:
+            self.rbm_layers[0].set_visible_groups(visible_groups)
         data = shared(train_set_x, engine=self.engine)
         held_out = None if validation_set_x is None else shared(validation_set_x, engine=self.engine)
         self._print('... getting the pretraining functions')

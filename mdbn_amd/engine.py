@@ -73,6 +73,22 @@ CdCall = namedtuple("CdCall", "args stats scratch data indexes keep announce thi
 StepCache = namedtuple("StepCache", "args update args_ref update_ref key scratch W tensors")
 
 
+class GroupTable(object):
+    """The table of a layer with K-ary softmax visible units (``utils.group_boundaries``), in the two copies the library
+    takes: ``tensor`` (int32, on the engine's device: what the kernel reads) and ``host`` (int32 numpy: what the library
+    checks before a launch).  Immutable: a layer that changes its groups gets a new table."""
+
+    def __init__(self, engine, boundaries):
+        self.host = numpy.ascontiguousarray(boundaries, dtype=numpy.int32)
+        self.host.setflags(write=False)
+        self.tensor = torch.from_numpy(self.host.copy()).to(engine.device)
+        self.n_groups = int(self.host.size - 1)
+
+    def spans(self):
+        """[(first column, end column), ...] of the groups."""
+        return [(int(a), int(b)) for a, b in zip(self.host[:-1], self.host[1:])]
+
+
 class CDScratch(object):
     """Per-(B, V, H) buffers of one CD step; see mdbn_cd_args in include/mdbn_hip.h."""
 
@@ -849,6 +865,80 @@ class HipEngine(object):
         if call.args.W_planes:
             self._w_planes_written(W)            # (split on entry if they were stale)
         return call.stats, call.scratch
+
+    # ------------------------------------------------------------------ categorical visible units (mdbn_group_softmax_*)
+    def group_softmax(self, pre, groups, rng, v0=None):
+        """p(v | h) of a layer with softmax groups from the visible pre-activations ``pre`` [B, V] = h W^T + vbias
+        (mdbn_group_softmax_sample): ``(mean, sample)`` -- softmax inside every group of ``groups`` (a ``GroupTable``), sigmoid
+        on the other columns; one uniform of ``rng`` per group, at its first column, and one per Bernoulli column; ``rng``
+        None: no sample (None).  With ``v0`` also the un-normalised cost sum (device scalar): the categorical cross-entropy
+        of the groups from the log-sum-exp plus the Bernoulli cross-entropy of the other columns."""
+        pre = self.as_matrix(pre)
+        B, V = pre.shape
+        ldv = pre.stride(0)
+        mean = self.alloc_matrix(B, V, ldv)
+        sample = self.alloc_matrix(B, V, ldv) if rng is not None else None
+        cost = ws = None
+        if v0 is not None:
+            v0 = self.as_matrix(v0)
+            if v0.stride(0) != ldv:                     # the target is read with the output's ld
+                t = self.alloc_matrix(B, V, ldv)
+                t.copy_(v0)
+                v0 = t
+            cost = torch.zeros(4, dtype=torch.float32, device=self.device)
+        if B == 0:
+            return (mean, sample) if v0 is None else (mean, sample, cost[0])
+        if v0 is not None:
+            n = C.c_int64()
+            _lib.check(self.lib.mdbn_group_softmax_workspace_bytes(self.ctx, B, V, C.byref(n)), "mdbn_group_softmax_workspace_bytes")
+            ws = getattr(self, "_group_ws", None)
+            if ws is None or ws.numel() * 4 < n.value:
+                ws = self._group_ws = torch.empty(n.value // 4 + 64, dtype=torch.float32, device=self.device)
+        r = rng.c() if rng is not None else None
+        _lib.check(self.lib.mdbn_group_softmax_sample(
+            self.ctx, self._stream(), self._p(pre), B, ldv, V, self._p(groups.tensor), C.c_void_p(groups.host.ctypes.data),
+            groups.n_groups, self._p(mean), self._p(sample), None, C.byref(r) if r is not None else None, self._p(v0),
+            self._p(cost), self._p(ws), ws.numel() * 4 if ws is not None else 0), "mdbn_group_softmax_sample")
+        return (mean, sample) if v0 is None else (mean, sample, cost[0])
+
+    def cd_step_grouped(self, data, indexes, W, hbias, vbias, k, rng, groups, persistent=None, stats_slot=0, stats=None,
+                        keep_f32=None):
+        """``cd_step`` for a Bernoulli layer whose visibles hold the softmax groups ``groups`` (mdbn_cd_step_grouped): the same
+        ``(stats, scratch)``, the float32 copies in the scratch always written, the cost slot holding the cross-entropy of
+        ``group_softmax`` for the last Gibbs step against v0."""
+        call = self._cd_args(data, indexes, W, hbias, vbias, False, k, rng, persistent, False, stats_slot, False, stats,
+                             keep_f32=True)
+        a = call.args
+        a.W_planes, a.W_planes_valid, a.planes, a.planes_bytes = None, 0, None, 0      # (the composed step reads f32 operands only)
+        a.planes_alt, a.next_indexes, a.v0_ready, a.ahead_done = None, None, 0, None
+        _lib.check(self.lib.mdbn_cd_step_grouped(self.ctx, self._stream(), C.byref(a), self._p(groups.tensor),
+                                                 C.c_void_p(groups.host.ctypes.data), groups.n_groups), "mdbn_cd_step_grouped")
+        return call.stats, call.scratch
+
+    def center_hidden_rows(self, scratch, B, stats, V, H, ldv, ldh, mu, lam, row_scale, sparsity=None):
+        """The centred hidden-bias statistic s_h' = s_h - row_scale S'^T mu from the ROWS of the step's scratch
+        (mdbn_center_hidden_rows) instead of from S: [H] device vector.  Call it between ``center_offsets`` and ``center_stats``
+        (it reads the raw s_h and s_v of ``stats``) and hand the result to ``center_stats_store_hidden`` afterwards.  On
+        one-hot rows the route through S multiplies the float32 error of S by sum(mu).  ``sparsity``: the arguments
+        ``(q, v_mean, target, w_scale, b_scale)`` of the ``sparsity_stats`` call that transformed ``stats`` before, or None --
+        the rows do not know what that call added to S and s_h, so its share of S'^T mu is added here."""
+        V2, P2 = scratch.V2, scratch.P2
+        q, v_mean, target, w_scale, b_scale = sparsity if sparsity is not None else (None, None, 0.0, 0.0, 0.0)
+        out = self.alloc_vector(H)
+        ws = getattr(self, "_center_rows_ws", None)
+        if ws is None or ws.numel() < 2 * B + 3:
+            ws = self._center_rows_ws = torch.empty(2 * int(B) + 64, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.mdbn_center_hidden_rows(self.ctx, self._stream(), self._p(V2), V2.stride(0), self._p(P2), P2.stride(0),
+                                                    int(B), int(V), int(H), self._p(stats), self._p(mu), self._p(lam),
+                                                    float(row_scale), self._p(q), self._p(v_mean), float(target), float(w_scale),
+                                                    float(b_scale), self._p(out), self._p(ws), ws.numel() * 4),
+                   "mdbn_center_hidden_rows")
+        return out
+
+    @staticmethod
+    def center_stats_store_hidden(stats, V, H, ldh, s_h):
+        """Store ``center_hidden_rows``'s result over the s_h block of the packed statistics (after ``center_stats``)."""
+        stats[V * ldh:V * ldh + H].copy_(s_h)
 
     def cd_forward(self, data, indexes, W, hbias, vbias, gauss, k, rng, add_noise=False, sample_stats=False, stats=None,
                    comm_cus=0, next_indexes=None):

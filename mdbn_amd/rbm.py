@@ -20,10 +20,10 @@ import numpy
 import torch
 
 from . import dist as _dist
-from .engine import RngAddr, get_engine
+from .engine import GroupTable, RngAddr, get_engine
 from .rng import RandomStreams
 from .shared import HostTable, SharedArray, as_tensor, shared, weight_ld
-from .utils import get_minibatches_idx
+from .utils import get_minibatches_idx, group_boundaries
 
 
 class Scalar(object):
@@ -47,7 +47,7 @@ class UpdatePlan(object):
 
     def __init__(self, rbm, lr, k, lambda_1, lambda_2, weightcost, batch_size, persistent, W0,
                  symbolic_grad=False, centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0,
-                 sparsity_decay=0.9, sparsity_weights=True):
+                 sparsity_decay=0.9, sparsity_weights=True, grouped=None):
         self.rbm, self.lr, self.k = rbm, lr, int(k)
         self.lambda_1, self.lambda_2, self.weightcost = lambda_1, lambda_2, weightcost
         self.batch_size, self.persistent, self.W0 = batch_size, persistent, W0
@@ -64,6 +64,9 @@ class UpdatePlan(object):
         self.sparsity_target = None if sparsity_target is None else float(sparsity_target)
         self.sparsity_cost, self.sparsity_decay = float(sparsity_cost), float(sparsity_decay)
         self.sparsity_weights = bool(sparsity_weights)
+        # categorical visible units (StepFunction._statistics_step): the layer's GroupTable when its visibles hold softmax
+        # groups -- the step's statistics then come from engine.cd_step_grouped --, else None
+        self.grouped = grouped
 
 
 class LazyCost(object):
@@ -229,6 +232,9 @@ class StepFunction(object):
             raise NotImplementedError("a sparsity target on a data-parallel group of %d ranks: the activity estimate needs "
                                       "the means of the whole minibatch in the all-reduce, which is not built yet"
                                       % self.group.world_size)
+        if p.grouped is not None and self.group is not None and self.group.world_size > 1:
+            raise NotImplementedError("categorical visible units (visible_groups) on a data-parallel group of %d ranks: the "
+                                      "grouped step is not sharded yet" % self.group.world_size)
         self._pending = None                # Pending: the deferred half of the last overlapped step
         self._feed = None                   # HostFeed of a host-resident table, made by its first announcement or step
         self._n_calls = 0
@@ -389,7 +395,7 @@ class StepFunction(object):
         batch_size = p.batch_size if (p.batch_size is not None and not p.symbolic_grad) else mb.n_global
         step = self.rbm._take_step()
         distributed = self.group is not None and self.group.world_size > 1
-        if p.centered or p.sparse:
+        if p.centered or p.sparse or p.grouped is not None:
             return self._statistics_step(mb, step, lr, momentum, batch_size, next_indexes)
         if not distributed and p.persistent is None and mb.hi > mb.lo:
             return self._single_device_step(mb, step, lr, momentum, batch_size, next_indexes)
@@ -474,7 +480,13 @@ class StepFunction(object):
         Centred gradient (Melchior et al. 2016, Algorithm 1), after the sparsity transform: the offsets slide towards the
         means of v0 and ph_mean of this minibatch (the first step of a layer sets them to those means), the statistics are
         corrected for the offsets -- S' = S - mu s_h' - s_v lam', s_v' = s_v - rho S' lam, s_h' = s_h - rho S'^T mu,
-        rho = n_rows / batch_size."""
+        rho = n_rows / batch_size.
+
+        Categorical visible units (a layer with ``visible_groups``): the statistics come from ``cd_step_grouped`` -- inside a
+        group p(v | h) is a softmax and the chain carries one-hot samples --, everything after that call is unchanged, so
+        both transforms compose with it.  The monitoring cost is the cost slot of that call, the cross-entropy of the last
+        Gibbs step against v0 (categorical inside the groups), under PCD too: the pseudo-likelihood flips one bit, and a
+        one-hot group with one bit flipped is outside the model's support."""
         p, rbm, eng = self.plan, self.rbm, self.engine
         data = mb.data
         persistent = None
@@ -488,8 +500,14 @@ class StepFunction(object):
             self._stats_slots[0] = eng.new_stats_buffer(V, H, ldv, ldh)
         stats = self._stats_slots[0]
         self._n_calls += 1
-        _, scratch = eng.cd_step(data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, rbm.gauss, p.k,
-                                 self._rng_addr(step, mb.lo), persistent=persistent, stats=stats, keep_f32=True)
+        if p.grouped is not None:
+            _, scratch = eng.cd_step_grouped(data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, p.k,
+                                             self._rng_addr(step, mb.lo), p.grouped, persistent=persistent, stats=stats,
+                                             keep_f32=True)
+        else:
+            _, scratch = eng.cd_step(data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, rbm.gauss, p.k,
+                                     self._rng_addr(step, mb.lo), persistent=persistent, stats=stats, keep_f32=True)
+        sparsity = None                                 # what sparsity_stats was given (the centred row route below needs it)
         if p.sparse:
             first = rbm.h_activity is None
             if first:
@@ -500,17 +518,25 @@ class StepFunction(object):
                     self._v_mean = eng.alloc_vector(V)
                 v_mean = self._v_mean
             eng.sparsity_activity(scratch, mb.n_global, rbm.h_activity.tensor, v_mean, 1.0 if first else 1.0 - p.sparsity_decay)
-            eng.sparsity_stats(stats, V, H, ldv, ldh, rbm.h_activity.tensor, v_mean, p.sparsity_target,
-                               p.sparsity_cost * float(batch_size) if p.sparsity_weights else 0.0,
-                               p.sparsity_cost * float(mb.n_global))
+            sparsity = (rbm.h_activity.tensor, v_mean, p.sparsity_target,
+                        p.sparsity_cost * float(batch_size) if p.sparsity_weights else 0.0, p.sparsity_cost * float(mb.n_global))
+            eng.sparsity_stats(stats, V, H, ldv, ldh, *sparsity)
         if p.centered:
             first = rbm.v_offset is None
             if first:
                 rbm.v_offset = SharedArray(None, engine=eng, _tensor=eng.alloc_vector(V))
                 rbm.h_offset = SharedArray(None, engine=eng, _tensor=eng.alloc_vector(H))
             eng.center_offsets(scratch, mb.n_global, rbm.v_offset.tensor, rbm.h_offset.tensor, 1.0 if first else p.offset_rate)
-            eng.center_stats(stats, V, H, ldv, ldh, rbm.v_offset.tensor, rbm.h_offset.tensor, float(mb.n_global) / float(batch_size))
-        cost, cost_scale = self._pcd_monitor(mb, stats, False) if p.persistent is not None else \
+            rho = float(mb.n_global) / float(batch_size)
+            # a layer with groups: s_h' from the rows of the scratch, not from S (the same number; on one-hot rows the sum over
+            # S cancels (mu . mu) s_h and multiplies the float32 error of S by sum(mu): engine.center_hidden_rows)
+            # (with what the sparsity transform added to S and s_h, which the rows do not hold)
+            s_h = eng.center_hidden_rows(scratch, mb.n_global, stats, V, H, ldv, ldh, rbm.v_offset.tensor, rbm.h_offset.tensor,
+                                         rho, sparsity=sparsity) if p.grouped is not None else None
+            eng.center_stats(stats, V, H, ldv, ldh, rbm.v_offset.tensor, rbm.h_offset.tensor, rho)
+            if s_h is not None:
+                eng.center_stats_store_hidden(stats, V, H, ldh, s_h)
+        cost, cost_scale = self._pcd_monitor(mb, stats, False) if (p.persistent is not None and p.grouped is None) else \
             (None, self._cost_scale(mb.n_global))
         self._rows_consumed(mb, next_indexes)
         hp = Hyper(lr, momentum, batch_size, mb.n_global, cost_scale, ldv)
@@ -619,11 +645,17 @@ class RBM(object):
     gauss = False
 
     def __init__(self, input=None, n_visible=784, n_hidden=500, W=None, hbias=None,
-                 vbias=None, numpy_rng=None, theano_rng=None, engine=None):
+                 vbias=None, numpy_rng=None, theano_rng=None, engine=None, visible_groups=None):
         """Same arguments as reference rbm.py:49-59.  ``W`` / ``hbias`` / ``vbias`` may be
         ``SharedArray`` objects shared with another network (a DBN's HiddenLayer),
         ndarrays, or None (initialised as rbm.py:100-131).  ``theano_rng`` is a
-        ``mdbn_amd.RandomStreams``."""
+        ``mdbn_amd.RandomStreams``.
+
+        ``visible_groups``: categorical visible units (Salakhutdinov, Mnih & Hinton 2007) -- an int K: all visibles in
+        groups of K (``n_visible % K == 0``); or ascending column boundaries ``[g_0, ..., g_G]``: group g is columns
+        g_g .. g_{g+1} - 1 (2 .. 64 columns each), the columns outside [g_0, g_G) stay Bernoulli units.  A data row holds
+        exactly one 1 in every group (``utils.one_hot_groups``).  p(v | h) is a softmax inside a group; the free energy,
+        ``propup`` and the CD statistics are those of the Bernoulli layer.  None: no groups, nothing changes."""
         self.engine = engine if engine is not None else get_engine()
         self.n_visible = n_visible
         self.n_hidden = n_hidden
@@ -677,6 +709,23 @@ class RBM(object):
         self.bit_i_idx = 0                     # rbm.py:425
         self._rng_step = 0
         self._n_updates = 0
+        self.visible_groups = None             # GroupTable of a layer with softmax visible units (device + host copy), or None
+        self.set_visible_groups(visible_groups)
+
+    def set_visible_groups(self, visible_groups):
+        """Declare (or with None remove) the softmax groups of the visible layer: see ``__init__``.  Step functions built
+        before keep the table they were built with."""
+        if visible_groups is None:
+            self.visible_groups = None
+            return
+        if self.gauss:
+            raise ValueError("visible_groups: a Gaussian visible layer (GRBM) has no categorical units")
+        self.visible_groups = GroupTable(self.engine, group_boundaries(visible_groups, self.n_visible))
+
+    def _no_groups(self, what):
+        if self.visible_groups is not None:
+            raise NotImplementedError("%s on a layer with categorical visible units (visible_groups) is not built yet: it "
+                                      "would sample the groups as independent sigmoid units" % what)
 
     @property
     def down_W(self):
@@ -753,6 +802,7 @@ class RBM(object):
         ``n_sweeps`` sweeps; the works of the swap attempts after ``burn_in`` bridge neighbouring temperatures
         (``estimator``: "mid" or "bar"); the error is the delete-one-ladder jackknife.  Consumes 3 n_sweeps RNG steps.  Where
         chains mix badly AIS under-estimates log Z without its error showing it; ``check_log_partition`` runs both."""
+        self._no_groups("log_partition")
         if method == "tempering":
             r = self.tempered_chains(n_ladders, betas=betas, n_betas=16 if n_betas is None else n_betas, base_vbias=base_vbias,
                                      data=data).log_partition(n_sweeps, burn_in, path=path, method=estimator)
@@ -786,6 +836,7 @@ class RBM(object):
         """``(mean log p(data), std_err)``: mean(-free_energy(data)) - log_Z with ``log_partition(**ais)``'s estimate (the
         standard error is that of log_Z; ``data`` also gives the base rate unless ``base_vbias`` / ``data`` is passed;
         ``method="tempering"`` and its keywords reach ``log_partition`` like any other)."""
+        self._no_groups("log_likelihood")
         if "base_vbias" not in ais and "data" not in ais:
             ais = dict(ais, data=data)
         log_Z, err = self.log_partition(**ais)
@@ -823,17 +874,52 @@ class RBM(object):
                                                self.hbias.tensor, rng=self._rng())
         return [self._wrap(pre), self._wrap(mean), self._wrap(sample)]
 
+    def _grouped_down(self, hid, rng, W=None):
+        """(pre, mean, sample) of p(v | h) on a layer with softmax groups: the linear pre-activations h W^T + vbias, then
+        ``engine.group_softmax`` (sample None without ``rng``)."""
+        pre = self.engine.propdown(as_tensor(hid, self.engine), self.W.tensor if W is None else W, self.vbias.tensor,
+                                   gauss=True, add_noise=False, rng=None)[1]
+        mean, sample = self.engine.group_softmax(pre, self.visible_groups, rng)
+        return pre, mean, sample
+
     def propdown(self, hid):
-        '''[pre_sigmoid_activation, sigmoid(pre)] (rbm.py:215-227)'''
+        '''[pre_sigmoid_activation, sigmoid(pre)] (rbm.py:215-227); with ``visible_groups``: [pre, grouped means] -- softmax
+        inside every group, sigmoid on the other columns'''
+        if self.visible_groups is not None:
+            self._take_step()                                  # (one step per call, as without groups)
+            pre, mean, _ = self._grouped_down(hid, None)
+            return [self._wrap(pre), self._wrap(mean)]
         pre, mean, _ = self.engine.propdown(as_tensor(hid, self.engine), self.W.tensor, self.vbias.tensor,
                                             gauss=False, rng=self._rng())
         return [self._wrap(pre), self._wrap(mean)]
 
     def sample_v_given_h(self, h0_sample):
-        ''' [pre_sigmoid_v1, v1_mean, v1_sample] (rbm.py:229-240) '''
+        ''' [pre_sigmoid_v1, v1_mean, v1_sample] (rbm.py:229-240); with ``visible_groups`` the sample holds exactly one 1 in
+        every group (one uniform per group, at its first column) '''
+        if self.visible_groups is not None:
+            pre, mean, sample = self._grouped_down(h0_sample, self._rng())
+            return [self._wrap(pre), self._wrap(mean), self._wrap(sample)]
         pre, mean, sample = self.engine.propdown(as_tensor(h0_sample, self.engine), self.W.tensor,
                                                  self.vbias.tensor, gauss=False, rng=self._rng())
         return [self._wrap(pre), self._wrap(mean), self._wrap(sample)]
+
+    def group_posterior(self, v, group):
+        """Exact p(category | all other visibles) of softmax group ``group`` for every row of ``v``: float64 [N, K],
+        softmax_c(-F(v with the group set to category c)) -- K free energies on the device, the finish in float64 on the
+        host.  What ``v`` holds inside the group is ignored.  With a label block in the joint layer this is the class
+        prediction of a classification RBM (Larochelle & Bengio 2008).  No random number is consumed."""
+        if self.visible_groups is None:
+            raise ValueError("group_posterior needs a layer with visible_groups")
+        lo, hi = self.visible_groups.spans()[range(self.visible_groups.n_groups)[int(group)]]
+        x = self.engine.as_matrix(as_tensor(v, self.engine)).clone()
+        neg_F = numpy.empty((x.shape[0], hi - lo), dtype=numpy.float64)
+        for c in range(hi - lo):
+            x[:, lo:hi] = 0.0
+            x[:, lo + c] = 1.0
+            neg_F[:, c] = -self.free_energy(x).tensor.detach().cpu().to(torch.float64).numpy()
+        neg_F -= neg_F.max(axis=1, keepdims=True)
+        p = numpy.exp(neg_F)
+        return p / p.sum(axis=1, keepdims=True)
 
     def gibbs_hvh(self, h0_sample):
         ''' One Gibbs step starting from the hidden state (rbm.py:242-248) '''
@@ -855,7 +941,8 @@ class RBM(object):
         without the per-step allocations and launches' host overhead.  Consumes 2 * n_steps RNG steps."""
         step = self._rng_step
         self._rng_step += 2 * int(n_steps)
-        if not hasattr(self.engine, "gibbs_chain"):          # checker engine: compose the eager steps
+        if not hasattr(self.engine, "gibbs_chain") or self.visible_groups is not None:
+            # checker engine, or a layer with softmax groups (no chain call of its own): compose the eager steps
             self._rng_step = step
             out, v = None, v0_sample
             for _ in range(int(n_steps)):
@@ -890,6 +977,7 @@ class RBM(object):
         reference (``gibbs_vhv``: the hidden MEAN goes down, noise only if not ``error_free``) is a mean-field iteration, and
         its averages are not posterior means; ``sampler=True`` runs the Gibbs sampler of the same model instead (the hidden
         SAMPLE goes down, the visible draw always carries its N(0, 1) noise).  It changes nothing for a Bernoulli layer."""
+        self._no_groups("gibbs_vhv_clamped")
         sampler = bool(sampler and self.gauss)
         n_steps, burn_in = int(n_steps), int(burn_in)
         if n_steps < 1 or not 0 <= burn_in < n_steps:
@@ -934,6 +1022,7 @@ class RBM(object):
         model, not the reference's mean-field chain), and v_mean / h_mean are averaged over the steps from
         ``burn_in`` on and over the chains.  Observed entries of ``v_hat`` are the observed values.  Consumes
         2 * n_steps RNG steps."""
+        self._no_groups("impute")
         x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
         N, n_chains = x.shape[0], int(n_chains)
         mask = self._clamp_mask(observed_mask, N)
@@ -964,6 +1053,7 @@ class RBM(object):
         base-rate model of a row is ``base_vbias`` on its free columns).  The logsumexp and the delta-method standard error of
         every row are float64 numpy on the host (``ais_estimate_rows``); a row with no free column has std_err 0.  Consumes
         2K - 1 RNG steps."""
+        self._no_groups("conditional_log_partition")
         x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
         if x.ndim != 2 or x.shape[1] != self.n_visible or x.shape[0] < 1:
             raise ValueError("v must be [N >= 1, %d], got %r" % (self.n_visible, x.shape))
@@ -985,6 +1075,7 @@ class RBM(object):
         estimate's); the free energy is the device's, the rest float64 on the host.  A row with no free column gets log_p = 0,
         std_err = 0.  A Bernoulli layer gives probability to 0 / 1 states only: free entries of ``v`` that are neither are
         refused (observed entries may hold any real value: they enter through v W alone)."""
+        self._no_groups("conditional_log_likelihood")
         x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
         if x.ndim != 2 or x.shape[1] != self.n_visible or x.shape[0] < 1:
             raise ValueError("v must be [N >= 1, %d], got %r" % (self.n_visible, x.shape))
@@ -1009,6 +1100,7 @@ class RBM(object):
         plain chain never leaves.  ``start_h``: [n_ladders, H] (every temperature of a ladder starts there) or
         [n_ladders * R, H]; None: zeros.  A GRBM ladder runs the Gibbs sampler of its model (hidden sample down, unit noise),
         not the reference's mean-field chain.  Each sweep consumes 3 RNG steps."""
+        self._no_groups("tempered_chains")
         from .temper import TemperedChains
         if betas is None:
             betas = numpy.linspace(0.0, 1.0, int(n_betas))
@@ -1055,7 +1147,13 @@ class RBM(object):
         running estimate of those means -- the first sparse step sets it to the means of ph_mean over its minibatch,
         afterwards q += (1 - ``sparsity_decay``) (mean - q) -- and the step adds c (p - q_j) to the hidden-bias gradient and,
         with ``sparsity_weights`` (False: the bias-only form of Lee et al.), c (p - q_j) <v_i> to the weight gradient.  q is
-        optimiser state; without a target, or at cost 0, the step is the plain one.  Composes with ``centered``."""
+        optimiser state; without a target, or at cost 0, the step is the plain one.  Composes with ``centered``.
+        A layer with ``visible_groups`` trains by the grouped step (``StepFunction._statistics_step``): softmax inside the
+        groups, the same statistics and update; both options above compose with it, ``symbolic_grad`` does not.  Its
+        monitoring cost is the cross-entropy of the reconstruction (categorical inside the groups) under PCD as well: the
+        pseudo-likelihood flips one bit of a row, which takes a one-hot group out of the model's support."""
+        if self.visible_groups is not None and symbolic_grad:
+            raise NotImplementedError("symbolic_grad=True on a layer with categorical visible units (visible_groups) is not supported")
         sparse = sparsity_target is not None and float(sparsity_cost) > 0.0
         if sparsity_target is not None and not 0.0 < float(sparsity_target) < 1.0:
             raise ValueError("sparsity_target must lie in (0, 1), got %r" % (sparsity_target,))
@@ -1094,8 +1192,8 @@ class RBM(object):
         updates = UpdatePlan(self, lr, k, lambda_1, lambda_2, weightcost, batch_size, persistent, W0,
                              symbolic_grad=symbolic_grad, centered=centered, offset_rate=offset_rate,
                              sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
-                             sparsity_weights=sparsity_weights)
-        cost = CostHandle('pseudo_likelihood' if persistent is not None else 'reconstruction')
+                             sparsity_weights=sparsity_weights, grouped=self.visible_groups)
+        cost = CostHandle('pseudo_likelihood' if (persistent is not None and self.visible_groups is None) else 'reconstruction')
         return cost, updates
 
     def _pseudo_likelihood_value(self, x):
@@ -1115,7 +1213,11 @@ class RBM(object):
 
     def get_reconstruction_cost(self, pre_sigmoid_nv, v0):
         """rbm.py:449-482 evaluated on given arrays (monitoring helper; the step function
-        computes the same quantity fused into the last propdown)."""
+        computes the same quantity fused into the last propdown).  With ``visible_groups``: the categorical cross-entropy
+        of the groups, formed from the log-sum-exp, plus the Bernoulli cross-entropy of the other columns; mean over rows."""
+        if self.visible_groups is not None:
+            pre = as_tensor(pre_sigmoid_nv, self.engine)
+            return float(self.engine.group_softmax(pre, self.visible_groups, None, v0=as_tensor(v0, self.engine))[2]) / pre.shape[0]
         return float(self.engine.recon_cost(as_tensor(pre_sigmoid_nv, self.engine), as_tensor(v0, self.engine),
                                             gauss=False))
 
@@ -1123,7 +1225,7 @@ class RBM(object):
     def training(self, train_set_x, validation_set_x, training_epochs, batch_size=10,
                  learning_rate=0.1, k=1, initial_momentum=0.0, final_momentum=0.0,
                  weightcost=0.0, lambda_2=0.0, persistent=True, display_fn=None, graph_output=False, tempering=None,
-                 centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9,
+                 visible_groups=None, centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9,
                  sparsity_weights=True):
         """rbm.py:484-520 (note: like the reference, ``lambda_2`` is accepted but not used).
 
@@ -1131,7 +1233,12 @@ class RBM(object):
         parallel-tempering ladders of R temperatures (Desjardins et al. 2010) -- every step is ``chains.run(1)``,
         ``chains.to_persistent``, the unchanged PCD step, ``chains.from_persistent``; the ladders stay in ``self.tempered``.
         None: nothing changes.  ``centered`` / ``offset_rate``: the centred gradient, ``sparsity_*``: the sparsity target
-        (``get_cost_updates``)."""
+        (``get_cost_updates``).  ``visible_groups`` (not None): ``set_visible_groups`` first -- the layer trains with
+        categorical visible units."""
+        if visible_groups is not None:
+            self.set_visible_groups(visible_groups)
+        if tempering is not None:
+            self._no_groups("training(tempering=)")
         if persistent:
             persistent_chain = shared(numpy.zeros((batch_size, self.n_hidden), dtype=numpy.float32),
                                       engine=self.engine)               # rbm.py:496-498
@@ -1215,7 +1322,9 @@ class GRBM(RBM):
     gauss = True
 
     def __init__(self, input=None, n_visible=784, n_hidden=500, W=None, hbias=None, vbias=None,
-                 numpy_rng=None, theano_rng=None, error_free=True, engine=None):
+                 numpy_rng=None, theano_rng=None, error_free=True, engine=None, visible_groups=None):
+        if visible_groups is not None:
+            raise ValueError("visible_groups: a Gaussian visible layer (GRBM) has no categorical units")
         super(GRBM, self).__init__(input, n_visible, n_hidden, W, hbias, vbias, numpy_rng,
                                    theano_rng, engine=engine)
         self.error_free = error_free
@@ -1249,10 +1358,12 @@ class GRBM(RBM):
     def training(self, train_set_x, validation_set_x, training_epochs, batch_size=10,
                  learning_rate=0.01, k=1, initial_momentum=0.0, final_momentum=0.0,
                  weightcost=0.0, lambda_1=0.0, lambda_2=0.1, persistent=False,
-                 display_fn=None, graph_output=False, centered=False, offset_rate=0.01, sparsity_target=None,
-                 sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
+                 display_fn=None, graph_output=False, visible_groups=None, centered=False, offset_rate=0.01,
+                 sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         """rbm.py:701-728: always CD (``persistent`` is ignored, as in the reference).  ``centered`` / ``offset_rate``: the
-        centred gradient, ``sparsity_*``: the sparsity target (``get_cost_updates``)."""
+        centred gradient, ``sparsity_*``: the sparsity target (``get_cost_updates``).  ``visible_groups`` is refused."""
+        if visible_groups is not None:
+            raise ValueError("visible_groups: a Gaussian visible layer (GRBM) has no categorical units")
         cost, updates = self.get_cost_updates(lr=learning_rate, k=k, lambda_1=lambda_1,
                                               lambda_2=lambda_2, weightcost=weightcost,
                                               batch_size=batch_size, centered=centered, offset_rate=offset_rate,

@@ -121,3 +121,47 @@ def find_unique_classes(dbn_output):
     labels[order] = numpy.cumsum(opens_class) - 1
     patterns = ranked[opens_class]
     return labels, cdist(patterns, patterns, metric='hamming')
+
+
+# ---------------------------------------------------------------------------------- categorical visible units
+GROUP_MAX = 64      # largest softmax group the library serves (MDBN_GROUP_MAX, include/mdbn_hip.h)
+
+
+def group_boundaries(visible_groups, n_visible):
+    """The table of a layer with K-ary softmax visible units as int32 column offsets ``[g_0, ..., g_G]`` (group g is columns
+    g_g .. g_{g+1} - 1).  ``visible_groups``: an int K -- all ``n_visible`` units in groups of K, ``n_visible % K == 0`` --
+    or a sequence of strictly ascending boundaries inside [0, n_visible] whose groups have 2 .. ``GROUP_MAX`` columns (the
+    groups are adjacent; the columns before the first and after the last boundary are Bernoulli units).  ValueError
+    otherwise."""
+    if isinstance(visible_groups, (int, numpy.integer)) and not isinstance(visible_groups, bool):
+        K = int(visible_groups)
+        if K < 2 or K > GROUP_MAX or n_visible % K != 0:
+            raise ValueError("visible_groups=%d: a group size is 2 .. %d and divides n_visible = %d" % (K, GROUP_MAX, n_visible))
+        return numpy.arange(0, n_visible + 1, K, dtype=numpy.int32)
+    b = numpy.asarray(getattr(visible_groups, "host", visible_groups))
+    if b.ndim != 1 or b.size < 2 or not numpy.issubdtype(b.dtype, numpy.integer):
+        raise ValueError("visible_groups must be an int or a sequence of at least two integer boundaries, got %r" % (visible_groups,))
+    b = b.astype(numpy.int64)
+    sizes = numpy.diff(b)
+    if b[0] < 0 or b[-1] > n_visible or (sizes < 2).any() or (sizes > GROUP_MAX).any():
+        raise ValueError("visible_groups: boundaries must ascend inside [0, %d] in steps of 2 .. %d, got %r"
+                         % (n_visible, GROUP_MAX, b.tolist()))
+    return b.astype(numpy.int32)
+
+
+def one_hot_groups(codes, n_categories):
+    """Integer table ``codes`` [N, G] with entries in 0 .. ``n_categories`` - 1 -> float32 [N, G * n_categories]: column
+    g * n_categories + c is 1 where ``codes[:, g] == c``.  The layout ``RBM(visible_groups=n_categories)`` expects (a
+    copy-number call -2 .. 2 is passed as ``calls + 2`` with 5 categories).  Codes out of range, or not integers, are refused."""
+    c = numpy.asarray(codes)
+    K = int(n_categories)
+    if K < 2:
+        raise ValueError("n_categories must be at least 2, got %r" % (n_categories,))
+    if c.ndim != 2 or not (numpy.issubdtype(c.dtype, numpy.integer) or numpy.issubdtype(c.dtype, numpy.bool_)):
+        raise ValueError("codes must be an integer table [N, G], got dtype %s and shape %r" % (c.dtype, c.shape))
+    c = c.astype(numpy.int64)
+    if c.size and (c.min() < 0 or c.max() >= K):
+        raise ValueError("codes must lie in 0 .. %d, got %d .. %d" % (K - 1, c.min(), c.max()))
+    out = numpy.zeros((c.shape[0], c.shape[1], K), dtype=numpy.float32)
+    numpy.put_along_axis(out, c[:, :, None], 1.0, axis=2)
+    return out.reshape(c.shape[0], c.shape[1] * K)
