@@ -666,6 +666,43 @@ int  mdbn_sparsity_activity(mdbn_ctx *ctx, void *stream, const float *ph, int64_
 int  mdbn_sparsity_stats(mdbn_ctx *ctx, void *stream, float *stats, int64_t V, int64_t H, int64_t ldv, int64_t ldh,
                          const float *q, const float *v_mean, float target, float w_scale, float b_scale);
 
+/* Learned per-column variance of a Gaussian visible layer (Hinton's practical guide, section 13.2; Krizhevsky 2009; Cho et
+ * al. 2011).  With s = log sigma [V] and u = x exp(-s) ("the row in units"), p(x) = p_u(u) exp(-sum_i s_i), where p_u is the
+ * unit-variance Gaussian layer of (W, hbias, vbias): the CD chain, its GEMMs, the statistics and the update run on u unchanged,
+ * log Z does not depend on s, and the gradient of the mean log-likelihood of the rows of a minibatch with respect to s_i is
+ * exact -- g_i = mean_r[u_ri (u_ri - m_ri)] - 1 with m = vbias + ph_mean W^T; the -1 is the model expectation, no chain
+ * state enters.
+ *
+ * mdbn_sigma_scale_rows: dst[r, i] = src[indexes[r], i] * expf(sign * log_sigma[i]) for i < V and 0 for V <= i < ld_dst,
+ * r < B.  sign = -1 takes raw rows to units (the gather of a training step, for mdbn_cd_step on the identity minibatch),
+ * sign = +1 takes units back to raw.  src [n_src, ld_src], indexes as for mdbn_gather_rows (NULL: row r; int32 or int64;
+ * negative values count from the end, out-of-range ones are clamped).  The factor of a column is formed once per thread, with
+ * expf; with log_sigma = 0 it is exactly 1 and dst holds what mdbn_gather_rows copies.  Pad columns of src are not read, so
+ * they may hold anything.  src and dst 16-byte aligned, ld % 4 == 0.
+ *
+ * mdbn_sigma_update: U [B, ldu] the rows in units (rows 0..B-1 of V2 after a mdbn_cd_step with keep_f32 = 1) and M [B, ldm]
+ * their conditional means m (mdbn_propdown_sample, gauss = 1, of ph_mean: rows 0..B-1 of P2), with the parameters as they were
+ * BEFORE mdbn_apply_update.  Over the first n_rows rows (1 <= n_rows <= B; the others are not read), in ascending order in
+ * float32 with a compensation term,
+ *   q_i = sum_r U_ri (U_ri - M_ri),  g_i = q_i / n_rows - 1,
+ *   log_sigma_i = min(max(log_sigma_i + speed_i lr, lo), hi)   (the OLD speed),   speed_i = g_i + (speed_i - g_i) momentum,
+ * the rule mdbn_apply_update applies to vbias (src/rbm.py:361-365), without shrink or weight cost.  [lo, hi] is a guard against
+ * overflow of exp, not a tuned value.  Up to 64 rows one launch does it all; above, the rows are split into slices of 16 whose
+ * partial sums go to `workspace` (mdbn_sigma_workspace_bytes(B, V); 16-byte aligned; 0 bytes and NULL allowed up to 64 rows)
+ * and a second launch adds them in ascending order.  No atomics: two runs agree bit for bit.  Pad columns of U and M are not
+ * read; no statistics buffer is involved.  lr = 0 leaves log_sigma as it is and still moves the speed.
+ *
+ * Bad arguments (a size < 1, B > 2^19, n_rows outside [1, B], a null pointer, a misaligned buffer, a leading dimension below V
+ * or no multiple of 4, an identity minibatch longer than src, sign not +-1, lr < 0, momentum outside [0, 1], lo > hi, any of
+ * them NaN, a short workspace) return MDBN_EINVAL without a launch. */
+int  mdbn_sigma_workspace_bytes(mdbn_ctx *ctx, int64_t B, int64_t V, int64_t *bytes);
+int  mdbn_sigma_scale_rows(mdbn_ctx *ctx, void *stream, const float *src, int64_t n_src, int64_t ld_src, const void *indexes,
+                           int index_is_64, int64_t B, int64_t V, const float *log_sigma, float sign, float *dst,
+                           int64_t ld_dst);
+int  mdbn_sigma_update(mdbn_ctx *ctx, void *stream, const float *U, int64_t ldu, const float *M, int64_t ldm, int64_t B,
+                       int64_t V, int64_t n_rows, float lr, float momentum, float lo, float hi, float *log_sigma,
+                       float *log_sigma_speed, void *workspace, int64_t workspace_bytes);
+
 /* Up-down fine-tuning of a DBN (Hinton, Osindero & Teh 2006, contrastive wake-sleep): the delta rules of a directed layer
  * whose recognition weights W (upwards) and generative weights G (downwards) have been untied.  Both rules are CD statistics
  * with chosen operands, applied by the unchanged update rule (src/rbm.py:347-365) that `upd` describes: upd->stats and

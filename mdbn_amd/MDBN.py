@@ -96,12 +96,13 @@ def train_modalities(modalities, rng, group="auto", shuffle_seed=None, graph_out
 
 def train_bottom_layer(train_set, validation_set, batch_size=20, k=1, layers_sizes=[40],
                        pretraining_epochs=[800], pretrain_lr=[0.005], lambda_1=0.0, lambda_2=0.1,
-                       rng=None, graph_output=False, visible_groups=None, sparsity_target=None, sparsity_cost=0.0,
-                       sparsity_decay=0.9, sparsity_weights=True, centered=False, offset_rate=0.01):
+                       rng=None, graph_output=False, visible_groups=None, learn_sigma=None, sparsity_target=None,
+                       sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True, centered=False, offset_rate=0.01):
     """DBN of one modality, Gaussian first layer (MDBN.py:45-76).  Returns the network and its
     outputs for the training and the validation rows (None without validation rows).  ``sparsity_*``: the sparsity target,
     ``centered`` / ``offset_rate``: the centred gradient (``RBM.get_cost_updates``).  ``visible_groups``: a categorical
-    modality, on a Bernoulli first layer with those softmax groups (``build_bottom_layer``)."""
+    modality, on a Bernoulli first layer with those softmax groups (``build_bottom_layer``).  ``learn_sigma``: the Gaussian
+    first layer learns a standard deviation per column at that rate (``DBN.training``)."""
     rows = shared(train_set)
     held_out = None if validation_set is None else shared(validation_set)
     n_visible, n_top = rows.shape[1], layers_sizes[-1]
@@ -112,7 +113,7 @@ def train_bottom_layer(train_set, validation_set, batch_size=20, k=1, layers_siz
                rows, held_out, batch_size, graph_output, k=k, pretraining_epochs=pretraining_epochs,
                pretrain_lr=pretrain_lr, lambda_1=lambda_1, lambda_2=lambda_2, centered=centered, offset_rate=offset_rate,
                sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
-               sparsity_weights=sparsity_weights)
+               sparsity_weights=sparsity_weights, **({} if learn_sigma is None else dict(learn_sigma=learn_sigma)))
     return net, net.get_output(rows), net.get_output(held_out)
 
 

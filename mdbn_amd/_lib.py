@@ -131,6 +131,9 @@ SIGNATURES = {
     "mdbn_center_stats": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _i64],
     "mdbn_sparsity_activity": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp],
     "mdbn_sparsity_stats": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _f32],
+    "mdbn_sigma_workspace_bytes": [_vp, _i64, _i64, C.POINTER(_i64)],
+    "mdbn_sigma_scale_rows": [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i64, _i64, _vp, _f32, _vp, _i64],
+    "mdbn_sigma_update": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _i64],
     "mdbn_group_softmax_workspace_bytes": [_vp, _i64, _i64, C.POINTER(_i64)],
     "mdbn_group_softmax_sample": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _rngp, _vp, _vp, _vp, _i64],
     "mdbn_center_hidden_rows": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _f32, _f32, _f32,

@@ -85,7 +85,9 @@ def stack_bound(bottoms, joint, n_samples=64, log_z=None, chunk_rows=16384, trac
     if not bottoms or (joint is None and len(bottoms) != 1):
         raise ValueError("one DBN, or modality DBNs under a joint DBN")
     nets = [net for net, _ in bottoms]
-    datas = [shared(d, engine=net.engine) for net, d in bottoms]
+    for net in nets:
+        net.rbm_layers[0]._no_sigma("log_likelihood_bound")
+    datas =[shared(d, engine=net.engine) for net, d in bottoms]
     N = len(datas[0])
     if N < 1:
         raise ValueError("no data rows")

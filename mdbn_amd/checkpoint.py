@@ -10,7 +10,8 @@ epoch are lost, so it cannot resume).  ``save_network(..., resume=True)`` adds
 ``<name>_resume``: visible biases, the three speeds, RNG seed / stream / step, the update count and
 -- where a step function with a weight cost was built -- the frozen weight-cost constant W0
 (rbm.py:415) of every RBM layer, the offsets of a layer trained by the centred gradient (``v_offset`` / ``h_offset``) and the
-activity estimate of a layer trained with a sparsity target (``h_activity``);
+activity estimate of a layer trained with a sparsity target (``h_activity``), ``log_sigma`` / ``log_sigma_speed`` of a Gaussian
+layer with a learned per-column variance;
 ``load_network`` restores them when present, and the next ``get_cost_updates`` of a restored layer reuses that W0 instead of
 snapshotting the resumed W.
 
@@ -41,6 +42,8 @@ def _resume_state(dbn):
             out[-1].update(v_offset=r.v_offset.get_value(), h_offset=r.h_offset.get_value())
         if r.h_activity is not None:            # sparsity target: the running activity estimate
             out[-1].update(h_activity=r.h_activity.get_value())
+        if r.log_sigma is not None:             # learned per-column variance: a parameter and its speed
+            out[-1].update(log_sigma=r.log_sigma.get_value(), log_sigma_speed=r.log_sigma_speed.get_value())
         if r.W_gen is not None:                 # up-down fine-tuning: the untied generative weights and their speed
             out[-1].update(W_gen=r.W_gen.get_value(), W_gen_speed=r.W_gen_speed.get_value())
     return out
@@ -106,6 +109,10 @@ def load_network(input_file, names=None, engine=None):
                     r.h_offset = shared(numpy.asarray(st['h_offset'], dtype=numpy.float32), name='h_offset', engine=r.engine)
                 if st.get('h_activity') is not None:
                     r.h_activity = shared(numpy.asarray(st['h_activity'], dtype=numpy.float32), name='h_activity', engine=r.engine)
+                if st.get('log_sigma') is not None:
+                    r.log_sigma = shared(numpy.asarray(st['log_sigma'], dtype=numpy.float32), name='log_sigma', engine=r.engine)
+                    r.log_sigma_speed = shared(numpy.asarray(st['log_sigma_speed'], dtype=numpy.float32), name='log_sigma_speed',
+                                               engine=r.engine)
                 if st.get('W_gen') is not None:
                     ld = r.W.tensor.stride(0)       # (the layout of W: the delta rules walk both)
                     r.W_gen = shared(numpy.asarray(st['W_gen'], dtype=numpy.float32), name='W_gen', engine=r.engine, ld=ld)

@@ -1,4 +1,4 @@
-// What a feature driver of the C ABI (mdbn_comm.hip, mdbn_drv_groups.hip, mdbn_drv_samplers.hip, mdbn_drv_train.hip, mdbn_feeder.hip) may use of
+// What a feature driver of the C ABI (mdbn_comm.hip, mdbn_drv_groups.hip, mdbn_drv_samplers.hip, mdbn_drv_sigma.hip, mdbn_drv_train.hip, mdbn_feeder.hip) may use of
 // the core (mdbn_capi.hip): the context record, the error macros, the leading-dimension helpers, the workspace of the
 // propagation GEMMs and one affine pass over it, and the two halves of an update rule as a kernel takes them.  The planner, the
 // kernel timing and the g_opt_* option names are NOT here: a driver that needs one of them does not compile, and that

@@ -114,6 +114,8 @@ class DBN(object):
                             W=sigmoid_layer.W, hbias=sigmoid_layer.b, engine=self.engine,
                             **(dict(visible_groups=visible_groups) if (i == 0 and visible_groups is not None) else {}))
             self.rbm_layers.append(rbm_layer)
+            if i == 0 and gauss:
+                sigmoid_layer.sigma_of = rbm_layer      # log_sigma, once the layer has one, is shared like W and b
         self._lower_cache = {}
         self.trainer_state = None    # where DBN.training stands (set while it runs with on_step; see training())
 
@@ -163,7 +165,8 @@ class DBN(object):
         host or device matrix) is taken down through ``rbm_layers[layer] .. rbm_layers[0]`` by the layers' conditional means
         (sigmoid(h W^T + vbias); the linear mean h W^T + vbias at a Gaussian bottom layer).  Returns a host array
         [rows, n_ins].  No random number is consumed: no layer's RNG counter moves.  An input layer with
-        ``visible_groups`` returns its grouped means (softmax inside every group)."""
+        ``visible_groups`` returns its grouped means (softmax inside every group); one with ``log_sigma`` returns raw units
+        (its mean times sigma)."""
         if h is None:
             return None
         from .engine import RngAddr
@@ -178,6 +181,7 @@ class DBN(object):
             # (a layer untied by fine_tune goes down through its generative weights)
             x = self.engine.propdown(x, r.down_W, r.vbias.tensor, gauss=r.gauss, add_noise=False,
                                      rng=RngAddr(r.theano_rng.seed, r.stream_id, 0, 0, 0))[1]
+            x = r._raw(x)
         return self.engine.to_numpy(x)
 
     def layer_log_likelihood(self, i, data, **ais):
@@ -198,6 +202,7 @@ class DBN(object):
         consumes ONE RNG step of its own RBM.  A one-layer network draws nothing and gives ``log_likelihood``."""
         from .bound import stack_bound
         self.rbm_layers[0]._no_groups("log_likelihood_bound")
+        self.rbm_layers[0]._no_sigma("log_likelihood_bound")
         return stack_bound([(self, data)], None, n_samples=n_samples, log_z=log_z, chunk_rows=chunk_rows, trace=trace, **ais)
 
     def fine_tune(self, train_set_x, epochs, batch_size=20, *, lr, k=1, momentum=0.0, weightcost=0.0, lambda_1=0.0,
@@ -216,6 +221,7 @@ class DBN(object):
         methods keep to W, so a lower layer's own free energy and AIS then describe its recognition RBM, not the model."""
         from . import updown
         self.rbm_layers[0]._no_groups("fine_tune")
+        self.rbm_layers[0]._no_sigma("fine_tune")
         return updown.fine_tune([self], None, [train_set_x], epochs, batch_size, lr=lr, k=k, momentum=momentum,
                                 weightcost=weightcost, lambda_1=lambda_1, lambda_2=lambda_2, top_lr=top_lr, on_epoch=on_epoch,
                                 path=path)
@@ -231,7 +237,9 @@ class DBN(object):
             # what the cached activations depend on: the lower layers' training steps, direct writes to
             # their parameters (SharedArray.set_value, e.g. weights loaded into an existing DBN) and
             # in-place writes to the data tensor
-            version = tuple((r._n_updates, r.W.version, r.hbias.version) for r in self.rbm_layers[:i]) + \
+            # (... and a log_sigma given to, or taken from, the input layer: set_sigma makes a new array)
+            version = tuple((r._n_updates, r.W.version, r.hbias.version, id(r.log_sigma), getattr(r.log_sigma, "version", 0))
+                            for r in self.rbm_layers[:i]) + \
                 (train_set_x.version, 0 if isinstance(train_set_x, HostTable) else getattr(train_set_x.tensor, "_version", 0))
             hit = self._lower_cache.get(i)
             if self.cache_lower and hit is not None and hit[0] == version and hit[1] is train_set_x:
@@ -242,11 +250,12 @@ class DBN(object):
         return provider
 
     def training_functions(self, train_set_x, batch_size, k, lambda_1=0.0, lambda_2=0.1,
-                           monitor=False, centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0,
-                           sparsity_decay=0.9, sparsity_weights=True):
+                           monitor=False, learn_sigma=None, centered=False, offset_rate=0.01, sparsity_target=None,
+                           sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         '''Per-layer step functions ``fn(indexes=, momentum=, lr=)`` and free-energy functions
         ``fn(train_sample, test_sample)`` (dbn.py:238-332).  ``centered`` / ``offset_rate``: every layer trains by the
-        centred gradient; ``sparsity_*``: every layer trains with the sparsity target (``RBM.get_cost_updates``).'''
+        centred gradient; ``sparsity_*``: every layer trains with the sparsity target; ``learn_sigma``: the Gaussian INPUT
+        layer (layer 0 only) learns a standard deviation per column at that rate (``RBM.get_cost_updates``).'''
         center = dict(centered=centered, offset_rate=offset_rate) if centered else {}
         if sparsity_target is not None:
             center.update(sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
@@ -256,7 +265,10 @@ class DBN(object):
         train_set_x = shared(train_set_x, engine=self.engine)
         train_fns, free_energy_gap_fns = [], []
         for i, rbm in enumerate(self.rbm_layers):
-            if isinstance(rbm, GRBM):
+            if i == 0 and learn_sigma is not None:       # (a Bernoulli input layer refuses it)
+                cost, updates = rbm.get_cost_updates(learning_rate, lambda_1=lambda_1, lambda_2=lambda_2, batch_size=batch_size,
+                                                     persistent=None, k=k, learn_sigma=learn_sigma, **center)
+            elif isinstance(rbm, GRBM):
                 cost, updates = rbm.get_cost_updates(learning_rate, lambda_1=lambda_1,
                                                      lambda_2=lambda_2, batch_size=batch_size,
                                                      persistent=None, k=k, **center)
@@ -270,8 +282,8 @@ class DBN(object):
 
     def training(self, train_set_x, batch_size, k, pretraining_epochs, pretrain_lr,
                  lambda_1=0.0, lambda_2=0.1, validation_set_x=None, monitor=False,
-                 graph_output=False, resume=None, on_step=None, visible_groups=None, centered=False, offset_rate=0.01,
-                 sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
+                 graph_output=False, resume=None, on_step=None, visible_groups=None, learn_sigma=None, centered=False,
+                 offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         '''Greedy layer-wise pre-training (dbn.py:334-517).  Returns, per layer, the list of
         (iteration, cost, free_energy_gap) records taken at the validation points.
 
@@ -284,7 +296,9 @@ class DBN(object):
         offsets are part of the resume state.  ``sparsity_target`` / ``sparsity_cost`` / ``sparsity_decay`` /
         ``sparsity_weights``: every layer trains with the sparsity target; the layers' activity estimates are part of the
         resume state.  ``visible_groups`` (not None): the input layer's ``set_visible_groups`` first -- it trains with
-        categorical visible units (a Gaussian input layer refuses).'''
+        categorical visible units (a Gaussian input layer refuses).  ``learn_sigma``: the Gaussian input layer learns a
+        standard deviation per column at that rate (``training_functions``); its ``log_sigma`` and speed are part of the resume
+        state.'''
         if visible_groups is not None:
             self.rbm_layers[0].set_visible_groups(visible_groups)
         data = shared(train_set_x, engine=self.engine)
@@ -295,7 +309,7 @@ class DBN(object):
             self._print('Validation set sample size %i' % held_out.shape[0])
         step_fns, energy_fns = self.training_functions(train_set_x=data, batch_size=batch_size, k=k,
                                                        lambda_1=lambda_1, lambda_2=lambda_2, monitor=monitor,
-                                                       centered=centered, offset_rate=offset_rate,
+                                                       learn_sigma=learn_sigma, centered=centered, offset_rate=offset_rate,
                                                        sparsity_target=sparsity_target, sparsity_cost=sparsity_cost,
                                                        sparsity_decay=sparsity_decay, sparsity_weights=sparsity_weights)
         self._print('... pre-training the model')

@@ -412,9 +412,11 @@ class HipEngine(object):
             C.byref(r) if r is not None else None, self._p(ws), ws.numel() * 4), "mdbn_propup_sample")
         return pre, mean, sample
 
-    def propdown(self, h, W, vbias, gauss=False, add_noise=False, rng=None, v0=None):
+    def propdown(self, h, W, vbias, gauss=False, add_noise=False, rng=None, v0=None, out=None):
         """[pre, mean, sample] of rbm.py:215-240 (RBM) / rbm.py:647-660 (GRBM).
-        With ``v0`` also returns the un-normalised reconstruction-cost sum (device scalar)."""
+        With ``v0`` also returns the un-normalised reconstruction-cost sum (device scalar).  ``out`` (a noise-free Gaussian
+        pass only): the [B, V] matrix that receives the mean -- nothing is allocated and no sample is written; all three
+        entries of the result are ``out``."""
         h = self.as_matrix(h)
         B, H = h.shape
         V = W.shape[0]
@@ -423,6 +425,14 @@ class HipEngine(object):
             h2 = self.alloc_matrix(B, H, W.stride(0))
             h2.copy_(h)
             h = h2
+        if out is not None:
+            assert gauss and not add_noise and v0 is None and tuple(out.shape) == (B, V), "out=: the noise-free Gaussian mean"
+            if B > 0:
+                ws = self.workspace(min(B, 4096), V, H)
+                _lib.check(self.lib.mdbn_propdown_sample(
+                    self.ctx, self._stream(), self._p(h), B, h.stride(0), self._p(W), V, H, out.stride(0), self._p(vbias), 1, 0,
+                    None, self._p(out), None, None, None, None, self._p(ws), ws.numel() * 4), "mdbn_propdown_sample")
+            return out, out, out
         mean = self.alloc_matrix(B, V)
         sample = self.alloc_matrix(B, V)
         pre = mean if gauss else self.alloc_matrix(B, V)     # GRBM: "pre" is the mean (rbm.py:660)
@@ -1138,6 +1148,41 @@ class HipEngine(object):
                                                 self._p(q), self._p(v_mean), float(target), float(w_scale), float(b_scale)),
                    "mdbn_sparsity_stats")
         return stats
+
+    # ------------------------------------------------------------------ learned per-column variance (mdbn_sigma_*)
+    def sigma_scale_rows(self, src, indexes, log_sigma, sign, out=None):
+        """``src[indexes] * exp(sign * log_sigma)`` (mdbn_sigma_scale_rows): ``sign`` = -1 takes raw rows to units -- the
+        gather of a training step of a layer with a learned variance --, +1 takes units back to raw.  ``indexes``: None (the
+        rows of ``src`` as they are) or an index list / tensor.  ``out``: the [B, V] matrix to fill (its pad columns are
+        written as zeros); None: a new one on ``src``'s leading dimension."""
+        src = self.as_matrix(src)
+        idx = None if indexes is None else self.index_tensor(indexes, src.shape[0])
+        B, V = (src.shape[0] if idx is None else idx.numel()), src.shape[1]
+        if out is None:
+            out = self.alloc_matrix(B, V, src.stride(0))
+        assert tuple(out.shape) == (B, V) and log_sigma.numel() == V, "sigma_scale_rows: shapes"
+        if B == 0:
+            return out
+        _lib.check(self.lib.mdbn_sigma_scale_rows(
+            self.ctx, self._stream(), self._p(src), src.shape[0], src.stride(0), self._p(idx),
+            int(idx is not None and idx.dtype == torch.int64), B, V, self._p(log_sigma), float(sign), self._p(out), out.stride(0)),
+            "mdbn_sigma_scale_rows")
+        return out
+
+    def sigma_update(self, U, M, n_rows, lr, momentum, lo, hi, log_sigma, log_sigma_speed):
+        """The step of ``log_sigma`` [V] and its speed, IN PLACE (mdbn_sigma_update): g = mean over the first ``n_rows`` rows
+        of U (U - M), minus 1 -- ``U`` the rows in units (rows of a ``cd_step(keep_f32=True)``'s V2), ``M`` their conditional
+        means vbias + ph_mean W^T --, then the visible bias's rule with rate ``lr`` and the clamp [lo, hi]."""
+        B, V = U.shape
+        n = C.c_int64()
+        _lib.check(self.lib.mdbn_sigma_workspace_bytes(self.ctx, int(B), int(V), C.byref(n)), "mdbn_sigma_workspace_bytes")
+        ws = getattr(self, "_sigma_ws", None)
+        if n.value and (ws is None or ws.numel() * 4 < n.value):
+            ws = self._sigma_ws = torch.empty(n.value // 4 + 64, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.mdbn_sigma_update(
+            self.ctx, self._stream(), self._p(U), U.stride(0), self._p(M), M.stride(0), int(B), int(V), int(n_rows), float(lr),
+            float(momentum), float(lo), float(hi), self._p(log_sigma), self._p(log_sigma_speed),
+            self._p(ws) if n.value else None, ws.numel() * 4 if n.value else 0), "mdbn_sigma_update")
 
     # ------------------------------------------------------------------ up-down fine-tuning (mdbn_updown_*)
     UPDOWN_PATHS = {"auto": 0, "fused": 1, "composed": 2}

@@ -49,12 +49,21 @@ class HiddenLayer(object):
         self.W = shared(W, name='W', engine=self.engine)
         self.b = shared(b, name='b', engine=self.engine)
         self.activation = activation
+        self.sigma_of = None        # the GRBM this layer shares W and b with, when that may carry a learned variance (DBN)
         self.output = LayerOutput(self)
         self.params = [self.W, self.b]
 
+    @property
+    def log_sigma(self):
+        """The ``log_sigma`` of the GRBM this layer shares its parameters with (``sigma_of``), or None: shared as W and b are."""
+        return None if self.sigma_of is None else self.sigma_of.log_sigma
+
     def forward(self, x):
-        """Device forward pass for a data matrix (mlp.py:103-107)."""
+        """Device forward pass for a data matrix (mlp.py:103-107); with ``log_sigma`` the input is taken to units first, as
+        the RBM's ``propup`` does."""
         x = as_tensor(x, self.engine)
+        if self.log_sigma is not None:
+            x = self.engine.sigma_scale_rows(x, None, self.log_sigma.tensor, -1.0)
         if self.activation is sigmoid:
             _, mean, _ = self.engine.propup(x, self.W.tensor, self.b.tensor,
                                             want_pre=False, want_sample=False)

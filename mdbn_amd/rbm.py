@@ -47,7 +47,7 @@ class UpdatePlan(object):
 
     def __init__(self, rbm, lr, k, lambda_1, lambda_2, weightcost, batch_size, persistent, W0,
                  symbolic_grad=False, centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0,
-                 sparsity_decay=0.9, sparsity_weights=True, grouped=None):
+                 sparsity_decay=0.9, sparsity_weights=True, grouped=None, learn_sigma=None):
         self.rbm, self.lr, self.k = rbm, lr, int(k)
         self.lambda_1, self.lambda_2, self.weightcost = lambda_1, lambda_2, weightcost
         self.batch_size, self.persistent, self.W0 = batch_size, persistent, W0
@@ -67,6 +67,10 @@ class UpdatePlan(object):
         # categorical visible units (StepFunction._statistics_step): the layer's GroupTable when its visibles hold softmax
         # groups -- the step's statistics then come from engine.cd_step_grouped --, else None
         self.grouped = grouped
+        # learned per-column variance (StepFunction._statistics_step): a layer with ``log_sigma`` trains on its rows in units
+        # x exp(-log_sigma); ``learn_sigma``: the rate of log_sigma's own exact gradient step, None: sigma stays as it is
+        self.sigma = rbm.log_sigma is not None
+        self.learn_sigma = None if learn_sigma is None else float(learn_sigma)
 
 
 class LazyCost(object):
@@ -235,6 +239,10 @@ class StepFunction(object):
         if p.grouped is not None and self.group is not None and self.group.world_size > 1:
             raise NotImplementedError("categorical visible units (visible_groups) on a data-parallel group of %d ranks: the "
                                       "grouped step is not sharded yet" % self.group.world_size)
+        if p.sigma and self.group is not None and self.group.world_size > 1:
+            raise NotImplementedError("a layer with log_sigma (learned per-column variance) on a data-parallel group of %d "
+                                      "ranks: the step of log_sigma needs the rows of the whole minibatch, which is not "
+                                      "built yet" % self.group.world_size)
         self._pending = None                # Pending: the deferred half of the last overlapped step
         self._feed = None                   # HostFeed of a host-resident table, made by its first announcement or step
         self._n_calls = 0
@@ -246,6 +254,7 @@ class StepFunction(object):
         # equal-sized modalities, alternating layers) must not share them
         self._stats_slots = [None, None]
         self._v_mean = None                 # [V] means of v0 of the current minibatch (a sparse step with sparsity_weights)
+        self._sigma_rows = {}               # n -> ([n, V] staging of the minibatch in units, [n, V] conditional means): a layer with log_sigma
         self._fast = []                     # warm: [engine.StepCache] of the previous single-device call (cd_train_step_cached)
         # nan_guard: check cost and parameters for NaN / Inf after every call (synchronises; what the
         # reference's commented-out NanGuardMode would do, rbm.py:542-543, dbn.py:311)
@@ -395,7 +404,7 @@ class StepFunction(object):
         batch_size = p.batch_size if (p.batch_size is not None and not p.symbolic_grad) else mb.n_global
         step = self.rbm._take_step()
         distributed = self.group is not None and self.group.world_size > 1
-        if p.centered or p.sparse or p.grouped is not None:
+        if p.centered or p.sparse or p.grouped is not None or p.sigma:
             return self._statistics_step(mb, step, lr, momentum, batch_size, next_indexes)
         if not distributed and p.persistent is None and mb.hi > mb.lo:
             return self._single_device_step(mb, step, lr, momentum, batch_size, next_indexes)
@@ -486,9 +495,29 @@ class StepFunction(object):
         group p(v | h) is a softmax and the chain carries one-hot samples --, everything after that call is unchanged, so
         both transforms compose with it.  The monitoring cost is the cost slot of that call, the cross-entropy of the last
         Gibbs step against v0 (categorical inside the groups), under PCD too: the pseudo-likelihood flips one bit, and a
-        one-hot group with one bit flipped is outside the model's support."""
+        one-hot group with one bit flipped is outside the model's support.
+
+        Learned per-column variance (a GRBM with ``log_sigma`` s): the minibatch is gathered as u = x exp(-s), the rows in
+        units (``sigma_scale_rows`` into a staging matrix this step function keeps), and the unchanged CD step runs on that
+        staging matrix with the identity index -- statistics, offsets and activities all live in units, so both transforms
+        compose without change, and the monitoring cost is the cost slot of that call, in units.  With ``learn_sigma`` the
+        conditional means m = vbias + ph_mean W^T (one noise-free propdown of the scratch's ph_mean, no RNG step) and
+        ``sigma_update`` follow: g = mean_r[u (u - m)] - 1, exact -- no chain state enters --, taken at the parameters of
+        before ``apply_update``; log_sigma then takes the visible bias's rule at rate ``learn_sigma``, clamped to
+        ``GRBM.log_sigma_range``."""
         p, rbm, eng = self.plan, self.rbm, self.engine
         data = mb.data
+        fed = mb                                        # the rows as they arrived (a fed buffer goes back once they are read)
+        if p.sigma:
+            n = mb.n_global                             # (one device: this call holds the whole minibatch)
+            if n not in self._sigma_rows:
+                if len(self._sigma_rows) > 4:           # (a full and a ragged minibatch per epoch, as a rule)
+                    self._sigma_rows.clear()
+                self._sigma_rows[n] = (eng.alloc_matrix(n, rbm.n_visible, data.stride(0)),
+                                       eng.alloc_matrix(n, rbm.n_visible, data.stride(0)) if p.learn_sigma is not None else None)
+            data, cond_mean = self._sigma_rows[n]
+            eng.sigma_scale_rows(mb.data, mb.idx, rbm.log_sigma.tensor, -1.0, out=data)
+            mb = mb._replace(data=data, idx=None, staged=False)
         persistent = None
         if p.persistent is not None:
             persistent = p.persistent.tensor
@@ -507,6 +536,12 @@ class StepFunction(object):
         else:
             _, scratch = eng.cd_step(data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, rbm.gauss, p.k,
                                      self._rng_addr(step, mb.lo), persistent=persistent, stats=stats, keep_f32=True)
+        if p.sigma and p.learn_sigma is not None:       # (all gradients of a step are taken at the old parameters)
+            n = mb.n_global
+            eng.propdown(scratch.P2[:n], rbm.W.tensor, rbm.vbias.tensor, gauss=True, out=cond_mean)
+            lo, hi = rbm.log_sigma_range
+            eng.sigma_update(scratch.V2[:n], cond_mean, n, p.learn_sigma, momentum, lo, hi, rbm.log_sigma.tensor,
+                             rbm.log_sigma_speed.tensor)
         sparsity = None                                 # what sparsity_stats was given (the centred row route below needs it)
         if p.sparse:
             first = rbm.h_activity is None
@@ -538,7 +573,7 @@ class StepFunction(object):
                 eng.center_stats_store_hidden(stats, V, H, ldh, s_h)
         cost, cost_scale = self._pcd_monitor(mb, stats, False) if (p.persistent is not None and p.grouped is None) else \
             (None, self._cost_scale(mb.n_global))
-        self._rows_consumed(mb, next_indexes)
+        self._rows_consumed(fed, next_indexes)
         hp = Hyper(lr, momentum, batch_size, mb.n_global, cost_scale, ldv)
         out = eng.apply_update(*self._update_args(stats, hp, 0))
         rbm._n_updates += 1
@@ -595,7 +630,8 @@ class StepFunction(object):
     def _check_finite(self, cost):
         rbm = self.rbm
         c = float(cost)
-        bad = self.engine.count_nonfinite(rbm.W.tensor, rbm.W_speed.tensor, rbm.hbias.tensor, rbm.vbias.tensor) \
+        sigma = () if rbm.log_sigma is None else (rbm.log_sigma.tensor, rbm.log_sigma_speed.tensor)
+        bad = self.engine.count_nonfinite(rbm.W.tensor, rbm.W_speed.tensor, rbm.hbias.tensor, rbm.vbias.tensor, *sigma) \
             if self._has_count else 0
         if bad or not numpy.isfinite(c):
             raise FloatingPointError("step %d of %s: cost = %r, %d non-finite parameter / speed values (learning rate "
@@ -706,6 +742,8 @@ class RBM(object):
                                                # (SharedArray [H]; optimiser state: None until the first sparse step)
         self.W_gen = self.W_gen_speed = None   # generative (top-down) weights of a layer untied by up-down fine-tuning
                                                # (SharedArray [V, H] on W's leading dimension; None: tied, W serves both ways)
+        self.log_sigma = self.log_sigma_speed = None   # learned per-column variance of a Gaussian layer (GRBM.set_sigma):
+                                               # SharedArray [V] each, a parameter and its speed; None: unit variance
         self.bit_i_idx = 0                     # rbm.py:425
         self._rng_step = 0
         self._n_updates = 0
@@ -726,6 +764,24 @@ class RBM(object):
         if self.visible_groups is not None:
             raise NotImplementedError("%s on a layer with categorical visible units (visible_groups) is not built yet: it "
                                       "would sample the groups as independent sigmoid units" % what)
+
+    def _no_sigma(self, what):
+        if self.log_sigma is not None:
+            raise NotImplementedError("%s on a layer with log_sigma (learned per-column variance) is not built yet: it would "
+                                      "run the unit-variance model on raw rows" % what)
+
+    def _units(self, v):
+        """``v`` (raw rows) as the unit-variance model sees them: v exp(-log_sigma), a device matrix; without ``log_sigma``
+        ``v`` itself."""
+        if self.log_sigma is None:
+            return v
+        return self.engine.sigma_scale_rows(as_tensor(v, self.engine), None, self.log_sigma.tensor, -1.0)
+
+    def _raw(self, u):
+        """The way back: ``u`` (a device matrix in units, or None) times exp(log_sigma); without ``log_sigma`` ``u`` itself."""
+        if self.log_sigma is None or u is None:
+            return u
+        return self.engine.sigma_scale_rows(u, None, self.log_sigma.tensor, 1.0)
 
     @property
     def down_W(self):
@@ -752,7 +808,11 @@ class RBM(object):
 
     # ------------------------------------------------------------------ energies
     def free_energy(self, v_sample):
-        ''' Function to compute the free energy (rbm.py:166-171) '''
+        ''' Function to compute the free energy (rbm.py:166-171); with ``log_sigma`` s: of the raw rows,
+        F(x) = F_u(x exp(-s)) + sum(s) '''
+        if self.log_sigma is not None:
+            F = self.engine.free_energy(self._units(v_sample), self.W.tensor, self.hbias.tensor, self.vbias.tensor, self.gauss)
+            return self._wrap(F + self.log_sigma.tensor.sum())
         return self._wrap(self.engine.free_energy(as_tensor(v_sample, self.engine), self.W.tensor,
                                                   self.hbias.tensor, self.vbias.tensor, self.gauss))
 
@@ -772,6 +832,8 @@ class RBM(object):
         if isinstance(data, torch.Tensor):
             data = data.detach().cpu().numpy()
         x = numpy.asarray(getattr(data, "get_value", lambda: data)(), dtype=numpy.float64)
+        if self.log_sigma is not None:          # the base-rate model of the unit-variance layer: the data in units
+            x = x * numpy.exp(-numpy.asarray(self.log_sigma.get_value(), dtype=numpy.float64))[None, :]
         mean = x.mean(axis=0)
         if self.gauss:
             return mean.astype(numpy.float32)
@@ -804,6 +866,7 @@ class RBM(object):
         chains mix badly AIS under-estimates log Z without its error showing it; ``check_log_partition`` runs both."""
         self._no_groups("log_partition")
         if method == "tempering":
+            self._no_sigma("log_partition(method=\"tempering\")")       # (AIS needs no change: log Z is the unit model's)
             r = self.tempered_chains(n_ladders, betas=betas, n_betas=16 if n_betas is None else n_betas, base_vbias=base_vbias,
                                      data=data).log_partition(n_sweeps, burn_in, path=path, method=estimator)
             return r.log_z, r.stderr
@@ -823,6 +886,7 @@ class RBM(object):
         ``tempering_stderr``, ``bracket`` = (log_z_fwd, log_z_rev) of the tempering run (biased low / high), ``z`` =
         |ais - tempering| / sqrt(se_ais^2 + se_tempering^2) and ``detail`` (the ``LogZ`` of the tempering run).  Asserts
         nothing: a large ``z``, or an AIS value below the bracket, says the AIS chains missed a mode (INTEGRATION)."""
+        self._no_sigma("check_log_partition")
         if base_vbias is None:
             base_vbias = self.base_rate_vbias(data) if data is not None else self.vbias.get_value()
         ais, se_a = self.log_partition(n_chains=n_chains, n_betas=n_betas, base_vbias=base_vbias, path=path)
@@ -835,8 +899,11 @@ class RBM(object):
     def log_likelihood(self, data, **ais):
         """``(mean log p(data), std_err)``: mean(-free_energy(data)) - log_Z with ``log_partition(**ais)``'s estimate (the
         standard error is that of log_Z; ``data`` also gives the base rate unless ``base_vbias`` / ``data`` is passed;
-        ``method="tempering"`` and its keywords reach ``log_partition`` like any other)."""
+        ``method="tempering"`` and its keywords reach ``log_partition`` like any other).  With ``log_sigma`` s the free energy
+        carries the sum(s) term of the change of variables and log_Z is the unit model's: nats per raw row."""
         self._no_groups("log_likelihood")
+        if ais.get("method", "ais") == "tempering":
+            self._no_sigma("log_likelihood(method=\"tempering\")")
         if "base_vbias" not in ais and "data" not in ais:
             ais = dict(ais, data=data)
         log_Z, err = self.log_partition(**ais)
@@ -846,7 +913,7 @@ class RBM(object):
     # ------------------------------------------------------------------ propagation
     def propup(self, vis):
         '''[pre_sigmoid_activation, sigmoid(pre)] (rbm.py:187-199)'''
-        pre, mean, _ = self.engine.propup(as_tensor(vis, self.engine), self.W.tensor, self.hbias.tensor,
+        pre, mean, _ = self.engine.propup(as_tensor(self._units(vis), self.engine), self.W.tensor, self.hbias.tensor,
                                           want_sample=False)
         return [self._wrap(pre), self._wrap(mean)]
 
@@ -862,7 +929,7 @@ class RBM(object):
         q = eng.alloc_vector(self.n_hidden)
         seen, step = 0, max(1, int(chunk_rows))
         for lo in range(0, x.shape[0], step):
-            rows = x[lo:lo + step]
+            rows = self._units(x[lo:lo + step])
             mean = eng.propup(rows, self.W.tensor, self.hbias.tensor, want_pre=False, want_sample=False)[1]
             seen += rows.shape[0]
             eng.sparsity_activity(ActivityRows(mean), rows.shape[0], q, None, float(rows.shape[0]) / float(seen))
@@ -870,7 +937,7 @@ class RBM(object):
 
     def sample_h_given_v(self, v0_sample):
         ''' [pre_sigmoid_h1, h1_mean, h1_sample] (rbm.py:201-213) '''
-        pre, mean, sample = self.engine.propup(as_tensor(v0_sample, self.engine), self.W.tensor,
+        pre, mean, sample = self.engine.propup(as_tensor(self._units(v0_sample), self.engine), self.W.tensor,
                                                self.hbias.tensor, rng=self._rng())
         return [self._wrap(pre), self._wrap(mean), self._wrap(sample)]
 
@@ -884,14 +951,15 @@ class RBM(object):
 
     def propdown(self, hid):
         '''[pre_sigmoid_activation, sigmoid(pre)] (rbm.py:215-227); with ``visible_groups``: [pre, grouped means] -- softmax
-        inside every group, sigmoid on the other columns'''
+        inside every group, sigmoid on the other columns; with ``log_sigma``: both entries times sigma, raw units as every
+        visible-side result of such a layer (the first is then the conditional mean sigma (vbias + W h))'''
         if self.visible_groups is not None:
             self._take_step()                                  # (one step per call, as without groups)
             pre, mean, _ = self._grouped_down(hid, None)
             return [self._wrap(pre), self._wrap(mean)]
         pre, mean, _ = self.engine.propdown(as_tensor(hid, self.engine), self.W.tensor, self.vbias.tensor,
                                             gauss=False, rng=self._rng())
-        return [self._wrap(pre), self._wrap(mean)]
+        return [self._wrap(self._raw(pre)), self._wrap(self._raw(mean))]
 
     def sample_v_given_h(self, h0_sample):
         ''' [pre_sigmoid_v1, v1_mean, v1_sample] (rbm.py:229-240); with ``visible_groups`` the sample holds exactly one 1 in
@@ -949,10 +1017,19 @@ class RBM(object):
                 out = self.gibbs_vhv(v)
                 v = out[5]
             return out
-        out = self.engine.gibbs_chain(as_tensor(v0_sample, self.engine), self.W.tensor, self.hbias.tensor,
+        out = self.engine.gibbs_chain(as_tensor(self._units(v0_sample), self.engine), self.W.tensor, self.hbias.tensor,
                                       self.vbias.tensor, self.gauss, int(n_steps),
                                       RngAddr(self.theano_rng.seed, self.stream_id, step, 0, 0),
                                       add_noise=self.gauss and not getattr(self, "error_free", True))
+        if self.log_sigma is not None:          # the visible half back in raw units (pre_v and v_mean are one matrix)
+            out = list(out)
+            back = {}
+            for i in (3, 4, 5):
+                if out[i] is not None:
+                    key = out[i].data_ptr()
+                    if key not in back:
+                        back[key] = self._raw(out[i])
+                    out[i] = back[key]
         return [self._wrap(t) for t in out]
 
     # ------------------------------------------------------------------ clamped Gibbs sampling / imputation
@@ -978,6 +1055,7 @@ class RBM(object):
         its averages are not posterior means; ``sampler=True`` runs the Gibbs sampler of the same model instead (the hidden
         SAMPLE goes down, the visible draw always carries its N(0, 1) noise).  It changes nothing for a Bernoulli layer."""
         self._no_groups("gibbs_vhv_clamped")
+        self._no_sigma("gibbs_vhv_clamped")
         sampler = bool(sampler and self.gauss)
         n_steps, burn_in = int(n_steps), int(burn_in)
         if n_steps < 1 or not 0 <= burn_in < n_steps:
@@ -1023,6 +1101,7 @@ class RBM(object):
         ``burn_in`` on and over the chains.  Observed entries of ``v_hat`` are the observed values.  Consumes
         2 * n_steps RNG steps."""
         self._no_groups("impute")
+        self._no_sigma("impute")
         x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
         N, n_chains = x.shape[0], int(n_chains)
         mask = self._clamp_mask(observed_mask, N)
@@ -1054,6 +1133,7 @@ class RBM(object):
         every row are float64 numpy on the host (``ais_estimate_rows``); a row with no free column has std_err 0.  Consumes
         2K - 1 RNG steps."""
         self._no_groups("conditional_log_partition")
+        self._no_sigma("conditional_log_partition")
         x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
         if x.ndim != 2 or x.shape[1] != self.n_visible or x.shape[0] < 1:
             raise ValueError("v must be [N >= 1, %d], got %r" % (self.n_visible, x.shape))
@@ -1076,6 +1156,7 @@ class RBM(object):
         std_err = 0.  A Bernoulli layer gives probability to 0 / 1 states only: free entries of ``v`` that are neither are
         refused (observed entries may hold any real value: they enter through v W alone)."""
         self._no_groups("conditional_log_likelihood")
+        self._no_sigma("conditional_log_likelihood")
         x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
         if x.ndim != 2 or x.shape[1] != self.n_visible or x.shape[0] < 1:
             raise ValueError("v must be [N >= 1, %d], got %r" % (self.n_visible, x.shape))
@@ -1101,6 +1182,7 @@ class RBM(object):
         [n_ladders * R, H]; None: zeros.  A GRBM ladder runs the Gibbs sampler of its model (hidden sample down, unit noise),
         not the reference's mean-field chain.  Each sweep consumes 3 RNG steps."""
         self._no_groups("tempered_chains")
+        self._no_sigma("tempered_chains")
         from .temper import TemperedChains
         if betas is None:
             betas = numpy.linspace(0.0, 1.0, int(n_betas))
@@ -1131,8 +1213,8 @@ class RBM(object):
 
     # ------------------------------------------------------------------ CD-k / PCD-k
     def get_cost_updates(self, lr=0.1, k=1, lambda_1=0.0, lambda_2=0.0, weightcost=0.0,
-                         batch_size=None, persistent=None, symbolic_grad=False, centered=False, offset_rate=0.01,
-                         sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
+                         batch_size=None, persistent=None, symbolic_grad=False, learn_sigma=None, centered=False,
+                         offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         """One step of CD-k or PCD-k (rbm.py:258-376).  Returns ``(cost, updates)``; pass
         ``updates`` to ``mdbn_amd.function`` to obtain the step function.
 
@@ -1151,7 +1233,22 @@ class RBM(object):
         A layer with ``visible_groups`` trains by the grouped step (``StepFunction._statistics_step``): softmax inside the
         groups, the same statistics and update; both options above compose with it, ``symbolic_grad`` does not.  Its
         monitoring cost is the cross-entropy of the reconstruction (categorical inside the groups) under PCD as well: the
-        pseudo-likelihood flips one bit of a row, which takes a one-hot group out of the model's support."""
+        pseudo-likelihood flips one bit of a row, which takes a one-hot group out of the model's support.
+        ``learn_sigma`` eta > 0 (a GRBM only): the layer learns a standard deviation per visible column (``GRBM.set_sigma``
+        says what the model is) -- ``self.log_sigma`` is created as zeros on first use, so the layer starts as the plain
+        GRBM, and every step moves it by its exact gradient at rate eta under the visible bias's momentum rule
+        (``StepFunction._statistics_step``).  A layer whose ``log_sigma`` is set trains in units with or without it: None
+        keeps sigma as it is.  The monitoring cost of such a layer is in units.  Composes with ``centered`` and the sparsity
+        target, not with ``symbolic_grad``."""
+        if learn_sigma is not None:
+            if not self.gauss:
+                raise ValueError("learn_sigma: a Bernoulli visible layer has no variance to learn (a GRBM has)")
+            if not float(learn_sigma) > 0.0 or not numpy.isfinite(float(learn_sigma)):
+                raise ValueError("learn_sigma must be a positive rate, got %r" % (learn_sigma,))
+        if symbolic_grad and (learn_sigma is not None or self.log_sigma is not None):
+            raise NotImplementedError("symbolic_grad=True on a layer with log_sigma (learned per-column variance) is not supported")
+        if learn_sigma is not None and self.log_sigma is None:
+            self.set_sigma(1.0)
         if self.visible_groups is not None and symbolic_grad:
             raise NotImplementedError("symbolic_grad=True on a layer with categorical visible units (visible_groups) is not supported")
         sparse = sparsity_target is not None and float(sparsity_cost) > 0.0
@@ -1192,7 +1289,7 @@ class RBM(object):
         updates = UpdatePlan(self, lr, k, lambda_1, lambda_2, weightcost, batch_size, persistent, W0,
                              symbolic_grad=symbolic_grad, centered=centered, offset_rate=offset_rate,
                              sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
-                             sparsity_weights=sparsity_weights, grouped=self.visible_groups)
+                             sparsity_weights=sparsity_weights, grouped=self.visible_groups, learn_sigma=learn_sigma)
         cost = CostHandle('pseudo_likelihood' if (persistent is not None and self.visible_groups is None) else 'reconstruction')
         return cost, updates
 
@@ -1209,7 +1306,7 @@ class RBM(object):
 
     def get_pseudo_likelihood_cost(self, v):
         """Stochastic approximation to the pseudo-likelihood (rbm.py:421-447) of rows ``v``."""
-        return float(self._pseudo_likelihood_value(as_tensor(v, self.engine)))
+        return float(self._pseudo_likelihood_value(as_tensor(self._units(v), self.engine)))
 
     def get_reconstruction_cost(self, pre_sigmoid_nv, v0):
         """rbm.py:449-482 evaluated on given arrays (monitoring helper; the step function
@@ -1239,6 +1336,7 @@ class RBM(object):
             self.set_visible_groups(visible_groups)
         if tempering is not None:
             self._no_groups("training(tempering=)")
+            self._no_sigma("training(tempering=)")
         if persistent:
             persistent_chain = shared(numpy.zeros((batch_size, self.n_hidden), dtype=numpy.float32),
                                       engine=self.engine)               # rbm.py:496-498
@@ -1317,9 +1415,13 @@ class RBM(object):
 
 
 class GRBM(RBM):
-    """Gaussian-Bernoulli RBM, unit variance, mean-field visibles (rbm.py:631-728)."""
+    """Gaussian-Bernoulli RBM, mean-field visibles (rbm.py:631-728): unit variance as the reference's, or with a standard
+    deviation per visible column once ``set_sigma`` / ``get_cost_updates(learn_sigma=)`` has made ``log_sigma``."""
 
     gauss = True
+    # Clamp of log_sigma in a training step: sigma between 0.01 and 100.  A guard that keeps exp(+-log_sigma) and the scaled
+    # rows far from float32 overflow if a step goes wrong -- not a tuned value; z-scored data sits well inside it.
+    log_sigma_range = (-4.6, 4.6)
 
     def __init__(self, input=None, n_visible=784, n_hidden=500, W=None, hbias=None, vbias=None,
                  numpy_rng=None, theano_rng=None, error_free=True, engine=None, visible_groups=None):
@@ -1329,11 +1431,38 @@ class GRBM(RBM):
                                    theano_rng, engine=engine)
         self.error_free = error_free
 
+    @property
+    def sigma(self):
+        """Host copy of the standard deviations exp(log_sigma), float32 [n_visible]; None on a unit-variance layer."""
+        return None if self.log_sigma is None else numpy.exp(self.log_sigma.get_value()).astype(numpy.float32)
+
+    def set_sigma(self, values):
+        """Give the layer a standard deviation per visible column: ``values`` a positive scalar or [n_visible] array (None:
+        back to the unit-variance layer).  With s = log sigma and u = x exp(-s), the row in units, the model is
+        p(x) = p_u(u) exp(-sum(s)), p_u the unit-variance GRBM of (W, hbias, vbias): p(h | x) = sigmoid(hbias + u W),
+        x | h ~ N(sigma (vbias + W h), sigma^2), F(x) = F_u(u) + sum(s), and log Z is p_u's.  Makes ``log_sigma`` and a zero
+        ``log_sigma_speed``; the eager methods then take and return raw rows, and step functions built from now on train in
+        units (``get_cost_updates``).  ``set_sigma(1.0)`` is the plain GRBM bit for bit."""
+        if values is None:
+            self.log_sigma = self.log_sigma_speed = None
+            return
+        v = numpy.asarray(values, dtype=numpy.float64)
+        if v.ndim == 0:
+            v = numpy.full(self.n_visible, float(v))
+        if v.shape != (self.n_visible,) or not numpy.all(numpy.isfinite(v)) or not numpy.all(v > 0.0):
+            raise ValueError("set_sigma needs a positive scalar or %d positive values" % self.n_visible)
+        self.log_sigma = shared(numpy.log(v).astype(numpy.float32), name='log_sigma', engine=self.engine)
+        self.log_sigma_speed = shared(numpy.zeros(self.n_visible, dtype=numpy.float32), name='log_sigma_speed', engine=self.engine)
+
     def sample_v_given_h(self, h0_sample):
-        ''' [v1_mean, v1_mean, v1_sample]; linear mean, optional N(0,1) noise (rbm.py:647-660) '''
+        ''' [v1_mean, v1_mean, v1_sample]; linear mean, optional N(0,1) noise (rbm.py:647-660); with ``log_sigma``: both
+        scaled back to raw units, so the noise has the column's standard deviation '''
         pre, mean, sample = self.engine.propdown(as_tensor(h0_sample, self.engine), self.W.tensor,
                                                  self.vbias.tensor, gauss=True,
                                                  add_noise=not self.error_free, rng=self._rng())
+        if self.log_sigma is not None:
+            mean, sample = self._raw(mean), (self._raw(sample) if not self.error_free else None)
+            sample = mean if sample is None else sample
         return [self._wrap(mean), self._wrap(mean), self._wrap(sample)]
 
     def gibbs_hvh(self, h0_sample):
@@ -1358,15 +1487,17 @@ class GRBM(RBM):
     def training(self, train_set_x, validation_set_x, training_epochs, batch_size=10,
                  learning_rate=0.01, k=1, initial_momentum=0.0, final_momentum=0.0,
                  weightcost=0.0, lambda_1=0.0, lambda_2=0.1, persistent=False,
-                 display_fn=None, graph_output=False, visible_groups=None, centered=False, offset_rate=0.01,
+                 display_fn=None, graph_output=False, visible_groups=None, learn_sigma=None, centered=False, offset_rate=0.01,
                  sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         """rbm.py:701-728: always CD (``persistent`` is ignored, as in the reference).  ``centered`` / ``offset_rate``: the
-        centred gradient, ``sparsity_*``: the sparsity target (``get_cost_updates``).  ``visible_groups`` is refused."""
+        centred gradient, ``sparsity_*``: the sparsity target, ``learn_sigma``: the rate of the learned per-column variance
+        (``get_cost_updates``).  ``visible_groups`` is refused."""
         if visible_groups is not None:
             raise ValueError("visible_groups: a Gaussian visible layer (GRBM) has no categorical units")
         cost, updates = self.get_cost_updates(lr=learning_rate, k=k, lambda_1=lambda_1,
                                               lambda_2=lambda_2, weightcost=weightcost,
-                                              batch_size=batch_size, centered=centered, offset_rate=offset_rate,
+                                              batch_size=batch_size, learn_sigma=learn_sigma, centered=centered,
+                                              offset_rate=offset_rate,
                                               sparsity_target=sparsity_target, sparsity_cost=sparsity_cost,
                                               sparsity_decay=sparsity_decay, sparsity_weights=sparsity_weights)
         return self.learn_model(train_set_x=train_set_x, validation_set_x=validation_set_x,

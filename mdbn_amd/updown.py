@@ -160,6 +160,8 @@ def fine_tune(nets, joint, inputs, epochs, batch_size=20, lr=None, k=1, momentum
         raise TypeError("fine_tune needs lr=")
     if path not in PATHS:
         raise ValueError("path must be one of %r, got %r" % (sorted(PATHS), path))
+    for net in nets:
+        net.rbm_layers[0]._no_sigma("fine_tune")
     directed, top = plan(nets, joint)
     _single_device()
     if len(inputs) != len(nets) or any(x is None for x in inputs):
