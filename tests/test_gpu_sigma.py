@@ -8,11 +8,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import _center_np as cn
 import _sigma_np as sg
-import _sparsity_np as sn
+import _step_forms as sf
 from oracle import rbm_np
-from oracle.philox_np import PhiloxDraws
 from _margins import check
 
 pytestmark = pytest.mark.gpu
@@ -192,36 +190,7 @@ def test_every_einval_case_returns_without_touching_its_outputs(hip_engine):
 
 
 # ------------------------------------------------------------------------------------------------------------------ (b) whole steps
-def shadow_engine():
-    """The engine of tests/_shadow.py (chain taps on) riding the statistics step of a layer with log_sigma: what every
-    cd_step saw and recorded, and the gradient of every sigma_update (read off a copy: momentum 0 makes the new speed g)."""
-    from _shadow import ShadowEngine
-    import mdbn_amd
-
-    class SigmaShadow(ShadowEngine):
-        def __init__(self):
-            ShadowEngine.__init__(self)
-            self.rides, self.grads = [], []
-
-        def cd_step(self, data, indexes, W, hbias, vbias, gauss, k, rng, persistent=None, add_noise=False, stats_slot=0,
-                    sample_stats=False, stats=None, comm_cus=0, keep_f32=None):
-            assert indexes is None and keep_f32 is True
-            stats, sc = mdbn_amd.HipEngine.cd_step(self, data, None, W, hbias, vbias, gauss, k, rng, persistent=persistent,
-                                                   add_noise=add_noise, stats=stats, keep_f32=keep_f32)
-            B, V, H = data.shape[0], W.shape[0], W.shape[1]
-            self.rides.append(dict(step=rng.step, u=sc.V2.cpu().numpy()[:B].copy(), ph=sc.P2.cpu().numpy()[:B].copy(),
-                                   trace_h=sc.trace_h.cpu().numpy()[:, :, :H].copy(), stats=stats.cpu().numpy().copy(),
-                                   ldv=sc.V2.stride(0), ldh=sc.P2.stride(0)))
-            return stats, sc
-
-        def sigma_update(self, U, M, n_rows, lr, momentum, lo, hi, log_sigma, log_sigma_speed):
-            s, speed = log_sigma.clone(), log_sigma_speed.clone()
-            mdbn_amd.HipEngine.sigma_update(self, U, M, n_rows, 0.0, 0.0, lo, hi, s, speed)
-            self.grads.append(speed.cpu().numpy().copy())
-            return mdbn_amd.HipEngine.sigma_update(self, U, M, n_rows, lr, momentum, lo, hi, log_sigma, log_sigma_speed)
-
-    return SigmaShadow()
-
+shadow_engine = sf.sigma_engine         # (the riding engine and the whole-step loop live in tests/_step_forms.py)
 
 CASES = [  # id, V, H, B, k, error_free, variant
     ("ragged_60x24", 60, 24, 33, 1, True, "alone"),
@@ -230,28 +199,9 @@ CASES = [  # id, V, H, B, k, error_free, variant
     ("tall_1024x256_centred", 1024, 256, 512, 1, True, "centered"),
     ("tall_1024x256_sparse", 1024, 256, 512, 1, True, "sparse"),
 ]
-STEPS, ETA, LR, L2 = 4, 0.05, 0.002, 0.1
-SPARSITY = dict(sparsity_target=0.2, sparsity_cost=1.0, sparsity_decay=0.9)
-
-
-def twin_update(st, state, variant, u, ph, nv, nh, B, momentum):
-    """One update of the float64 state from the means of a chain, by the transforms' twins."""
-    n = u.shape[0]
-    S, s_h, s_v = rbm_np.cd_statistics(u, ph, nv, nh)
-    if variant == "sparse":
-        first = state.get("q") is None
-        q, v_mean = sn.activity(np.zeros(ph.shape[1]) if first else state["q"], u, ph, 1.0 if first else 1.0 - SPARSITY["sparsity_decay"])
-        S, s_h, s_v = sn.stats(S, s_h, s_v, q, v_mean, SPARSITY["sparsity_target"], SPARSITY["sparsity_cost"] * B,
-                               SPARSITY["sparsity_cost"] * n)
-        state["q"] = q
-    if variant == "centered":
-        first = state.get("offsets") is None
-        mu, lam = cn.center_offsets(*((np.zeros(u.shape[1]), np.zeros(ph.shape[1])) if first else state["offsets"]), u, ph,
-                                    1.0 if first else 0.05)
-        S, s_h, s_v = cn.center_stats(S, s_h, s_v, mu, lam, float(n) / float(B))
-        state["offsets"] = (mu, lam)
-    g = rbm_np.rbm_grad(st, S, s_h, s_v, B, n, 0.0)
-    rbm_np.apply_update(st, g[0], g[1], g[2], LR, 0.0, L2, momentum)
+STEPS, ETA, LR, L2 = sf.STEPS, sf.ETA, sf.SIGMA_LR, sf.SIGMA_L2
+SPARSITY = sf.SPARSITY
+assert (STEPS, ETA, LR, L2) == (4, 0.05, 0.002, 0.1) and SPARSITY == dict(sparsity_target=0.2, sparsity_cost=1.0, sparsity_decay=0.9)
 
 
 @pytest.mark.parametrize("name,V,H,B,k,error_free,variant", CASES, ids=[c[0] for c in CASES])
@@ -259,65 +209,12 @@ def test_sigma_steps_teacher_forced_along_the_device_chain(built_lib, name, V, H
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    import mdbn_amd
     eng = shadow_engine()                           # product defaults; keep_f32 stays off but for the call that asks
     assert not eng.keep_f32
-    N = 2 * B + 7
-    rs = np.random.RandomState(31)
-    spread = np.exp(rs.uniform(-1.0, 1.0, size=V))
-    data = (rs.normal(size=(N, V)) * spread[None, :]).astype(np.float32)
-    rbm = mdbn_amd.GRBM(n_visible=V, n_hidden=H, numpy_rng=np.random.RandomState(123), theano_rng=mdbn_amd.RandomStreams(7),
-                        error_free=error_free, engine=eng)
-    st = rbm_np.RBMState(V, H, W=rbm.W.get_value(), gauss=True)
-    extra = dict(alone={}, centered=dict(centered=True, offset_rate=0.05), sparse=SPARSITY)[variant]
-    _, updates = rbm.get_cost_updates(lr=LR, k=k, batch_size=B, lambda_2=L2, learn_sigma=ETA, **extra)
-    fn = mdbn_amd.function(updates, mdbn_amd.shared(data, engine=eng), data_parallel=None)
-    order = [eng.index_tensor(rs.permutation(N)[:B], N) for _ in range(STEPS)]
-    ls, ls_speed, state = np.zeros(V), np.zeros(V), {}
-    worst = dict(units=0.0, prob=0.0, stat=0.0, g=0.0, cost=0.0)
-    for t in range(STEPS):
-        mom = 0.5 if t < 2 else 0.9
-        c = float(fn(indexes=order[t], momentum=mom))
-        ride, g_dev = eng.rides[t], eng.grads[t]
-        assert ride["step"] == t and len(eng.rides) == t + 1 and len(eng.grads) == t + 1
-        x = data[order[t].cpu().numpy()].astype(np.float64)
-        u = x * np.exp(-ls)[None, :]                # the twin's rows in units, from the twin's own log_sigma
-        worst["units"] = max(worst["units"], float((np.abs(ride["u"] - u) / np.maximum(np.abs(u), 1e-30)).max()))
-        ph, _, out, flips = rbm_np.cd_chain_forced(st, u, PhiloxDraws(7, rbm.stream_id, t), k, ride["trace_h"], None, tie=1e-6)
-        assert flips <= 3
-        worst["prob"] = max(worst["prob"], float(np.abs(ride["ph"] - ph).max()))
-        S, s_h, s_v, _ = cn.unpack(ride["stats"], V, H, ride["ldv"], ride["ldh"])
-        for got, want in zip((S, s_h, s_v), rbm_np.cd_statistics(u, ph, out[1], out[4])):
-            worst["stat"] = max(worst["stat"], float(np.abs(got - want).max() / max(1.0, np.abs(want).max())))
-        want_cost = rbm_np.reconstruction_cost(st, out[0], u)       # the monitoring cost, in units
-        worst["cost"] = max(worst["cost"], abs(c - want_cost) / abs(want_cost))
-        g, scale = sg.grad(u, ph @ st.W.T + st.vbias)               # at the parameters of before the update
-        worst["g"] = max(worst["g"], float((np.abs(g_dev - g) / np.maximum(1.0, scale)).max()))
-        twin_update(st, state, variant, u, ph, out[1], out[4], B, mom)
-        ls, ls_speed = sg.update(ls, ls_speed, g, ETA, mom)
-    want = dict({n: getattr(st, n) for n in NAMES[:6]}, log_sigma=ls, log_sigma_speed=ls_speed)
-    errs = [(n, float(np.abs(getattr(rbm, n).get_value() - want[n]).max() / max(1.0, np.abs(want[n]).max()))) for n in NAMES]
-    held = data[:64]
-    F_dev = rbm.free_energy(held).get_value().astype(np.float64)
-    F_twin = sg.free_energy(st, held.astype(np.float64), ls)
-    fe = float((np.abs(F_dev - F_twin) / np.maximum(1.0, np.abs(F_twin))).max())
-    print("%s: %s; %s; free energy %.3e" % (name, ", ".join("%s %.3e" % e for e in errs),
-                                          ", ".join("%s %.3e" % kv for kv in sorted(worst.items())), fe))
-    assert np.abs(ls).max() > 1e-3                  # (log_sigma moved)
-    # one product rounding and expf on top of a log_sigma that may sit 2e-6 from the twin's
-    check("sigma step %s: rows in units rel" % name, worst["units"], REL + 2e-6)
-    check("sigma step %s: ph_mean in P2" % name, worst["prob"], 2e-6, "prob")
-    check("sigma step %s: S, s_h, s_v / max" % name, worst["stat"], 1e-5, "stats")
-    check("sigma step %s: g / max(1, mean|u (u - m)|)" % name, worst["g"], 1e-5, "stats")
-    check("sigma step %s: cost rel" % name, worst["cost"], 1e-5)
-    for pname, err in errs:
-        check("sigma step %s: %s after %d steps / max" % (name, pname, STEPS), err, 2e-6, "update")
-    check("sigma step %s: free energy rel" % name, fe, 1e-4, "free_energy")
-    if variant == "centered":
-        check("sigma step %s: v_offset" % name, np.abs(rbm.v_offset.get_value() - state["offsets"][0]).max(), 2e-6)
-        check("sigma step %s: h_offset" % name, np.abs(rbm.h_offset.get_value() - state["offsets"][1]).max(), 2e-6)
-    if variant == "sparse":
-        check("sigma step %s: h_activity" % name, np.abs(rbm.h_activity.get_value() - state["q"]).max(), 2e-6)
+    r = sf.run_sigma(eng, V, H, B, k, error_free, variant)
+    assert not eng.keep_f32 and [n for n, _ in r.errs] == list(NAMES)
+    sf.check_sigma(name, r, REL)                    # (every figure printed, then the bounds as they were)
+    assert ("offsets" in r.state) == (variant == "centered") and ("q" in r.state) == (variant == "sparse")
 
 
 # ------------------------------------------------------------------------------------------------------------------ (c)

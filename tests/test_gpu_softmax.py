@@ -8,11 +8,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import _center_np as cn
 import _softmax_np as sm
+import _step_forms as sf
 from _margins import check
 from oracle import rbm_np
-from oracle.philox_np import PhiloxDraws
 
 pytestmark = pytest.mark.gpu
 
@@ -259,66 +258,9 @@ CASES = [  # id, V, H, B, k, boundaries (int: every visible in groups of K), per
     ("cd1_1024x256_k4_centered_sparse_bias_only", 1024, 256, 512, 1, 4, False, "both_bias"),
     ("cd1_60x24_k5_centered_sparse", 60, 24, 33, 1, 5, False, "both"),
 ]
-HP = dict(lr=0.1, weightcost=2e-4)
-
-
-def _run(eng, V, H, B, k, groups, persistent, mode, steps=STEPS):
-    import mdbn_amd
-    from mdbn_amd.utils import group_boundaries
-    bounds = group_boundaries(groups, V).tolist()
-    N = 3 * B + 7
-    rs = np.random.RandomState(31)
-    data = sm.one_hot_data(rs, N, V, bounds)
-    rbm = mdbn_amd.RBM(n_visible=V, n_hidden=H, numpy_rng=np.random.RandomState(123), theano_rng=mdbn_amd.RandomStreams(7), engine=eng,
-                       visible_groups=groups)
-    st = rbm_np.RBMState(V, H, W=rbm.W.get_value())
-    st.freeze_W0()
-    chain = (rs.uniform(size=(B, H)) < 0.5).astype(np.float32) if persistent else None
-    _, updates = rbm.get_cost_updates(k=k, batch_size=B, persistent=chain, **dict(HP, **sm.MODE_KEYWORDS[mode]))
-    fn = mdbn_amd.function(updates, mdbn_amd.shared(data, engine=eng), data_parallel=None)
-    order = [eng.index_tensor(rs.permutation(N)[:B], N) for _ in range(steps + 1)]
-    eng.trace_chain = True
-    state, flips = None, 0
-    try:
-        for t in range(steps):
-            mom = 0.5 if t < 2 else 0.9
-            chain0 = updates.persistent.get_value().astype(np.float64) if persistent else None
-            c = fn(indexes=order[t], momentum=mom, next_indexes=order[t + 1])
-            sc = eng.last_scratch
-            V2, P2 = sc.V2.cpu().numpy(), sc.P2.cpu().numpy()
-            v0 = data[order[t].cpu().numpy()].astype(np.float64)
-            ph, _, out, n = sm.cd_chain(st, v0, PhiloxDraws(7, rbm.stream_id, t), k, bounds, persistent=chain0,
-                                        trace_h=sc.trace_h.cpu().numpy()[:, :, :H], trace_v=sc.trace_v.cpu().numpy()[:, :, :V])
-            flips += n
-            assert n <= 3, "%d draws of step %d differ from the twin's" % (n, t)
-            assert np.array_equal(V2[:B], v0.astype(np.float32)), "rows 0..B-1 of V2 are not v0"
-            check("grouped step: ph_mean in P2", np.abs(P2[:B] - ph).max(), 2e-6, "prob")
-            check("grouped step: nv_mean in V2", np.abs(V2[B:] - out[1]).max(), 2e-6, "nv_mean")
-            check("grouped step: -nh_mean in P2", np.abs(P2[B:] + out[4]).max(), 2e-6, "prob")
-            assert np.array_equal(sc.vs.cpu().numpy(), sc.trace_v.cpu().numpy()[k - 1, :, :V])
-            if persistent:
-                assert np.array_equal(updates.persistent.get_value(), sc.trace_h.cpu().numpy()[k, :, :H]), "chain != recorded nh_sample"
-            want = sm.grouped_cost(out[0], v0, bounds) / B
-            check("grouped step: cost rel", abs(float(c) - want) / abs(want), 1e-5)
-            state = sm.update(st, state, v0, ph, out[1], out[4], B, HP["lr"], mode=mode, momentum=mom, weightcost=HP["weightcost"])
-            # the packed [S | s_h | s_v] the update read, after the transforms of the mode, and the offsets: the scales of
-            # tests/test_gpu_center.py (a centred bias statistic is a sum over S': rho max sum |mu S'| and rho max sum |S' lam|)
-            S, s_h, s_v, offsets = sm.transformed_stats(mode, state, v0, ph, out[1], out[4], B)
-            ldv, ldh = (V + 3) & ~3, rbm.W.tensor.stride(0)
-            gS, gsh, gsv, _ = cn.unpack(fn._stats_slots[0].cpu().numpy(), V, H, ldv, ldh)
-            sh_scale, sv_scale = np.abs(s_h).max(), np.abs(s_v).max()
-            if offsets is not None:
-                sh_scale = max(sh_scale, np.abs(offsets[0][:, None] * S).sum(axis=0).max())
-                sv_scale = max(sv_scale, np.abs(S * offsets[1][None, :]).sum(axis=1).max())
-                check("grouped step: v_offset", np.abs(rbm.v_offset.get_value() - offsets[0]).max(), 2e-6)
-                check("grouped step: h_offset", np.abs(rbm.h_offset.get_value() - offsets[1]).max(), 2e-6)
-            check("grouped step %s: S / max|S|" % mode, np.abs(gS - S).max() / np.abs(S).max(), 1e-5, "stats")
-            check("grouped step %s: s_h / scale" % mode, np.abs(gsh - s_h).max() / sh_scale, 1e-5, "stats")
-            check("grouped step %s: s_v / scale" % mode, np.abs(gsv - s_v).max() / sv_scale, 1e-5, "stats")
-        eng.synchronize()
-    finally:
-        eng.trace_chain = False
-    return rbm, st, flips, data, bounds
+HP = sf.GROUPED_HP
+assert HP == dict(lr=0.1, weightcost=2e-4) and sf.STEPS == STEPS
+_run = sf.run_grouped           # (the whole-step loop lives in tests/_step_forms.py)
 
 
 @pytest.mark.parametrize("name,V,H,B,k,groups,persistent,mode", CASES, ids=[c[0] for c in CASES])
@@ -331,11 +273,10 @@ def test_grouped_steps_against_the_teacher_forced_twin(built_lib, name, V, H, B,
         pytest.skip("no GPU")
     import mdbn_amd
     eng = mdbn_amd.HipEngine()                      # product defaults
-    rbm, st, flips, data, bounds = _run(eng, V, H, B, k, groups, persistent, mode)
-    errs = [(p, np.abs(getattr(rbm, p).get_value() - getattr(st, p)).max() / max(1.0, np.abs(getattr(st, p)).max())) for p in PARAMS]
-    print("%s: %s, %d draws differ" % (name, ", ".join("%s %.3e" % e for e in errs), flips))   # every figure before the first assertion
-    for p, err in errs:
-        check("grouped step %s: %s after %d steps / max" % (name, p, STEPS), err, 2e-6, "update")
+    r = _run(eng, V, H, B, k, groups, persistent, mode)
+    rbm, data = r.rbm, r.data
+    assert [p for p, _ in r.errs] == list(PARAMS)
+    sf.check_grouped(name, r)                       # (every figure printed, then 2e-6 on each parameter and speed)
     if name == "cd2_label_block":
         # the class prediction of the label block: exact p(label | pixels) against the twin's float64 enumeration
         rows = data[:16]

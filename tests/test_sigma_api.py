@@ -308,6 +308,126 @@ def test_the_full_batch_fixed_point():
     assert np.abs(want).max() > 1.0
 
 
+# ------------------------------------------------------------------------------------------------------------------ minibatch forms
+def follow(s, rbm, data, batches, chain=None):
+    """The float64 loop of ``make()``'s plan without a transform, from the state ``s`` taken before the first step; ``chain``:
+    PCD from that chain (the cost is then the pseudo-likelihood of the rows in units).  -> (log_sigma, speed, costs, chain)"""
+    ls, speed, costs = np.zeros(V), np.zeros(V), []
+    lo, hi = mdbn_amd.GRBM.log_sigma_range
+    for t, b in enumerate(batches):
+        b = np.asarray(b.cpu() if isinstance(b, torch.Tensor) else b)
+        n, momentum = len(b), (0.5 if t < 3 else 0.9)
+        u = data[b] * np.exp(-ls)[None, :]
+        ph, _, out = rbm_np.cd_chain(s, u, PhiloxDraws(rbm.theano_rng.seed, rbm.stream_id, t, 0), 2, chain)
+        if chain is not None:
+            costs.append(rbm_np.pseudo_likelihood_cost(s, u))
+            s.bit_i_idx = (s.bit_i_idx + 1) % V
+            chain = out[5]
+        else:
+            costs.append(rbm_np.reconstruction_cost(s, out[0], u))
+        g = (u * (u - (ph @ s.W.T + s.vbias))).mean(axis=0) - 1.0
+        S, s_h, s_v = rbm_np.cd_statistics(u, ph, out[1], out[4])
+        rbm_np.apply_update(s, S / 10.0, s_h / n, s_v / n, lrs(t), 0.0, 0.1, momentum)
+        ls, speed = np.clip(ls + speed * ETA, lo, hi), g + (speed - g) * momentum
+    return ls, speed, costs, chain
+
+
+def state_of(rbm):
+    return rbm_np.RBMState(V, H, W=rbm.W.tensor.numpy(), hbias=rbm.hbias.tensor.numpy(), vbias=rbm.vbias.tensor.numpy(), gauss=True)
+
+
+def run(fn, batches, hint=False):
+    return [float(fn(indexes=b, momentum=0.5 if t < 3 else 0.9, lr=lrs(t),
+                     **(dict(next_indexes=batches[t + 1]) if hint and t + 1 < len(batches) else {}))) for t, b in enumerate(batches)]
+
+
+def everything(rbm):
+    return [getattr(rbm, n).tensor.numpy().copy() for n in ("W", "hbias", "vbias", "W_speed", "hbias_speed", "vbias_speed", "log_sigma",
+                                                            "log_sigma_speed")]
+
+
+def test_the_hint_of_the_next_minibatch_changes_nothing():
+    res = []
+    for hint in (False, True):
+        fn, rbm, log, batches, inner, _ = make()
+        res.append((run(fn, batches, hint), everything(rbm)))
+        assert take(log) == (SIGMA + UPDATE) * len(batches)         # (the hint reaches no engine call)
+    assert res[0][0] == res[1][0] and all(np.array_equal(a, b) for a, b in zip(res[0][1], res[1][1]))
+
+
+def test_a_short_minibatch_has_staging_rows_of_its_own():
+    """10, 10, 7, 10, 1, 10 rows at batch_size 10: rows 7 .. 9 (1 .. 9) of the ten-row staging matrices hold NaN while the short
+    steps run, and the results are those of the float64 loop."""
+    fn, rbm, log, batches, inner, data = make()
+    s = state_of(rbm)
+    costs = []
+    for t, b in enumerate(batches):
+        if len(b) < 10:
+            for m in fn._sigma_rows[10]:
+                m[len(b):] = float("nan")
+        costs.append(float(fn(indexes=b, momentum=0.5 if t < 3 else 0.9, lr=lrs(t))))
+    assert sorted(fn._sigma_rows) == [1, 7, 10] and all(np.isfinite(m.numpy()).all() for m in fn._sigma_rows[10])
+    ls, speed, want, _ = follow(s, rbm, data, batches)
+    assert np.isfinite(costs).all() and np.allclose(costs, want, rtol=1e-9)
+    assert close(rbm.log_sigma.tensor.numpy(), ls) and close(rbm.log_sigma_speed.tensor.numpy(), speed)
+    for name in ("W", "hbias", "vbias", "W_speed", "hbias_speed", "vbias_speed"):
+        assert close(getattr(rbm, name).tensor.numpy(), getattr(s, name)), name
+
+
+def test_pcd_with_learn_sigma_keeps_its_chain_and_monitors_the_rows_in_units():
+    rs = np.random.RandomState(8)
+    chain0 = (rs.uniform(size=(10, H)) < 0.5).astype(np.float32)
+    fn, rbm, log, batches, inner, data = make(persistent=chain0.copy())
+    batches = [b for b in batches if len(b) == 10]
+    s = state_of(rbm)
+    costs = run(fn, batches)
+    assert take(log) == (SIGMA + [("apply_update", 0)]) * len(batches) and rbm.bit_i_idx == len(batches)
+    ls, speed, want, chain = follow(s, rbm, data, batches, chain=chain0.astype(np.float64))
+    assert np.array_equal(fn.plan.persistent.get_value(), chain.astype(np.float32))
+    assert np.allclose(costs, want, rtol=1e-9)                  # the pseudo-likelihood of the rows IN UNITS ...
+    s2 = state_of(rbm)
+    s2.bit_i_idx = rbm.bit_i_idx - 1
+    assert abs(rbm_np.pseudo_likelihood_cost(s2, data[batches[-1]]) - want[-1]) > 1e-3 * abs(want[-1])    # ... not of the raw rows
+    assert close(rbm.log_sigma.tensor.numpy(), ls) and close(rbm.W.tensor.numpy(), s.W) and np.abs(ls).max() > 1e-2
+    with pytest.raises(ValueError):
+        fn(indexes=np.arange(7), momentum=0.5)                  # 7 rows against a 10-row chain: as the plain PCD step
+
+
+def test_index_forms_int32_int64_and_a_repeated_row():
+    _, batches = problem()
+    forms = {"int64": [torch.from_numpy(b) for b in batches],
+             "int32": [torch.from_numpy(b.astype(np.int32)) for b in batches],
+             "list": [[int(i) for i in b[:-1]] + [int(b[0])] if len(b) > 1 else [int(b[0])] for b in batches]}
+    res = {}
+    for form, idx in forms.items():
+        fn, rbm, log, _, inner, data = make()
+        s = state_of(rbm)
+        costs = run(fn, idx)
+        ls, speed, want, _ = follow(s, rbm, data, idx)
+        assert np.allclose(costs, want, rtol=1e-9), form
+        assert close(rbm.log_sigma.tensor.numpy(), ls) and close(rbm.W.tensor.numpy(), s.W), form
+        res[form] = (costs, everything(rbm))
+    assert res["int32"][0] == res["int64"][0] and all(np.array_equal(a, b) for a, b in zip(res["int32"][1], res["int64"][1]))
+    assert res["list"][0] != res["int64"][0]
+
+
+def test_the_first_hidden_layer_of_a_pretrained_dbn_takes_raw_rows_to_units():
+    mdbn_amd.DBN.verbose = False
+    eng = SigmaOracle()
+    x = problem()[0]
+    net = mdbn_amd.DBN(numpy_rng=np.random.RandomState(1), n_ins=V, hidden_layers_sizes=[H], n_outs=4, engine=eng)
+    net.data_parallel = None
+    net.shuffle_rng = np.random.RandomState(3)
+    net.training(x, batch_size=10, k=1, pretraining_epochs=[3, 2], pretrain_lr=[0.005, 0.1], learn_sigma=0.05)
+    rbm, first = net.rbm_layers[0], net.sigmoid_layers[0]
+    assert first.log_sigma is rbm.log_sigma and net.sigmoid_layers[1].log_sigma is None
+    ls = rbm.log_sigma.tensor.numpy()
+    want = rbm_np.sigmoid((x * np.exp(-ls)[None, :]) @ rbm.W.tensor.numpy() + rbm.hbias.tensor.numpy())
+    got = first.forward(x).numpy()
+    assert np.abs(got - want).max() < 1e-12 and np.abs(ls).max() > 1e-3
+    assert np.abs(got - rbm_np.sigmoid(x @ rbm.W.tensor.numpy() + rbm.hbias.tensor.numpy())).max() > 1e-3
+
+
 # ------------------------------------------------------------------------------------------------------------------ identities
 def eager(rbm, x, h):
     """Every eager call of the surface, as host arrays (the RNG steps advance alike on both layers)."""

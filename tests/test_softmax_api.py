@@ -289,6 +289,52 @@ def test_six_steps_equal_a_hand_written_float64_loop(mode):
     assert np.abs(prbm.W.tensor.numpy() - rbm.W.tensor.numpy()).max() > 1e-6
 
 
+# ------------------------------------------------------------------------------------------------------------------ minibatch forms
+def run_forms(mode, batches, hint=False):
+    """Six steps of ``make(mode)`` on the index lists ``batches`` (any form), then the float64 loop on the same lists.
+    -> (costs, parameters and speeds, the layer, the twin's state, the twin's costs)"""
+    import torch
+    fn, rbm, log, _, inner, data = make(mode)
+    s = rbm_np.RBMState(V, H, W=rbm.W.tensor.numpy(), hbias=rbm.hbias.tensor.numpy(), vbias=rbm.vbias.tensor.numpy())
+    s.freeze_W0()
+    state, costs, want = None, [], []
+    for t, b in enumerate(batches):
+        momentum, lr = (0.5 if t < 3 else 0.9), (0.05 if t % 2 else 0.02)
+        extra = dict(next_indexes=batches[t + 1]) if hint and t + 1 < len(batches) else {}
+        costs.append(float(fn(indexes=b, momentum=momentum, lr=lr, **extra)))
+        rows = np.asarray(b.cpu() if isinstance(b, torch.Tensor) else b)
+        v0 = data[rows]
+        ph, _, out, _ = sm.cd_chain(s, v0, PhiloxDraws(rbm.theano_rng.seed, rbm.stream_id, t, 0), 2, BOUNDS)
+        want.append(sm.grouped_cost(out[0], v0, BOUNDS) / len(rows))
+        state = sm.update(s, state, v0, ph, out[1], out[4], 10, lr, mode=mode, momentum=momentum, weightcost=2e-4)
+    return costs, [getattr(rbm, name).tensor.numpy().copy() for name in PARAMS], rbm, s, want
+
+
+@pytest.mark.parametrize("mode", ["plain", "both"])
+def test_the_hint_of_the_next_minibatch_changes_nothing_on_a_ragged_schedule(mode):
+    _, batches = problem()                                      # 10, 10, 7, 10, 1, 10 rows at batch_size 10
+    plain, hinted = run_forms(mode, batches), run_forms(mode, batches, hint=True)
+    assert plain[0] == hinted[0] and all(np.array_equal(a, b) for a, b in zip(plain[1], hinted[1]))
+    for name, got in zip(PARAMS, hinted[1]):
+        assert np.abs(got - getattr(hinted[3], name)).max() < 1e-12, name
+    assert np.allclose(hinted[0], hinted[4], rtol=1e-12)
+
+
+def test_index_forms_int32_int64_and_a_repeated_row():
+    import torch
+    _, batches = problem()
+    forms = {"int64": [torch.from_numpy(b) for b in batches],
+             "int32": [torch.from_numpy(b.astype(np.int32)) for b in batches],
+             "list": [[int(i) for i in b[:-1]] + [int(b[0])] if len(b) > 1 else [int(b[0])] for b in batches]}
+    res = {form: run_forms("plain", idx) for form, idx in forms.items()}
+    for form, (costs, params, rbm, s, want) in res.items():
+        assert np.allclose(costs, want, rtol=1e-12), form
+        for name, got in zip(PARAMS, params):
+            assert np.abs(got - getattr(s, name)).max() < 1e-12, (form, name)
+    assert res["int32"][0] == res["int64"][0] and all(np.array_equal(a, b) for a, b in zip(res["int32"][1], res["int64"][1]))
+    assert res["list"][0] != res["int64"][0]
+
+
 # ------------------------------------------------------------------------------------------------------------------ refused
 def test_every_refused_combination_raises():
     eng = sm.GroupedOracle()
