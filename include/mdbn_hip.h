@@ -805,6 +805,32 @@ int  mdbn_group_softmax_sample(mdbn_ctx *ctx, void *stream, const float *pre, in
 int  mdbn_cd_step_grouped(mdbn_ctx *ctx, void *stream, const mdbn_cd_args *a, const int32_t *group_start,
                           const int32_t *group_start_host, int64_t n_groups);
 
+/* mdbn_ais_run_grouped: mdbn_ais_run (free, no clamp) for a Bernoulli layer whose visibles hold softmax groups: the
+ * arguments of mdbn_ais_run, then the table under the convention above.  On one-hot rows
+ *   log p*_beta(v) = sum_j softplus(beta a_j(v)) + v . b_beta
+ * is the Bernoulli expression, so the weight update, the hidden draw, the double logw, the 2K - 1 Philox steps, the paths,
+ * the traces and the cut of a long schedule are mdbn_ais_run's, bit for bit.  What changes is the visible draw, v_1 ~ p_0
+ * included: on a group  v ~ softmax_c(x_c)  over its tempered pre-activations
+ *   x_c = fma(beta, m_c, fma(beta, vbias_c - base_vbias_c, base_vbias_c)),   m = h W^T   (beta = 0, m = 0 for v_1)
+ * with the arithmetic and the addressing of mdbn_group_softmax_sample: mx = max_c x_c, e_c = exp(x_c - mx) (the hardware
+ * exponential), Z = sum_c e_c in ascending c in float32, mean_c = e_c / Z (correctly rounded), the category the first c with
+ * u < C_c (C_c: the running float32 sum of the means) and the last one when none qualifies; ONE uniform per (chain, group),
+ * the Philox word of the group's FIRST column (draw index 0, step rng->step + 2k, the global chain row) -- the uniforms of
+ * its other columns are not used.  A Bernoulli column outside the span keeps mdbn_ais_run's draw, so n_groups = 0 gives
+ * mdbn_ais_run's logw, v_state and traces bit for bit on both paths.  Every recorded visible row holds exactly one 1 per
+ * group.  The base model changes with the draw (left to the caller, float64 on the host):
+ *   log Z_A = H log 2 + sum_{Bernoulli i} softplus(base_vbias_i) + sum_g logsumexp_{c in g} base_vbias_c.
+ * path 1 needs no LDS beyond mdbn_ais_run's image, so the shapes that fit are the same; workspace: mdbn_ais_workspace_bytes.
+ * MDBN_EINVAL with a message, before any launch and with every output untouched: gauss, an invalid table (not ascending, a
+ * group of fewer than 2 or more than MDBN_GROUP_MAX columns, a boundary beyond V, a missing copy), path = 1 on a shape
+ * that does not fit, and whatever mdbn_ais_run refuses. */
+int  mdbn_ais_run_grouped(mdbn_ctx *ctx, void *stream, const float *W, int64_t V, int64_t H, int64_t ldh,
+                          const float *hbias, const float *vbias, const float *base_vbias, int gauss,
+                          const float *betas, int64_t n_betas, int64_t M, int64_t ldv, float *v_state,
+                          double *logw, float *trace_h, float *trace_v, int path, const mdbn_rng *rng,
+                          void *workspace, int64_t workspace_bytes, const int32_t *group_start,
+                          const int32_t *group_start_host, int64_t n_groups);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)) (the float32 softplus terms summed in

@@ -111,6 +111,8 @@ SIGNATURES = {
     "mdbn_ais_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
     "mdbn_ais_run": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp,
                      _vp, _vp, _vp, _i32, _rngp, _vp, _i64],
+    "mdbn_ais_run_grouped": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp,
+                             _vp, _vp, _vp, _i32, _rngp, _vp, _i64, _vp, _vp, _i64],
     "mdbn_ais_cond_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
     "mdbn_ais_cond_run": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64,
                           _vp, _vp, _vp, _vp, _i32, _rngp, _vp, _i64],

@@ -14,6 +14,15 @@ constexpr int AIS_CUT = 4096;               // temperatures one launch of the on
                                             // (~3 us per temperature) and the Philox addressing makes the cut invisible
 constexpr int AIS_NT = 256;                 // threads of the general path's per-temperature kernels: one wave per chain
 
+// Categorical visible units (mdbn_ais_run_grouped): the unit map of GroupSoftmaxArgs (mdbn_groups.h) -- group g is columns
+// group_start[g] .. group_start[g + 1] - 1 of the span [span_lo, span_hi), the columns outside it are Bernoulli units.  `on`
+// selects the grouped kernels (n_groups = 0 with `on`: they run with every column a Bernoulli unit and give the plain run
+// bit for bit).  span_lo / span_hi come from the caller's checked host copy; what the device copy says is clamped to them.
+struct AisGroups {
+    const int32_t* group_start;                      // device [n_groups + 1] (not read with n_groups = 0)
+    int n_groups, span_lo, span_hi, on;
+};
+
 // One-launch path (LDS-resident layers, small_shape_ok): temperatures k0 + 1 .. k1 of chains 0 .. M - 1.
 struct AisSmallArgs {
     int M, V, H, gauss;
@@ -28,6 +37,7 @@ struct AisSmallArgs {
     float* v_state;                                  // [M][ldv]: k0 > 0: v_{k0 + 1} on entry; v_{min(k1 + 1, K)} on return
     double* logw;                                    // [M]: k0 > 0: log w after temperature k0 on entry; after k1 on return
     float* trace_h; float* trace_v;                  // [K - 1][M][ldh], [K][M][ldv] or NULL
+    AisGroups groups;                                // softmax groups of the visible layer (Bernoulli, no clamp) or {}
 };
 
 // General path, per temperature k: pre_h = v_k W + c is in `pre` (the propup GEMM), then
@@ -49,6 +59,7 @@ struct AisStepArgs {
     const float* d2;                                 // [mask_rows]: sum over the free columns of (b - b_A)^2 (Gaussian; launch_ais_d2)
     double* logw;                                    // [M]
     float* trace;                                    // this temperature's trace slot or NULL
+    AisGroups groups;                                // softmax groups of the visible layer (Bernoulli, no clamp) or {}
 };
 
 bool ais_small_ok(int64_t M, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh);

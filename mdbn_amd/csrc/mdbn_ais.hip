@@ -23,6 +23,13 @@
 // the free run bit for bit; the Philox addressing is unchanged (a held column's uniform is drawn and not used).  CLAMP = false
 // is the free run: no mask, no obs, one d2 for all chains.
 //
+// Softmax groups (mdbn_ais_run_grouped): a visible layer that holds a span of one-hot groups between Bernoulli columns
+// (mdbn_groups.hip).  log p*_beta(v) is the Bernoulli expression on one-hot rows, so the weight update, the hidden draw, the
+// double log w, the Philox steps and the hand-over of a cut run are the free run's; only the visible draw of a group column
+// changes (v_1 ~ p_0 included): v ~ softmax_c(x_c) over the group's tempered pre-activations x_c, ONE uniform per (chain,
+// group) -- the Philox word of the group's first column -- by the group draw of mdbn_sampler_kit.h, which both paths compose
+// from the same float32 operations in the same order.  A Bernoulli column outside the span keeps its draw; no clamp.
+//
 // ais_small_kernel (LDS-resident layers): the shape of small_cd_kernel -- W staged once into one CU's LDS, a workgroup owns
 // four-chain slabs (one Philox block) and runs the whole loop over the temperatures on the exact-f32 4x4x1 MFMA passes of
 // mdbn_small_passes.h.  No workgroup ever waits for, or exchanges anything with, another.  Both passes hand column `tid` to
@@ -38,6 +45,7 @@
 #include "mdbn_small_passes.h"
 #include "mdbn_sampler_kit.h"
 #include "mdbn_ais.h"
+#include "mdbn_groups.h"                    // MDBN_GROUP_MAX and the unit map the grouped visible kernel shares
 
 namespace mdbn {
 
@@ -93,17 +101,29 @@ bool ais_clamp_ok(const Args& a)
            (a.mask != nullptr || (a.C == 1 && a.mask_rows == 1));
 }
 
+// ... and of the groups: none, or a Bernoulli layer without a clamp whose span lies inside the row (the rule of
+// launch_group_softmax)
+bool ais_groups_ok(const AisGroups& g, int V, int gauss, const float* mask)
+{
+    if (!g.on) return g.n_groups == 0;
+    return !gauss && !mask && g.n_groups >= 0 && (g.n_groups == 0 || g.group_start) && g.span_lo >= 0 && g.span_lo <= g.span_hi &&
+           g.span_hi <= V && (g.n_groups == 0) == (g.span_lo == g.span_hi) && g.n_groups <= g.span_hi - g.span_lo;
+}
+
 }  // namespace
 
-template <bool GAUSS, bool TRACE, bool CLAMP>
+template <bool GAUSS, bool TRACE, bool CLAMP, bool GROUPS = false>
 __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
 {
+    static_assert(!GROUPS || (!GAUSS && !CLAMP), "softmax groups: a Bernoulli layer without a clamp");
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const SmallLayout& L = a.L;
     lds_f* const lds = (lds_f*)sm;
     // small_layout's buffers under the roles they have here
     lds_f* const Wl = lds + L.oW;
     lds_f* const X = lds + L.oXa;           // [4][ldx] visible state v_k (after the clamp)
+    lds_f* const PX = lds + L.oX0;          // (groups) [V64][4] tempered pre-activations x_c of the group columns, then their means
+    lds_f* const EX = lds + L.oXb;          // (groups) [V64][4] e_c = exp(x_c - max): the Bernoulli layout's third row buffer
     lds_f* const Hs = lds + L.oHs;          // [4][ldhs] hidden sample h_k
     lds_f* const part = lds + L.oPart;
     lds_f* const hbl = lds + L.oHb;         // c
@@ -128,6 +148,24 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
         for (int i = lane; i < L.V64; i += 64) d2 += dbl[i] * dbl[i];
         d2 = wave_sum(d2);
     }
+    // ---- (groups) this thread's column belongs to the group [c0, c1) for the whole launch; c1 = c0: a Bernoulli column.
+    // The last g with group_start[g] <= tid; the caller checked its host copy, the device copy is clamped to the span all the
+    // same (group_softmax_kernel), and a walk never leaves [c0, c1)
+    int c0 = 0, c1 = 0;
+    if constexpr (GROUPS) {
+        const AisGroups& G = a.groups;
+        if (tid >= G.span_lo && tid < G.span_hi && G.n_groups > 0) {
+            int lo = 0, hi = G.n_groups - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (G.group_start[mid] <= tid) lo = mid; else hi = mid - 1;
+            }
+            c0 = min(max(G.group_start[lo], G.span_lo), tid);
+            c1 = min(min(max(G.group_start[lo + 1], tid + 1), G.span_hi), c0 + MDBN_GROUP_MAX);
+            if (c1 <= tid) c0 = c1 = 0;     // (a table the host copy does not describe: the column falls back to a Bernoulli unit)
+        }
+    }
+    const bool grp = GROUPS && c1 > c0;
 
     for (int slab = blockIdx.x; slab < nslabs; slab += gridDim.x) {
         const int row0 = slab * SM_ROWS;
@@ -186,17 +224,61 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
                     if (ok[e]) trace[(int64_t)(row0 + e) * ldv + col] = v[e];
             }
         };
+        // (groups) a visible draw in two parts.  group_x, in the place of the Bernoulli draw: the four tempered pre-activations
+        // of a group column go into PX.  group_pick, every thread of the workgroup, after the barrier that follows: e_c into
+        // EX -- ONE exponential per (chain, column) --, barrier, Z and the column's mean over x_c in PX, barrier, the running
+        // sum of the means up to the thread's own column and its 0 / 1 entry (mdbn_sampler_kit.h: the group draw).  One uniform
+        // per (chain, group): the Philox word of the group's first column.  Two barriers, whatever the groups.
+        // PX and EX hold a column's four chains side by side ([column][4]: one 16-byte read per category serves all four).
+        auto group_x = [&](float beta, const float (&m)[4], float bA, float db, int col) {
+            *(lds_f4*)(PX + 4 * col) = sf32x4{tempered_pre_v(beta, m[0], bA, db), tempered_pre_v(beta, m[1], bA, db),
+                                              tempered_pre_v(beta, m[2], bA, db), tempered_pre_v(beta, m[3], bA, db)};
+        };
+        auto group_pick = [&](const PhiloxKey& key, float (&v)[4], float (&s)[4]) {
+            if (grp) {
+                sf32x4 mx = *(const lds_f4*)(PX + 4 * c0);
+                for (int c = c0 + 1; c < c1; ++c) {
+                    const sf32x4 x = *(const lds_f4*)(PX + 4 * c);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], x[e]);
+                }
+                const sf32x4 x = *(const lds_f4*)(PX + 4 * tid);
+                *(lds_f4*)(EX + 4 * tid) = sf32x4{group_exp(x[0], mx[0]), group_exp(x[1], mx[1]), group_exp(x[2], mx[2]), group_exp(x[3], mx[3])};
+            }
+            SM_SYNC();
+            if (grp) {
+                sf32x4 Z = {0.f, 0.f, 0.f, 0.f};
+                for (int c = c0; c < c1; ++c) Z += *(const lds_f4*)(EX + 4 * c);
+                const sf32x4 ex = *(const lds_f4*)(EX + 4 * tid);
+                *(lds_f4*)(PX + 4 * tid) = sf32x4{group_mean(ex[0], Z[0]), group_mean(ex[1], Z[1]), group_mean(ex[2], Z[2]), group_mean(ex[3], Z[3])};
+            }
+            SM_SYNC();
+            if (grp) {
+                uint32_t w[4];
+                philox_rows4(key, 0u, grow0, (uint32_t)c0, w);
+                const float db = dbl[tid];
+                sf32x4 before = {0.f, 0.f, 0.f, 0.f};
+                for (int c = c0; c < tid; ++c) before += *(const lds_f4*)(PX + 4 * c);
+                const sf32x4 upto = before + *(const lds_f4*)(PX + 4 * tid);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = ok[e] ? group_entry(philox_u01(w[e]), before[e], upto[e], tid == c1 - 1) : 0.f;
+                    s[e] = v[e] * db;
+                }
+            }
+        };
         // ---- the chain's start: v_1 ~ p_0 (step s) under the clamp, or the state an earlier launch left
         double lw = 0.0;
+        float v[4], s[4];                    // this thread's column of the visible state, from a draw to put_v
         if (tid < L.V64) {
             const int col = tid;
             const bool live = col < V;
             const float bA = bAl[col], db = dbl[col];
             const bool okc[4] = {ok[0] && live, ok[1] && live, ok[2] && live, ok[3] && live};
-            float v[4], s[4];
             if (a.k0 == 0) {
                 const float m0[4] = {0.f, 0.f, 0.f, 0.f};
-                ais_draw_v<GAUSS>(a.rng, grow0, col, 0.0f, bA, db, m0, okc, v, s);
+                if (grp) group_x(0.0f, m0, bA, db, col);
+                else ais_draw_v<GAUSS>(a.rng, grow0, col, 0.0f, bA, db, m0, okc, v, s);
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -205,7 +287,14 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
                 }
             }
             if constexpr (CLAMP) ais_clamp(ob, held, v, s);
-            put_v(v, s, col, a.k0 == 0 ? a.trace_v : nullptr);
+            if constexpr (!GROUPS) put_v(v, s, col, a.k0 == 0 ? a.trace_v : nullptr);
+        }
+        if constexpr (GROUPS) {
+            if (a.k0 == 0) {
+                SM_SYNC();
+                group_pick(a.rng, v, s);
+            }
+            if (tid < L.V64) put_v(v, s, tid, a.k0 == 0 ? a.trace_v : nullptr);
         }
         if (a.k0 > 0 && tid < SM_ROWS && row0 + tid < M) lw = a.logw[row0 + tid];
         SM_SYNC();
@@ -254,11 +343,16 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
                             const float bA = bAl[col], db = dbl[col];
                             const bool okc[4] = {ok[0] && live, ok[1] && live, ok[2] && live, ok[3] && live};
                             const float m[4] = {x[0], x[1], x[2], x[3]};
-                            float v[4], s[4];
-                            ais_draw_v<GAUSS>(kv, grow0, col, b1, bA, db, m, okc, v, s);
+                            if (grp) group_x(b1, m, bA, db, col);
+                            else ais_draw_v<GAUSS>(kv, grow0, col, b1, bA, db, m, okc, v, s);
                             if constexpr (CLAMP) ais_clamp(ob, held, v, s);
-                            put_v(v, s, col, TRACE && a.trace_v ? a.trace_v + (int64_t)k * M * ldv : nullptr);
+                            if constexpr (!GROUPS) put_v(v, s, col, TRACE && a.trace_v ? a.trace_v + (int64_t)k * M * ldv : nullptr);
                         });
+                if constexpr (GROUPS) {                                // (sm_down's closing barrier: PX is complete)
+                    group_pick(kv, v, s);
+                    if (tid < L.V64) put_v(v, s, tid, TRACE && a.trace_v ? a.trace_v + (int64_t)k * M * ldv : nullptr);
+                    SM_SYNC();
+                }
                 if (tid < SM_ROWS) {
                     s1 = 0.f;
                     for (int t = 0; t < L.tiles_dn; ++t) s1 += redV[tid * 8 + t];
@@ -287,13 +381,15 @@ hipError_t launch_ais_small(const AisSmallArgs& a, hipStream_t s)
 {
     if (!ais_small_ok(a.M, a.V, a.H, a.gauss, a.ldv, a.ldh) || a.k0 < 0 || a.k1 <= a.k0 || a.k1 > a.K || !ais_clamp_ok(a))
         return hipErrorInvalidValue;
+    if (!ais_groups_ok(a.groups, a.V, a.gauss, a.mask)) return hipErrorInvalidValue;
     const SmallLayout L = small_layout(a.V, a.H, a.gauss != 0);
     const bool trace = a.trace_h || a.trace_v;
-    const int variant = (a.mask ? 4 : 0) | (a.gauss ? 2 : 0) | (trace ? 1 : 0);
-    void (*const kerns[8])(AisSmallArgs) = {
+    const int variant = a.groups.on ? 8 | (trace ? 1 : 0) : (a.mask ? 4 : 0) | (a.gauss ? 2 : 0) | (trace ? 1 : 0);
+    void (*const kerns[10])(AisSmallArgs) = {
         ais_small_kernel<false, false, false>, ais_small_kernel<false, true, false>, ais_small_kernel<true, false, false>,
         ais_small_kernel<true, true, false>,   ais_small_kernel<false, false, true>, ais_small_kernel<false, true, true>,
-        ais_small_kernel<true, false, true>,   ais_small_kernel<true, true, true>};
+        ais_small_kernel<true, false, true>,   ais_small_kernel<true, true, true>,
+        ais_small_kernel<false, false, false, true>, ais_small_kernel<false, true, false, true>};
     // one workgroup per slab up to one per CU of the chip (no partials to sum here: the cap only bounds the W stagings)
     const int nslabs = (a.M + SM_ROWS - 1) / SM_ROWS;
     const dim3 grid(nslabs < 256 ? nslabs : 256), block(SM_NT);
@@ -398,6 +494,88 @@ __global__ __launch_bounds__(AIS_NT) void ais_visible_kernel(AisStepArgs a)
     if (tid < 4 && row0 + tid < a.M) a.s1[row0 + tid] = tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3];
 }
 
+// ais_visible_kernel<false, false> for a layer with softmax groups: a thread walks UNITS tid, tid + AIS_NT, ... -- the unit map
+// of GroupSoftmaxArgs (mdbn_groups.h), with the pad columns V .. ldv - 1 as Bernoulli units behind the span, written as zeros
+// like the plain kernel writes them.  A Bernoulli unit is the plain kernel's column; a group is walked three times per chain
+// (group_draw: max, Z, means) with x_c formed from a.pre on the fly, its uniform the Philox word of its first column.  With
+// n_groups = 0 a unit is a column and every sum has the plain kernel's operands in its order: the same bits.
+__global__ __launch_bounds__(AIS_NT) void ais_visible_grouped_kernel(AisStepArgs a)
+{
+    __shared__ float red[4 * (AIS_NT / 64)];
+    const int row0 = (int)blockIdx.x * 4, tid = threadIdx.x;
+    const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
+    const float beta = a.k == 0 ? 0.0f : a.betas[a.k];
+    PhiloxKey key = a.rng;
+    key.step = a.rng.step + (uint32_t)(2 * a.k);
+    const AisGroups& G = a.groups;
+    const int units = G.span_lo + G.n_groups + ((int)a.ldv - G.span_hi);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int unit = tid; unit < units; unit += AIS_NT) {
+        int c0, K = 0;                                   // first column; K = 0: a Bernoulli column
+        if (unit < G.span_lo) {
+            c0 = unit;
+        } else if (unit < G.span_lo + G.n_groups) {
+            const int g = unit - G.span_lo;
+            // (the caller checked its host copy; the device copy is clamped to the span all the same)
+            c0 = min(max(G.group_start[g], G.span_lo), G.span_hi - 1);
+            K = min(min(max(G.group_start[g + 1], c0 + 1), G.span_hi) - c0, MDBN_GROUP_MAX);
+        } else {
+            c0 = G.span_hi + (unit - G.span_lo - G.n_groups);
+        }
+        if (K == 0) {
+            const int col = c0;
+            const bool live = col < a.V;
+            const float bA = live ? a.base_vbias[col] : 0.f, db = live ? a.vbias[col] - bA : 0.f;
+            bool ok[4];
+            float m[4], v[4], s[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                ok[e] = live && row0 + e < a.M;
+                m[e] = ok[e] && a.k > 0 ? a.pre[(int64_t)(row0 + e) * a.ldv + col] : 0.f;
+            }
+            ais_draw_v<false>(key, grow0, col, beta, bA, db, m, ok, v, s);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc[e] += s[e];
+                if (row0 + e < a.M) {
+                    a.v[(int64_t)(row0 + e) * a.ldv + col] = v[e];
+                    if (a.trace) a.trace[(int64_t)(row0 + e) * a.ldv + col] = v[e];
+                }
+            }
+            continue;
+        }
+        uint32_t w[4];
+        philox_rows4(key, 0u, grow0, (uint32_t)c0, w);
+        const float* bAp = a.base_vbias + c0;
+        const float* bp = a.vbias + c0;
+        bool live[4];
+        int64_t off[4];
+        float u[4], se[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            live[e] = row0 + e < a.M;
+            off[e] = (int64_t)(row0 + e) * a.ldv + c0;
+            u[e] = philox_u01(w[e]);
+        }
+        const bool has_m = a.k > 0;
+        group_draw(K, u,
+                   [&](int c, int e) {
+                       const float bA = bAp[c];
+                       return tempered_pre_v(beta, live[e] && has_m ? a.pre[off[e] + c] : 0.f, bA, bp[c] - bA);
+                   },
+                   [&](int c, int e, float v) {
+                       if (!live[e]) return;
+                       se[e] += v * (bp[c] - bAp[c]);
+                       a.v[off[e] + c] = v;
+                       if (a.trace) a.trace[off[e] + c] = v;
+                   });
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] += se[e];
+    }
+    rows4_block_sum<AIS_NT>(acc, red);
+    if (tid < 4 && row0 + tid < a.M) a.s1[row0 + tid] = tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3];
+}
+
 hipError_t launch_ais_d2(const AisStepArgs& a, float* d2, hipStream_t s)
 {
     if (!ais_clamp_ok(a)) return hipErrorInvalidValue;
@@ -414,9 +592,11 @@ hipError_t launch_ais_hidden(const AisStepArgs& a, hipStream_t s)
 
 hipError_t launch_ais_visible(const AisStepArgs& a, hipStream_t s)
 {
-    if (!ais_clamp_ok(a) || a.k < 0 || a.k >= a.K) return hipErrorInvalidValue;
+    if (!ais_clamp_ok(a) || a.k < 0 || a.k >= a.K || !ais_groups_ok(a.groups, a.V, a.gauss, a.mask)) return hipErrorInvalidValue;
     const dim3 grid((a.M + 3) / 4), block(AIS_NT);
-    if (a.mask) {
+    if (a.groups.on) {
+        hipLaunchKernelGGL(ais_visible_grouped_kernel, grid, block, 0, s, a);
+    } else if (a.mask) {
         if (a.gauss) hipLaunchKernelGGL((ais_visible_kernel<true, true>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((ais_visible_kernel<false, true>), grid, block, 0, s, a);
     } else {

@@ -134,6 +134,9 @@ inline int64_t ru64(int64_t x) { return (x + 63) & ~int64_t(63); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int check_mat(const void* p, int64_t ld, int64_t cols, const char* name);
+// the table of a layer with softmax groups as the host holds it (mdbn_drv_groups.hip: the rules of mdbn_group_softmax_sample)
+// -> the span [lo, hi) the groups cover; n_groups = 0: lo = hi = V
+int check_groups(const int32_t* dev, const int32_t* host, int64_t n_groups, int64_t V, int& lo, int& hi);
 PhiloxKey make_key(const mdbn_rng& r, uint32_t draw);
 
 // carve-up of the caller's workspace

@@ -10,11 +10,9 @@
 using namespace mdbn;
 using namespace mdbn::capi;
 
-namespace {
-
 // The table as the host holds it: strictly ascending boundaries inside [0, V], every group of 2 .. MDBN_GROUP_MAX columns.
 // n_groups = 0: no table is read (both pointers may be NULL).  -> the span [lo, hi) the groups cover
-int check_groups(const int32_t* dev, const int32_t* host, int64_t n_groups, int64_t V, int& lo, int& hi)
+int mdbn::capi::check_groups(const int32_t* dev, const int32_t* host, int64_t n_groups, int64_t V, int& lo, int& hi)
 {
     REQUIRE(n_groups >= 0 && n_groups <= V / 2, "n_groups = %lld: between 0 and V / 2", (long long)n_groups);
     lo = hi = (int)V;
@@ -31,6 +29,8 @@ int check_groups(const int32_t* dev, const int32_t* host, int64_t n_groups, int6
     lo = host[0]; hi = host[n_groups];
     return MDBN_OK;
 }
+
+namespace {
 
 int64_t group_partial_floats(int64_t B, int64_t V) { return ru64(group_softmax_blocks(B, V)); }    // (units <= V)
 

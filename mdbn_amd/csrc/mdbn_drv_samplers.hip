@@ -119,12 +119,13 @@ int ais_workspace_bytes(int64_t M, int64_t clamp_rows, int64_t V, int64_t H, int
     return MDBN_OK;
 }
 
-// Both runs once their own shape rule holds (the rules that need no device still come first): M chains, free (clamp == NULL)
-// or clamped; `sizer` names the entry point's own *_workspace_bytes
+// The three runs once their own rules hold (the rules that need no device still come first): M chains, free (clamp == NULL)
+// or clamped, or free on a layer with softmax groups (groups.on: the checked table of mdbn_ais_run_grouped); `sizer` names the
+// entry point's own *_workspace_bytes
 int ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias, const float* vbias,
             const float* base_vbias, int gauss, const float* betas, int64_t n_betas, int64_t M, const AisClamp* clamp, int64_t ldv,
             float* v_state, double* logw, float* trace_h, float* trace_v, int path, const mdbn_rng* rng, void* workspace,
-            int64_t workspace_bytes, const char* sizer)
+            int64_t workspace_bytes, const char* sizer, const AisGroups& groups = AisGroups{})
 {
     REQUIRE(n_betas >= 2, "n_betas = %lld: a schedule has at least beta_0 = 0 and beta_K = 1", (long long)n_betas);
     if (clamp)
@@ -160,6 +161,7 @@ int ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, i
         a.K = K;
         a.rng = make_key(*rng, 0u);
         a.obs = obs; a.mask = mask; a.mask_rows = mask_rows; a.C = C;
+        a.groups = groups;
         a.v_state = v_state ? v_state : wsf;
         a.logw = logw;
         a.trace_h = trace_h; a.trace_v = trace_v;
@@ -187,6 +189,7 @@ int ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, i
     st.betas = betas; st.vbias = vbias; st.base_vbias = base_vbias;
     st.rng = make_key(*rng, 0u);
     st.obs = obs; st.mask = mask; st.mask_rows = mask_rows; st.C = C;
+    st.groups = groups;
     st.pre = pre; st.h = h; st.v = v; st.s1 = s1; st.d2 = d2; st.logw = logw;
     if (gauss) HIP_OK(launch_ais_d2(st, d2, s));         // (read under gauss only)
     st.k = 0; st.trace = trace_v;
@@ -232,6 +235,23 @@ int mdbn_ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t
     REQUIRE(M < (1ll << 31) && n_betas < (1ll << 30), "M / n_betas too large");
     return ais_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, gauss, betas, n_betas, M, nullptr, ldv, v_state, logw, trace_h,
                    trace_v, path, rng, workspace, workspace_bytes, "mdbn_ais_workspace_bytes");
+}
+
+int mdbn_ais_run_grouped(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+                         const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t n_betas, int64_t M,
+                         int64_t ldv, float* v_state, double* logw, float* trace_h, float* trace_v, int path, const mdbn_rng* rng,
+                         void* workspace, int64_t workspace_bytes, const int32_t* group_start, const int32_t* group_start_host,
+                         int64_t n_groups)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
+    REQUIRE(M < (1ll << 31) && n_betas < (1ll << 30) && V <= (1 << 24), "M / n_betas / V too large");
+    REQUIRE(!gauss, "categorical visible units: a Gaussian layer (gauss = 1) has no groups");
+    AisGroups g{};
+    CHECK(check_groups(group_start, group_start_host, n_groups, V, g.span_lo, g.span_hi));
+    g.group_start = group_start; g.n_groups = (int)n_groups; g.on = 1;
+    return ais_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, 0, betas, n_betas, M, nullptr, ldv, v_state, logw, trace_h,
+                   trace_v, path, rng, workspace, workspace_bytes, "mdbn_ais_workspace_bytes", g);
 }
 
 int mdbn_ais_cond_workspace_bytes(mdbn_ctx* ctx, int64_t N, int64_t C, int64_t V, int64_t H, int64_t n_betas, int path, int64_t* bytes)

@@ -80,6 +80,54 @@ __device__ __forceinline__ float box_muller(float u1, float u2)     // N(0, 1) f
     return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
 
+// the tempered visible pre-activation b_A + beta (b - b_A) + beta m of one (row, column)
+__device__ __forceinline__ float tempered_pre_v(float beta, float m, float bA, float db)
+{
+    return fmaf(beta, m, fmaf(beta, db, bA));
+}
+
+// ---- the category draw of a softmax group of K columns (the arithmetic of group_softmax_kernel, mdbn_groups.hip), from its
+// tempered pre-activations x_c:  mx = max_c x_c,  e_c = __expf(x_c - mx),  Z = sum_c e_c (ascending c, f32),
+// mean_c = e_c / Z (correctly rounded),  C_c = the running f32 sum of the means;  the category is the first c with u < C_c and
+// the last one when none qualifies.  C never falls (a sum of non-negative terms, rounded to nearest), so column c is the
+// drawn one exactly when u >= C_{c-1} (C_{-1} = 0) and (u < C_c or c = K - 1): a thread that owns one column decides its
+// own entry from the two sums (ais_small_kernel), a thread that owns the group walks it (group_draw, the general path).
+// Both forms add the same operands in the same order.
+__device__ __forceinline__ float group_exp(float x, float mx) { return __expf(x - mx); }
+__device__ __forceinline__ float group_mean(float e, float Z) { return __fdiv_rn(e, Z); }
+__device__ __forceinline__ float group_entry(float u, float C_before, float C, bool last)
+{
+    return !(u < C_before) && (u < C || last) ? 1.0f : 0.0f;
+}
+
+// one group of a 4-row block by one thread in three walks (max, Z, means): x(c, e) = the pre-activation of category c in row e,
+// out(c, e, v) takes the 0 / 1 entry; K has no register cost.  The four rows go side by side through every walk -- their loads
+// do not depend on each other, so a walk waits for memory once per category, not once per (category, row); each row's sums
+// are its own, in ascending c.
+template <class X, class Out>
+__device__ __forceinline__ void group_draw(int K, const float (&u)[4], X&& x, Out&& out)
+{
+    float mx[4], Z[4] = {0.f, 0.f, 0.f, 0.f}, cum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) mx[e] = x(0, e);
+    for (int c = 1; c < K; ++c) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], x(c, e));
+    }
+    for (int c = 0; c < K; ++c) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) Z[e] += group_exp(x(c, e), mx[e]);
+    }
+    for (int c = 0; c < K; ++c) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float before = cum[e];
+            cum[e] += group_mean(group_exp(x(c, e), mx[e]), Z[e]);
+            out(c, e, group_entry(u[e], before, cum[e], c == K - 1));
+        }
+    }
+}
+
 // v | h for one (4-row group, column), every row at its own beta: pre = b_A + beta (b - b_A) + beta m, then the draw.
 // `s` receives the column's share of s1.
 template <bool GAUSS>
@@ -91,7 +139,7 @@ __device__ __forceinline__ void tempered_draw_v(const PhiloxKey& key, uint64_t g
     if (GAUSS) philox_rows4(key, MDBN_NORMAL_BIT, grow0, (uint32_t)col, wb);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        pre[e] = fmaf(beta[e], m[e], fmaf(beta[e], db, bA));
+        pre[e] = tempered_pre_v(beta[e], m[e], bA, db);
         if (GAUSS) {
             const float z = box_muller(philox_u01(wa[e]), philox_u01(wb[e]));
             v[e] = ok[e] ? pre[e] + z : 0.f;

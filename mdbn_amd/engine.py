@@ -610,9 +610,10 @@ class HipEngine(object):
             x = t
         return x
 
-    def _ais(self, W, hbias, vbias, base_vbias, gauss, betas, M, rng, path, trace, clamp=None):
-        """What ``ais`` and ``ais_conditional`` share: M chains through mdbn_ais_run, or with ``clamp`` = (obs, mask, mask_rows,
-        N, chains per row), padded device matrices, through mdbn_ais_cond_run.  Returns ``(logw [M] float64 numpy, trace_h,
+    def _ais(self, W, hbias, vbias, base_vbias, gauss, betas, M, rng, path, trace, clamp=None, groups=None):
+        """What ``ais``, ``ais_grouped`` and ``ais_conditional`` share: M chains through mdbn_ais_run, or with ``clamp`` = (obs,
+        mask, mask_rows, N, chains per row), padded device matrices, through mdbn_ais_cond_run, or with ``groups`` (a
+        ``GroupTable``, no clamp) through mdbn_ais_run_grouped, whose workspace is mdbn_ais_run's.  Returns ``(logw [M] float64 numpy, trace_h,
         trace_v, v_state)``: the traces numpy (None without ``trace``), the final visible state [M, V] a device tensor."""
         V, H = W.shape
         ldh, ldv = W.stride(0), padded_ld(V)
@@ -625,6 +626,10 @@ class HipEngine(object):
             else base_vbias.to(device=self.device, dtype=torch.float32).contiguous()
         name = "mdbn_ais_run" if clamp is None else "mdbn_ais_cond_run"
         sizer = name.replace("run", "workspace_bytes")
+        table = ()
+        if groups is not None:
+            name = "mdbn_ais_run_grouped"
+            table = (self._p(groups.tensor), C.c_void_p(groups.host.ctypes.data), groups.n_groups)
         ws = self._sampler_workspace(getattr(self.lib, sizer), sizer, ((M,) if clamp is None else clamp[3:]) + (V,), H, ldh, path,
                                      extra=(K + 1,))
         logw = torch.zeros(M, dtype=torch.float64, device=self.device)
@@ -636,7 +641,7 @@ class HipEngine(object):
         _lib.check(getattr(self.lib, name)(
             self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base), int(bool(gauss)),
             self._p(d_betas), K + 1, *chains, ldv, self._p(v_state), self._p(logw), self._p(trace_h), self._p(trace_v),
-            int(path), C.byref(r), self._p(ws), ws.numel() * 4), name)
+            int(path), C.byref(r), self._p(ws), ws.numel() * 4, *table), name)
         if trace:
             trace_h, trace_v = trace_h.cpu().numpy()[:K - 1, :, :H], trace_v.cpu().numpy()[:, :, :V]
         return logw.cpu().numpy(), trace_h, trace_v, v_state
@@ -648,6 +653,15 @@ class HipEngine(object):
         the hidden [K-1, M, H] and visible [K, M, V] samples of every temperature.  ``path``: 0 = by shape, 1 = the
         one-launch kernel (LDS-resident layers), 2 = the general path.  Consumes 2K - 1 RNG steps from ``rng.step``."""
         logw, trace_h, trace_v, _ = self._ais(W, hbias, vbias, base_vbias, gauss, betas, int(n_chains), rng, path, trace)
+        return (logw, trace_h, trace_v) if trace else logw
+
+    def ais_grouped(self, W, hbias, vbias, base_vbias, betas, n_chains, rng, groups, path=0, trace=False):
+        """``ais`` for a Bernoulli layer whose visibles hold the softmax groups ``groups`` (a ``GroupTable``), in ONE library
+        call (mdbn_ais_run_grouped): a group's visible draw is one category of its softmax over the tempered pre-activations,
+        from one uniform at the group's first column; everything else, the returns and the 2K - 1 RNG steps are ``ais``'s.
+        The per-chain weights belong with the grouped base model (``ais_estimate(..., groups=)``)."""
+        logw, trace_h, trace_v, _ = self._ais(W, hbias, vbias, base_vbias, False, betas, int(n_chains), rng, path, trace,
+                                              groups=groups)
         return (logw, trace_h, trace_v) if trace else logw
 
     def ais_conditional(self, W, hbias, vbias, base_vbias, gauss, betas, obs, mask, n_chains, rng, path=0, trace=False, state=False):

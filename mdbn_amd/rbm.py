@@ -645,13 +645,15 @@ def function(updates, train_set_x=None, input_fn=None, name=None, data_parallel=
                         data_parallel=data_parallel, overlap=overlap)
 
 
-def ais_estimate(logw, base_vbias, n_hidden, gauss):
+def ais_estimate(logw, base_vbias, n_hidden, gauss, groups=None):
     """``(log_Z, std_err)`` from the per-chain log importance weights of an AIS run (float64 on the host):
     log Z_A + logsumexp(logw) - log M with log Z_A = H log 2 + sum softplus(b_A) (Bernoulli) | H log 2 + V/2 log 2 pi
-    (unit-variance Gaussian visibles), and the delta-method standard error std(w) / (mean(w) sqrt(M))."""
+    (unit-variance Gaussian visibles), and the delta-method standard error std(w) / (mean(w) sqrt(M)).  ``groups`` (a
+    ``GroupTable`` or its boundaries): the weights of a run on a layer with softmax groups (``HipEngine.ais_grouped``) --
+    a group contributes logsumexp_{c in g} b_A,c to log Z_A (``temper.base_log_partition``)."""
     from .temper import base_log_partition
     logw = numpy.asarray(logw, dtype=numpy.float64)
-    log_ZA = base_log_partition(base_vbias, n_hidden, gauss)
+    log_ZA = base_log_partition(base_vbias, n_hidden, gauss, groups)
     top = logw.max()
     w = numpy.exp(logw - top)
     log_Z = log_ZA + top + numpy.log(w.mean())
@@ -765,6 +767,18 @@ class RBM(object):
             raise NotImplementedError("%s on a layer with categorical visible units (visible_groups) is not built yet: it "
                                       "would sample the groups as independent sigmoid units" % what)
 
+    def _check_one_hot(self, data):
+        """ValueError unless every group of every row of ``data`` (host copy) holds exactly one 1 and zeros."""
+        if isinstance(data, torch.Tensor):
+            data = data.detach().cpu().numpy()
+        x = numpy.asarray(getattr(data, "get_value", lambda: data)())
+        for lo, hi in self.visible_groups.spans():
+            g = x[:, lo:hi]
+            bad = numpy.nonzero(~(((g == 0) | (g == 1)).all(axis=1) & (g.sum(axis=1) == 1)))[0]
+            if bad.size:
+                raise ValueError("row %d of the data does not hold exactly one 1 in the group of columns %d .. %d"
+                                 % (int(bad[0]), lo, hi - 1))
+
     def _no_sigma(self, what):
         if self.log_sigma is not None:
             raise NotImplementedError("%s on a layer with log_sigma (learned per-column variance) is not built yet: it would "
@@ -828,7 +842,9 @@ class RBM(object):
     # ------------------------------------------------------------------ likelihood (annealed importance sampling)
     def base_rate_vbias(self, data):
         """Visible bias of the base-rate model of ``data`` (host matrix): Bernoulli: the logit of the smoothed column
-        means (N mean + 0.05) / (N + 0.1) -- a constant column stays finite --; Gaussian: the column means."""
+        means (N mean + 0.05) / (N + 0.1) -- a constant column stays finite --; Gaussian: the column means.  On a softmax group
+        of K columns (``visible_groups``) the log of the smoothed category shares, b_A,c = log((n_c + 0.05) / (N + 0.05 K)) with
+        n_c the column's count: the group's logsumexp is 0 and a category never seen stays finite."""
         if isinstance(data, torch.Tensor):
             data = data.detach().cpu().numpy()
         x = numpy.asarray(getattr(data, "get_value", lambda: data)(), dtype=numpy.float64)
@@ -838,7 +854,12 @@ class RBM(object):
         if self.gauss:
             return mean.astype(numpy.float32)
         p = (x.shape[0] * mean + 0.05) / (x.shape[0] + 0.1)
-        return (numpy.log(p) - numpy.log1p(-p)).astype(numpy.float32)
+        bA = numpy.log(p) - numpy.log1p(-p)
+        if self.visible_groups is not None:
+            n = x.sum(axis=0)
+            for lo, hi in self.visible_groups.spans():
+                bA[lo:hi] = numpy.log((n[lo:hi] + 0.05) / (x.shape[0] + 0.05 * (hi - lo)))
+        return bA.astype(numpy.float32)
 
     def _ais_schedule(self, betas, n_betas, base_vbias, data):
         """``(betas float32, K, base_vbias float32)`` of an AIS run from the arguments of ``log_partition``: ``betas`` None:
@@ -863,8 +884,12 @@ class RBM(object):
         ladders of ``n_betas`` temperatures (None: 16; or ``betas``, from 0 to 1) from the same base-rate model run
         ``n_sweeps`` sweeps; the works of the swap attempts after ``burn_in`` bridge neighbouring temperatures
         (``estimator``: "mid" or "bar"); the error is the delete-one-ladder jackknife.  Consumes 3 n_sweeps RNG steps.  Where
-        chains mix badly AIS under-estimates log Z without its error showing it; ``check_log_partition`` runs both."""
-        self._no_groups("log_partition")
+        chains mix badly AIS under-estimates log Z without its error showing it; ``check_log_partition`` runs both.
+
+        A layer with ``visible_groups``: the same run with a group's visible draw one category of its softmax
+        (``HipEngine.ais_grouped``) and the base model's log Z_A with a logsumexp per group; ``method="tempering"`` is refused."""
+        if self.visible_groups is not None and (method == "tempering" or not hasattr(self.engine, "ais_grouped")):
+            self._no_groups("log_partition(method=\"tempering\")" if method == "tempering" else "log_partition on this engine")
         if method == "tempering":
             self._no_sigma("log_partition(method=\"tempering\")")       # (AIS needs no change: log Z is the unit model's)
             r = self.tempered_chains(n_ladders, betas=betas, n_betas=16 if n_betas is None else n_betas, base_vbias=base_vbias,
@@ -874,10 +899,15 @@ class RBM(object):
             raise ValueError("method must be 'ais' or 'tempering', got %r" % (method,))
         betas, K, base_vbias = self._ais_schedule(betas, n_betas, base_vbias, data)
         step = self._rng_step
-        logw = self.engine.ais(self.W.tensor, self.hbias.tensor, self.vbias.tensor, base_vbias, self.gauss, betas,
-                               int(n_chains), RngAddr(self.theano_rng.seed, self.stream_id, step, 0, 0), path=path)
+        rng = RngAddr(self.theano_rng.seed, self.stream_id, step, 0, 0)
+        if self.visible_groups is not None:
+            logw = self.engine.ais_grouped(self.W.tensor, self.hbias.tensor, self.vbias.tensor, base_vbias, betas, int(n_chains),
+                                           rng, self.visible_groups, path=path)
+        else:
+            logw = self.engine.ais(self.W.tensor, self.hbias.tensor, self.vbias.tensor, base_vbias, self.gauss, betas,
+                                   int(n_chains), rng, path=path)
         self._rng_step = step + 2 * K - 1
-        return ais_estimate(logw, base_vbias, self.n_hidden, self.gauss)
+        return ais_estimate(logw, base_vbias, self.n_hidden, self.gauss, self.visible_groups)
 
     def check_log_partition(self, data=None, base_vbias=None, path=0, n_chains=512, n_betas=None, n_ladders=64,
                             n_ladder_betas=16, n_sweeps=1200, burn_in=300, estimator="mid"):
@@ -887,6 +917,7 @@ class RBM(object):
         |ais - tempering| / sqrt(se_ais^2 + se_tempering^2) and ``detail`` (the ``LogZ`` of the tempering run).  Asserts
         nothing: a large ``z``, or an AIS value below the bracket, says the AIS chains missed a mode (INTEGRATION)."""
         self._no_sigma("check_log_partition")
+        self._no_groups("check_log_partition")
         if base_vbias is None:
             base_vbias = self.base_rate_vbias(data) if data is not None else self.vbias.get_value()
         ais, se_a = self.log_partition(n_chains=n_chains, n_betas=n_betas, base_vbias=base_vbias, path=path)
@@ -900,8 +931,13 @@ class RBM(object):
         """``(mean log p(data), std_err)``: mean(-free_energy(data)) - log_Z with ``log_partition(**ais)``'s estimate (the
         standard error is that of log_Z; ``data`` also gives the base rate unless ``base_vbias`` / ``data`` is passed;
         ``method="tempering"`` and its keywords reach ``log_partition`` like any other).  With ``log_sigma`` s the free energy
-        carries the sum(s) term of the change of variables and log_Z is the unit model's: nats per raw row."""
-        self._no_groups("log_likelihood")
+        carries the sum(s) term of the change of variables and log_Z is the unit model's: nats per raw row.  With
+        ``visible_groups`` every group of every row of ``data`` must hold exactly one 1 (checked on the host: ValueError)."""
+        if self.visible_groups is not None:
+            if ais.get("method", "ais") == "tempering" or not hasattr(self.engine, "ais_grouped"):
+                self._no_groups("log_likelihood(method=\"tempering\")" if ais.get("method", "ais") == "tempering"
+                                else "log_likelihood on this engine")
+            self._check_one_hot(data)
         if ais.get("method", "ais") == "tempering":
             self._no_sigma("log_likelihood(method=\"tempering\")")
         if "base_vbias" not in ais and "data" not in ais:

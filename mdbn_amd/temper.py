@@ -23,12 +23,22 @@ def attempts(n_ladders, n_betas, sweep0, n_sweeps):
     return int(n_ladders) * ((g[:, None] - rho[None, :]) % 2 == 0).sum(axis=0)
 
 
-def base_log_partition(base_vbias, n_hidden, gauss):
+def base_log_partition(base_vbias, n_hidden, gauss, groups=None):
     """log Z of the base-rate model (beta = 0): H log 2 + sum softplus(b_A) (Bernoulli) | H log 2 + V/2 log 2 pi
-    (unit-variance Gaussian visibles), float64."""
+    (unit-variance Gaussian visibles), float64.  ``groups`` (a ``GroupTable`` or its boundaries; Bernoulli only): the columns
+    of a softmax group hold one 1 between them, so group g contributes logsumexp_{c in g} b_A,c instead of its columns'
+    softplus."""
     bA = numpy.asarray(base_vbias, dtype=numpy.float64)
-    return n_hidden * numpy.log(2.0) + (0.5 * bA.size * numpy.log(2.0 * numpy.pi) if gauss
-                                        else numpy.logaddexp(0.0, bA).sum())
+    if groups is None:
+        return n_hidden * numpy.log(2.0) + (0.5 * bA.size * numpy.log(2.0 * numpy.pi) if gauss
+                                            else numpy.logaddexp(0.0, bA).sum())
+    if gauss:
+        raise ValueError("groups: a Gaussian visible layer has no categorical units")
+    b = numpy.asarray(getattr(groups, "host", groups), dtype=numpy.int64)
+    total = n_hidden * numpy.log(2.0) + numpy.logaddexp(0.0, bA[:b[0]]).sum() + numpy.logaddexp(0.0, bA[b[-1]:]).sum()
+    for lo, hi in zip(b[:-1], b[1:]):
+        total += numpy.logaddexp.reduce(bA[lo:hi])
+    return total
 
 
 LogZ = collections.namedtuple("LogZ", "log_z log_z_fwd log_z_rev stderr ratios_fwd ratios_rev acceptance attempts method")
