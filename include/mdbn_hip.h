@@ -831,6 +831,31 @@ int  mdbn_ais_run_grouped(mdbn_ctx *ctx, void *stream, const float *W, int64_t V
                           void *workspace, int64_t workspace_bytes, const int32_t *group_start,
                           const int32_t *group_start_host, int64_t n_groups);
 
+/* mdbn_gibbs_clamped_grouped: mdbn_gibbs_clamped for a Bernoulli layer (no gauss, no add_noise) whose visibles hold
+ * softmax groups: its arguments, then the table under the convention above.  The chain, the Philox steps (rng->step + 2t
+ * hidden, rng->step + 2t + 1 visible, draw 0), burn_in, the accumulators, the taps, path and steps_per_launch are
+ * mdbn_gibbs_clamped's.  What changes:
+ *   visible draw of a group: v ~ softmax_c(x_c), x_c = (h_sample W^T)_c + vbias_c, with the arithmetic and the addressing of
+ *     mdbn_group_softmax_sample (mx, e_c = exp(x_c - mx), Z in ascending c, mean_c = e_c / Z correctly rounded, the first c
+ *     with u < C_c, else the last); ONE uniform per (row, group): the Philox word of the group's FIRST column.  v_mean of a
+ *     group column is mean_c.  A Bernoulli column outside the span keeps mdbn_gibbs_clamped's draw.
+ *   clamp of a group: a group is held or free as a WHOLE, by the mask entry at its FIRST column (the mask entries at its
+ *     other columns are not read): defined for any mask, no device-side check.  A held group's columns are put back to obs as
+ *     they are (any real values: they enter through v W alone).  Every recorded row of a free group holds exactly one 1.
+ * n_groups = 0 reads no table and gives mdbn_gibbs_clamped(gauss = 0) bit for bit on both paths.  path 1 needs no LDS beyond
+ * mdbn_gibbs_clamped's image, so the shapes that fit are the same; path 2 runs per step the propup pass, a propdown pass to the
+ * linear pre-activations (into v_mean) and ONE kernel that draws, clamps, accumulates and taps.  Workspace:
+ * mdbn_gibbs_clamped_workspace_bytes.  MDBN_EINVAL with a message, before any launch: an invalid table (not ascending, a
+ * group of fewer than 2 or more than MDBN_GROUP_MAX columns, a boundary beyond V, a missing copy) and whatever
+ * mdbn_gibbs_clamped refuses. */
+int  mdbn_gibbs_clamped_grouped(mdbn_ctx *ctx, void *stream, float *v, const float *obs, const float *mask,
+                                int64_t mask_rows, int64_t B, int64_t ldv, const float *W, int64_t V, int64_t H,
+                                int64_t ldh, const float *hbias, const float *vbias, int64_t n_steps, int64_t burn_in,
+                                float *h_mean, float *h_sample, float *v_mean, float *v_avg, float *h_avg,
+                                float *trace_h, float *trace_v, int path, int64_t steps_per_launch,
+                                const mdbn_rng *rng, void *workspace, int64_t workspace_bytes,
+                                const int32_t *group_start, const int32_t *group_start_host, int64_t n_groups);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)) (the float32 softplus terms summed in

@@ -119,6 +119,8 @@ SIGNATURES = {
     "mdbn_gibbs_clamped_workspace_bytes": [_vp, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
     "mdbn_gibbs_clamped": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _i64,
                            _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _rngp, _vp, _i64],
+    "mdbn_gibbs_clamped_grouped": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64,
+                                   _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _rngp, _vp, _i64, _vp, _vp, _i64],
     "mdbn_pt_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
     "mdbn_pt_run": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp,
                     _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _rngp, _vp, _i64],

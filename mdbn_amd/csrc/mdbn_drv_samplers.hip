@@ -311,16 +311,17 @@ int mdbn_gibbs_clamped_workspace_bytes(mdbn_ctx* ctx, int64_t B, int64_t V, int6
     return MDBN_OK;
 }
 
-int mdbn_gibbs_clamped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, const float* mask, int64_t mask_rows,
-                       int64_t B, int64_t ldv, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
-                       const float* vbias, int gauss, int add_noise, int64_t n_steps, int64_t burn_in, float* h_mean,
-                       float* h_sample, float* v_mean, float* v_avg, float* h_avg, float* trace_h, float* trace_v,
-                       int path, int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes)
+namespace {
+
+// Both runs once their own rules hold: the plain chain, or (groups.on: the checked table of mdbn_gibbs_clamped_grouped) the
+// chain of a Bernoulli layer with softmax groups
+int clamp_run(mdbn_ctx* ctx, void* stream, float* v, const float* obs, const float* mask, int64_t mask_rows,
+              int64_t B, int64_t ldv, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+              const float* vbias, int gauss, int add_noise, int64_t n_steps, int64_t burn_in, float* h_mean,
+              float* h_sample, float* v_mean, float* v_avg, float* h_avg, float* trace_h, float* trace_v,
+              int path, int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes,
+              const ClampGroups& groups = ClampGroups{})
 {
-    CtxScope ctx_scope(ctx);
-    // (the argument rules first: they need no device)
-    REQUIRE(B >= 1 && V >= 1 && H >= 1, "bad shape B=%lld V=%lld H=%lld", (long long)B, (long long)V, (long long)H);
-    REQUIRE(B < (1ll << 31), "B too large");
     REQUIRE(n_steps >= 1 && n_steps < (1ll << 30), "n_steps = %lld must be in [1, 2^30)", (long long)n_steps);
     REQUIRE(burn_in >= 0 && burn_in < n_steps, "burn_in = %lld must be in [0, n_steps = %lld)", (long long)burn_in, (long long)n_steps);
     REQUIRE(mask_rows == 1 || mask_rows == B, "mask_rows = %lld is neither 1 nor B = %lld", (long long)mask_rows, (long long)B);
@@ -360,6 +361,7 @@ int mdbn_gibbs_clamped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, 
         a.h_mean = h_mean; a.h_sample = h_sample; a.v_mean = v_mean; a.v_avg = v_avg; a.h_avg = h_avg;
         a.acc_v = acc_v; a.acc_h = acc_h;
         a.trace_h = trace_h; a.trace_v = trace_v;
+        a.groups = groups;
         const int64_t cut = steps_per_launch ? steps_per_launch : CLAMP_CUT;
         for (int64_t t0 = 0; t0 < n_steps; t0 += cut) {       // a launch stays short; the state travels in v / acc_v / acc_h
             a.t0 = (int)t0; a.t1 = (int)std::min(n_steps, t0 + cut);
@@ -379,13 +381,38 @@ int mdbn_gibbs_clamped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, 
     c.n_avg = (float)(n_steps - burn_in);
     c.acc_v = acc_v; c.acc_h = acc_h; c.v_avg = v_avg; c.h_avg = h_avg;
     c.entry = 1; c.v_new = v;
-    HIP_OK(launch_clamp_step(c, s));
+    ClampStepGroupedArgs cg{};
+    cg.groups = groups;
+    if (groups.on) {
+        cg.c = c;
+        HIP_OK(launch_clamp_step_grouped(cg, s));
+    } else {
+        HIP_OK(launch_clamp_step(c, s));
+    }
     c.entry = 0;
     for (int64_t t = 0; t < n_steps; ++t) {
         const bool last = t + 1 == n_steps;
         mdbn_rng rh = *rng, rv = *rng;
         rh.step = rng->step + (uint32_t)(2 * t);     rh.draw = 0;
         rv.step = rng->step + (uint32_t)(2 * t + 1); rv.draw = 0;
+        if (groups.on) {
+            // the propup of the plain chain; the propdown to the LINEAR pre-activations h_sample W^T + vbias, into v_mean (as
+            // mdbn_cd_step_grouped forms them); then the draw, the clamp, the accumulators and the taps in one kernel
+            Affine up(v, B, ldv, W, V, H, ldh, hbias);
+            up.mean = h_mean; up.sample = h_sample; up.rng = &rh;
+            CHECK(run_affine(up, ws, s, nullptr));
+            Affine down(h_sample, B, ldh, W, V, H, ldh, vbias, ldv, 1);
+            down.mean = v_mean;
+            down.x_binary = true;                        // our own 0/1 hidden samples
+            CHECK(run_affine(down, ws, s, nullptr));
+            c.accumulate = t >= burn_in; c.last = last;
+            c.trace_h = trace_h ? trace_h + t * B * ldh : nullptr;
+            c.trace_v = trace_v ? trace_v + t * B * ldv : nullptr;
+            cg.c = c;
+            cg.rng = make_key(rv, 0u);
+            HIP_OK(launch_clamp_step_grouped(cg, s));
+            continue;
+        }
         // the passes of mdbn_gibbs_chain.  The visible state may hold real observed values: never the 0/1 operand hint there
         Affine up(v, B, ldv, W, V, H, ldh, hbias);
         up.mean = h_mean; up.sample = (feed_sample || last || trace_h) ? h_sample : nullptr; up.rng = &rh;
@@ -401,6 +428,39 @@ int mdbn_gibbs_clamped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, 
         HIP_OK(launch_clamp_step(c, s));
     }
     return MDBN_OK;
+}
+
+}  // namespace
+
+int mdbn_gibbs_clamped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, const float* mask, int64_t mask_rows,
+                       int64_t B, int64_t ldv, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+                       const float* vbias, int gauss, int add_noise, int64_t n_steps, int64_t burn_in, float* h_mean,
+                       float* h_sample, float* v_mean, float* v_avg, float* h_avg, float* trace_h, float* trace_v,
+                       int path, int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes)
+{
+    CtxScope ctx_scope(ctx);
+    // (the argument rules first: they need no device)
+    REQUIRE(B >= 1 && V >= 1 && H >= 1, "bad shape B=%lld V=%lld H=%lld", (long long)B, (long long)V, (long long)H);
+    REQUIRE(B < (1ll << 31), "B too large");
+    return clamp_run(ctx, stream, v, obs, mask, mask_rows, B, ldv, W, V, H, ldh, hbias, vbias, gauss, add_noise, n_steps, burn_in,
+                     h_mean, h_sample, v_mean, v_avg, h_avg, trace_h, trace_v, path, steps_per_launch, rng, workspace, workspace_bytes);
+}
+
+int mdbn_gibbs_clamped_grouped(mdbn_ctx* ctx, void* stream, float* v, const float* obs, const float* mask, int64_t mask_rows,
+                               int64_t B, int64_t ldv, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+                               const float* vbias, int64_t n_steps, int64_t burn_in, float* h_mean, float* h_sample,
+                               float* v_mean, float* v_avg, float* h_avg, float* trace_h, float* trace_v, int path,
+                               int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes,
+                               const int32_t* group_start, const int32_t* group_start_host, int64_t n_groups)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(B >= 1 && V >= 1 && H >= 1, "bad shape B=%lld V=%lld H=%lld", (long long)B, (long long)V, (long long)H);
+    REQUIRE(B < (1ll << 31) && V <= (1 << 24), "B / V too large");
+    ClampGroups g{};
+    CHECK(check_groups(group_start, group_start_host, n_groups, V, g.span_lo, g.span_hi));
+    g.group_start = group_start; g.n_groups = (int)n_groups; g.on = 1;
+    return clamp_run(ctx, stream, v, obs, mask, mask_rows, B, ldv, W, V, H, ldh, hbias, vbias, 0, 0, n_steps, burn_in, h_mean,
+                     h_sample, v_mean, v_avg, h_avg, trace_h, trace_v, path, steps_per_launch, rng, workspace, workspace_bytes, g);
 }
 
 // ---------------------------------------------------------------------------------- parallel tempering

@@ -104,8 +104,9 @@ __device__ __forceinline__ float group_entry(float u, float C_before, float C, b
 // out(c, e, v) takes the 0 / 1 entry; K has no register cost.  The four rows go side by side through every walk -- their loads
 // do not depend on each other, so a walk waits for memory once per category, not once per (category, row); each row's sums
 // are its own, in ascending c.
+// group_draw_mean: out(c, e, v, mean) also takes mean_c (the clamped chain keeps it).
 template <class X, class Out>
-__device__ __forceinline__ void group_draw(int K, const float (&u)[4], X&& x, Out&& out)
+__device__ __forceinline__ void group_draw_mean(int K, const float (&u)[4], X&& x, Out&& out)
 {
     float mx[4], Z[4] = {0.f, 0.f, 0.f, 0.f}, cum[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -122,10 +123,17 @@ __device__ __forceinline__ void group_draw(int K, const float (&u)[4], X&& x, Ou
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float before = cum[e];
-            cum[e] += group_mean(group_exp(x(c, e), mx[e]), Z[e]);
-            out(c, e, group_entry(u[e], before, cum[e], c == K - 1));
+            const float mean = group_mean(group_exp(x(c, e), mx[e]), Z[e]);
+            cum[e] += mean;
+            out(c, e, group_entry(u[e], before, cum[e], c == K - 1), mean);
         }
     }
+}
+
+template <class X, class Out>
+__device__ __forceinline__ void group_draw(int K, const float (&u)[4], X&& x, Out&& out)
+{
+    group_draw_mean(K, u, x, [&](int c, int e, float v, float) { out(c, e, v); });
 }
 
 // v | h for one (4-row group, column), every row at its own beta: pre = b_A + beta (b - b_A) + beta m, then the draw.

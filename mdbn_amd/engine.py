@@ -508,11 +508,25 @@ class HipEngine(object):
         the model -- the hidden SAMPLE goes down and the visible draw always carries its N(0, 1) noise (the library's gauss = 2)
         -- instead of the reference's chain, which feeds the hidden mean down and whose averages are not posterior means.
         ``v`` is not modified; no host synchronisation.  Consumes 2 * n_steps RNG steps."""
+        return self._gibbs_clamped(v, obs, mask, W, hbias, vbias, (2 if sampler else 1) if gauss else 0, n_steps, rng, burn_in,
+                                   add_noise, path, steps_per_launch, trace)
+
+    def gibbs_clamped_grouped(self, v, obs, mask, W, hbias, vbias, n_steps, rng, groups, burn_in=0, path=0, steps_per_launch=0,
+                              trace=False):
+        """``gibbs_clamped`` for a Bernoulli layer whose visibles hold the softmax groups ``groups`` (a ``GroupTable``), in ONE
+        library call (mdbn_gibbs_clamped_grouped): a free group's visible draw is one category of its softmax, from one uniform
+        at the group's first column, and its v_mean the softmax; a group is held or free as a whole, by the mask entry at its
+        FIRST column.  Everything else, the returns and the 2 * n_steps RNG steps are ``gibbs_clamped``'s."""
+        return self._gibbs_clamped(v, obs, mask, W, hbias, vbias, 0, n_steps, rng, burn_in, False, path, steps_per_launch, trace,
+                                   groups=groups)
+
+    def _gibbs_clamped(self, v, obs, mask, W, hbias, vbias, gauss, n_steps, rng, burn_in, add_noise, path, steps_per_launch, trace,
+                       groups=None):
+        """What ``gibbs_clamped`` (``gauss``: the library's 0 | 1 | 2) and ``gibbs_clamped_grouped`` (``groups``) share."""
         v = self.as_matrix(v)
         B, V = v.shape
         H = W.shape[1]
         ldh, ldv = W.stride(0), padded_ld(V)
-        gauss = (2 if sampler else 1) if gauss else 0
         n_steps, burn_in = int(n_steps), int(burn_in)
         mask = self.as_matrix(mask)
         mask_rows = int(mask.shape[0])
@@ -528,11 +542,15 @@ class HipEngine(object):
         ws = self._sampler_workspace(self.lib.mdbn_gibbs_clamped_workspace_bytes, "mdbn_gibbs_clamped_workspace_bytes", (B, V), H, ldh,
                                      path, cache_attr="_clamp_ws")
         r = rng.c()
-        _lib.check(self.lib.mdbn_gibbs_clamped(
+        name, kind, table = "mdbn_gibbs_clamped", (gauss, int(bool(add_noise))), ()
+        if groups is not None:
+            name, kind = "mdbn_gibbs_clamped_grouped", ()
+            table = (self._p(groups.tensor), C.c_void_p(groups.host.ctypes.data), groups.n_groups)
+        _lib.check(getattr(self.lib, name)(
             self.ctx, self._stream(), self._p(state), self._p(obs), self._p(mask), mask_rows, B, ldv, self._p(W), V, H, ldh,
-            self._p(hbias), self._p(vbias), gauss, int(bool(add_noise)), n_steps, burn_in, self._p(h_mean),
+            self._p(hbias), self._p(vbias), *kind, n_steps, burn_in, self._p(h_mean),
             self._p(h_sample), self._p(v_mean), self._p(v_avg), self._p(h_avg), self._p(trace_h), self._p(trace_v),
-            int(path), int(steps_per_launch), C.byref(r), self._p(ws), ws.numel() * 4), "mdbn_gibbs_clamped")
+            int(path), int(steps_per_launch), C.byref(r), self._p(ws), ws.numel() * 4, *table), name)
         out = (state, h_mean, h_sample, v_mean, v_avg, h_avg)
         if trace:
             out += (trace_h[:, :, :H], trace_v[:, :, :V])

@@ -1077,6 +1077,14 @@ class RBM(object):
             raise ValueError("observed_mask must be [%d] or [1 | %d, %d], got %r" % (self.n_visible, B, self.n_visible, m.shape))
         return (m != 0).astype(numpy.float32)
 
+    def _check_group_mask(self, mask):
+        """ValueError unless every row of the 0 / 1 ``mask`` is constant over every group (a group is held or free as a whole)."""
+        for lo, hi in self.visible_groups.spans():
+            bad = numpy.nonzero((mask[:, lo:hi] != mask[:, lo:lo + 1]).any(axis=1))[0]
+            if bad.size:
+                raise ValueError("row %d of observed_mask splits the group of columns %d .. %d: a group is observed or missing "
+                                 "as a whole" % (int(bad[0]), lo, hi - 1))
+
     def gibbs_vhv_clamped(self, v, observed_mask, n_steps, burn_in=0, trace=False, path=0, sampler=False):
         """``n_steps`` of ``gibbs_vhv`` with the visibles where ``observed_mask`` is nonzero held at their values in ``v``
         (the other entries of ``v`` start the chain), as ONE device call (mdbn_gibbs_clamped).  ``observed_mask``: [B, V]
@@ -1089,8 +1097,14 @@ class RBM(object):
         A Bernoulli layer's chain is a Gibbs sampler, so its averages estimate the posterior means.  The GRBM chain of the
         reference (``gibbs_vhv``: the hidden MEAN goes down, noise only if not ``error_free``) is a mean-field iteration, and
         its averages are not posterior means; ``sampler=True`` runs the Gibbs sampler of the same model instead (the hidden
-        SAMPLE goes down, the visible draw always carries its N(0, 1) noise).  It changes nothing for a Bernoulli layer."""
-        self._no_groups("gibbs_vhv_clamped")
+        SAMPLE goes down, the visible draw always carries its N(0, 1) noise).  It changes nothing for a Bernoulli layer.
+
+        A layer with ``visible_groups`` (on an engine with ``gibbs_clamped_grouped``; refused elsewhere): a free group's draw is
+        one category of its softmax and its v_mean the softmax (mdbn_gibbs_clamped_grouped); a group is held or free as a whole,
+        so a mask that is not constant over a group is a ValueError, raised before anything is drawn."""
+        grouped = self.visible_groups is not None
+        if grouped and not hasattr(self.engine, "gibbs_clamped_grouped"):
+            self._no_groups("gibbs_vhv_clamped on this engine")
         self._no_sigma("gibbs_vhv_clamped")
         sampler = bool(sampler and self.gauss)
         n_steps, burn_in = int(n_steps), int(burn_in)
@@ -1099,6 +1113,14 @@ class RBM(object):
         x = as_tensor(v, self.engine)
         mask = self._clamp_mask(observed_mask, x.shape[0])
         step = self._rng_step
+        if grouped:
+            self._check_group_mask(mask)
+            self._rng_step = step + 2 * n_steps
+            res = self.engine.gibbs_clamped_grouped(x, x, mask, self.W.tensor, self.hbias.tensor, self.vbias.tensor, n_steps,
+                                                    RngAddr(self.theano_rng.seed, self.stream_id, step, 0, 0), self.visible_groups,
+                                                    burn_in=burn_in, path=path, trace=trace)
+            state, h_mean, h_sample, v_mean, v_avg, h_avg = res[:6]
+            return [self._wrap(t) for t in (None, h_mean, h_sample, None, v_mean, state, v_avg, h_avg) + tuple(res[6:])]
         if not hasattr(self.engine, "gibbs_clamped"):        # checker engine: compose the eager steps
             held = as_tensor(numpy.broadcast_to(mask, tuple(x.shape)).copy(), self.engine) != 0
             obs, state = x, x
@@ -1135,14 +1157,24 @@ class RBM(object):
         chains (consecutive Philox rows) of ``n_steps`` Gibbs steps (``sampler=True``: a GRBM runs the Gibbs sampler of its
         model, not the reference's mean-field chain), and v_mean / h_mean are averaged over the steps from
         ``burn_in`` on and over the chains.  Observed entries of ``v_hat`` are the observed values.  Consumes
-        2 * n_steps RNG steps."""
-        self._no_groups("impute")
+        2 * n_steps RNG steps.
+
+        A layer with ``visible_groups`` (on an engine with ``gibbs_clamped_grouped``; refused elsewhere): a free group starts
+        at the softmax of its ``vbias``, and its ``v_hat`` sums to 1; ``observed_mask`` must be constant over every group."""
+        if self.visible_groups is not None and not hasattr(self.engine, "gibbs_clamped_grouped"):
+            self._no_groups("impute on this engine")
         self._no_sigma("impute")
         x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
         N, n_chains = x.shape[0], int(n_chains)
         mask = self._clamp_mask(observed_mask, N)
         b = numpy.asarray(self.vbias.get_value(), dtype=numpy.float64)
-        base = (b if self.gauss else 1.0 / (1.0 + numpy.exp(-b))).astype(numpy.float32)
+        base = b if self.gauss else 1.0 / (1.0 + numpy.exp(-b))
+        if self.visible_groups is not None:
+            self._check_group_mask(mask)
+            for lo, hi in self.visible_groups.spans():
+                e = numpy.exp(b[lo:hi] - b[lo:hi].max())
+                base[lo:hi] = e / e.sum()
+        base = base.astype(numpy.float32)
         held = numpy.broadcast_to(mask != 0, x.shape)
         start = numpy.where(held, x, base[None, :]).astype(numpy.float32)
         if n_chains > 1:
