@@ -856,6 +856,31 @@ int  mdbn_gibbs_clamped_grouped(mdbn_ctx *ctx, void *stream, float *v, const flo
                                 const mdbn_rng *rng, void *workspace, int64_t workspace_bytes,
                                 const int32_t *group_start, const int32_t *group_start_host, int64_t n_groups);
 
+/* mdbn_ais_cond_run_grouped: mdbn_ais_cond_run for a Bernoulli layer (no gauss) whose visibles hold softmax groups: its
+ * arguments without `gauss`, then the table under the convention above.  The run is mdbn_ais_cond_run(gauss = 0): N C
+ * chains, chain m clamped to data row m / C, the 2K - 1 Philox steps and their addressing, the double logw, the traces, the
+ * cut of a long schedule and path.  What changes:
+ *   visible draw of a free group (v_1 ~ p_0 included): mdbn_ais_run_grouped's -- v ~ softmax_c(x_c) over
+ *     x_c = fma(beta, m_c, fma(beta, vbias_c - base_vbias_c, base_vbias_c)), ONE uniform per (chain, group): the Philox word
+ *     of the group's FIRST column.  A Bernoulli column outside the span keeps mdbn_ais_cond_run's draw and clamp.
+ *   clamp of a group: mdbn_gibbs_clamped_grouped's rule -- a group is held or free as a WHOLE, by the mask entry at its FIRST
+ *     column in the chain's mask row (the entries at its other columns are not read): defined for any mask, no device-side
+ *     check.  A held group's columns take obs as they are (any real values: they enter through v W alone) and add 0.f to s1,
+ *     each at its own place in the free run's sum; its uniform is drawn and not used.
+ * Two limits, bit for bit in logw, v_state and both traces on both paths: n_groups = 0 is mdbn_ais_cond_run(gauss = 0); a mask
+ * of zeros is mdbn_ais_run_grouped with M = N C.  The base model of data row r (left to the caller, float64 on the host):
+ *   log Z_A,r = H log 2 + sum_{free Bernoulli i} softplus(base_vbias_i) + sum_{free groups g} logsumexp_{c in g} base_vbias_c.
+ * path 1 needs no LDS beyond mdbn_ais_run's image; workspace: mdbn_ais_cond_workspace_bytes.  MDBN_EINVAL with a message,
+ * before any launch and with every output untouched: an invalid table (not ascending, a group of fewer than 2 or more than
+ * MDBN_GROUP_MAX columns, a boundary beyond V, a missing copy), path = 1 on a shape that does not fit, and whatever
+ * mdbn_ais_cond_run refuses. */
+int  mdbn_ais_cond_run_grouped(mdbn_ctx *ctx, void *stream, const float *W, int64_t V, int64_t H, int64_t ldh,
+                               const float *hbias, const float *vbias, const float *base_vbias, const float *betas,
+                               int64_t n_betas, const float *obs, const float *mask, int64_t mask_rows, int64_t N,
+                               int64_t C, int64_t ldv, float *v_state, double *logw, float *trace_h, float *trace_v,
+                               int path, const mdbn_rng *rng, void *workspace, int64_t workspace_bytes,
+                               const int32_t *group_start, const int32_t *group_start_host, int64_t n_groups);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)) (the float32 softplus terms summed in

@@ -212,7 +212,11 @@ def modality_log_likelihood(nets, joint, inputs, target, n_chains=64, n_betas=10
     taken from (``RBM.base_rate_vbias``; None: the rows' own activations).  Returns a dict: ``log_p [N]``, ``std_err [N]``
     (that of the AIS estimate of each row's partition function), ``baseline [N]`` (the same 0 / 1 block under independent
     Bernoulli units at the block's base rate, float64 on the host), ``gain`` = mean(log_p - baseline) and ``gain_std_err`` =
-    sqrt(sum std_err^2) / N.  Consumes 2 n_betas - 1 RNG steps of the joint layer's first RBM."""
+    sqrt(sum std_err^2) / N.  Consumes 2 n_betas - 1 RNG steps of the joint layer's first RBM.
+
+    The blocks are the modality tops.  A one-hot label block of a joint layer with ``visible_groups`` is not one of ``nets`` and
+    is not scored here: call ``joint.rbm_layers[0].conditional_log_likelihood(v, unit_mask)`` with a mask that frees the label
+    block (a group is observed or missing as a whole)."""
     import numpy
     widths = [net.stacked_layers_sizes[-1] for net in nets]
     if len(inputs) != len(nets) or any(x is None for x in inputs):

@@ -116,6 +116,8 @@ SIGNATURES = {
     "mdbn_ais_cond_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
     "mdbn_ais_cond_run": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64,
                           _vp, _vp, _vp, _vp, _i32, _rngp, _vp, _i64],
+    "mdbn_ais_cond_run_grouped": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64,
+                                  _vp, _vp, _vp, _vp, _i32, _rngp, _vp, _i64, _vp, _vp, _i64],
     "mdbn_gibbs_clamped_workspace_bytes": [_vp, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
     "mdbn_gibbs_clamped": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _i64,
                            _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _rngp, _vp, _i64],

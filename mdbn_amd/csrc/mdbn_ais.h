@@ -37,7 +37,7 @@ struct AisSmallArgs {
     float* v_state;                                  // [M][ldv]: k0 > 0: v_{k0 + 1} on entry; v_{min(k1 + 1, K)} on return
     double* logw;                                    // [M]: k0 > 0: log w after temperature k0 on entry; after k1 on return
     float* trace_h; float* trace_v;                  // [K - 1][M][ldh], [K][M][ldv] or NULL
-    AisGroups groups;                                // softmax groups of the visible layer (Bernoulli, no clamp) or {}
+    AisGroups groups;                                // softmax groups of the visible layer (Bernoulli; free or clamped) or {}
 };
 
 // General path, per temperature k: pre_h = v_k W + c is in `pre` (the propup GEMM), then
@@ -59,7 +59,7 @@ struct AisStepArgs {
     const float* d2;                                 // [mask_rows]: sum over the free columns of (b - b_A)^2 (Gaussian; launch_ais_d2)
     double* logw;                                    // [M]
     float* trace;                                    // this temperature's trace slot or NULL
-    AisGroups groups;                                // softmax groups of the visible layer (Bernoulli, no clamp) or {}
+    AisGroups groups;                                // softmax groups of the visible layer (Bernoulli; free or clamped) or {}
 };
 
 bool ais_small_ok(int64_t M, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh);

@@ -28,7 +28,12 @@
 // double log w, the Philox steps and the hand-over of a cut run are the free run's; only the visible draw of a group column
 // changes (v_1 ~ p_0 included): v ~ softmax_c(x_c) over the group's tempered pre-activations x_c, ONE uniform per (chain,
 // group) -- the Philox word of the group's first column -- by the group draw of mdbn_sampler_kit.h, which both paths compose
-// from the same float32 operations in the same order.  A Bernoulli column outside the span keeps its draw; no clamp.
+// from the same float32 operations in the same order.  A Bernoulli column outside the span keeps its draw.
+//
+// Both (mdbn_ais_cond_run_grouped): a group is held or free as a WHOLE, by the mask entry at its FIRST column in the chain's
+// mask row (the entries at its other columns are not read).  A held group's columns take obs as they are and enter s1 as 0.f,
+// each at its own place; its uniform is drawn and not used.  A Bernoulli column keeps the clamp above.  With n_groups = 0 the
+// run is mdbn_ais_cond_run's, with no held unit mdbn_ais_run_grouped's, bit for bit.
 //
 // ais_small_kernel (LDS-resident layers): the shape of small_cd_kernel -- W staged once into one CU's LDS, a workgroup owns
 // four-chain slabs (one Philox block) and runs the whole loop over the temperatures on the exact-f32 4x4x1 MFMA passes of
@@ -101,12 +106,12 @@ bool ais_clamp_ok(const Args& a)
            (a.mask != nullptr || (a.C == 1 && a.mask_rows == 1));
 }
 
-// ... and of the groups: none, or a Bernoulli layer without a clamp whose span lies inside the row (the rule of
+// ... and of the groups: none, or a Bernoulli layer, free or under a clamp, whose span lies inside the row (the rule of
 // launch_group_softmax)
-bool ais_groups_ok(const AisGroups& g, int V, int gauss, const float* mask)
+bool ais_groups_ok(const AisGroups& g, int V, int gauss)
 {
     if (!g.on) return g.n_groups == 0;
-    return !gauss && !mask && g.n_groups >= 0 && (g.n_groups == 0 || g.group_start) && g.span_lo >= 0 && g.span_lo <= g.span_hi &&
+    return !gauss && g.n_groups >= 0 && (g.n_groups == 0 || g.group_start) && g.span_lo >= 0 && g.span_lo <= g.span_hi &&
            g.span_hi <= V && (g.n_groups == 0) == (g.span_lo == g.span_hi) && g.n_groups <= g.span_hi - g.span_lo;
 }
 
@@ -115,7 +120,7 @@ bool ais_groups_ok(const AisGroups& g, int V, int gauss, const float* mask)
 template <bool GAUSS, bool TRACE, bool CLAMP, bool GROUPS = false>
 __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
 {
-    static_assert(!GROUPS || (!GAUSS && !CLAMP), "softmax groups: a Bernoulli layer without a clamp");
+    static_assert(!GROUPS || !GAUSS, "softmax groups: a Bernoulli layer");
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const SmallLayout& L = a.L;
     lds_f* const lds = (lds_f*)sm;
@@ -179,15 +184,17 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
         }
         if (slab != (int)blockIdx.x) SM_SYNC();                        // (the previous slab's last readers are done)
 
-        // ---- the clamp of this thread's column, in registers for the whole slab
+        // ---- the clamp of this thread's column, in registers for the whole slab (a group column: held with its group, by the
+        // mask entry at the group's first column; its observed value is its own)
         float ob[4] = {0.f, 0.f, 0.f, 0.f};
         bool held[4] = {false, false, false, false};
         if constexpr (CLAMP) {
             if (tid < V) {
+                const int mcol = grp ? c0 : tid;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     if (!ok[e]) continue;
-                    held[e] = a.mask[mrow[e] + tid] != 0.f;
+                    held[e] = a.mask[mrow[e] + mcol] != 0.f;
                     ob[e] = a.obs[(int64_t)((row0 + e) / a.C) * ldv + tid];
                 }
             }
@@ -286,7 +293,7 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
                     s[e] = okc[e] ? (GAUSS ? (v[e] - bA) * db : v[e] * db) : 0.f;
                 }
             }
-            if constexpr (CLAMP) ais_clamp(ob, held, v, s);
+            if constexpr (CLAMP && !GROUPS) ais_clamp(ob, held, v, s);
             if constexpr (!GROUPS) put_v(v, s, col, a.k0 == 0 ? a.trace_v : nullptr);
         }
         if constexpr (GROUPS) {
@@ -294,7 +301,10 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
                 SM_SYNC();
                 group_pick(a.rng, v, s);
             }
-            if (tid < L.V64) put_v(v, s, tid, a.k0 == 0 ? a.trace_v : nullptr);
+            if (tid < L.V64) {                                         // (a group column has its v / s only now: the clamp follows the pick)
+                if constexpr (CLAMP) ais_clamp(ob, held, v, s);
+                put_v(v, s, tid, a.k0 == 0 ? a.trace_v : nullptr);
+            }
         }
         if (a.k0 > 0 && tid < SM_ROWS && row0 + tid < M) lw = a.logw[row0 + tid];
         SM_SYNC();
@@ -345,12 +355,15 @@ __global__ __launch_bounds__(SM_NT) void ais_small_kernel(AisSmallArgs a)
                             const float m[4] = {x[0], x[1], x[2], x[3]};
                             if (grp) group_x(b1, m, bA, db, col);
                             else ais_draw_v<GAUSS>(kv, grow0, col, b1, bA, db, m, okc, v, s);
-                            if constexpr (CLAMP) ais_clamp(ob, held, v, s);
+                            if constexpr (CLAMP && !GROUPS) ais_clamp(ob, held, v, s);
                             if constexpr (!GROUPS) put_v(v, s, col, TRACE && a.trace_v ? a.trace_v + (int64_t)k * M * ldv : nullptr);
                         });
                 if constexpr (GROUPS) {                                // (sm_down's closing barrier: PX is complete)
                     group_pick(kv, v, s);
-                    if (tid < L.V64) put_v(v, s, tid, TRACE && a.trace_v ? a.trace_v + (int64_t)k * M * ldv : nullptr);
+                    if (tid < L.V64) {
+                        if constexpr (CLAMP) ais_clamp(ob, held, v, s);
+                        put_v(v, s, tid, TRACE && a.trace_v ? a.trace_v + (int64_t)k * M * ldv : nullptr);
+                    }
                     SM_SYNC();
                 }
                 if (tid < SM_ROWS) {
@@ -381,15 +394,16 @@ hipError_t launch_ais_small(const AisSmallArgs& a, hipStream_t s)
 {
     if (!ais_small_ok(a.M, a.V, a.H, a.gauss, a.ldv, a.ldh) || a.k0 < 0 || a.k1 <= a.k0 || a.k1 > a.K || !ais_clamp_ok(a))
         return hipErrorInvalidValue;
-    if (!ais_groups_ok(a.groups, a.V, a.gauss, a.mask)) return hipErrorInvalidValue;
+    if (!ais_groups_ok(a.groups, a.V, a.gauss)) return hipErrorInvalidValue;
     const SmallLayout L = small_layout(a.V, a.H, a.gauss != 0);
     const bool trace = a.trace_h || a.trace_v;
-    const int variant = a.groups.on ? 8 | (trace ? 1 : 0) : (a.mask ? 4 : 0) | (a.gauss ? 2 : 0) | (trace ? 1 : 0);
-    void (*const kerns[10])(AisSmallArgs) = {
+    const int variant = a.groups.on ? 8 | (a.mask ? 2 : 0) | (trace ? 1 : 0) : (a.mask ? 4 : 0) | (a.gauss ? 2 : 0) | (trace ? 1 : 0);
+    void (*const kerns[12])(AisSmallArgs) = {
         ais_small_kernel<false, false, false>, ais_small_kernel<false, true, false>, ais_small_kernel<true, false, false>,
         ais_small_kernel<true, true, false>,   ais_small_kernel<false, false, true>, ais_small_kernel<false, true, true>,
         ais_small_kernel<true, false, true>,   ais_small_kernel<true, true, true>,
-        ais_small_kernel<false, false, false, true>, ais_small_kernel<false, true, false, true>};
+        ais_small_kernel<false, false, false, true>, ais_small_kernel<false, true, false, true>,
+        ais_small_kernel<false, false, true, true>,  ais_small_kernel<false, true, true, true>};
     // one workgroup per slab up to one per CU of the chip (no partials to sum here: the cap only bounds the W stagings)
     const int nslabs = (a.M + SM_ROWS - 1) / SM_ROWS;
     const dim3 grid(nslabs < 256 ? nslabs : 256), block(SM_NT);
@@ -499,6 +513,9 @@ __global__ __launch_bounds__(AIS_NT) void ais_visible_kernel(AisStepArgs a)
 // like the plain kernel writes them.  A Bernoulli unit is the plain kernel's column; a group is walked three times per chain
 // (group_draw: max, Z, means) with x_c formed from a.pre on the fly, its uniform the Philox word of its first column.  With
 // n_groups = 0 a unit is a column and every sum has the plain kernel's operands in its order: the same bits.
+// CLAMP: a Bernoulli unit is ais_visible_kernel<false, true>'s column; a group is held by the mask entry at its first column, and
+// then its columns take obs and add 0.f to s1 (the draw is made and not used).
+template <bool CLAMP>
 __global__ __launch_bounds__(AIS_NT) void ais_visible_grouped_kernel(AisStepArgs a)
 {
     __shared__ float red[4 * (AIS_NT / 64)];
@@ -509,6 +526,11 @@ __global__ __launch_bounds__(AIS_NT) void ais_visible_grouped_kernel(AisStepArgs
     key.step = a.rng.step + (uint32_t)(2 * a.k);
     const AisGroups& G = a.groups;
     const int units = G.span_lo + G.n_groups + ((int)a.ldv - G.span_hi);
+    int64_t drow[4];                         // (clamp) where the chain's data row starts in obs (and in a per-row mask)
+    if constexpr (CLAMP) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) drow[e] = (int64_t)((row0 + e) / a.C) * a.ldv;
+    }
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int unit = tid; unit < units; unit += AIS_NT) {
         int c0, K = 0;                                   // first column; K = 0: a Bernoulli column
@@ -526,14 +548,19 @@ __global__ __launch_bounds__(AIS_NT) void ais_visible_grouped_kernel(AisStepArgs
             const int col = c0;
             const bool live = col < a.V;
             const float bA = live ? a.base_vbias[col] : 0.f, db = live ? a.vbias[col] - bA : 0.f;
-            bool ok[4];
-            float m[4], v[4], s[4];
+            bool ok[4], held[4];
+            float m[4], v[4], s[4], ob[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 ok[e] = live && row0 + e < a.M;
                 m[e] = ok[e] && a.k > 0 ? a.pre[(int64_t)(row0 + e) * a.ldv + col] : 0.f;
+                if constexpr (CLAMP) {
+                    held[e] = ok[e] && a.mask[(a.mask_rows == 1 ? 0 : drow[e]) + col] != 0.f;
+                    ob[e] = held[e] ? a.obs[drow[e] + col] : 0.f;
+                }
             }
             ais_draw_v<false>(key, grow0, col, beta, bA, db, m, ok, v, s);
+            if constexpr (CLAMP) ais_clamp(ob, held, v, s);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 acc[e] += s[e];
@@ -548,7 +575,7 @@ __global__ __launch_bounds__(AIS_NT) void ais_visible_grouped_kernel(AisStepArgs
         philox_rows4(key, 0u, grow0, (uint32_t)c0, w);
         const float* bAp = a.base_vbias + c0;
         const float* bp = a.vbias + c0;
-        bool live[4];
+        bool live[4], held[4] = {false, false, false, false};
         int64_t off[4];
         float u[4], se[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -556,6 +583,7 @@ __global__ __launch_bounds__(AIS_NT) void ais_visible_grouped_kernel(AisStepArgs
             live[e] = row0 + e < a.M;
             off[e] = (int64_t)(row0 + e) * a.ldv + c0;
             u[e] = philox_u01(w[e]);
+            if constexpr (CLAMP) held[e] = live[e] && a.mask[(a.mask_rows == 1 ? 0 : drow[e]) + c0] != 0.f;
         }
         const bool has_m = a.k > 0;
         group_draw(K, u,
@@ -565,7 +593,12 @@ __global__ __launch_bounds__(AIS_NT) void ais_visible_grouped_kernel(AisStepArgs
                    },
                    [&](int c, int e, float v) {
                        if (!live[e]) return;
-                       se[e] += v * (bp[c] - bAp[c]);
+                       float sc = v * (bp[c] - bAp[c]);
+                       if constexpr (CLAMP) {
+                           v = held[e] ? a.obs[drow[e] + c0 + c] : v;
+                           sc = held[e] ? 0.f : sc;
+                       }
+                       se[e] += sc;
                        a.v[off[e] + c] = v;
                        if (a.trace) a.trace[off[e] + c] = v;
                    });
@@ -592,10 +625,11 @@ hipError_t launch_ais_hidden(const AisStepArgs& a, hipStream_t s)
 
 hipError_t launch_ais_visible(const AisStepArgs& a, hipStream_t s)
 {
-    if (!ais_clamp_ok(a) || a.k < 0 || a.k >= a.K || !ais_groups_ok(a.groups, a.V, a.gauss, a.mask)) return hipErrorInvalidValue;
+    if (!ais_clamp_ok(a) || a.k < 0 || a.k >= a.K || !ais_groups_ok(a.groups, a.V, a.gauss)) return hipErrorInvalidValue;
     const dim3 grid((a.M + 3) / 4), block(AIS_NT);
     if (a.groups.on) {
-        hipLaunchKernelGGL(ais_visible_grouped_kernel, grid, block, 0, s, a);
+        if (a.mask) hipLaunchKernelGGL(ais_visible_grouped_kernel<true>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(ais_visible_grouped_kernel<false>, grid, block, 0, s, a);
     } else if (a.mask) {
         if (a.gauss) hipLaunchKernelGGL((ais_visible_kernel<true, true>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((ais_visible_kernel<false, true>), grid, block, 0, s, a);

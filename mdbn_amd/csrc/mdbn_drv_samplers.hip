@@ -119,9 +119,9 @@ int ais_workspace_bytes(int64_t M, int64_t clamp_rows, int64_t V, int64_t H, int
     return MDBN_OK;
 }
 
-// The three runs once their own rules hold (the rules that need no device still come first): M chains, free (clamp == NULL)
-// or clamped, or free on a layer with softmax groups (groups.on: the checked table of mdbn_ais_run_grouped); `sizer` names the
-// entry point's own *_workspace_bytes
+// The four runs once their own rules hold (the rules that need no device still come first): M chains, free (clamp == NULL)
+// or clamped, each also on a layer with softmax groups (groups.on: the checked table of mdbn_ais_run_grouped /
+// mdbn_ais_cond_run_grouped); `sizer` names the entry point's own *_workspace_bytes
 int ais_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias, const float* vbias,
             const float* base_vbias, int gauss, const float* betas, int64_t n_betas, int64_t M, const AisClamp* clamp, int64_t ldv,
             float* v_state, double* logw, float* trace_h, float* trace_v, int path, const mdbn_rng* rng, void* workspace,
@@ -274,6 +274,24 @@ int mdbn_ais_cond_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, in
     const AisClamp clamp{obs, mask, mask_rows, N, C};
     return ais_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, gauss, betas, n_betas, N * C, &clamp, ldv, v_state, logw,
                    trace_h, trace_v, path, rng, workspace, workspace_bytes, "mdbn_ais_cond_workspace_bytes");
+}
+
+int mdbn_ais_cond_run_grouped(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+                              const float* vbias, const float* base_vbias, const float* betas, int64_t n_betas, const float* obs,
+                              const float* mask, int64_t mask_rows, int64_t N, int64_t C, int64_t ldv, float* v_state,
+                              double* logw, float* trace_h, float* trace_v, int path, const mdbn_rng* rng, void* workspace,
+                              int64_t workspace_bytes, const int32_t* group_start, const int32_t* group_start_host,
+                              int64_t n_groups)
+{
+    CtxScope ctx_scope(ctx);
+    CHECK(cais_chain_rules(N, C, V, H));
+    REQUIRE(n_betas < (1ll << 30) && V <= (1 << 24), "n_betas / V too large");
+    AisGroups g{};
+    CHECK(check_groups(group_start, group_start_host, n_groups, V, g.span_lo, g.span_hi));
+    g.group_start = group_start; g.n_groups = (int)n_groups; g.on = 1;
+    const AisClamp clamp{obs, mask, mask_rows, N, C};
+    return ais_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, 0, betas, n_betas, N * C, &clamp, ldv, v_state, logw,
+                   trace_h, trace_v, path, rng, workspace, workspace_bytes, "mdbn_ais_cond_workspace_bytes", g);
 }
 
 // ---------------------------------------------------------------------------------- clamped Gibbs sampling

@@ -629,9 +629,10 @@ class HipEngine(object):
         return x
 
     def _ais(self, W, hbias, vbias, base_vbias, gauss, betas, M, rng, path, trace, clamp=None, groups=None):
-        """What ``ais``, ``ais_grouped`` and ``ais_conditional`` share: M chains through mdbn_ais_run, or with ``clamp`` = (obs,
-        mask, mask_rows, N, chains per row), padded device matrices, through mdbn_ais_cond_run, or with ``groups`` (a
-        ``GroupTable``, no clamp) through mdbn_ais_run_grouped, whose workspace is mdbn_ais_run's.  Returns ``(logw [M] float64 numpy, trace_h,
+        """What ``ais``, ``ais_grouped``, ``ais_conditional`` and ``ais_conditional_grouped`` share: M chains through
+        mdbn_ais_run, or with ``clamp`` = (obs, mask, mask_rows, N, chains per row), padded device matrices, through
+        mdbn_ais_cond_run, or with ``groups`` (a ``GroupTable``) through mdbn_ais_run_grouped / mdbn_ais_cond_run_grouped (no
+        ``gauss`` argument), whose workspaces are those of the calls without groups.  Returns ``(logw [M] float64 numpy, trace_h,
         trace_v, v_state)``: the traces numpy (None without ``trace``), the final visible state [M, V] a device tensor."""
         V, H = W.shape
         ldh, ldv = W.stride(0), padded_ld(V)
@@ -644,9 +645,11 @@ class HipEngine(object):
             else base_vbias.to(device=self.device, dtype=torch.float32).contiguous()
         name = "mdbn_ais_run" if clamp is None else "mdbn_ais_cond_run"
         sizer = name.replace("run", "workspace_bytes")
-        table = ()
+        table, kind = (), (int(bool(gauss)),)
         if groups is not None:
-            name = "mdbn_ais_run_grouped"
+            name = name + "_grouped"
+            if clamp is not None:
+                kind = ()
             table = (self._p(groups.tensor), C.c_void_p(groups.host.ctypes.data), groups.n_groups)
         ws = self._sampler_workspace(getattr(self.lib, sizer), sizer, ((M,) if clamp is None else clamp[3:]) + (V,), H, ldh, path,
                                      extra=(K + 1,))
@@ -657,7 +660,7 @@ class HipEngine(object):
         r = rng.c()
         chains = (M,) if clamp is None else (self._p(clamp[0]), self._p(clamp[1])) + tuple(clamp[2:])
         _lib.check(getattr(self.lib, name)(
-            self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base), int(bool(gauss)),
+            self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base), *kind,
             self._p(d_betas), K + 1, *chains, ldv, self._p(v_state), self._p(logw), self._p(trace_h), self._p(trace_v),
             int(path), C.byref(r), self._p(ws), ws.numel() * 4, *table), name)
         if trace:
@@ -689,6 +692,20 @@ class HipEngine(object):
         the hidden [K-1, N n_chains, H] and visible [K, N n_chains, V] samples of every temperature (chain m belongs to row
         m // n_chains) and, with ``state``, last of all the final visible state [N n_chains, V].  ``mask``: [N, V], or [1, V] for
         every row.  ``betas``, ``base_vbias`` and ``path`` as ``ais``.  Consumes 2K - 1 RNG steps from ``rng.step``."""
+        return self._ais_conditional(W, hbias, vbias, base_vbias, gauss, betas, obs, mask, n_chains, rng, path, trace, state)
+
+    def ais_conditional_grouped(self, W, hbias, vbias, base_vbias, betas, obs, mask, n_chains, rng, groups, path=0, trace=False,
+                                state=False):
+        """``ais_conditional`` for a Bernoulli layer whose visibles hold the softmax groups ``groups`` (a ``GroupTable``), in
+        ONE library call (mdbn_ais_cond_run_grouped): a free group's visible draw is one category of its softmax over the
+        tempered pre-activations, from one uniform at the group's first column; a group is held or free as a whole, by the mask
+        entry at its FIRST column.  Everything else, the returns and the 2K - 1 RNG steps are ``ais_conditional``'s.  The
+        weights belong with the grouped base model (``ais_estimate_rows(..., groups=)``)."""
+        return self._ais_conditional(W, hbias, vbias, base_vbias, False, betas, obs, mask, n_chains, rng, path, trace, state,
+                                     groups=groups)
+
+    def _ais_conditional(self, W, hbias, vbias, base_vbias, gauss, betas, obs, mask, n_chains, rng, path, trace, state, groups=None):
+        """What ``ais_conditional`` and ``ais_conditional_grouped`` (``groups``) share."""
         obs = self.as_matrix(obs)
         N, V = (int(x) for x in obs.shape)
         if V != W.shape[0]:
@@ -702,7 +719,7 @@ class HipEngine(object):
         if mask_rows not in (1, N):
             raise ValueError("mask has %d rows: neither 1 nor the %d rows of obs" % (mask_rows, N))
         clamp = (self._padded(obs, N, V, ldv), self._padded(mask, mask_rows, V, ldv), mask_rows, N, Cn)
-        logw, trace_h, trace_v, v_state = self._ais(W, hbias, vbias, base_vbias, gauss, betas, N * Cn, rng, path, trace, clamp)
+        logw, trace_h, trace_v, v_state = self._ais(W, hbias, vbias, base_vbias, gauss, betas, N * Cn, rng, path, trace, clamp, groups)
         out = (logw.reshape(N, Cn),)
         if trace:
             out += (trace_h, trace_v)

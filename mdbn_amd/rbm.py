@@ -661,15 +661,27 @@ def ais_estimate(logw, base_vbias, n_hidden, gauss, groups=None):
     return float(log_Z), float(err)
 
 
-def ais_estimate_rows(logw, base_vbias, mask, n_hidden, gauss):
+def ais_estimate_rows(logw, base_vbias, mask, n_hidden, gauss, groups=None):
     """``(log_Z [N], std_err [N])`` from the log importance weights ``logw`` [N, C] of a clamped AIS run (float64 on the host),
     per data row r: log Z_A,r + logsumexp_c(logw[r]) - log C, with the base-rate model over the row's free columns (``mask``
     [1 | N, V] zero) alone -- log Z_A,r = H log 2 + sum_free softplus(b_A) (Bernoulli) | H log 2 + |free| / 2 log 2 pi
-    (Gaussian) -- and ``ais_estimate``'s delta-method standard error std(w) / (mean(w) sqrt(C)) of each row."""
+    (Gaussian) -- and ``ais_estimate``'s delta-method standard error std(w) / (mean(w) sqrt(C)) of each row.  ``groups`` (a
+    ``GroupTable`` or its boundaries; Bernoulli only): the weights of a run on a layer with softmax groups
+    (``HipEngine.ais_conditional_grouped``) -- a group is free when the mask at its FIRST column is 0, and a free group
+    contributes logsumexp_{c in g} b_A,c instead of its columns' softplus."""
     logw = numpy.asarray(logw, dtype=numpy.float64)
     free = numpy.broadcast_to(numpy.asarray(mask) == 0, (logw.shape[0], numpy.asarray(mask).shape[1]))
     bA = numpy.asarray(base_vbias, dtype=numpy.float64)
     per_col = numpy.full(bA.shape, 0.5 * numpy.log(2.0 * numpy.pi)) if gauss else numpy.logaddexp(0.0, bA)
+    if groups is not None:
+        if gauss:
+            raise ValueError("groups: a Gaussian visible layer has no categorical units")
+        b = numpy.asarray(getattr(groups, "host", groups), dtype=numpy.int64)
+        free, per_col = free.copy(), per_col.copy()
+        for lo, hi in zip(b[:-1], b[1:]):           # the group's term sits at its first column, under that column's mask
+            per_col[lo] = numpy.logaddexp.reduce(bA[lo:hi])
+            per_col[lo + 1:hi] = 0.0
+            free[:, lo + 1:hi] = False
     log_ZA = n_hidden * numpy.log(2.0) + (free * per_col[None, :]).sum(axis=1)
     top = logw.max(axis=1)
     w = numpy.exp(logw - top[:, None])
@@ -1199,20 +1211,33 @@ class RBM(object):
         ``betas`` / ``n_betas`` / ``base_vbias`` / ``data``: the schedule and the base-rate model, as ``log_partition`` (the
         base-rate model of a row is ``base_vbias`` on its free columns).  The logsumexp and the delta-method standard error of
         every row are float64 numpy on the host (``ais_estimate_rows``); a row with no free column has std_err 0.  Consumes
-        2K - 1 RNG steps."""
-        self._no_groups("conditional_log_partition")
+        2K - 1 RNG steps.
+
+        A layer with ``visible_groups`` (on an engine with ``ais_conditional_grouped``; refused elsewhere): a free group's draw
+        is one category of its softmax (mdbn_ais_cond_run_grouped) and the base model counts it as one logsumexp; a group is
+        held or free as a whole, so a mask that is not constant over a group is a ValueError, raised before anything is drawn."""
+        grouped = self.visible_groups is not None
+        if grouped and not hasattr(self.engine, "ais_conditional_grouped"):
+            self._no_groups("conditional_log_partition on this engine")
         self._no_sigma("conditional_log_partition")
         x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
         if x.ndim != 2 or x.shape[1] != self.n_visible or x.shape[0] < 1:
             raise ValueError("v must be [N >= 1, %d], got %r" % (self.n_visible, x.shape))
         mask = self._clamp_mask(observed_mask, x.shape[0])
+        if grouped:
+            self._check_group_mask(mask)
         betas, K, base_vbias = self._ais_schedule(betas, n_betas, base_vbias, data)
         step = self._rng_step
-        logw = self.engine.ais_conditional(self.W.tensor, self.hbias.tensor, self.vbias.tensor, base_vbias, self.gauss, betas,
-                                           numpy.where(numpy.broadcast_to(mask != 0, x.shape), x, numpy.float32(0)), mask, int(n_chains),
-                                           RngAddr(self.theano_rng.seed, self.stream_id, step, 0, 0), path=path)
+        obs = numpy.where(numpy.broadcast_to(mask != 0, x.shape), x, numpy.float32(0))
+        rng = RngAddr(self.theano_rng.seed, self.stream_id, step, 0, 0)
+        if grouped:
+            logw = self.engine.ais_conditional_grouped(self.W.tensor, self.hbias.tensor, self.vbias.tensor, base_vbias, betas, obs,
+                                                       mask, int(n_chains), rng, self.visible_groups, path=path)
+        else:
+            logw = self.engine.ais_conditional(self.W.tensor, self.hbias.tensor, self.vbias.tensor, base_vbias, self.gauss, betas,
+                                               obs, mask, int(n_chains), rng, path=path)
         self._rng_step = step + 2 * K - 1
-        return ais_estimate_rows(logw, base_vbias, mask, self.n_hidden, self.gauss)
+        return ais_estimate_rows(logw, base_vbias, mask, self.n_hidden, self.gauss, self.visible_groups)
 
     def conditional_log_likelihood(self, v, observed_mask, **ais):
         """``(log_p [N], std_err [N])``: log p(v_F | v_O) of every row of ``v`` -- its free block F (``observed_mask`` zero)
@@ -1222,15 +1247,31 @@ class RBM(object):
         with ``conditional_log_partition(v, observed_mask, **ais)``'s estimate of log_Z_r (the standard error is that
         estimate's); the free energy is the device's, the rest float64 on the host.  A row with no free column gets log_p = 0,
         std_err = 0.  A Bernoulli layer gives probability to 0 / 1 states only: free entries of ``v`` that are neither are
-        refused (observed entries may hold any real value: they enter through v W alone)."""
-        self._no_groups("conditional_log_likelihood")
+        refused (observed entries may hold any real value: they enter through v W alone).
+
+        A layer with ``visible_groups`` (on an engine with ``ais_conditional_grouped``; refused elsewhere): ``observed_mask``
+        must be constant over every group, and every FREE group of every row must hold exactly one 1 (ValueError otherwise,
+        before anything is drawn; a held group may hold anything).  With one group free this is log p(category | everything
+        else) of a classification RBM, the log of ``group_posterior``'s entry, with a standard error."""
+        grouped = self.visible_groups is not None
+        if grouped and not hasattr(self.engine, "ais_conditional_grouped"):
+            self._no_groups("conditional_log_likelihood on this engine")
         self._no_sigma("conditional_log_likelihood")
         x = numpy.asarray(getattr(v, "get_value", lambda: v)(), dtype=numpy.float32)
         if x.ndim != 2 or x.shape[1] != self.n_visible or x.shape[0] < 1:
             raise ValueError("v must be [N >= 1, %d], got %r" % (self.n_visible, x.shape))
-        held = numpy.broadcast_to(self._clamp_mask(observed_mask, x.shape[0]) != 0, x.shape)
+        mask = self._clamp_mask(observed_mask, x.shape[0])
+        if grouped:
+            self._check_group_mask(mask)
+        held = numpy.broadcast_to(mask != 0, x.shape)
         if not self.gauss and not numpy.isin(x[~held], (0.0, 1.0)).all():
             raise ValueError("a Bernoulli layer scores 0 / 1 states: a free entry of v is neither")
+        if grouped:
+            for lo, hi in self.visible_groups.spans():
+                bad = numpy.nonzero(~held[:, lo] & (x[:, lo:hi].sum(axis=1) != 1))[0]
+                if bad.size:
+                    raise ValueError("row %d of v does not hold exactly one 1 in the free group of columns %d .. %d"
+                                     % (int(bad[0]), lo, hi - 1))
         log_Z, err = self.conditional_log_partition(x, observed_mask, **ais)
         neg_F = -numpy.asarray(self.free_energy(x).get_value(), dtype=numpy.float64)
         b = numpy.asarray(self.vbias.get_value(), dtype=numpy.float64)[None, :]
