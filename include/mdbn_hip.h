@@ -831,6 +831,32 @@ int  mdbn_ais_run_grouped(mdbn_ctx *ctx, void *stream, const float *W, int64_t V
                           void *workspace, int64_t workspace_bytes, const int32_t *group_start,
                           const int32_t *group_start_host, int64_t n_groups);
 
+/* mdbn_pt_run_grouped: mdbn_pt_run / mdbn_pt_run_z for a Bernoulli layer whose visibles hold softmax groups: the arguments
+ * of mdbn_pt_run_z (zacc and trace_work each nullable), then the table under the convention above.  On one-hot rows
+ * log p*_beta(v) is the Bernoulli expression, so the swap decision, the works, the hidden draw, the rank map, the counts,
+ * the 3 n Philox steps, the paths, the traces and the cuts of a long run are mdbn_pt_run_z's, bit for bit.  What changes is
+ * the visible draw: on a group  v ~ softmax_c(x_c)  over its tempered pre-activations at the beta of the row's OWN rank,
+ *   x_c = fma(beta, m_c, fma(beta, vbias_c - base_vbias_c, base_vbias_c)),   m = h W^T,
+ * with the arithmetic and the addressing of mdbn_ais_run_grouped (mx, the hardware exponential, Z in ascending c, correctly
+ * rounded means, the running sum C; the first c with u < C_c, the last one when none qualifies); ONE uniform per (replica
+ * row, group): the Philox word of the group's FIRST column at step rng->step + 3t, draw index 0, the global replica row --
+ * the uniforms of its other columns are not used.  s1 gets v_c (vbias - base_vbias)_c of every column, and from burn_in on
+ * the top-rank row adds the group's softmax mean mean_c (not a sigmoid) to v_avg.  A Bernoulli column outside the span
+ * keeps mdbn_pt_run's draw, so n_groups = 0 gives every output of mdbn_pt_run / mdbn_pt_run_z bit for bit on both paths.
+ * Every recorded visible row holds exactly one 1 per group.  The base model of the ladder's log Z (betas[0] = 0; left to
+ * the caller, float64 on the host):
+ *   log Z_A = H log 2 + sum_{Bernoulli i} softplus(base_vbias_i) + sum_g logsumexp_{c in g} base_vbias_c.
+ * path 1 needs no LDS beyond mdbn_pt_run's image, so the shapes that fit are the same; workspace:
+ * mdbn_pt_run_z_workspace_bytes.  MDBN_EINVAL with a message, before any launch and with every output untouched: gauss, an
+ * invalid table (the rules of mdbn_ais_run_grouped), and whatever mdbn_pt_run_z refuses. */
+int  mdbn_pt_run_grouped(mdbn_ctx *ctx, void *stream, const float *W, int64_t V, int64_t H, int64_t ldh,
+                         const float *hbias, const float *vbias, const float *base_vbias, int gauss,
+                         const float *betas, int64_t R, int64_t M, int64_t ldv, float *v, float *h, int32_t *rank,
+                         int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t *accepted, float *v_avg, float *h_avg,
+                         float *trace_v, float *trace_h, int32_t *trace_swaps, int path, int64_t steps_per_launch,
+                         const mdbn_rng *rng, void *workspace, int64_t workspace_bytes, double *zacc, double *trace_work,
+                         const int32_t *group_start, const int32_t *group_start_host, int64_t n_groups);
+
 /* mdbn_gibbs_clamped_grouped: mdbn_gibbs_clamped for a Bernoulli layer (no gauss, no add_noise) whose visibles hold
  * softmax groups: its arguments, then the table under the convention above.  The chain, the Philox steps (rng->step + 2t
  * hidden, rng->step + 2t + 1 visible, draw 0), burn_in, the accumulators, the taps, path and steps_per_launch are

@@ -129,6 +129,9 @@ SIGNATURES = {
     "mdbn_pt_run_z_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
     "mdbn_pt_run_z": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp,
                       _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _rngp, _vp, _i64, _vp, _vp],
+    "mdbn_pt_run_grouped": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp,
+                            _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _rngp, _vp, _i64, _vp, _vp,
+                            _vp, _vp, _i64],
     "mdbn_rowll_workspace_bytes": [_vp, _i64, _i64, _i64, C.POINTER(_i64)],
     "mdbn_propdown_rowll": [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64],
     "mdbn_sample_replicas": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _rngp],

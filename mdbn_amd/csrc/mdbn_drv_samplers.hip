@@ -531,13 +531,14 @@ int pt_workspace_bytes(mdbn_ctx* ctx, int64_t M, int64_t R, int64_t V, int64_t H
     return MDBN_OK;
 }
 
-// mdbn_pt_run (z = false: zacc and trace_work NULL) and mdbn_pt_run_z: one statement of the rules and of the run
+// mdbn_pt_run (z = false: zacc and trace_work NULL), mdbn_pt_run_z and (groups.on: the checked table of mdbn_pt_run_grouped,
+// gauss = 0) the run of a Bernoulli layer with softmax groups: one statement of the rules and of the run
 int pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
            const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t R, int64_t M, int64_t ldv,
            float* v, float* h, int32_t* rank, int64_t n_sweeps, int64_t burn_in, int64_t sweep0, int32_t* accepted,
            float* v_avg, float* h_avg, float* trace_v, float* trace_h, int32_t* trace_swaps, int path,
            int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes, bool z, double* zacc,
-           double* trace_work)
+           double* trace_work, const AisGroups& groups = AisGroups{})
 {
     // (the argument rules first: they need no device)
     REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
@@ -587,6 +588,7 @@ int pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, in
         a.rng = make_key(*rng, 0u);
         a.trace_v = trace_v; a.trace_h = trace_h; a.trace_swaps = trace_swaps;
         a.zacc = zacc; a.trace_work = trace_work;
+        a.groups = groups;
         const int64_t cut = steps_per_launch ? steps_per_launch : pt_default_cut(R);
         for (int64_t t0 = 0; t0 < n_sweeps; t0 += cut) {      // a launch stays short; the state travels in h / rank / counts / sums
             a.t0 = (int)t0; a.t1 = (int)std::min(n_sweeps, t0 + cut);
@@ -614,6 +616,7 @@ int pt_run(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, in
     st.n_avg = (float)(n_sweeps - burn_in); st.sweep0 = sweep0;
     st.rng = make_key(*rng, 0u);
     st.zacc = zacc;
+    st.groups = groups;
     if (zacc || trace_work) {
         st.g = g;
         if (gauss) HIP_OK(launch_pt_gnorm(vbias, base_vbias, (int)V, g, s));
@@ -676,6 +679,26 @@ int mdbn_pt_run_z(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_
     return pt_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, gauss, betas, R, M, ldv, v, h, rank, n_sweeps, burn_in, sweep0,
                   accepted, v_avg, h_avg, trace_v, trace_h, trace_swaps, path, steps_per_launch, rng, workspace, workspace_bytes, true,
                   zacc, trace_work);
+}
+
+int mdbn_pt_run_grouped(mdbn_ctx* ctx, void* stream, const float* W, int64_t V, int64_t H, int64_t ldh, const float* hbias,
+                        const float* vbias, const float* base_vbias, int gauss, const float* betas, int64_t R, int64_t M,
+                        int64_t ldv, float* v, float* h, int32_t* rank, int64_t n_sweeps, int64_t burn_in, int64_t sweep0,
+                        int32_t* accepted, float* v_avg, float* h_avg, float* trace_v, float* trace_h, int32_t* trace_swaps,
+                        int path, int64_t steps_per_launch, const mdbn_rng* rng, void* workspace, int64_t workspace_bytes,
+                        double* zacc, double* trace_work, const int32_t* group_start, const int32_t* group_start_host,
+                        int64_t n_groups)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(M >= 1 && V >= 1 && H >= 1, "bad shape M=%lld V=%lld H=%lld", (long long)M, (long long)V, (long long)H);
+    REQUIRE(V <= (1 << 24), "V too large");
+    REQUIRE(!gauss, "categorical visible units: a Gaussian layer (gauss = 1) has no groups");
+    AisGroups g{};
+    CHECK(check_groups(group_start, group_start_host, n_groups, V, g.span_lo, g.span_hi));
+    g.group_start = group_start; g.n_groups = (int)n_groups; g.on = 1;
+    return pt_run(ctx, stream, W, V, H, ldh, hbias, vbias, base_vbias, 0, betas, R, M, ldv, v, h, rank, n_sweeps, burn_in, sweep0,
+                  accepted, v_avg, h_avg, trace_v, trace_h, trace_swaps, path, steps_per_launch, rng, workspace, workspace_bytes, true,
+                  zacc, trace_work, g);
 }
 
 // ---------------------------------------------------------------------------------- variational bound (mdbn_bound.hip)

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "mdbn_kernels.h"
 #include "mdbn_small.h"
+#include "mdbn_ais.h"                       // AisGroups: the unit map of a layer with softmax groups
 
 namespace mdbn {
 
@@ -55,9 +56,10 @@ struct PtSmallArgs {
     float* trace_v; float* trace_h; int* trace_swaps;    // [n][M R][ldv], [n][M R][ldh], [n][M][2][R] or NULL
     double* zacc;                                    // [M][R - 1][4] = {m_f, s_f, m_r, s_r} of the works (in and out) or NULL
     double* trace_work;                              // [n][M][R - 1][2] = (d_fwd, d_rev), NaN where not attempted, or NULL
+    AisGroups groups;                                // softmax groups of the visible layer (Bernoulli only) or {}
 };
 
-// General path, one sweep: pt_visible_kernel after the propdown GEMM, pt_swap_hidden_kernel after the propup GEMM.
+// General path, one sweep: pt_visible_kernel (groups.on: pt_visible_grouped_kernel) after the propdown GEMM, pt_swap_hidden_kernel after the propup GEMM.
 struct PtStepArgs {
     int M, R, V, H, gauss;
     int64_t ldv, ldh;
@@ -74,6 +76,7 @@ struct PtStepArgs {
     double* zacc;                                    // [M][R - 1][4] (mdbn_temper.hip: the works) or NULL
     double* trace_work;                              // this sweep's [M][R - 1][2] or NULL
     const double* g;                                 // |b - b_A|^2 (launch_pt_gnorm); read when gauss and zacc / trace_work
+    AisGroups groups;                                // softmax groups of the visible layer (Bernoulli only) or {}
 };
 
 bool pt_small_ok(int64_t M, int64_t R, int64_t V, int64_t H, int gauss, int64_t ldv, int64_t ldh);

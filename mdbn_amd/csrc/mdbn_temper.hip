@@ -27,6 +27,13 @@
 // the two exponentials float32); the caller starts it at (-inf, 0) and it is in-and-out like the rank map.  trace_work taps
 // (d_fwd, d_rev) of every sweep (NaN: the pair was not tried).  Neither consumes a random number nor touches a decision.
 //
+// Softmax groups (mdbn_pt_run_grouped): a visible layer that holds a span of one-hot groups between Bernoulli columns
+// (mdbn_groups.hip).  On one-hot rows log p*_beta(v) is the Bernoulli expression, so the swap decision, the works, the hidden
+// draw, the rank map, the counts and the cuts are the plain run's; only the visible draw of a group changes -- v ~
+// softmax_c(x_c) over the group's tempered pre-activations at the beta of the row's rank, ONE uniform per (replica row,
+// group): the Philox word of the group's first column at step s + 3t, draw 0, by the group draw of mdbn_sampler_kit.h -- and
+// with it the beta = 1 mean that v_sum takes from the top-rank row: the group's softmax mean.  s1 gets v_c (b - b_A)_c.
+//
 // pt_small_kernel (LDS-resident layers, R a multiple of 4): W staged once into the workgroup's LDS; a workgroup owns whole
 // ladders, the R rows of h and a stay in LDS, a sweep runs R / 4 four-row slabs through sm_down / sm_up of
 // mdbn_small_passes.h, the swap phase reads the per-row sums from LDS and exchanges ranks there.  Nothing crosses a workgroup.
@@ -39,6 +46,7 @@
 #include "mdbn_small_passes.h"
 #include "mdbn_sampler_kit.h"
 #include "mdbn_temper.h"
+#include "mdbn_groups.h"                    // MDBN_GROUP_MAX and the unit map the grouped visible kernel shares
 
 namespace mdbn {
 
@@ -103,20 +111,36 @@ __device__ __forceinline__ double pt_gnorm_wave(int n, int lane, F db)
     return t;
 }
 
+// what a launcher asks of the groups: none, or a Bernoulli layer whose span lies inside the row (the rule of launch_ais_visible)
+bool pt_groups_ok(const AisGroups& g, int V, int gauss)
+{
+    if (!g.on) return g.n_groups == 0;
+    return !gauss && g.n_groups >= 0 && (g.n_groups == 0 || g.group_start) && g.span_lo >= 0 && g.span_lo <= g.span_hi &&
+           g.span_hi <= V && (g.n_groups == 0) == (g.span_lo == g.span_hi) && g.n_groups <= g.span_hi - g.span_lo;
+}
+
 }  // namespace
 
 // Z: the variants of mdbn_pt_run_z (the works; their tap rides with TRACE).  The Bernoulli variant without taps is held to
 // the 128 VGPRs of two workgroups per CU, which pt_small_preferred counts on (127, no scratch; unbounded the compiler takes 129
 // and a sweep at 100 -> 24 with 512 ladders costs 43 instead of 24 us); the bound 1 leaves the other variants as they were.
-template <bool GAUSS, bool TRACE, bool Z = false>
-__global__ __launch_bounds__(SM_NT, (Z && !GAUSS && !TRACE) ? 4 : 1) void pt_small_kernel(PtSmallArgs a)
+// GROUPS (mdbn_pt_run_grouped): a thread whose column lies in a softmax group leaves the slab's four tempered pre-activations
+// in PX instead of drawing; after the pass's closing barrier every thread takes its group's maximum and writes its own e_c into
+// EX, forms Z and its mean, then the running sum up to its own column and decides its own 0 / 1 entry (the group draw of
+// mdbn_sampler_kit.h; ais_small_kernel).  PX / EX are small_layout's oX0 / oXb, which the plain kernel leaves unused, so
+// pt_layout -- and pt_small_ok -- serve both.  The variants without taps are held to 128 VGPRs like the Z one.
+template <bool GAUSS, bool TRACE, bool Z = false, bool GROUPS = false>
+__global__ __launch_bounds__(SM_NT, ((Z || GROUPS) && !GAUSS && !TRACE) ? 4 : 1) void pt_small_kernel(PtSmallArgs a)
 {
+    static_assert(!GROUPS || !GAUSS, "softmax groups: a Bernoulli layer");
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const SmallLayout& L = a.L;
     const PtLayout& P = a.P;
     lds_f* const lds = (lds_f*)sm;
     lds_f* const Wl = lds + L.oW;
+    lds_f* const PX = lds + L.oX0;          // (groups) [V64][4] tempered pre-activations x_c of the group columns, then their means
     lds_f* const X = lds + L.oXa;           // [4][ldx] the slab's visible draw
+    lds_f* const EX = lds + L.oXb;          // (groups) [V64][4] e_c = exp(x_c - max)
     lds_f* const part = lds + L.oPart;
     lds_f* const hbl = lds + L.oHb;         // c
     lds_f* const bAl = lds + L.oVb;         // b_A
@@ -149,6 +173,25 @@ __global__ __launch_bounds__(SM_NT, (Z && !GAUSS && !TRACE) ? 4 : 1) void pt_sma
     const bool vlive = tid < V, hlive = tid < H;
     double g = 0.0;                                                      // (the deciding threads tid < R - 1 sit in wave 0)
     if (Z && GAUSS && wave == 0) g = pt_gnorm_wave(V, lane, [&](int i) { return a.vbias[i] - a.base_vbias[i]; });
+    // ---- (groups) this thread's column belongs to the group [c0, c1) for the whole launch; c1 = c0: a Bernoulli column.
+    // The last g with group_start[g] <= tid; the caller checked its host copy, the device copy is clamped to the span all the
+    // same (ais_small_kernel), and a walk never leaves [c0, c1)
+    int c0 = 0, c1 = 0;
+    if constexpr (GROUPS) {
+        const AisGroups& G = a.groups;
+        if (tid >= G.span_lo && tid < G.span_hi && G.n_groups > 0) {
+            int lo = 0, hi = G.n_groups - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (G.group_start[mid] <= tid) lo = mid; else hi = mid - 1;
+            }
+            c0 = min(max(G.group_start[lo], G.span_lo), tid);
+            c1 = min(min(max(G.group_start[lo + 1], tid + 1), G.span_hi), c0 + MDBN_GROUP_MAX);
+            if (c1 <= tid) c0 = c1 = 0;     // (a table the host copy does not describe: the column falls back to a Bernoulli unit)
+        }
+    }
+    const bool grp = GROUPS && c1 > c0;
+    const int cc = c0 | (c1 << 16);          // (one register for the launch: V64 <= 512)
 
     for (int m = blockIdx.x; m < M; m += gridDim.x) {
         SM_SYNC();                                                       // (staging | the previous ladder's last readers are done)
@@ -196,6 +239,97 @@ __global__ __launch_bounds__(SM_NT, (Z && !GAUSS && !TRACE) ? 4 : 1) void pt_sma
                     bp[e] = pr >= 0 ? betl[pr] : bo[e];
                     top[e] = rho == R - 1;
                 }
+                if constexpr (GROUPS) {
+                    // The visible draw in two parts (ais_small_kernel).  In the pass: a Bernoulli column draws as the plain kernel
+                    // does, a group column leaves x_c in PX.  After the pass's closing barrier, every thread of the workgroup:
+                    // e_c into EX -- ONE exponential per (row, column) --, barrier, Z and the column's mean, barrier, the running
+                    // sum of the means up to the thread's own column and its 0 / 1 entry.  One uniform per (row, group): the Philox
+                    // word of the group's first column.  Two barriers, whatever the groups; then X, redV, v and the taps.
+                    // A column's entries wait in X, its share of s1 in its own EX slot (a Bernoulli column's is otherwise unused, a group
+                    // column's has been read by then): nothing of a draw stays in a register across a pass or a barrier, and every
+                    // column leaves through the one tail below.
+                    sm_down(Hs + SM_ROWS * q * L.ldhs, Wl, L, wave, lane,
+                            [&](const sf32x4& x, int col) {                // col == tid
+                                asm volatile("" : "+v"(col));              // (as `me` below)
+                                const float bA = bAl[col], db = dbl[col];
+                                const float mm[4] = {x[0], x[1], x[2], x[3]};
+                                if (grp) {
+                                    *(lds_f4*)(PX + 4 * col) = sf32x4{tempered_pre_v(bo[0], mm[0], bA, db), tempered_pre_v(bo[1], mm[1], bA, db),
+                                                                      tempered_pre_v(bo[2], mm[2], bA, db), tempered_pre_v(bo[3], mm[3], bA, db)};
+                                } else {
+                                    float v[4], pre[4], s[4];
+                                    tempered_draw_v<false>(kv, grow0, col, bo, bA, db, mm, okv, v, pre, s);
+#pragma unroll
+                                    for (int e = 0; e < 4; ++e) {
+                                        X[e * L.ldx + col] = v[e];
+                                        if (acc && top[e] && vlive) vacc += sigmoidf_(pre[e]);
+                                    }
+                                    *(lds_f4*)(EX + 4 * col) = sf32x4{s[0], s[1], s[2], s[3]};
+                                }
+                            });
+                    // (slab-local copies of the group's bounds and of the thread's slot: with the launch-wide values the compiler
+                    //  hoists every walk's addresses and trip counts out of the sweeps, ~20 VGPRs held across the passes)
+                    int gg = cc, me = tid;
+                    asm volatile("" : "+v"(gg), "+v"(me));
+                    const int g0 = gg & 0xffff, g1 = gg >> 16;
+                    if (grp) {
+                        sf32x4 mx = *(const lds_f4*)(PX + 4 * g0);
+                        for (int c = g0 + 1; c < g1; ++c) {
+                            const sf32x4 x = *(const lds_f4*)(PX + 4 * c);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], x[e]);
+                        }
+                        const sf32x4 x = *(const lds_f4*)(PX + 4 * me);
+                        *(lds_f4*)(EX + 4 * me) = sf32x4{group_exp(x[0], mx[0]), group_exp(x[1], mx[1]), group_exp(x[2], mx[2]), group_exp(x[3], mx[3])};
+                    }
+                    SM_SYNC();
+                    if (grp) {
+                        sf32x4 Zs = {0.f, 0.f, 0.f, 0.f};
+                        for (int c = g0; c < g1; ++c) Zs += *(const lds_f4*)(EX + 4 * c);
+                        const sf32x4 ex = *(const lds_f4*)(EX + 4 * me);
+                        *(lds_f4*)(PX + 4 * me) = sf32x4{group_mean(ex[0], Zs[0]), group_mean(ex[1], Zs[1]), group_mean(ex[2], Zs[2]), group_mean(ex[3], Zs[3])};
+                    }
+                    SM_SYNC();
+                    if (grp) {
+                        uint32_t w[4];
+                        philox_rows4(kv, 0u, grow0, (uint32_t)g0, w);
+                        const float u[4] = {philox_u01(w[0]), philox_u01(w[1]), philox_u01(w[2]), philox_u01(w[3])};
+                        sf32x4 before = {0.f, 0.f, 0.f, 0.f};
+                        for (int c = g0; c < me; ++c) before += *(const lds_f4*)(PX + 4 * c);
+                        const sf32x4 mean = *(const lds_f4*)(PX + 4 * me);
+                        const float db = dbl[me];
+                        sf32x4 s4;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float ve = group_entry(u[e], before[e], before[e] + mean[e], me == g1 - 1);
+                            X[e * L.ldx + me] = ve;
+                            s4[e] = ve * db;
+                            if (acc && top[e]) vacc += mean[e];              // (the group's softmax mean at beta = 1)
+                        }
+                        *(lds_f4*)(EX + 4 * me) = s4;
+                    }
+                    if (tid < L.V64) {                                     // (whole waves: V64 is a multiple of 64; own slots: no barrier)
+                        const int col = me;
+                        const sf32x4 s4 = *(const lds_f4*)(EX + 4 * col);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float ts = wave_sum(s4[e]);
+                            if (lane == 0) redV[(SM_ROWS * q + e) * 8 + (col >> 6)] = ts;
+                        }
+                        if (col < (int)ldv && (out_v || (TRACE && a.trace_v))) {
+                            const float v[4] = {X[col], X[L.ldx + col], X[2 * L.ldx + col], X[3 * L.ldx + col]};
+                            if (out_v) {
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) a.v[(int64_t)(row0 + e) * ldv + col] = v[e];
+                            }
+                            if (TRACE && a.trace_v) {
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) a.trace_v[((int64_t)t * M * R + row0 + e) * ldv + col] = v[e];
+                            }
+                        }
+                    }
+                    SM_SYNC();
+                } else
                 sm_down(Hs + SM_ROWS * q * L.ldhs, Wl, L, wave, lane,
                         [&](const sf32x4& x, int col) {                    // col == tid
                             const float bA = bAl[col], db = dbl[col];
@@ -357,9 +491,27 @@ hipError_t launch_pt_small(const PtSmallArgs& a, hipStream_t s)
     if (!pt_small_ok(a.M, a.R, a.V, a.H, a.gauss, a.ldv, a.ldh) || a.t0 < 0 || a.t1 <= a.t0 || a.t1 > a.n || a.burn_in < 0 ||
         a.burn_in >= a.n)
         return hipErrorInvalidValue;
+    if (!pt_groups_ok(a.groups, a.V, a.gauss)) return hipErrorInvalidValue;
     const SmallLayout L = small_layout(a.V, a.H, a.gauss != 0);
     const PtLayout P = pt_layout(L, a.R);
     const bool trace = a.trace_h || a.trace_v || a.trace_swaps || a.trace_work;      // (the tap of the works rides with the others)
+    if (a.groups.on) {
+        // the variants of a layer with softmax groups: 2 Z + TRACE (their dynamic-LDS limits are raised apart from the others)
+        void (*const gkerns[4])(PtSmallArgs) = {pt_small_kernel<false, false, false, true>, pt_small_kernel<false, true, false, true>,
+                                                pt_small_kernel<false, false, true, true>, pt_small_kernel<false, true, true, true>};
+        static bool gattr_set[4] = {false, false, false, false};
+        const int gv = ((a.zacc || a.trace_work) ? 2 : 0) | (trace ? 1 : 0);
+        if (!gattr_set[gv]) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gkerns[gv]), hipFuncAttributeMaxDynamicSharedMemorySize, SM_MAX_LDS);
+            if (e != hipSuccess) return e;
+            gattr_set[gv] = true;
+        }
+        const dim3 ggrid(a.M < 1024 ? a.M : 1024), gblock(SM_NT);
+        PtSmallArgs gk = a;
+        gk.L = L; gk.P = P;
+        hipLaunchKernelGGL(gkerns[gv], ggrid, gblock, P.bytes, s, gk);
+        return hipGetLastError();
+    }
     const int variant = (a.gauss ? 2 : 0) | (trace ? 1 : 0);
     void (*const kerns[4])(PtSmallArgs) = {pt_small_kernel<false, false>, pt_small_kernel<false, true>, pt_small_kernel<true, false>,
                                            pt_small_kernel<true, true>};
@@ -428,6 +580,115 @@ __global__ __launch_bounds__(PT_NT) void pt_visible_kernel(PtStepArgs a)
                 if (a.last && a.v_avg) a.v_avg[o] = t / a.n_avg;
             }
         }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float t = wave_sum(acc[e]);
+        if (lane == 0) red[e * (PT_NT / 64) + wave] = t;
+    }
+    __syncthreads();
+    if (tid < 4 && okr[tid]) {
+        float t = 0.f;
+        for (int w = 0; w < PT_NT / 64; ++w) t += red[tid * (PT_NT / 64) + w];
+        a.s1[row0 + tid] = t;
+    }
+}
+
+// pt_visible_kernel<false> for a layer with softmax groups: a thread walks UNITS tid, tid + PT_NT, ... -- the unit map of
+// GroupSoftmaxArgs (mdbn_groups.h), with the pad columns V .. ldv - 1 as Bernoulli units behind the span, written as zeros
+// like the plain kernel writes them.  A Bernoulli unit is the plain kernel's column; a group is walked three times, its four
+// replica rows side by side and every row at the beta of its own rank (group_draw_mean: max, Z, means), with x_c formed from
+// a.pre on the fly, its uniform the Philox word of its first column.  The top-rank row adds the group's softmax mean to
+// v_sum.  With n_groups = 0 a unit is a column and every sum has the plain kernel's operands in its order: the same bits.
+__global__ __launch_bounds__(PT_NT) void pt_visible_grouped_kernel(PtStepArgs a)
+{
+    __shared__ float red[4 * (PT_NT / 64)];
+    const int row0 = (int)blockIdx.x * 4, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int rows = a.M * a.R;
+    const uint64_t grow0 = a.rng.row_offset + (uint64_t)row0;
+    PhiloxKey key = a.rng;
+    key.step = a.rng.step + (uint32_t)(3 * a.t);
+    const AisGroups& G = a.groups;
+    const int units = G.span_lo + G.n_groups + ((int)a.ldv - G.span_hi);
+    float beta[4];
+    bool okr[4], top[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        okr[e] = row0 + e < rows;
+        const int rho = okr[e] ? a.rank[row0 + e] : 0;
+        beta[e] = a.betas[rho];
+        top[e] = okr[e] && rho == a.R - 1;
+    }
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int unit = tid; unit < units; unit += PT_NT) {
+        int c0, K = 0;                                   // first column; K = 0: a Bernoulli column
+        if (unit < G.span_lo) {
+            c0 = unit;
+        } else if (unit < G.span_lo + G.n_groups) {
+            const int g = unit - G.span_lo;
+            // (the caller checked its host copy; the device copy is clamped to the span all the same)
+            c0 = min(max(G.group_start[g], G.span_lo), G.span_hi - 1);
+            K = min(min(max(G.group_start[g + 1], c0 + 1), G.span_hi) - c0, MDBN_GROUP_MAX);
+        } else {
+            c0 = G.span_hi + (unit - G.span_lo - G.n_groups);
+        }
+        if (K == 0) {
+            const int col = c0;
+            const bool live = col < a.V;
+            const float bA = live ? a.base_vbias[col] : 0.f, db = live ? a.vbias[col] - bA : 0.f;
+            bool ok[4];
+            float m[4], v[4], pre[4], s[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                ok[e] = live && okr[e];
+                m[e] = ok[e] ? a.pre[(int64_t)(row0 + e) * a.ldv + col] : 0.f;
+            }
+            tempered_draw_v<false>(key, grow0, col, beta, bA, db, m, ok, v, pre, s);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc[e] += s[e];
+                if (!okr[e]) continue;
+                a.v[(int64_t)(row0 + e) * a.ldv + col] = v[e];             // (pad columns: zeros)
+                if (a.trace_v) a.trace_v[(int64_t)(row0 + e) * a.ldv + col] = v[e];
+                if (a.accumulate && top[e]) {                              // (one row of a ladder holds the top rank: no other writer)
+                    const int64_t o = (int64_t)((row0 + e) / a.R) * a.ldv + col;
+                    const float t = a.v_sum[o] + (live ? sigmoidf_(pre[e]) : 0.f);
+                    a.v_sum[o] = t;
+                    if (a.last && a.v_avg) a.v_avg[o] = t / a.n_avg;
+                }
+            }
+            continue;
+        }
+        uint32_t w[4];
+        philox_rows4(key, 0u, grow0, (uint32_t)c0, w);
+        const float* bAp = a.base_vbias + c0;
+        const float* bp = a.vbias + c0;
+        int64_t off[4];
+        float u[4], se[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            off[e] = (int64_t)(row0 + e) * a.ldv + c0;
+            u[e] = philox_u01(w[e]);
+        }
+        group_draw_mean(K, u,
+                        [&](int c, int e) {
+                            const float bA = bAp[c];
+                            return tempered_pre_v(beta[e], okr[e] ? a.pre[off[e] + c] : 0.f, bA, bp[c] - bA);
+                        },
+                        [&](int c, int e, float v, float mean) {
+                            if (!okr[e]) return;
+                            se[e] += v * (bp[c] - bAp[c]);
+                            a.v[off[e] + c] = v;
+                            if (a.trace_v) a.trace_v[off[e] + c] = v;
+                            if (a.accumulate && top[e]) {                  // (the group's softmax mean at beta = 1)
+                                const int64_t o = (int64_t)((row0 + e) / a.R) * a.ldv + c0 + c;
+                                const float t = a.v_sum[o] + mean;
+                                a.v_sum[o] = t;
+                                if (a.last && a.v_avg) a.v_avg[o] = t / a.n_avg;
+                            }
+                        });
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] += se[e];
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -562,9 +823,10 @@ __global__ __launch_bounds__(64) void pt_gnorm_kernel(const float* vbias, const 
 
 hipError_t launch_pt_visible(const PtStepArgs& a, hipStream_t s)
 {
-    if (a.M < 1 || a.R < 2 || a.t < 0) return hipErrorInvalidValue;
+    if (a.M < 1 || a.R < 2 || a.t < 0 || !pt_groups_ok(a.groups, a.V, a.gauss)) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)(((int64_t)a.M * a.R + 3) / 4);
-    if (a.gauss) hipLaunchKernelGGL((pt_visible_kernel<true>), dim3(blocks), dim3(PT_NT), 0, s, a);
+    if (a.groups.on) hipLaunchKernelGGL(pt_visible_grouped_kernel, dim3(blocks), dim3(PT_NT), 0, s, a);
+    else if (a.gauss) hipLaunchKernelGGL((pt_visible_kernel<true>), dim3(blocks), dim3(PT_NT), 0, s, a);
     else hipLaunchKernelGGL((pt_visible_kernel<false>), dim3(blocks), dim3(PT_NT), 0, s, a);
     return hipGetLastError();
 }

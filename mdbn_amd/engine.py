@@ -740,6 +740,23 @@ class HipEngine(object):
         mdbn_pt_run_z: the works of the swap attempts accumulated as {m_f, s_f, m_r, s_r} per ladder and pair (start it at
         m = -inf, s = 0) and, appended to the returned tuple, ``trace_work [n, M, R - 1, 2]`` (float64: (d_fwd, d_rev), NaN
         where the pair was not tried).  Every other output is bit-identical with and without them."""
+        return self._temper(W, hbias, vbias, base_vbias, gauss, betas, v, h, rank, n_sweeps, rng, burn_in, sweep0, path,
+                            steps_per_launch, trace, zacc, trace_work)
+
+    def temper_grouped(self, W, hbias, vbias, base_vbias, betas, v, h, rank, n_sweeps, rng, groups, burn_in=0, sweep0=0, path=0,
+                       steps_per_launch=0, trace=False, zacc=None, trace_work=False):
+        """``temper`` for a Bernoulli layer whose visibles hold the softmax groups ``groups`` (a ``GroupTable``), in ONE library
+        call (mdbn_pt_run_grouped): a group's visible draw is one category of its softmax over the tempered pre-activations at
+        the beta of the row's rank, from one uniform at the group's first column, and the beta = 1 visible mean in ``v_avg``
+        is the group's softmax mean; the swaps, the works, the hidden draw, the returns and the 3 * n_sweeps RNG steps are
+        ``temper``'s.  The works belong with the grouped base model (``base_log_partition(..., groups=)``)."""
+        return self._temper(W, hbias, vbias, base_vbias, False, betas, v, h, rank, n_sweeps, rng, burn_in, sweep0, path,
+                            steps_per_launch, trace, zacc, trace_work, groups=groups)
+
+    def _temper(self, W, hbias, vbias, base_vbias, gauss, betas, v, h, rank, n_sweeps, rng, burn_in, sweep0, path,
+                steps_per_launch, trace, zacc, trace_work, groups=None):
+        """What ``temper`` and ``temper_grouped`` (``groups``: through mdbn_pt_run_grouped, on the workspace of
+        mdbn_pt_run_z) share."""
         V, H = W.shape
         M, R = (int(x) for x in rank.shape)
         ldh, ldv = W.stride(0), padded_ld(V)
@@ -761,14 +778,17 @@ class HipEngine(object):
         if zacc is not None and (zacc.dtype != torch.float64 or tuple(zacc.shape) != (M, R - 1, 4) or not zacc.is_contiguous()):
             raise ValueError("zacc must be a contiguous float64 tensor [%d, %d, 4]" % (M, R - 1))
         trace_w = torch.zeros((n_t, M, R - 1, 2), dtype=torch.float64, device=self.device) if trace_work else None
-        sizer = "mdbn_pt_run_z_workspace_bytes" if works else "mdbn_pt_workspace_bytes"
+        sizer = "mdbn_pt_run_z_workspace_bytes" if works or groups is not None else "mdbn_pt_workspace_bytes"
         ws = self._sampler_workspace(getattr(self.lib, sizer), sizer, (M, R, V), H, ldh, path, cache_attr="_pt_ws")
         r = rng.c()
         args = (self.ctx, self._stream(), self._p(W), V, H, ldh, self._p(hbias), self._p(vbias), self._p(base_vbias),
                 int(bool(gauss)), betas.ctypes.data_as(C.c_void_p), R, M, ldv, self._p(v), self._p(h), self._p(rank), n_sweeps,
                 burn_in, int(sweep0), self._p(accepted), self._p(v_avg), self._p(h_avg), self._p(trace_v), self._p(trace_h),
                 self._p(trace_s), int(path), int(steps_per_launch), C.byref(r), self._p(ws), ws.numel() * 4)
-        if works:
+        if groups is not None:
+            table = (self._p(groups.tensor), C.c_void_p(groups.host.ctypes.data), groups.n_groups)
+            _lib.check(self.lib.mdbn_pt_run_grouped(*(args + (self._p(zacc), self._p(trace_w)) + table)), "mdbn_pt_run_grouped")
+        elif works:
             _lib.check(self.lib.mdbn_pt_run_z(*(args + (self._p(zacc), self._p(trace_w)))), "mdbn_pt_run_z")
         else:
             _lib.check(self.lib.mdbn_pt_run(*args), "mdbn_pt_run")

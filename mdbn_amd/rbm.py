@@ -899,9 +899,10 @@ class RBM(object):
         chains mix badly AIS under-estimates log Z without its error showing it; ``check_log_partition`` runs both.
 
         A layer with ``visible_groups``: the same run with a group's visible draw one category of its softmax
-        (``HipEngine.ais_grouped``) and the base model's log Z_A with a logsumexp per group; ``method="tempering"`` is refused."""
-        if self.visible_groups is not None and (method == "tempering" or not hasattr(self.engine, "ais_grouped")):
-            self._no_groups("log_partition(method=\"tempering\")" if method == "tempering" else "log_partition on this engine")
+        (``HipEngine.ais_grouped``) and the base model's log Z_A with a logsumexp per group; ``method="tempering"`` runs the
+        grouped ladder (``HipEngine.temper_grouped``) from the same base model."""
+        if self.visible_groups is not None and not hasattr(self.engine, "temper_grouped" if method == "tempering" else "ais_grouped"):
+            self._no_groups("log_partition(method=\"tempering\") on this engine" if method == "tempering" else "log_partition on this engine")
         if method == "tempering":
             self._no_sigma("log_partition(method=\"tempering\")")       # (AIS needs no change: log Z is the unit model's)
             r = self.tempered_chains(n_ladders, betas=betas, n_betas=16 if n_betas is None else n_betas, base_vbias=base_vbias,
@@ -929,7 +930,8 @@ class RBM(object):
         |ais - tempering| / sqrt(se_ais^2 + se_tempering^2) and ``detail`` (the ``LogZ`` of the tempering run).  Asserts
         nothing: a large ``z``, or an AIS value below the bracket, says the AIS chains missed a mode (INTEGRATION)."""
         self._no_sigma("check_log_partition")
-        self._no_groups("check_log_partition")
+        if self.visible_groups is not None and not (hasattr(self.engine, "ais_grouped") and hasattr(self.engine, "temper_grouped")):
+            self._no_groups("check_log_partition on this engine")
         if base_vbias is None:
             base_vbias = self.base_rate_vbias(data) if data is not None else self.vbias.get_value()
         ais, se_a = self.log_partition(n_chains=n_chains, n_betas=n_betas, base_vbias=base_vbias, path=path)
@@ -946,9 +948,9 @@ class RBM(object):
         carries the sum(s) term of the change of variables and log_Z is the unit model's: nats per raw row.  With
         ``visible_groups`` every group of every row of ``data`` must hold exactly one 1 (checked on the host: ValueError)."""
         if self.visible_groups is not None:
-            if ais.get("method", "ais") == "tempering" or not hasattr(self.engine, "ais_grouped"):
-                self._no_groups("log_likelihood(method=\"tempering\")" if ais.get("method", "ais") == "tempering"
-                                else "log_likelihood on this engine")
+            tempering = ais.get("method", "ais") == "tempering"
+            if not hasattr(self.engine, "temper_grouped" if tempering else "ais_grouped"):
+                self._no_groups("log_likelihood(method=\"tempering\") on this engine" if tempering else "log_likelihood on this engine")
             self._check_one_hot(data)
         if ais.get("method", "ais") == "tempering":
             self._no_sigma("log_likelihood(method=\"tempering\")")
@@ -1289,8 +1291,13 @@ class RBM(object):
         visible bias) -- with swaps between neighbouring temperatures, so that the beta = 1 replica crosses between modes a
         plain chain never leaves.  ``start_h``: [n_ladders, H] (every temperature of a ladder starts there) or
         [n_ladders * R, H]; None: zeros.  A GRBM ladder runs the Gibbs sampler of its model (hidden sample down, unit noise),
-        not the reference's mean-field chain.  Each sweep consumes 3 RNG steps."""
-        self._no_groups("tempered_chains")
+        not the reference's mean-field chain.  Each sweep consumes 3 RNG steps.
+
+        A layer with ``visible_groups`` (on an engine with ``temper_grouped``; refused elsewhere): a group's visible draw is one
+        category of its softmax at the row's temperature, ``v_avg`` holds the softmax means, and the ladder's log Z starts
+        from the grouped base model (a logsumexp per group)."""
+        if self.visible_groups is not None and not hasattr(self.engine, "temper_grouped"):
+            self._no_groups("tempered_chains on this engine")
         self._no_sigma("tempered_chains")
         from .temper import TemperedChains
         if betas is None:
@@ -1438,13 +1445,15 @@ class RBM(object):
         ``tempering=R`` (with ``persistent``): PCD whose negative chains are the beta = 1 replicas of ``batch_size``
         parallel-tempering ladders of R temperatures (Desjardins et al. 2010) -- every step is ``chains.run(1)``,
         ``chains.to_persistent``, the unchanged PCD step, ``chains.from_persistent``; the ladders stay in ``self.tempered``.
-        None: nothing changes.  ``centered`` / ``offset_rate``: the centred gradient, ``sparsity_*``: the sparsity target
+        None: nothing changes.  On a layer with ``visible_groups`` the ladders are the grouped ones (``tempered_chains``) and
+        the step the grouped PCD step.  ``centered`` / ``offset_rate``: the centred gradient, ``sparsity_*``: the sparsity target
         (``get_cost_updates``).  ``visible_groups`` (not None): ``set_visible_groups`` first -- the layer trains with
         categorical visible units."""
         if visible_groups is not None:
             self.set_visible_groups(visible_groups)
         if tempering is not None:
-            self._no_groups("training(tempering=)")
+            if self.visible_groups is not None and not hasattr(self.engine, "temper_grouped"):
+                self._no_groups("training(tempering=) on this engine")
             self._no_sigma("training(tempering=)")
         if persistent:
             persistent_chain = shared(numpy.zeros((batch_size, self.n_hidden), dtype=numpy.float32),

@@ -2,7 +2,9 @@
 the inverse temperatures 0 <= beta_0 < ... < beta_{R-1} = 1 of the tempered family of the AIS estimate (base-rate visible
 bias b_A, b_beta = b_A + beta (b - b_A)) and advances them by sweeps with swaps between neighbouring temperatures
 (csrc/mdbn_temper.hip, include/mdbn_hip.h: mdbn_pt_run).  On an engine without ``temper`` (the CPU checker of the tests) the
-sweep is composed from the engine's eager calls: the same definitions, stated in Python.
+sweep is composed from the engine's eager calls: the same definitions, stated in Python.  A layer with ``visible_groups``
+(categorical visible units) runs through ``engine.temper_grouped`` (mdbn_pt_run_grouped: a group's visible draw is one category
+of its softmax at the row's temperature, ``v_avg`` holds softmax means) and is refused on an engine without it.
 
 ``TemperedChains.log_partition`` estimates log Z from the works of the swap attempts (mdbn_pt_run_z): the sweeps
 accumulate them on the device, ``estimate_log_z`` finishes in float64 numpy."""
@@ -197,7 +199,13 @@ class TemperedChains(object):
         step = rbm._rng_step
         rng = RngAddr(rbm.theano_rng.seed, rbm.stream_id, step, 0, 0)
         works = {} if zacc is None and not trace_work else dict(zacc=zacc, trace_work=trace_work)
-        if hasattr(eng, "temper"):
+        if rbm.visible_groups is not None:
+            if not hasattr(eng, "temper_grouped"):          # (the eager sweep below would draw a group as independent sigmoid units)
+                rbm._no_groups("tempering on this engine")
+            out = eng.temper_grouped(rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, self._base, self.betas, self.v, self.h,
+                                     self.rank, n, rng, rbm.visible_groups, burn_in=burn_in, sweep0=self.n_done, path=path,
+                                     steps_per_launch=steps_per_launch, trace=trace, **works)
+        elif hasattr(eng, "temper"):
             out = eng.temper(rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, self._base, rbm.gauss, self.betas, self.v,
                              self.h, self.rank, n, rng, burn_in=burn_in, sweep0=self.n_done, path=path,
                              steps_per_launch=steps_per_launch, trace=trace, **works)
@@ -241,7 +249,7 @@ class TemperedChains(object):
             raise ValueError("a neighbour pair has no swap attempt after burn-in: run at least two sweeps after it")
         all_tries = attempts(self.n_ladders, self.n_betas, self.n_done, n)
         zacc, accepted, works = self.accumulate_works(n, burn_in, path, steps_per_launch, trace_work=method == "bar")
-        log_z0 = base_log_partition(self.base_vbias, self.rbm.n_hidden, self.rbm.gauss)
+        log_z0 = base_log_partition(self.base_vbias, self.rbm.n_hidden, self.rbm.gauss, groups=self.rbm.visible_groups)
         r = estimate_log_z(zacc.cpu().numpy(), tries, log_z0, method, None if works is None else works[burn_in:])
         return r._replace(acceptance=accepted / all_tries.astype(numpy.float64))
 
