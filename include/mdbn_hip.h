@@ -250,6 +250,9 @@ int  mdbn_kernel_timing_read(mdbn_ctx *ctx, int64_t *n_launches, double *total_m
  * *n_launches receives the number recorded (may exceed cap). */
 int  mdbn_kernel_timing_detail(mdbn_ctx *ctx, int64_t cap, double *ms, double *alg_flop,
                                double *pipe_flop, int32_t *kind, int64_t *n_launches);
+/* Introspection (tests): launches of the narrow one-plane propdown (kind 2210) that this context has sent to the 64-deep
+ * form of its kernel since it was created. */
+int  mdbn_narrow_deep_launches(mdbn_ctx *ctx, int64_t *n_launches);
 
 /* bytes of split-K / reduction scratch the calls below need for shapes up to (B, V, H) */
 int  mdbn_workspace_bytes(int64_t B, int64_t V, int64_t H, int64_t *bytes);

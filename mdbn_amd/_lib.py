@@ -68,6 +68,7 @@ SIGNATURES = {
     "mdbn_bal_segment": [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)],
     "mdbn_kernel_timing": [_vp, _i32],
     "mdbn_kernel_timing_read": [_vp, C.POINTER(_i64), C.POINTER(C.c_double)],
+    "mdbn_narrow_deep_launches": [_vp, C.POINTER(_i64)],
     "mdbn_kernel_timing_detail": [_vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(_i64)],
     "mdbn_workspace_bytes": [_i64, _i64, _i64, C.POINTER(_i64)],

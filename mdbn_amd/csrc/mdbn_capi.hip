@@ -7,6 +7,7 @@
 #include <initializer_list>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <utility>
@@ -193,6 +194,10 @@ bool prefer_skinny(int64_t M, int64_t N, int64_t K)
 // 0 = every slab store behind the last MFMA.  Same bits either way.  1 also routes the fused-update statistics launch with the
 // early parameter half to gemm_planes_statstail_kernel (half of the new speed stored under the last stages' MFMAs).
 #define g_opt_slab_tail (t_opt->slab_tail)
+// (no option name; environment MDBN_NARROW_DEEP at mdbn_ctx_create, default 1): the narrow one-plane propdown runs on 64-deep
+// stages wherever narrow_deep_ok holds (mdbn_planes.hip).  Same bits either way; the variable exists for the tests that
+// compare the two forms in one process.
+#define g_opt_narrow_deep (t_opt->narrow_deep)
 // mdbn_set_option("feed_copy_streams"): a row feeder created afterwards moves each minibatch as 1 or 2 copies on as many
 // streams (two SDMA engines side by side)
 #define g_opt_feed_copy_streams (t_opt->feed_copy_streams)
@@ -527,6 +532,9 @@ int run_affine_planes(mdbn_ctx* ctx, int comm_cus, const unsigned short* A, int6
         !g_opt_bf16_inputs && (ap == 1 || ap == 3) && (int64_t)g.tiles_m * (Ndim / 64) <= 2 * ctx->num_cu &&
         (!e.target || (e.ld_target % 4 == 0 && ((uintptr_t)e.target & 15) == 0))) {      // its epilogue reads targets as float4
         g.bn = 64; g.tiles_n = (int)(Ndim / 64); g.splitk = 1; g.kchunk = (int)Kdim;
+        g.fused = 1; g.ms = 16;                  // (what the fused branch below and timed_gemm_planes set: narrow_deep_ok reads them)
+        g.deep = g_opt_narrow_deep && narrow_deep_ok(g, LAY_K, LAY_K);
+        if (g.deep) ++ctx->narrow_deep_launches;
     }
     const bool fuse = !bal && g_opt_fused_epilogue && g.splitk == 1;
     const int nb = fuse ? g.tiles_m * g.tiles_n : epilogue_blocks(rows, e.ld);
@@ -982,6 +990,7 @@ int mdbn_ctx_create(mdbn_ctx** out, int device)
     mdbn_ctx* c = new mdbn_ctx;
     c->device = device;
     c->num_cu = prop.multiProcessorCount;
+    if (const char* e = getenv("MDBN_NARROW_DEEP")) c->opt.narrow_deep = atoi(e) != 0;
     *out = c;
     return MDBN_OK;
 }
@@ -1193,6 +1202,13 @@ int mdbn_kernel_timing(mdbn_ctx* ctx, int enable)
     REQUIRE(ctx != nullptr, "ctx is NULL");
     g_timing.enabled = enable != 0;
     g_timing.used = 0;
+    return MDBN_OK;
+}
+
+int mdbn_narrow_deep_launches(mdbn_ctx* ctx, int64_t* n_launches)
+{
+    REQUIRE(ctx && n_launches, "NULL argument");
+    *n_launches = ctx->narrow_deep_launches;
     return MDBN_OK;
 }
 

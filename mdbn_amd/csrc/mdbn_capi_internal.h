@@ -41,6 +41,7 @@ struct Options {
     int early_w = 1;
     int narrow_tiles = 1;
     int slab_tail = 1;
+    int narrow_deep = 1;       // no option name: read once from the process environment when the context is created (mdbn_ctx_create)
     int feed_copy_streams = 1;
     int gather_ahead = 1;
     int bf16_inputs = 0;
@@ -74,6 +75,7 @@ struct mdbn_ctx {
     mdbn::capi::Options opt;
     mdbn::capi::GemmTiming timing;                  // mdbn_kernel_timing: per context
     // mdbn_cd_forward -> mdbn_cd_statistics hand-over (host side only): the cost partials the chain's last visible pass left
+    int64_t narrow_deep_launches = 0;              // narrow propdown launches that took 64-deep stages (mdbn_narrow_deep_launches)
     int pending_n_cost = -1;
     const void* pending_stats = nullptr;
     void* comm = nullptr;      // ncclComm_t of mdbn_comm_init_rank (RCCL), or NULL

@@ -155,6 +155,7 @@ struct PlaneGemmArgs {
     int fin_enabled;
     int stats_tail;        // fused-update statistics launch (fused == 2, upd.early == 1, ms == 16): 1 = the new speed is stored
                            // half a tile at a time under the last stages' MFMAs (mdbn_planes.hip); sits in what was padding
+    int deep;              // narrow one-plane forward launch (bn == 64, ap == 1): 1 = 64-deep stages (narrow_deep_ok)
     FinArgs fin;
     GatherAhead ga;
     DeferredBias db;
@@ -182,6 +183,7 @@ __host__ __device__ inline int bal_tile_slabs(int t, int tiles, int S, int P)
 hipError_t launch_gemm_planes(int la, int lb, const PlaneGemmArgs& g, hipStream_t s);
 bool slab_tail_ok(const PlaneGemmArgs& g, int la, int lb);     // may this launch set g.slab_tail?
 bool stats_tail_ok(const PlaneGemmArgs& g, int la, int lb);    // may this launch set g.stats_tail?
+bool narrow_deep_ok(const PlaneGemmArgs& g, int la, int lb);   // may this launch set g.deep?
 hipError_t launch_gemm_planes_bal(int la, int lb, const PlaneGemmArgs& g, hipStream_t s);
 int bal_max_segments(int tiles, int stages, int P);     // slabs a balanced fused == 0 launch needs
 int bal_segment_host(int tiles, int S, int P, int w, int k, int* tile, int* s0, int* s1, int* nseg, int* nt);

@@ -25,11 +25,16 @@
 // and two stages are always in flight.  Measured (scripts/experiments/planes_gemm.py): ~1900 cycles per
 // stage against 1536 of MFMA issue; the chip holds only 1.3-1.6 GHz under this load, which is what bounds
 // the wall time.
+// The narrow (128 x 64) forward kernel with one plane of A also exists on 64-deep stages (KD = 64: pl_loader's KD branch,
+// pl_consume16_deep, launch_gemm_planes' g.deep; LDS image: mdbn_planes_image.h): 128-byte rows, eight whole lines per
+// LDS-DMA instruction, a stage = two k-halves of 24 MFMAs, one barrier per 48 MFMAs; same bits.  Measured: docs/LABNOTES.md
+// "Narrow tiles on 64-deep stages".
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
 #include "mdbn_kernels.h"
 #include "mdbn_device.h"
+#include "mdbn_planes_image.h"
 
 namespace mdbn {
 
@@ -118,7 +123,9 @@ __device__ __forceinline__ void deferred_bias_update(const DeferredBias& d, int 
     if (blockIdx.x == 0 && wave == 0 && lane == 0 && d.cost_out) d.cost_out[0] = d.cost_sum[0] * d.cost_scale;
 }
 
-template <int LA, int LB, int AP, int MS, bool EARLYW = false, int BN = 128>
+// KD = 32 | 64: reduction depth of a stage.  KD = 64 (narrow one-plane forward kernel only) stages 128-byte rows, eight per
+// instruction, into the image of mdbn_planes_image.h: 16 instructions for A, 3 x 8 for W, 40 KB of the 48-KB slot.
+template <int LA, int LB, int AP, int MS, bool EARLYW = false, int BN = 128, int KD = 32>
 __device__ __forceinline__ void pl_loader(const PlaneGemmArgs& g, char* smem, int w, int lane, int m0, int n0, int kbeg, int nt,
                                           EarlySpeed* es = nullptr)
 {
@@ -127,7 +134,9 @@ __device__ __forceinline__ void pl_loader(const PlaneGemmArgs& g, char* smem, in
     // AP = planes of A (3 | 1); AP = 0 is the bf16-input REPORTING mode: one plane of each operand, one product
     constexpr int NA = AP == 3 ? 3 : 1, NB = AP == 0 ? 1 : 3;
     constexpr int QB = BN / 16;                      // 1-KiB instructions per B plane
-    constexpr int NQ = 8 * NA + QB * NB, PER = NQ / PL_LW;
+    static_assert(KD == 32 || (KD == 64 && AP == 1 && BN == 64 && LA == LAY_K && LB == LAY_K && MS == 16 && !EARLYW),
+                  "64-deep stages: the narrow one-plane ROW x ROW kernel");
+    constexpr int NQ = KD == 64 ? deep_image::NQ : 8 * NA + QB * NB, PER = NQ / PL_LW;
     static_assert(NQ % PL_LW == 0, "staging instructions must divide over the loader waves");
     const char* src[PER];
     unsigned dst[PER];
@@ -135,6 +144,15 @@ __device__ __forceinline__ void pl_loader(const PlaneGemmArgs& g, char* smem, in
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
         const int q = w + j * PL_LW;
+        if constexpr (KD == 64) {
+            const deep_image::Piece pc = deep_image::loader_piece(q, lane);
+            const unsigned short* base = pc.is_a ? g.A : g.B + pc.plane * g.pb;
+            dst[j] = deep_image::instr_base(q);
+            src[j] = reinterpret_cast<const char*>(base + (int64_t)((pc.is_a ? m0 : n0) + pc.row) * (pc.is_a ? g.lda : g.ldb) + kbeg +
+                                                   8 * pc.src_chunk);
+            step[j] = 2 * KD;
+            continue;
+        }
         const bool isA = q < 8 * NA;
         const int plane = isA ? q / 8 : (q - 8 * NA) / QB, sub = isA ? (q & 7) : (q - 8 * NA) % QB;
         const int lay = isA ? LA : LB;
@@ -641,6 +659,75 @@ __device__ __forceinline__ void pl_consume16(char* smem, int nt, int lane, int w
     if (bar_wait_out) *bar_wait_out = bar_wait;
 }
 
+// MFMA waves of the 64-deep stage (narrow one-plane forward kernel: a wave owns 4 x 2 tiles of 16 x 16, image of
+// mdbn_planes_image.h).  The 32-deep consumer above covers the two or three LDS reads of a quarter with 6 MFMAs and meets a
+// barrier every 24; here a stage is two k-halves of 24 MFMAs, each holding all 4 A + 6 B fragments of its half (2 x 40
+// fragment VGPRs): k-half 1's ten reads go out one by one under k-half 0's MFMAs and are pinned ahead of the stage barrier,
+// the next stage's k-half 0 is read under k-half 1's -- every read has 24 MFMAs of cover and the barrier comes once per 48.
+// Per accumulator the chain is the 32-deep kernel's: for each 32-deep block in increasing k, b3 then b2 then b1.  Within a
+// k-half the MFMAs are issued plane-major (all eight tiles' b3, then b2, then b1), so no MFMA waits for its predecessor.
+template <int AP>
+__device__ __forceinline__ void pl_consume16_deep(char* smem, int nt, int lane, int wm, int wn, pf32x4a (&acc)[4][2],
+                                                  long long* bar_wait_out = nullptr)
+{
+    static_assert(AP == 1, "64-deep stages hold one plane of A (three would need 72 KB a slot)");
+    long long bar_wait = 0;
+    (void)bar_wait;
+    int offA[4][2], offB[2][2];
+#pragma unroll
+    for (int kh = 0; kh < 2; ++kh) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) offA[b][kh] = deep_image::plane_base(true, 0) + deep_image::frag_offset(wm + 16 * b, kh, lane);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) offB[b][kh] = deep_image::frag_offset(wn + 16 * b, kh, lane);
+    }
+    pbf16x8 A0[4], B0[3][2], A1[4], B1[3][2];
+#define DP_RD(FA, FB, BASE, KH)                                                               \
+    do {                                                                                      \
+        _Pragma("unroll") for (int b = 0; b < 4; ++b) FA[b] = *reinterpret_cast<const pbf16x8*>((BASE) + offA[b][KH]); \
+        _Pragma("unroll") for (int pl = 0; pl < 3; ++pl)                                      \
+            _Pragma("unroll") for (int b = 0; b < 2; ++b)                                     \
+                FB[pl][b] = *reinterpret_cast<const pbf16x8*>((BASE) + deep_image::plane_base(false, pl) + offB[b][KH]); \
+    } while (0)
+#define DP_MM(FA, FB)                                                                         \
+    _Pragma("unroll") for (int pl = 2; pl >= 0; --pl)                                         \
+        _Pragma("unroll") for (int a = 0; a < 4; ++a)                                         \
+            _Pragma("unroll") for (int b = 0; b < 2; ++b)                                     \
+                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[a], FB[pl][b], acc[a][b], 0, 0, 0);
+// issue order: the ten reads one by one under the first ten of the k-half's 24 MFMAs
+#define DP_ORD()                                                                              \
+    _Pragma("unroll") for (int i_ = 0; i_ < 10; ++i_) {                                       \
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                    \
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                    \
+    }                                                                                         \
+    __builtin_amdgcn_sched_group_barrier(0x008, 14, 0);
+// every read of a stage must have RETURNED before the barrier that frees its slot (see PIN above)
+#define DP_PIN(FA, FB)                                                                        \
+    do {                                                                                      \
+        _Pragma("unroll") for (int b = 0; b < 4; ++b) asm volatile("" :: "v"(FA[b]));         \
+        _Pragma("unroll") for (int pl = 0; pl < 3; ++pl)                                      \
+            _Pragma("unroll") for (int b = 0; b < 2; ++b) asm volatile("" :: "v"(FB[pl][b])); \
+    } while (0)
+    DP_RD(A0, B0, smem, 0);
+    // (the reload behind the last barrier reads a slot nobody writes any more; its values are never used)
+    for (int it = 0; it < nt; ++it) {
+        const char* base = smem + (it % PL_NSTAGE) * PL_STAGE;
+        const char* next = smem + ((it + 1) % PL_NSTAGE) * PL_STAGE;
+        DP_RD(A1, B1, base, 1); DP_MM(A0, B0); DP_ORD();
+        // (without this hipcc lifts the pins, and the wait for the last read with them, to the middle of the k-half: the
+        // read issued under MFMA 10 was waited for under MFMA 13)
+        __builtin_amdgcn_sched_barrier(0);
+        DP_PIN(A1, B1);
+        PL_MAIN_BARRIER();           // every read of this stage is done; the next has landed
+        DP_RD(A0, B0, next, 0); DP_MM(A1, B1); DP_ORD();
+    }
+#undef DP_RD
+#undef DP_MM
+#undef DP_ORD
+#undef DP_PIN
+    if (bar_wait_out) *bar_wait_out = bar_wait;
+}
+
 // FUSED: 0 = split-K slab / plain C store; 1 = activation + sampling epilogue on the parked tile (unsplit
 // forward pass); 2 = statistics GEMM: finalize units on the ramp-up, parameter update (+ W planes) on the
 // parked tile.  AP = planes of A (3, or 1 for 0/1 samples).
@@ -652,10 +739,11 @@ __device__ __forceinline__ void pl_consume16(char* smem, int nt, int lane, int w
 // commit 23f393d).  The chain store -> drain -> arrive -> poll -> load -> activate costs what the kernel boundary costs,
 // and the activation then runs on 512 threads per CU instead of 2048.  No kernel of this library waits for another
 // workgroup.)
-template <int LA, int LB, int AP, int FUSED, int MS, int BN = 128>
+template <int LA, int LB, int AP, int FUSED, int MS, int BN = 128, int KD = 32>
 __global__ __launch_bounds__(64 * (4 + PL_LW)) void gemm_planes_kernel(PlaneGemmArgs g)
 {
     static_assert(BN == 128 || (BN == 64 && MS == 16 && FUSED == 1 && LB == LAY_K), "64-column tiles: unsplit ROW-operand forward pass");
+    static_assert(KD == 32 || (KD == 64 && BN == 64 && AP == 1 && LA == LAY_K), "64-deep stages: narrow one-plane forward pass");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #if PL_ARGS_EARLY
     // the kernel arguments every wave needs before its first global access, requested in ONE batch at the top: hipcc loads
@@ -676,14 +764,14 @@ __global__ __launch_bounds__(64 * (4 + PL_LW)) void gemm_planes_kernel(PlaneGemm
     else { tm = t / g.tiles_n; tn = t - tm * g.tiles_n; }
     const int m0 = tm * 128, n0 = tn * BN;
     const int kbeg = ks * g.kchunk;
-    const int nt = g.kchunk / 32;
+    const int nt = g.kchunk / KD;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
 
     EarlySpeed es;
     (void)es;
     if (wave >= 4) {
-        pl_loader<LA, LB, AP, MS, (FUSED == 2 || (FUSED == 0 && LA == LAY_MN && LB == LAY_MN && AP == 3)) && MS == 16, BN>(
+        pl_loader<LA, LB, AP, MS, (FUSED == 2 || (FUSED == 0 && LA == LAY_MN && LB == LAY_MN && AP == 3)) && MS == 16, BN, KD>(
             g, smem, wave - 4, lane, m0, n0, kbeg, nt, &es);
         if constexpr (FUSED == 0) return;
     } else {
@@ -724,9 +812,11 @@ __global__ __launch_bounds__(64 * (4 + PL_LW)) void gemm_planes_kernel(PlaneGemm
 #endif
 #ifdef MDBN_STAMP
             long long bw = 0;
-            pl_consume16<LA, LB, AP, NBH>(smem, nt, lane, wm, wn, acc, false, &bw);
+            if constexpr (KD == 64) pl_consume16_deep<AP>(smem, nt, lane, wm, wn, acc, &bw);
+            else pl_consume16<LA, LB, AP, NBH>(smem, nt, lane, wm, wn, acc, false, &bw);
 #else
-            pl_consume16<LA, LB, AP, NBH>(smem, nt, lane, wm, wn, acc, false);
+            if constexpr (KD == 64) pl_consume16_deep<AP>(smem, nt, lane, wm, wn, acc);
+            else pl_consume16<LA, LB, AP, NBH>(smem, nt, lane, wm, wn, acc, false);
 #endif
             PL_MSTAMP(10);
 #ifdef MDBN_STAMP
@@ -944,10 +1034,10 @@ __global__ __launch_bounds__(64 * (4 + PL_LW)) void gemm_planes_kernel(PlaneGemm
     }
 }
 
-template <int LA, int LB, int AP, int FUSED, int MS, int BN = 128>
+template <int LA, int LB, int AP, int FUSED, int MS, int BN = 128, int KD = 32>
 static hipError_t launch_planes_m(const PlaneGemmArgs& g, hipStream_t s)
 {
-    auto kern = gemm_planes_kernel<LA, LB, AP, FUSED, MS, BN>;
+    auto kern = gemm_planes_kernel<LA, LB, AP, FUSED, MS, BN, KD>;
     static bool attr_set = false;
     constexpr int lds = PL_NSTAGE * PL_STAGE;        // 144 KB (the parked tile of the epilogues, 70 KB, reuses it)
     if (!attr_set) {
@@ -1322,12 +1412,32 @@ bool slab_tail_ok(const PlaneGemmArgs& g, int la, int lb)
            (int64_t)g.M * g.ldc * 4 < ((int64_t)1 << 31);
 }
 
+// PL_NARROW_DEEP = 1 (default): the narrow one-plane forward launch may run on 64-deep stages (g.deep, set by the caller
+// where narrow_deep_ok holds).  0 compiles the launch site out for A/B builds: every narrow launch then takes 32-deep stages.
+#ifndef PL_NARROW_DEEP
+#define PL_NARROW_DEEP 1
+#endif
+// may this narrow (bn == 64) launch set g.deep?  One plane of A; K a multiple of 128 (what the plane path's layers have
+// anyway) and at least 256, i.e. four or more deep stages: the ring wraps at least once; and every row piece of a stage a whole
+// 128-byte line: both leading dimensions and the W plane stride multiples of 64 elements
+bool narrow_deep_ok(const PlaneGemmArgs& g, int la, int lb)
+{
+    return PL_NARROW_DEEP && g.bn == 64 && la == LAY_K && lb == LAY_K && g.ap == 1 && g.fused == 1 && g.ms == 16 && !g.bal &&
+           g.splitk == 1 && g.kchunk == g.K && g.K % 128 == 0 && g.K >= 256 && g.lda % 64 == 0 && g.ldb % 64 == 0 && g.pb % 64 == 0;
+}
+
 hipError_t launch_gemm_planes(int la, int lb, const PlaneGemmArgs& g, hipStream_t s)
 {
     if (g.bn == 64) {       // unsplit forward pass on 128 x 64 tiles with the fused activation epilogue (propdown)
         if (g.M % 128 || g.N % 64 || g.K % 32 || g.kchunk != g.K || g.splitk != 1 || g.tiles_m != g.M / 128 || g.tiles_n != g.N / 64 ||
             (g.lda & 7) || (g.ldb & 7) || g.fused != 1 || la != LAY_K || lb != LAY_K || g.ms != 16 || (g.ap != 1 && g.ap != 3))
             return hipErrorInvalidValue;
+        if (g.deep) {       // 64-deep stages (the caller checked narrow_deep_ok)
+            if (!narrow_deep_ok(g, la, lb)) return hipErrorInvalidValue;
+#if PL_NARROW_DEEP
+            return launch_planes_m<LAY_K, LAY_K, 1, 1, 16, 64, 64>(g, s);
+#endif
+        }
         return g.ap == 1 ? launch_planes_m<LAY_K, LAY_K, 1, 1, 16, 64>(g, s) : launch_planes_m<LAY_K, LAY_K, 3, 1, 16, 64>(g, s);
     }
     if (g.M % 128 || g.N % 128 || g.kchunk % 32 || g.kchunk * g.splitk != g.K || g.tiles_m != g.M / 128 ||

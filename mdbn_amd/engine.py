@@ -1391,6 +1391,12 @@ class HipEngine(object):
                    "mdbn_kernel_timing_read")
         return n.value, ms.value
 
+    def narrow_deep_launches(self):
+        """Narrow one-plane propdown launches of this engine that took the 64-deep form of their kernel (tests)."""
+        n = C.c_int64()
+        _lib.check(self.lib.mdbn_narrow_deep_launches(self.ctx, C.byref(n)), "mdbn_narrow_deep_launches")
+        return n.value
+
     def kernel_timing_detail(self, cap=8192):
         """Per recorded GEMM launch: (ms, algorithmic FLOPs, FLOPs issued on its matrix pipe, kind)."""
         ms, alg, pipe = (C.c_double * cap)(), (C.c_double * cap)(), (C.c_double * cap)()
