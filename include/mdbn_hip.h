@@ -910,6 +910,28 @@ int  mdbn_ais_cond_run_grouped(mdbn_ctx *ctx, void *stream, const float *W, int6
                                int path, const mdbn_rng *rng, void *workspace, int64_t workspace_bytes,
                                const int32_t *group_start, const int32_t *group_start_host, int64_t n_groups);
 
+/* mdbn_propdown_rowll_grouped: mdbn_propdown_rowll (no `gauss`) for a Bernoulli layer whose visibles hold softmax groups --
+ * the directed term of the input layer in the variational bound of a stack on categorical data: its arguments without
+ * `gauss`, then the table under the convention above.  With pre_c = h[r] . W[c, :] + vbias_c and t = target[r / target_div],
+ *   out[r] = sum over groups g of ( sum_{c in g} t_c pre_c - m_g - log sum_{c in g} exp(pre_c - m_g) ),  m_g = max_{c in g} pre_c,
+ *          + sum over the columns outside the span of ( t_i pre_i - softplus(pre_i) )
+ * -- log softmax per group at the target's 1, finite at |pre| in the hundreds.  The group term is linear in t: the kernel
+ * never looks for the 1, and on a target row that is not one-hot in a group (precondition; the Python layer checks it) the
+ * value is that expression, not a log-probability.  The pre-activations exist in accumulators and, a 64 x 128 half tile at a
+ * time, in LDS only: main loop, tiling and products are mdbn_propdown_rowll's.  A group that crosses the edge of a
+ * 128-column tile (at most one edge: a group has at most MDBN_GROUP_MAX = 64 columns) leaves (max, sum of exp) of its two
+ * parts in the workspace and the second small launch, which adds a row's tiles in ascending order, joins them as
+ * M + log(s_a exp(m_a - M) + s_b exp(m_b - M)).  No atomics: two runs agree bit for bit.  The padding of h and W beyond H and
+ * of target beyond V is never used.  workspace: >= mdbn_rowll_grouped_workspace_bytes(R, V, H) (five floats per row and
+ * column tile).  MDBN_EINVAL with a message, before any launch and with out untouched: n_groups < 1 (a layer without groups
+ * has mdbn_propdown_rowll), an invalid table (not ascending, a group of fewer than 2 or more than MDBN_GROUP_MAX columns, a
+ * boundary beyond V, a missing copy), V > 2^24, a short workspace, and whatever mdbn_propdown_rowll refuses. */
+int  mdbn_rowll_grouped_workspace_bytes(mdbn_ctx *ctx, int64_t R, int64_t V, int64_t H, int64_t *bytes);
+int  mdbn_propdown_rowll_grouped(mdbn_ctx *ctx, void *stream, const float *h, int64_t R, int64_t ldh, const float *W,
+                                 int64_t V, int64_t H, const float *vbias, const float *target, int64_t ldv,
+                                 int64_t target_div, float *out, void *workspace, int64_t workspace_bytes,
+                                 const int32_t *group_start, const int32_t *group_start_host, int64_t n_groups);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)) (the float32 softplus terms summed in

@@ -135,6 +135,9 @@ SIGNATURES = {
                             _vp, _vp, _i64],
     "mdbn_rowll_workspace_bytes": [_vp, _i64, _i64, _i64, C.POINTER(_i64)],
     "mdbn_propdown_rowll": [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64],
+    "mdbn_rowll_grouped_workspace_bytes": [_vp, _i64, _i64, _i64, C.POINTER(_i64)],
+    "mdbn_propdown_rowll_grouped": [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64,
+                                    _vp, _vp, _i64],
     "mdbn_sample_replicas": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _rngp],
     "mdbn_center_workspace_bytes": [_vp, _i64, _i64, C.POINTER(_i64)],
     "mdbn_center_offsets": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp],

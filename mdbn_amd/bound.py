@@ -7,8 +7,10 @@ With the recognition model q(x_l | x_{l-1}) = Bernoulli(sigmoid(x_{l-1} W_l + b_
     B(x_0) = E_q[ sum_{l < L} ( log p(x_{l-1} | x_l) + H[q(. | x_{l-1})] ) - F_L(x_{L-1}) ] - log Z_L   <=   log p(x_0)
 
 The expectation is a mean over ``n_samples`` sampled configurations per data row (replica row n S + s belongs to data row n);
-the entropies are analytic.  The device forms every per-replica term (``HipEngine.sample_replicas``,
-``HipEngine.propdown_row_loglik``, ``free_energy``); sums over layers, means over replicas and everything after them are float64
+the entropies are analytic.  An input layer with ``visible_groups`` (K-ary softmax units) changes one term: its log p(x_0 | x_1)
+is a log-softmax per group (``HipEngine.propdown_row_loglik_grouped``); q, the entropies and the layers above are those of
+the Bernoulli layer, and a single such RBM takes log Z from its grouped AIS run.  The device forms every per-replica term
+(``HipEngine.sample_replicas``, ``HipEngine.propdown_row_loglik``, ``free_energy``); sums over layers, means over replicas and everything after them are float64
 numpy on the host, the rule of the AIS estimators."""
 import collections
 
@@ -47,11 +49,12 @@ def _host64(t):
     return t.detach().cpu().numpy().astype(numpy.float64)
 
 
-def _climb(net, x, n_sampled, div, row_offset, steps, keep):
+def _climb(net, x, n_sampled, div, row_offset, steps, keep, data_layer=True):
     """Sample ``x`` up through ``rbm_layers[:n_sampled]`` of ``net``: ``div`` replicas of every row at the first of them (1: the
     rows are replica rows already), one sample per replica row above.  Returns the top samples and the per-replica sum of
     log p(x_{l-1} | x_l) + H[q(. | x_{l-1})] over these layers (float64 numpy); ``keep`` (a dict of lists, or None) receives
-    the samples and terms."""
+    the samples and terms.  ``data_layer``: ``x`` is data, so a first layer with ``visible_groups`` scores it with a log-softmax
+    per group (``propdown_row_loglik_grouped``); the joint network's input is sampled units and keeps the sigmoid term."""
     eng = net.engine
     total = None
     for l in range(n_sampled):
@@ -59,7 +62,11 @@ def _climb(net, x, n_sampled, div, row_offset, steps, keep):
         mean = eng.propup(x, r.W.tensor, r.hbias.tensor, want_pre=False, want_sample=False)[1]
         sample, entropy = eng.sample_replicas(mean, div, RngAddr(r.theano_rng.seed, r.stream_id, steps[id(r)], 0, row_offset))
         # (the directed term is the generative model's: the generative weights of a layer untied by fine-tuning)
-        directed = _host64(eng.propdown_row_loglik(sample, r.down_W, r.vbias.tensor, x, r.gauss, target_div=div))
+        if l == 0 and data_layer and r.visible_groups is not None:
+            directed = eng.propdown_row_loglik_grouped(sample, r.down_W, r.vbias.tensor, x, r.visible_groups, target_div=div)
+        else:
+            directed = eng.propdown_row_loglik(sample, r.down_W, r.vbias.tensor, x, r.gauss, target_div=div)
+        directed = _host64(directed)
         entropy = _host64(entropy)
         term = directed + numpy.repeat(entropy, div)
         total = term if total is None else total + term
@@ -87,6 +94,9 @@ def stack_bound(bottoms, joint, n_samples=64, log_z=None, chunk_rows=16384, trac
     nets = [net for net, _ in bottoms]
     for net in nets:
         net.rbm_layers[0]._no_sigma("log_likelihood_bound")
+        # (a single RBM with groups has no directed term: its log_partition refuses where the engine lacks the grouped AIS)
+        if (joint is not None or net.n_layers > 1) and not hasattr(net.engine, "propdown_row_loglik_grouped"):
+            net.rbm_layers[0]._no_groups("log_likelihood_bound on this engine")
     datas =[shared(d, engine=net.engine) for net, d in bottoms]
     N = len(datas[0])
     if N < 1:
@@ -96,6 +106,11 @@ def stack_bound(bottoms, joint, n_samples=64, log_z=None, chunk_rows=16384, trac
     for net, d in zip(nets, datas):
         if d.shape[1] != net.n_ins:
             raise ValueError("data has %d columns, the network %d inputs" % (d.shape[1], net.n_ins))
+    for net, d in zip(nets, datas):
+        if net.rbm_layers[0].visible_groups is not None:
+            # categorical input units: the directed term is linear in the data row, which must be one-hot in every group
+            # (checked on the host copy; a HostTable through its host rows, without an upload)
+            net.rbm_layers[0]._check_one_hot(d)
     top_net = joint if joint is not None else nets[0]
     top = top_net.rbm_layers[-1]
     eng = top_net.engine
@@ -143,7 +158,7 @@ def stack_bound(bottoms, joint, n_samples=64, log_z=None, chunk_rows=16384, trac
             tops.append(x)
         if joint is not None:
             xj = eng.as_matrix(torch.cat(tops, dim=1))
-            xj, jterm = _climb(joint, xj, n_joint, 1, offset, steps, keeps[-1] if trace else None)
+            xj, jterm = _climb(joint, xj, n_joint, 1, offset, steps, keeps[-1] if trace else None, data_layer=False)
         else:
             xj, jterm = tops[0], None
         fe = _host64(eng.free_energy(xj, top.W.tensor, top.hbias.tensor, top.vbias.tensor, top.gauss))

@@ -26,6 +26,19 @@ struct RowllArgs {
     float* out;                              // [R]
 };
 
+// The same call for a layer whose visible columns [span_lo, span_hi) are softmax groups (table: include/mdbn_hip.h,
+// "Categorical visible units"): a group adds sum_c t_c pre_c - logsumexp_c pre_c, a column outside the span the Bernoulli term.
+// a.gauss = 0.  a.partial holds ROWLL_GP floats per (column tile, row): [tiles_n][ROWLL_GP][R] -- the tile's sum of everything
+// that is complete inside it, then (max, sum of exp(pre - max)) of the HEAD fragment (a group that began in the previous tile)
+// and of the TAIL fragment (a group that continues in the next one); a sum of 0 says "no such fragment".
+constexpr int ROWLL_GP = 5;
+struct RowllGroupArgs {
+    RowllArgs a;
+    const int32_t* group_start;              // device copy [n_groups + 1]; every value read is clamped to [span_lo, span_hi]
+    int n_groups;                            // >= 1
+    int span_lo, span_hi;                    // group_start_host[0], group_start_host[n_groups]: checked by the caller
+};
+
 struct ReplicaArgs {
     int64_t N, S, H, ldh;                    // data rows, replicas per row, live / stored columns
     const float* mean;                       // [N][ldh]
@@ -35,7 +48,9 @@ struct ReplicaArgs {
 };
 
 inline int64_t rowll_partial_floats(int64_t R, int64_t V) { return ((V + ROWLL_BN - 1) / ROWLL_BN) * R; }
+inline int64_t rowll_grouped_partial_floats(int64_t R, int64_t V) { return ROWLL_GP * rowll_partial_floats(R, V); }
 hipError_t launch_rowll(const RowllArgs& a, hipStream_t s);
+hipError_t launch_rowll_grouped(const RowllGroupArgs& g, hipStream_t s);
 hipError_t launch_sample_replicas(const ReplicaArgs& a, hipStream_t s);
 
 }  // namespace mdbn

@@ -732,6 +732,41 @@ int mdbn_propdown_rowll(mdbn_ctx* ctx, void* stream, const float* h, int64_t R, 
     return MDBN_OK;
 }
 
+int mdbn_rowll_grouped_workspace_bytes(mdbn_ctx* ctx, int64_t R, int64_t V, int64_t H, int64_t* bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(ctx && bytes && R > 0 && V > 0 && H > 0, "bad arguments");
+    *bytes = rowll_grouped_partial_floats(R, V) * (int64_t)sizeof(float);
+    return MDBN_OK;
+}
+
+int mdbn_propdown_rowll_grouped(mdbn_ctx* ctx, void* stream, const float* h, int64_t R, int64_t ldh, const float* W, int64_t V,
+                                int64_t H, const float* vbias, const float* target, int64_t ldv, int64_t target_div, float* out,
+                                void* workspace, int64_t workspace_bytes, const int32_t* group_start,
+                                const int32_t* group_start_host, int64_t n_groups)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(ctx && h && W && vbias && target && out && R > 0 && V > 0 && H > 0, "bad arguments");
+    REQUIRE(R <= (1 << 30) && V <= (1 << 24) && H <= (1 << 30), "shape too large");
+    REQUIRE(target_div >= 1 && target_div <= (1 << 30), "target_div must be >= 1");
+    REQUIRE(ldh >= H && ldv >= V && ldh % 4 == 0, "leading dimensions: ldh >= H, ldh %% 4 == 0, ldv >= V");
+    REQUIRE(aligned16(h) && aligned16(W), "h and W must be 16-byte aligned");
+    REQUIRE(n_groups >= 1, "n_groups = %lld: a layer without groups goes through mdbn_propdown_rowll", (long long)n_groups);
+    RowllGroupArgs g;
+    CHECK(check_groups(group_start, group_start_host, n_groups, V, g.span_lo, g.span_hi));
+    g.group_start = group_start; g.n_groups = (int)n_groups;
+    RowllArgs& a = g.a;
+    a.R = (int)R; a.V = (int)V; a.H = (int)H; a.gauss = 0; a.target_div = (int)target_div;
+    a.tiles_m = (int)((R + ROWLL_BM - 1) / ROWLL_BM); a.tiles_n = (int)((V + ROWLL_BN - 1) / ROWLL_BN);
+    REQUIRE((int64_t)a.tiles_m * a.tiles_n <= 0x7fffffff, "shape too large");
+    REQUIRE(workspace != nullptr && workspace_bytes >= rowll_grouped_partial_floats(R, V) * (int64_t)sizeof(float),
+            "workspace of mdbn_rowll_grouped_workspace_bytes needed");
+    a.ldh = ldh; a.ldv = ldv; a.h = h; a.W = W; a.vbias = vbias; a.target = target;
+    a.partial = reinterpret_cast<float*>(workspace); a.out = out;
+    HIP_OK(launch_rowll_grouped(g, (hipStream_t)stream));
+    return MDBN_OK;
+}
+
 int mdbn_sample_replicas(mdbn_ctx* ctx, void* stream, const float* mean, int64_t N, int64_t H, int64_t ldh, int64_t S,
                          float* sample, float* entropy, const mdbn_rng* rng)
 {

@@ -199,9 +199,10 @@ class DBN(object):
         pass through; base rate: the data seen through the layers below, as ``layer_log_likelihood`` -- unless ``log_z`` is
         given), ``rows`` / ``row_stderr`` [N] and, with ``trace``, what was sampled.  Data rows are walked in chunks of
         ``chunk_rows // n_samples`` (a host-resident table is streamed); the chunking changes no draw.  Every sampled layer
-        consumes ONE RNG step of its own RBM.  A one-layer network draws nothing and gives ``log_likelihood``."""
+        consumes ONE RNG step of its own RBM.  A one-layer network draws nothing and gives ``log_likelihood``.  With
+        ``visible_groups`` the input layer's directed term is a log-softmax per group and every group of every data row must
+        hold exactly one 1 (ValueError); an engine without ``propdown_row_loglik_grouped`` refuses (NotImplementedError)."""
         from .bound import stack_bound
-        self.rbm_layers[0]._no_groups("log_likelihood_bound")
         self.rbm_layers[0]._no_sigma("log_likelihood_bound")
         return stack_bound([(self, data)], None, n_samples=n_samples, log_z=log_z, chunk_rows=chunk_rows, trace=trace, **ais)
 

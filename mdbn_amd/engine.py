@@ -575,6 +575,22 @@ class HipEngine(object):
         visible conditional (sigmoid(h W^T + vbias); N(h W^T + vbias, I) with ``gauss``) as a float32 device vector [R]
         (mdbn_propdown_rowll: the propdown GEMM reduced against the target in its epilogue, no [R, V] matrix is written).
         ``target``: [ceil(R / target_div), V].  ``h`` must hold 0 / 1 only."""
+        return self._row_loglik(h, W, vbias, target, target_div, "mdbn_propdown_rowll", "mdbn_rowll_workspace_bytes", "_rowll_ws",
+                                kind=(int(bool(gauss)),))
+
+    def propdown_row_loglik_grouped(self, h, W, vbias, target, groups, target_div=1):
+        """``propdown_row_loglik`` for a Bernoulli layer whose visible columns hold softmax groups (``groups``: its
+        ``GroupTable``): every group adds the log-softmax of its pre-activations at the target's 1, every column outside the
+        span the sigmoid term (mdbn_propdown_rowll_grouped: the same fused GEMM, no [R, V] matrix is written).  Every group of
+        every row of ``target`` must hold exactly one 1 (not checked here)."""
+        return self._row_loglik(h, W, vbias, target, target_div, "mdbn_propdown_rowll_grouped", "mdbn_rowll_grouped_workspace_bytes",
+                                "_rowll_grouped_ws",
+                                table=(self._p(groups.tensor), C.c_void_p(groups.host.ctypes.data), groups.n_groups))
+
+    def _row_loglik(self, h, W, vbias, target, target_div, name, sizer, cache_attr, kind=(), table=()):
+        """What ``propdown_row_loglik`` and ``propdown_row_loglik_grouped`` share: the shape checks, the cached workspace (one
+        per call name) and the library call ``name`` (``kind``: its arguments before ``out``, ``table``: those after the
+        workspace)."""
         h, target = self.as_matrix(h), self.as_matrix(target)
         R, H = (int(x) for x in h.shape)
         V = int(W.shape[0])
@@ -589,13 +605,14 @@ class HipEngine(object):
         if R == 0:
             return out
         n = C.c_int64()
-        _lib.check(self.lib.mdbn_rowll_workspace_bytes(self.ctx, R, V, H, C.byref(n)), "mdbn_rowll_workspace_bytes")
-        ws = getattr(self, "_rowll_ws", None)
+        _lib.check(getattr(self.lib, sizer)(self.ctx, R, V, H, C.byref(n)), sizer)
+        ws = getattr(self, cache_attr, None)
         if ws is None or ws.numel() * 4 < n.value:
-            ws = self._rowll_ws = torch.empty(n.value // 4 + 64, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.mdbn_propdown_rowll(
+            ws = torch.empty(n.value // 4 + 64, dtype=torch.float32, device=self.device)
+            setattr(self, cache_attr, ws)
+        _lib.check(getattr(self.lib, name)(
             self.ctx, self._stream(), self._p(h), R, h.stride(0), self._p(W), V, H, self._p(vbias), self._p(target),
-            target.stride(0), target_div, int(bool(gauss)), self._p(out), self._p(ws), ws.numel() * 4), "mdbn_propdown_rowll")
+            target.stride(0), target_div, *kind, self._p(out), self._p(ws), ws.numel() * 4, *table), name)
         return out
 
     def sample_replicas(self, mean, n_samples, rng):
