@@ -808,6 +808,44 @@ int  mdbn_group_softmax_sample(mdbn_ctx *ctx, void *stream, const float *pre, in
 int  mdbn_cd_step_grouped(mdbn_ctx *ctx, void *stream, const mdbn_cd_args *a, const int32_t *group_start,
                           const int32_t *group_start_host, int64_t n_groups);
 
+/* mdbn_updown_gen_step_grouped: the generative delta rule of up-down fine-tuning (mdbn_updown_gen_step) for the input layer
+ * of a network with softmax groups: the arguments of mdbn_updown_gen_step without `gauss`, then the table under the
+ * convention above.  The one conditional that changes is
+ *   g = p(x_lo | x_hi) = softmax inside every group, sigmoid on the Bernoulli columns, of pre = x_hi G^T + vbias;
+ * S = (x_lo - g)^T x_hi and s_v = sum_r (x_lo - g) are the exact gradient of sum_r log p(x_lo | x_hi) for a softmax as for a
+ * sigmoid, and the rule, its divisors and `upd` are those of mdbn_updown_gen_step.  cost_out (nullable, device):
+ * upd->cost_scale * sum_r -log p(x_lo | x_hi) = per group m + log sum_c exp(pre_c - m) - sum_c x_c pre_c (m = max_c pre_c:
+ * finite where a probability underflows; every group of every row of x_lo must hold exactly one 1, not checked) plus the
+ * cross-entropy of the Bernoulli columns: the cost of mdbn_group_softmax_sample against v0 = x_lo, minus the sum of
+ * mdbn_propdown_rowll_grouped.
+ *
+ * path 2 (composed; any shape, and what path 0 takes outside the one-pass regime) is the composed path of the plain call with
+ * the grouped means in place of the sigmoid: mdbn_propdown_sample(gauss = 1) stores the linear pre-activations, the kernel of
+ * mdbn_group_softmax_sample turns them into means in place (v0 = x_lo, its cost partials, no sample), then the stacked
+ * operands, mdbn_cd_stats and mdbn_apply_update with a throw-away hidden half; the partials are added in ascending order in
+ * float64.  path 1 (one pass over G; n <= 32 rows, ldh <= 512, MDBN_EINVAL elsewhere) is the one-pass kernel of
+ * mdbn_updown_gen_step with its workgroups' row ranges moved onto group boundaries -- a group belongs to the workgroup whose
+ * nominal range holds its first row; a range grows by at most 63 rows and may be empty --: a row of G outside the span is
+ * finished at once by the plain kernel's arithmetic (its new row of G and of the speed equal those of
+ * mdbn_updown_gen_step(gauss = 0) on the same inputs bit for bit), a row inside the span leaves its pre-activations in LDS, one
+ * thread per (group, minibatch row) forms the softmax there by the arithmetic of mdbn_group_softmax_sample (the hardware
+ * exponential, Z in ascending c, correctly rounded means) and overwrites them with the errors, and a second walk over the span
+ * rows reads the row of G once more (from cache) and the row of the speed for the first time and applies the rule.  G and its
+ * speed are still written once, S is never stored, the pad columns H..ldh-1 are neither read nor written.  The kernel clamps
+ * the device table to the span the host copy gives.  upd->W_planes, where given, are rewritten on every path.  No atomics,
+ * every sum in a fixed order: two runs agree bit for bit.  No call synchronises.  Workspace:
+ * mdbn_updown_gen_grouped_workspace_bytes (16-byte aligned).
+ * MDBN_EINVAL with a message, before any launch and with every output untouched: n_groups < 1 (the plain call exists), an
+ * invalid table (not ascending, a group of fewer than 2 or more than MDBN_GROUP_MAX columns, a boundary beyond V, a missing
+ * copy), path = 1 on a shape the one-pass geometry does not serve, a short workspace, and whatever mdbn_updown_gen_step
+ * refuses. */
+int  mdbn_updown_gen_grouped_workspace_bytes(mdbn_ctx *ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh,
+                                             int path, int64_t *bytes);
+int  mdbn_updown_gen_step_grouped(mdbn_ctx *ctx, void *stream, const float *x_lo, const float *x_hi, int64_t n,
+                                  const mdbn_update_args *upd, float *cost_out, int path, void *workspace,
+                                  int64_t workspace_bytes, const int32_t *group_start, const int32_t *group_start_host,
+                                  int64_t n_groups);
+
 /* mdbn_ais_run_grouped: mdbn_ais_run (free, no clamp) for a Bernoulli layer whose visibles hold softmax groups: the
  * arguments of mdbn_ais_run, then the table under the convention above.  On one-hot rows
  *   log p*_beta(v) = sum_j softplus(beta a_j(v)) + v . b_beta

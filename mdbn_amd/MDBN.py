@@ -188,7 +188,10 @@ def fine_tune(nets, joint, inputs, epochs, batch_size=20, *, lr, k=1, momentum=0
     ``updown.py``): every layer of every modality DBN and the joint DBN's lower layers are directed and get generative weights
     of their own, the joint DBN's last RBM is the top.  The wake pass concatenates the sampled modality tops in the order of
     ``nets``, the sleep pass splits the dream back by the same column blocks.  ``inputs``: one data matrix per modality, a list
-    or a dict {modality index: matrix}.  The epoch order comes from ``joint.shuffle_rng``.  Returns the per-epoch record
+    or a dict {modality index: matrix}.  A modality network whose input layer has ``visible_groups`` dreams one category per group
+    and is trained against the grouped means (its data rows must be one-hot per group: ValueError); groups in the JOINT network's
+    own input layer and an engine without ``updown_gen_step_grouped`` are refused (NotImplementedError) before anything is drawn.
+    The epoch order comes from ``joint.shuffle_rng``.  Returns the per-epoch record
     ``[(sum over the modalities of the mean -log p(x_0 | x_1) per row, the top RBM's mean monitoring cost), ...]``."""
     from . import updown
     if isinstance(inputs, dict):

@@ -11,6 +11,8 @@
 #include "mdbn_kernels.h"
 
 namespace mdbn {
+struct UpdownGeom;                         // mdbn_updown.h
+
 namespace capi {
 
 // Tuning knobs of ONE context (mdbn_set_option(ctx, ...) writes ctx->opt; a knob set on one context never changes what
@@ -189,6 +191,19 @@ int run_affine(const Affine& a, const Workspace& ws, hipStream_t s, int* n_cost_
 void fill_upd(UpdEpi& e, const mdbn_update_args& u, int64_t V, int64_t ldh, unsigned short* Wp);
 // ... and its bias / monitoring-cost half (H: the live hidden width)
 void fill_bias_upd(BiasUpd& b, const mdbn_update_args& u, int64_t H);
+
+// The delta rules of up-down fine-tuning (mdbn_drv_train.hip), as far as the grouped generative rule (mdbn_drv_groups.hip)
+// shares them.  Workspace of a delta-rule step, in floats (every piece a multiple of 64 floats: 16-byte aligned):
+struct UpdownWs {
+    int64_t V2, P2, pre, mean, stats, junk, partials, inner;
+    int64_t total() const { return V2 + P2 + pre + mean + stats + junk + partials + inner; }
+};
+int updown_check_shape(const mdbn_ctx* ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int path);
+// the rule's own arguments (`gen`: the visible half is updated, else the hidden)
+int updown_check_update(const mdbn_update_args* u, bool gen);
+// the carve-up of the generative half: fused = the cost partials of ug.G workgroups only, else the composed path's pieces
+int updown_gen_ws(bool fused, const UpdownGeom& ug, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, UpdownWs& w);
+float* updown_take(float*& p, int64_t floats);
 
 }  // namespace capi
 }  // namespace mdbn

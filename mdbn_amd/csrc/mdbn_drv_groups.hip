@@ -1,11 +1,13 @@
 // C-ABI drivers of the categorical visible units (declared in include/mdbn_hip.h): the grouped softmax kernel alone
-// (mdbn_groups.hip) and the CD step of a layer with groups, composed from the propagation passes of the core, that kernel and
-// mdbn_cd_stats.  Of the core they use what mdbn_capi_internal.h declares.
+// (mdbn_groups.hip), the CD step of a layer with groups, composed from the propagation passes of the core, that kernel and
+// mdbn_cd_stats, and the generative delta rule of up-down fine-tuning on such a layer (mdbn_updown.hip: the one-pass kernel, or
+// the composed path of the plain rule with the grouped means).  Of the core they use what mdbn_capi_internal.h declares.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
 #include "mdbn_capi_internal.h"
 #include "mdbn_groups.h"
+#include "mdbn_updown.h"
 
 using namespace mdbn;
 using namespace mdbn::capi;
@@ -33,6 +35,23 @@ int mdbn::capi::check_groups(const int32_t* dev, const int32_t* host, int64_t n_
 namespace {
 
 int64_t group_partial_floats(int64_t B, int64_t V) { return ru64(group_softmax_blocks(B, V)); }    // (units <= V)
+
+// the generative delta rule of a layer with groups: the one-pass kernel's regime is that of the plain rule (updown_geom)
+bool updown_gen_grouped_fused_ok(const mdbn_ctx* ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, UpdownGeom& ug)
+{
+    return updown_geom_grouped(n, V, H, ldv, ldh, std::min(ctx->num_cu, kTargetJobs), ug);
+}
+
+// ... and its workspace that of the plain rule, the composed path's cost partials those of the grouped softmax launch
+int updown_gen_grouped_ws(bool fused, const UpdownGeom& ug, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, UpdownWs& w)
+{
+    CHECK(updown_gen_ws(fused, ug, n, V, H, ldv, ldh, w));
+    if (fused) return MDBN_OK;
+    REQUIRE(group_softmax_blocks(n, V) <= 0x7fffffff, "n = %lld rows of V = %lld units: too many for one grouped softmax launch",
+            (long long)n, (long long)V);
+    w.partials = std::max(w.partials, group_partial_floats(n, V));
+    return MDBN_OK;
+}
 
 }  // namespace
 
@@ -183,6 +202,91 @@ int mdbn_cd_step_grouped(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a, con
             HIP_OK(hipMemcpyAsync(a->trace_h + (int64_t)t * B * ldh, hdst, sizeof(float) * B * ldh, hipMemcpyDeviceToDevice, s));
     }
     return mdbn_cd_stats(ctx, stream, a->V2, a->P2, B, V, H, ldv, ldh, a->stats, a->workspace, a->workspace_bytes);
+}
+
+// ---------------------------------------------------------------------------------- up-down fine-tuning, a layer with groups
+int mdbn_updown_gen_grouped_workspace_bytes(mdbn_ctx* ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int path,
+                                            int64_t* bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(bytes != nullptr, "bytes is NULL");
+    CHECK(updown_check_shape(ctx, n, V, H, ldv, ldh, path));
+    UpdownGeom ug{};
+    const bool ok = updown_gen_grouped_fused_ok(ctx, n, V, H, ldv, ldh, ug);
+    REQUIRE(path != 1 || ok, "the one-pass generative kernel serves n <= %d rows on ldh <= %d", UD_MAXB, UD_MAX_LDH);
+    UpdownWs w;
+    CHECK(updown_gen_grouped_ws(path != 2 && ok, ug, n, V, H, ldv, ldh, w));
+    *bytes = w.total() * (int64_t)sizeof(float);
+    return MDBN_OK;
+}
+
+int mdbn_updown_gen_step_grouped(mdbn_ctx* ctx, void* stream, const float* x_lo, const float* x_hi, int64_t n,
+                                 const mdbn_update_args* upd, float* cost_out, int path, void* workspace, int64_t workspace_bytes,
+                                 const int32_t* group_start, const int32_t* group_start_host, int64_t n_groups)
+{
+    CtxScope ctx_scope(ctx);
+    CHECK(updown_check_update(upd, true));
+    const int64_t V = upd->V, H = upd->H, ldv = upd->ldv, ldh = upd->ldh;
+    CHECK(updown_check_shape(ctx, n, V, H, ldv, ldh, path));
+    CHECK(check_mat(x_lo, ldv, V, "x_lo"));
+    CHECK(check_mat(x_hi, ldh, H, "x_hi"));
+    REQUIRE(cost_out == nullptr || (reinterpret_cast<uintptr_t>(cost_out) & 3u) == 0, "cost_out not aligned");
+    REQUIRE(workspace != nullptr && aligned16(workspace), "workspace must be a 16-byte aligned device pointer");
+    REQUIRE(n_groups >= 1, "n_groups = %lld: a layer without groups takes mdbn_updown_gen_step", (long long)n_groups);
+    int lo, hi;
+    CHECK(check_groups(group_start, group_start_host, n_groups, V, lo, hi));
+    UpdownGeom ug{};
+    const bool ok = updown_gen_grouped_fused_ok(ctx, n, V, H, ldv, ldh, ug);
+    REQUIRE(path != 1 || ok, "the one-pass generative kernel serves n <= %d rows on ldh <= %d", UD_MAXB, UD_MAX_LDH);
+    const bool fused = path != 2 && ok;
+    UpdownWs w;
+    CHECK(updown_gen_grouped_ws(fused, ug, n, V, H, ldv, ldh, w));
+    REQUIRE(workspace_bytes >= w.total() * (int64_t)sizeof(float), "workspace of mdbn_updown_gen_grouped_workspace_bytes needed");
+    hipStream_t s = (hipStream_t)stream;
+    float* p = reinterpret_cast<float*>(workspace);
+    const float scale = upd->cost_scale;
+
+    if (fused) {
+        UpdownGenGroupedArgs q{};
+        UpdownGenArgs& a = q.g;
+        a.n = (int)n; a.Bq = ug.Bq; a.V = (int)V; a.H = (int)H; a.ldv = ldv; a.ldh = ldh; a.rpw = ug.rpw; a.G = ug.G;
+        a.x_lo = x_lo; a.x_hi = x_hi; a.gauss = 0;
+        fill_upd(a.upd, *upd, V, ldh, reinterpret_cast<unsigned short*>(upd->W_planes));
+        a.vb = upd->vbias; a.vbs = upd->vbias_speed; a.inv_rows = 1.0f / upd->n_rows;
+        a.cost_partials = p;
+        q.group_start = group_start; q.n_groups = (int)n_groups; q.span_lo = lo; q.span_hi = hi;
+        HIP_OK(launch_updown_gen_grouped(q, ug, s));
+        if (cost_out) HIP_OK(launch_updown_cost_finish(p, ug.G, scale, cost_out, s));
+        return MDBN_OK;
+    }
+
+    float* V2 = updown_take(p, w.V2); float* P2 = updown_take(p, w.P2);
+    updown_take(p, w.pre); float* mean = updown_take(p, w.mean);
+    float* stats = updown_take(p, w.stats); float* junk = updown_take(p, w.junk);
+    float* partials = updown_take(p, w.partials);
+    void* inner = p;
+    const int64_t inner_bytes = w.inner * (int64_t)sizeof(float);
+    // the linear pre-activations x_hi G^T + c with the pre-step parameters, then the grouped means in place
+    CHECK(mdbn_propdown_sample(ctx, stream, x_hi, n, ldh, upd->W, V, H, ldv, upd->vbias, 1, 0, nullptr, mean, nullptr, nullptr,
+                               nullptr, nullptr, inner, inner_bytes));
+    GroupSoftmaxArgs g{};
+    g.pre = mean; g.mean = mean; g.v0 = cost_out ? x_lo : nullptr; g.cost_partials = cost_out ? partials : nullptr;
+    g.group_start = group_start; g.n_groups = (int)n_groups; g.span_lo = lo; g.span_hi = hi;
+    g.B = (int)n; g.V = (int)V; g.units = group_units((int)V, lo, hi, (int)n_groups); g.ld = ldv;
+    mdbn_rng zero{};
+    g.rng = make_key(zero, 0u);
+    HIP_OK(launch_group_softmax(g, s));
+    if (cost_out) HIP_OK(launch_updown_cost_finish(partials, (int)group_softmax_blocks(n, g.units), scale, cost_out, s));
+    // V2 = [x_lo; g], P2 = [x_hi; -x_hi]: S = (x_lo - g)^T x_hi, s_v = sum (x_lo - g)
+    UpdownStackArgs k{};
+    k.n = (int)n; k.V = (int)V; k.H = (int)H; k.ldv = ldv; k.ldh = ldh;
+    k.lo = x_lo; k.second = mean; k.hi = x_hi; k.neg = x_hi; k.V2 = V2; k.P2 = P2;
+    HIP_OK(launch_updown_stack(k, s));
+    CHECK(mdbn_cd_stats(ctx, stream, V2, P2, n, V, H, ldv, ldh, stats, inner, inner_bytes));
+    mdbn_update_args u = *upd;
+    u.stats = stats; u.hbias = junk; u.hbias_speed = junk + ldh; u.cost_out = nullptr;      // the hidden half must not move
+    CHECK(mdbn_apply_update(ctx, stream, &u));
+    return MDBN_OK;
 }
 
 }  // extern "C"

@@ -103,13 +103,11 @@ int mdbn_sparsity_stats(mdbn_ctx* ctx, void* stream, float* stats, int64_t V, in
 }
 
 // ---------------------------------------------------------------------------------- up-down fine-tuning (mdbn_updown.hip)
-namespace {
+}  // extern "C"
 
-// Workspace of the two delta-rule steps, in floats (every piece a multiple of 64 floats: 16-byte aligned)
-struct UpdownWs {
-    int64_t V2, P2, pre, mean, stats, junk, partials, inner;
-    int64_t total() const { return V2 + P2 + pre + mean + stats + junk + partials + inner; }
-};
+// (shared with the grouped generative rule of mdbn_drv_groups.hip through mdbn_capi_internal.h: UpdownWs is declared there)
+namespace mdbn {
+namespace capi {
 
 bool updown_gen_fused_ok(const mdbn_ctx* ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, UpdownGeom& ug)
 {
@@ -182,7 +180,10 @@ int updown_check_update(const mdbn_update_args* u, bool gen)
 
 float* updown_take(float*& p, int64_t floats) { float* r = p; p += floats; return r; }
 
-}  // namespace
+}  // namespace capi
+}  // namespace mdbn
+
+extern "C" {
 
 int mdbn_updown_gen_workspace_bytes(mdbn_ctx* ctx, int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int path, int64_t* bytes)
 {

@@ -58,6 +58,28 @@ struct UpdownGenArgs {
     float* cost_partials;                   // [G]: one per workgroup
 };
 
+// The one-pass generative kernel of a layer with softmax groups (updown_gen_grouped_kernel): the geometry of updown_geom, its
+// workgroups' ranges moved onto group boundaries.  A range grows by at most UD_GROUP_SLACK rows (a group has at most
+// MDBN_GROUP_MAX = 64 columns), and next to x_lo^T the workgroup holds the pre-activations (then the errors) of its rows:
+// dynamic LDS x_hi [Bq][ldh] | x_lo^T [rpw + 63][Bq] | pre / err [rpw + 63][Bq] | two costs per wave.  At Bq = 32, ldh = 512,
+// rpw = 256 that is 147 264 bytes of the CU's 160 KB: the row cap of the plain kernel stands.
+constexpr int UD_GROUP_SLACK = 63;
+constexpr int UD_GROUPED_MAX_LDS = (UD_MAXB * UD_MAX_LDH + 2 * (UD_MAX_RPW + UD_GROUP_SLACK) * UD_MAXB + 2 * (UD_NT / 64)) * 4;
+static_assert(UD_GROUPED_MAX_LDS <= 160 * 1024, "updown_gen_grouped_kernel: the LDS of the widest shape must fit a CU");
+
+__host__ __device__ inline bool updown_geom_grouped(int64_t n, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int num_cu, UpdownGeom& t)
+{
+    if (!updown_geom(n, V, H, ldv, ldh, num_cu, t)) return false;
+    t.lds = (t.Bq * (int)ldh + 2 * (t.rpw + UD_GROUP_SLACK) * t.Bq + 2 * (UD_NT / 64)) * 4;
+    return true;
+}
+
+struct UpdownGenGroupedArgs {
+    UpdownGenArgs g;                        // gauss = 0
+    const int32_t* group_start;             // [n_groups + 1], device; clamped to the span below
+    int n_groups, span_lo, span_hi;         // the span the caller's host copy gives
+};
+
 // V2 = [lo; second], P2 = [hi; -neg]: the stacked operands of mdbn_cd_stats.  Pad columns are written as zeros.
 struct UpdownStackArgs {
     int n, V, H;
@@ -77,6 +99,7 @@ struct UpdownCostArgs {
 };
 
 hipError_t launch_updown_gen(const UpdownGenArgs& a, const UpdownGeom& t, hipStream_t s);
+hipError_t launch_updown_gen_grouped(const UpdownGenGroupedArgs& a, const UpdownGeom& t, hipStream_t s);
 hipError_t launch_updown_stack(const UpdownStackArgs& a, hipStream_t s);
 hipError_t launch_updown_cost(const UpdownCostArgs& a, hipStream_t s);
 // cost_out[0] = (sum of the partials, ascending, in float64) * scale

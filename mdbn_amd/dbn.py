@@ -219,9 +219,11 @@ class DBN(object):
         monitoring cost), ...]`` per epoch; ``on_epoch(epoch, record)`` is called after each.  ``path``: "auto", or "composed" /
         "fused" to force how the delta rules run (``HipEngine.updown_gen_step``).  Afterwards ``down_pass``, the directed terms
         of ``log_likelihood_bound`` and ``MDBN.impute_modalities`` go through ``W_gen``; ``get_output`` and the RBM-level
-        methods keep to W, so a lower layer's own free energy and AIS then describe its recognition RBM, not the model."""
+        methods keep to W, so a lower layer's own free energy and AIS then describe its recognition RBM, not the model.  With
+        ``visible_groups`` the input layer's generative conditional is a softmax per group: the dream holds one category per group,
+        every group of every data row must hold exactly one 1 (ValueError), and an engine without ``updown_gen_step_grouped``
+        refuses (NotImplementedError)."""
         from . import updown
-        self.rbm_layers[0]._no_groups("fine_tune")
         self.rbm_layers[0]._no_sigma("fine_tune")
         return updown.fine_tune([self], None, [train_set_x], epochs, batch_size, lr=lr, k=k, momentum=momentum,
                                 weightcost=weightcost, lambda_1=lambda_1, lambda_2=lambda_2, top_lr=top_lr, on_epoch=on_epoch,

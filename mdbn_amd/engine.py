@@ -1283,7 +1283,7 @@ class HipEngine(object):
         p = self.UPDOWN_PATHS[path]
         u = _lib.UpdateArgs()
         u.W, u.W_speed = W.data_ptr(), W_speed.data_ptr()
-        if kind == "gen":
+        if kind in ("gen", "gen_grouped"):
             u.vbias, u.vbias_speed = bias.data_ptr(), bias_speed.data_ptr()
         else:
             u.hbias, u.hbias_speed = bias.data_ptr(), bias_speed.data_ptr()
@@ -1294,7 +1294,10 @@ class HipEngine(object):
         wp, _ = self.w_planes(W)
         u.W_planes = wp.data_ptr() if wp is not None else None    # kept in step with the matrix by every path that writes it
         nbytes = C.c_int64()
-        if kind == "gen":
+        if kind == "gen_grouped":
+            _lib.check(self.lib.mdbn_updown_gen_grouped_workspace_bytes(self.ctx, int(n), V, H, int(ldv), W.stride(0), p,
+                                                                        C.byref(nbytes)), "mdbn_updown_gen_grouped_workspace_bytes")
+        elif kind == "gen":
             _lib.check(self.lib.mdbn_updown_gen_workspace_bytes(self.ctx, int(n), V, H, int(ldv), W.stride(0), p, C.byref(nbytes)),
                        "mdbn_updown_gen_workspace_bytes")
         else:
@@ -1321,6 +1324,28 @@ class HipEngine(object):
         cost = self._next_cost_slot()
         _lib.check(self.lib.mdbn_updown_gen_step(self.ctx, self._stream(), self._p(x_lo), self._p(x_hi), n, int(bool(gauss)),
                                                  C.byref(u), self._p(cost), p, self._p(ws), ws.numel() * 4), "mdbn_updown_gen_step")
+        self._w_serial += 1
+        self._w_planes_written(G)
+        return cost
+
+    def updown_gen_step_grouped(self, x_lo, x_hi, G, G_speed, vbias, vbias_speed, groups, lr, lambda_1, lambda_2, weightcost,
+                                momentum, batch_size, n_rows, cost_scale=1.0, path="auto"):
+        """``updown_gen_step`` for the input layer of a network with softmax groups (``groups``: its ``GroupTable``;
+        mdbn_updown_gen_step_grouped): g = softmax inside every group, sigmoid on the other columns, of x_hi G^T + vbias; the
+        same statistics, rule and ``path``.  Returns ``cost_scale`` * sum_r -log p(x_lo | x_hi), the categorical cross-entropy
+        from the log-sum-exp plus the Bernoulli cross-entropy outside the span.  Every group of every row of ``x_lo`` must
+        hold exactly one 1 (not checked here)."""
+        x_lo = self.as_matrix(x_lo)
+        n, V = (int(v) for v in x_lo.shape)
+        if tuple(G.shape) != (V, x_hi.shape[1]) or x_hi.shape[0] != n:
+            raise ValueError("x_lo %r, x_hi %r and G %r do not fit" % (tuple(x_lo.shape), tuple(x_hi.shape), tuple(G.shape)))
+        x_hi = self._padded(x_hi, n, G.shape[1], G.stride(0))      # the C-ABI reads x_hi with G's ld
+        u, ws, p = self._updown_call("gen_grouped", n, G, G_speed, vbias, vbias_speed, x_lo.stride(0),
+                                     (lr, lambda_1, lambda_2, weightcost, momentum, batch_size, n_rows), cost_scale, path)
+        cost = self._next_cost_slot()
+        _lib.check(self.lib.mdbn_updown_gen_step_grouped(
+            self.ctx, self._stream(), self._p(x_lo), self._p(x_hi), n, C.byref(u), self._p(cost), p, self._p(ws), ws.numel() * 4,
+            self._p(groups.tensor), C.c_void_p(groups.host.ctypes.data), groups.n_groups), "mdbn_updown_gen_step_grouped")
         self._w_serial += 1
         self._w_planes_written(G)
         return cost

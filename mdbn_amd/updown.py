@@ -16,6 +16,13 @@ top RBM as ONE matrix.  Fine-tuning unties them -- ``rbm.W_gen``, a copy of W on
 
 all by the engine's update rule (lr, momentum, weightcost, lambda_1, lambda_2; S over batch_size, bias sums over the rows
 present).  At a Gaussian bottom layer y_0 is the linear mean, plus N(0, 1) noise exactly when that GRBM is ``error_free=False``.
+At the input layer of a network with ``visible_groups`` act is the softmax inside every group and the sigmoid on the other
+columns: y_0 holds one category per group, drawn by the engine's ``group_softmax`` from the linear pre-activations through
+``down_W`` (one uniform per group, at its first column: the addressing of ``RBM.sample_v_given_h``), g_0 is the grouped mean
+(``updown_gen_step_grouped``; the same S and s_v are the exact gradient of sum_r log p(x_0 | x_1)), and the recognition rule
+sees y_0 as the 0 / 1 matrix it is.  The data rows must be one-hot in every group (ValueError); an engine without
+``updown_gen_step_grouped`` and a JOINT network whose own input layer has groups -- its input is sampled, not one-hot data --
+are refused (NotImplementedError) before anything is drawn.
 Every draw advances ``_rng_step`` of the RBM whose conditional is sampled: two runs from the same seeds agree bit for bit.
 
 A stack is ``(nets, joint)`` as ``bound.stack_bound`` walks it: every layer of every modality DBN and the joint DBN's lower
@@ -77,6 +84,17 @@ def _single_device():
         raise NotImplementedError("up-down fine-tuning runs on one device (a process group of %d ranks is up)" % grp.world_size)
 
 
+def _check_groups(nets, joint):
+    """What a stack with categorical visible units needs, before anything is planned, drawn or called: an engine with the
+    grouped generative rule, and groups at the input layers of the modality networks only."""
+    for net in list(nets) + ([joint] if joint is not None else []):
+        if not hasattr(net.engine, "updown_gen_step_grouped"):
+            net.rbm_layers[0]._no_groups("fine_tune on this engine")
+    if joint is not None and joint.rbm_layers[0].visible_groups is not None:
+        raise NotImplementedError("fine_tune with categorical visible units (visible_groups) in the JOINT network's input layer is "
+                                  "not built: its input is sampled, not one-hot data")
+
+
 def _wake(eng, layers, x):
     xs = [x]
     for r in layers:
@@ -88,8 +106,13 @@ def _sleep(eng, layers, y_top):
     """The dream below ``y_top`` through ``layers`` (top-down) and its recognition means: (ys, rs), bottom first."""
     ys, rs = [y_top], []
     for r in reversed(layers):
-        noisy = bool(r.gauss and not getattr(r, "error_free", True))
-        y = eng.propdown(ys[0], r.down_W, r.vbias.tensor, gauss=r.gauss, add_noise=noisy, rng=_rng(r))[2]
+        if r.visible_groups is not None:
+            # one category per group from the linear pre-activations through the GENERATIVE weights (RBM._grouped_down reads W)
+            pre = eng.propdown(ys[0], r.down_W, r.vbias.tensor, gauss=True, add_noise=False, rng=None)[1]
+            y = eng.group_softmax(pre, r.visible_groups, _rng(r))[1]
+        else:
+            noisy = bool(r.gauss and not getattr(r, "error_free", True))
+            y = eng.propdown(ys[0], r.down_W, r.vbias.tensor, gauss=r.gauss, add_noise=noisy, rng=_rng(r))[2]
         rs.insert(0, eng.propup(y, r.W.tensor, r.hbias.tensor, want_pre=False, want_sample=False)[1])
         ys.insert(0, y)
     return ys, rs
@@ -134,8 +157,12 @@ def step(nets, joint, rows, hp):
     gen_cost = []
     for m, layers in enumerate(directed):
         for l, r in enumerate(layers):
-            c = eng.updown_gen_step(xs[m][l], xs[m][l + 1], r.W_gen.tensor, r.W_gen_speed.tensor, r.vbias.tensor,
-                                    r.vbias_speed.tensor, r.gauss, *rule, cost_scale=1.0 / n, path=hp.path)
+            if r.visible_groups is not None:
+                c = eng.updown_gen_step_grouped(xs[m][l], xs[m][l + 1], r.W_gen.tensor, r.W_gen_speed.tensor, r.vbias.tensor,
+                                                r.vbias_speed.tensor, r.visible_groups, *rule, cost_scale=1.0 / n, path=hp.path)
+            else:
+                c = eng.updown_gen_step(xs[m][l], xs[m][l + 1], r.W_gen.tensor, r.W_gen_speed.tensor, r.vbias.tensor,
+                                        r.vbias_speed.tensor, r.gauss, *rule, cost_scale=1.0 / n, path=hp.path)
             if l == 0 and (joint is None or m < len(nets)):
                 gen_cost.append(c)                      # -log p(x_0 | x_1) of the data rows, per row
             eng.updown_rec_step(ys[m][l], ys[m][l + 1], rs[m][l], r.W.tensor, r.W_speed.tensor, r.hbias.tensor,
@@ -162,6 +189,7 @@ def fine_tune(nets, joint, inputs, epochs, batch_size=20, lr=None, k=1, momentum
         raise ValueError("path must be one of %r, got %r" % (sorted(PATHS), path))
     for net in nets:
         net.rbm_layers[0]._no_sigma("fine_tune")
+    _check_groups(nets, joint)
     directed, top = plan(nets, joint)
     _single_device()
     if len(inputs) != len(nets) or any(x is None for x in inputs):
@@ -174,6 +202,10 @@ def fine_tune(nets, joint, inputs, epochs, batch_size=20, lr=None, k=1, momentum
     for net, t in zip(nets, tables):
         if t.shape[1] != net.n_ins:
             raise ValueError("data has %d columns, the network %d inputs" % (t.shape[1], net.n_ins))
+    for net, t in zip(nets, tables):
+        if net.rbm_layers[0].visible_groups is not None:
+            # g_0 is a softmax and the cost linear in the row only on one-hot groups (the host copy is checked, as the bound's)
+            net.rbm_layers[0]._check_one_hot(t)
     hp = Hyper(float(lr), float(lr if top_lr is None else top_lr), int(k), float(momentum), float(weightcost), float(lambda_1),
                float(lambda_2), int(batch_size), path)
     owner = joint if joint is not None else nets[0]
