@@ -79,7 +79,7 @@ typedef struct mdbn_cd_args {
     float       *hs;          /* [B, ldh] hidden chain state                                     */
     float       *vs;          /* [B, ldv] visible sample (RBM; GRBM with noise), may be NULL     */
     float       *stats;       /* packed [V*ldh | ldh | ldv | 4]: S, s_h, s_v, cost_sum           */
-    void        *workspace;   /* >= mdbn_workspace_bytes(B, V, H)                                */
+    void        *workspace;   /* >= mdbn_workspace_bytes(B, V, H)  (wider ld: _bytes_ld)         */
     int64_t      workspace_bytes;
     mdbn_rng     rng;         /* .draw is ignored (the step numbers its own draws)               */
     /* optional monitoring taps on the Gibbs chain (NULL = off; the role MonitorMode plays at
@@ -254,12 +254,34 @@ int  mdbn_kernel_timing_detail(mdbn_ctx *ctx, int64_t cap, double *ms, double *a
  * form of its kernel since it was created. */
 int  mdbn_narrow_deep_launches(mdbn_ctx *ctx, int64_t *n_launches);
 
-/* bytes of split-K / reduction scratch the calls below need for shapes up to (B, V, H) */
+/* WORKSPACE.  Every workspace is caller-owned and 16-byte aligned; a call is told its size and never touches a byte
+ * beyond it.
+ *  - mdbn_workspace_bytes(B, V, H): the bytes a CD step (mdbn_cd_step / _forward / _statistics / _train_step, mdbn_cd_stats,
+ *    the grouped step) of exactly this shape needs, on leading dimensions up to mdbn_padded_ld's (and a ragged hidden width
+ *    on ldh = round_up(H, 128), the plane path's).  The answer is NOT monotone in (B, V, H) -- fewer rows take more split-K
+ *    slabs -- so ask for every shape that runs.  A step on wider leading dimensions asks mdbn_workspace_bytes_ld: its
+ *    column-sum regions lie on the caller's strides.  A step handed fewer bytes than the sizer answers for its shape
+ *    and leading dimensions returns MDBN_ENOSPC before any launch.
+ *  - The propagate-only calls (mdbn_propup_sample, mdbn_propdown_sample, mdbn_gibbs_chain, mdbn_free_energy) accept ANY
+ *    workspace of at least MDBN_MIN_WORKSPACE_BYTES, whatever B: they keep a fixed region for cost partials and cut the
+ *    rows into chunks (multiples of four rows) whose split-K slabs fit in the rest -- results and random draws do not
+ *    depend on the cut; more bytes only mean fewer launches.  Fewer bytes: MDBN_ENOSPC before any launch (likewise, for
+ *    very wide layers, when not even a 4-row chunk fits).  mdbn_workspace_bytes[_ld][_ctx] never answer less than the
+ *    minimum, so their answer serves these calls too (the *_workspace_bytes of the feature calls size those calls
+ *    alone and may answer far less). */
+#define MDBN_MIN_WORKSPACE_BYTES 278528     /* 4 * (65536 cost partials + 4096 slab floats) */
 int  mdbn_workspace_bytes(int64_t B, int64_t V, int64_t H, int64_t *bytes);
 /* ... under the options of `ctx` (the plans, hence the scratch, depend on them) */
 int  mdbn_workspace_bytes_ctx(mdbn_ctx *ctx, int64_t B, int64_t V, int64_t H, int64_t *bytes);
+/* ... for a step on the leading dimensions (ldv, ldh), any the step accepts; the same answer as mdbn_workspace_bytes on
+ * those it covers */
+int  mdbn_workspace_bytes_ld(int64_t B, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int64_t *bytes);
+int  mdbn_workspace_bytes_ld_ctx(mdbn_ctx *ctx, int64_t B, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int64_t *bytes);
+/* MDBN_MIN_WORKSPACE_BYTES as the library was built (bindings without the header) */
+int  mdbn_min_workspace_bytes(int64_t *bytes);
 /* leading dimension this library recommends for a [., cols] matrix (currently round_up(cols, 4);
- * see the measurement note in csrc/mdbn_capi.hip).  Any ld % 4 == 0, ld >= cols is accepted. */
+ * see the measurement note in csrc/mdbn_capi.hip).  Any ld % 4 == 0, ld >= cols is accepted (a CD step on wider ones
+ * than this sizes its workspace with mdbn_workspace_bytes_ld). */
 int  mdbn_padded_ld(int64_t cols, int64_t *ld);
 /* bytes of plane scratch (mdbn_cd_args.planes) for a minibatch of B rows: planes of [v0; nv], [ph; -nh],
  * the hidden and the visible sample */

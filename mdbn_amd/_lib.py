@@ -73,6 +73,9 @@ SIGNATURES = {
                                   C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(_i64)],
     "mdbn_workspace_bytes": [_i64, _i64, _i64, C.POINTER(_i64)],
     "mdbn_workspace_bytes_ctx": [_vp, _i64, _i64, _i64, C.POINTER(_i64)],
+    "mdbn_workspace_bytes_ld": [_i64, _i64, _i64, _i64, _i64, C.POINTER(_i64)],
+    "mdbn_workspace_bytes_ld_ctx": [_vp, _i64, _i64, _i64, _i64, _i64, C.POINTER(_i64)],
+    "mdbn_min_workspace_bytes": [C.POINTER(_i64)],
     "mdbn_padded_ld": [_i64, C.POINTER(_i64)],
     "mdbn_planes_bytes": [_i64, _i64, _i64, C.POINTER(_i64)],
     "mdbn_planes_alt_bytes": [_i64, _i64, C.POINTER(_i64)],

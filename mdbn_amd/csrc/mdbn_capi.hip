@@ -353,6 +353,15 @@ struct WsSizes {
     int64_t total_bytes() const { return 4 * (ru64(slab) + ru64(cost) + ru64(colP) + ru64(colV)); }
 };
 
+// cost partials of a pass of B rows whose widest output lies on leading dimension ld: one column per thread in 64-thread
+// blocks at worst; fused epilogues write one partial per block (128 x 64 tiles, or 32-column strips: skinny)
+static int64_t cost_floats_for(int64_t B, int64_t ld)
+{
+    int64_t c = std::max<int64_t>(256, (((B + 3) / 4) * ld + 63) / 64) + 64;
+    c = std::max<int64_t>(c, ((B + 127) / 128) * ((ld + 63) / 64) + 64);
+    return std::max<int64_t>(c, ((B + 31) / 32) * ((ld + 31) / 32) + 64);
+}
+
 static WsSizes ws_sizes_dense(int64_t B, int64_t V, int64_t H)
 {
     const int64_t ldv = padded_ld(V), ldh = padded_ld(H);      // the largest ld the policy hands out
@@ -396,10 +405,7 @@ static WsSizes ws_sizes_dense(int64_t B, int64_t V, int64_t H)
         }
     }
     s.slab = std::max<int64_t>(s.slab, 4 * std::max(ldv, ldh) * 8);
-    s.cost = std::max<int64_t>(256, (((B + 3) / 4) * std::max(ldv, ldh) + 63) / 64) + 64;   // worst case: one column per thread, 64-thread blocks
-    // fused epilogues write one partial per block: 128 x 64 tiles, or 32-column strips (skinny)
-    s.cost = std::max<int64_t>(s.cost, ((B + 127) / 128) * ((std::max(ldv, ldh) + 63) / 64) + 64);
-    s.cost = std::max<int64_t>(s.cost, ((B + 31) / 32) * ((std::max(ldv, ldh) + 31) / 32) + 64);
+    s.cost = cost_floats_for(B, std::max(ldv, ldh));
     if (small_shape_ok(B, V, H, 0) || small_shape_ok(B, V, H, 1)) s.cost = std::max<int64_t>(s.cost, (int64_t)small_blocks(B) * SM_NW + 64);   // a cost partial per wave
     s.cost = std::max<int64_t>(s.cost, thin_cost + 64);
     s.cost = std::max<int64_t>(s.cost, gc_cost + 64);
@@ -411,7 +417,15 @@ static WsSizes ws_sizes_dense(int64_t B, int64_t V, int64_t H)
 
 // (a ragged hidden width may ride on a leading dimension padded to a multiple of 128 -- plane_shape_ok -- : every buffer is
 // then as large as the dense layer of that width needs)
-WsSizes ws_sizes(int64_t B, int64_t V, int64_t H)
+//
+// ldv / ldh (0: the policy's): the leading dimensions of the call.  The column-sum regions hold one row of the CALLER's
+// stride per row group, the statistics GEMM parks its slabs on the caller's ldh and the cost partials of a pass grow with
+// its output's stride, so a step on wider leading dimensions than the policy's needs more.  The forward passes' slabs are
+// not sized here: the fast paths test theirs against the real ld before they are chosen, and run_affine cuts a pass into
+// row chunks whose slabs and cost partials fit (under non-default epilogue geometry it may still find, after earlier
+// passes of the step, that they do not: MDBN_ENOSPC then, never a write outside the workspace).  On the leading
+// dimensions the policy hands out the answer is the same.
+WsSizes ws_sizes(int64_t B, int64_t V, int64_t H, int64_t ldv = 0, int64_t ldh = 0)
 {
     WsSizes s = ws_sizes_dense(B, V, H);
     if (H % 128 != 0) {
@@ -419,6 +433,14 @@ WsSizes ws_sizes(int64_t B, int64_t V, int64_t H)
         s.slab = std::max(s.slab, p.slab); s.cost = std::max(s.cost, p.cost);
         s.colP = std::max(s.colP, p.colP); s.colV = std::max(s.colV, p.colV);
     }
+    const int64_t ng = row_groups(B);
+    if (ldh > 0) {
+        s.colP = std::max(s.colP, 2 * ng * ldh);
+        const Plan st = plan_stats(V, H, 2 * B, ldh);
+        if (st.splitk > 1) s.slab = std::max(s.slab, st.slab_floats(V, ldh));
+    }
+    if (ldv > 0) s.colV = std::max(s.colV, ng * ldv);
+    if (ldv > 0 || ldh > 0) s.cost = std::max(s.cost, cost_floats_for(B, std::max(ldv, ldh)));
     return s;
 }
 
@@ -829,15 +851,23 @@ PhiloxKey make_key(const mdbn_rng& r, uint32_t draw)
 
 int64_t dense_workspace_bytes(int64_t B, int64_t V, int64_t H) { return ws_sizes(B, V, H).total_bytes(); }
 
-int carve(void* ws, int64_t bytes, int64_t B, int64_t V, int64_t H, Workspace& out, bool need_stats)
+// The propagate-only carve-up (carve(..., need_stats = false)): a fixed cost region at the end and at least 4096 floats of
+// slabs in front of it.  MDBN_MIN_WORKSPACE_BYTES of the header is this figure; the public sizers never answer less.
+constexpr int64_t kPropCostFloats = 1 << 16;
+constexpr int64_t kPropMinBytes = 4 * (kPropCostFloats + 4096);
+static_assert(kPropMinBytes == MDBN_MIN_WORKSPACE_BYTES, "mdbn_hip.h states the minimum of the propagation calls");
+
+int carve(void* ws, int64_t bytes, int64_t B, int64_t V, int64_t H, Workspace& out, bool need_stats, int64_t ldv, int64_t ldh)
 {
     REQUIRE(ws != nullptr && aligned16(ws), "workspace must be a 16-byte aligned device pointer");
-    const WsSizes s = ws_sizes(B, V, H);
+    const WsSizes s = ws_sizes(B, V, H, ldv, ldh);
     float* p = reinterpret_cast<float*>(ws);
     if (need_stats) {
         if (bytes < s.total_bytes())
-            return fail(MDBN_ENOSPC, "workspace %lld bytes < %lld needed for B=%lld V=%lld H=%lld",
-                        (long long)bytes, (long long)s.total_bytes(), (long long)B, (long long)V, (long long)H);
+            return fail(MDBN_ENOSPC, "workspace %lld bytes < %lld needed for B=%lld V=%lld H=%lld ldv=%lld ldh=%lld "
+                        "(mdbn_workspace_bytes_ld sizes a step on leading dimensions wider than mdbn_padded_ld's)",
+                        (long long)bytes, (long long)s.total_bytes(), (long long)B, (long long)V, (long long)H,
+                        (long long)ldv, (long long)ldh);
         out.slabs = p;            out.slab_floats = s.slab;  p += ru64(s.slab);
         out.cost_partials = p;    out.cost_floats = s.cost;  p += ru64(s.cost);
         out.colPpos = p;          out.colPneg = p + s.colP / 2;  p += ru64(s.colP);
@@ -845,9 +875,10 @@ int carve(void* ws, int64_t bytes, int64_t B, int64_t V, int64_t H, Workspace& o
     } else {
         // propagation only: a fixed cost region at the end, everything else is slabs
         const int64_t floats = bytes / 4;
-        const int64_t cost = 1 << 16;
-        if (floats < cost + 4096)
-            return fail(MDBN_ENOSPC, "workspace %lld bytes is too small", (long long)bytes);
+        const int64_t cost = kPropCostFloats;
+        if (bytes < kPropMinBytes)
+            return fail(MDBN_ENOSPC, "workspace %lld bytes is too small: a propagation call needs %lld (MDBN_MIN_WORKSPACE_BYTES)",
+                        (long long)bytes, (long long)kPropMinBytes);
         out.slabs = p;
         out.slab_floats = (floats - cost) & ~int64_t(63);
         out.cost_partials = p + out.slab_floats;
@@ -1250,8 +1281,30 @@ int mdbn_kernel_timing_detail(mdbn_ctx* ctx, int64_t cap, double* ms, double* al
 int mdbn_workspace_bytes(int64_t B, int64_t V, int64_t H, int64_t* bytes)
 {
     REQUIRE(bytes != nullptr && B > 0 && V > 0 && H > 0, "bad arguments");
-    *bytes = ws_sizes(B, V, H).total_bytes();
+    *bytes = std::max(ws_sizes(B, V, H).total_bytes(), kPropMinBytes);
     return MDBN_OK;
+}
+
+int mdbn_workspace_bytes_ld(int64_t B, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int64_t* bytes)
+{
+    REQUIRE(bytes != nullptr && B > 0 && V > 0 && H > 0, "bad arguments");
+    REQUIRE(ldv >= V && ldh >= H && ldv % 4 == 0 && ldh % 4 == 0, "leading dims must be multiples of 4, >= V / H");
+    *bytes = std::max(ws_sizes(B, V, H, ldv, ldh).total_bytes(), kPropMinBytes);
+    return MDBN_OK;
+}
+
+int mdbn_min_workspace_bytes(int64_t* bytes)
+{
+    REQUIRE(bytes != nullptr, "bytes is NULL");
+    *bytes = kPropMinBytes;
+    return MDBN_OK;
+}
+
+int mdbn_workspace_bytes_ld_ctx(mdbn_ctx* ctx, int64_t B, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int64_t* bytes)
+{
+    CtxScope ctx_scope(ctx);
+    REQUIRE(ctx != nullptr, "ctx is NULL");
+    return mdbn_workspace_bytes_ld(B, V, H, ldv, ldh, bytes);
 }
 
 int mdbn_workspace_bytes_ctx(mdbn_ctx* ctx, int64_t B, int64_t V, int64_t H, int64_t* bytes)
@@ -1470,7 +1523,7 @@ int mdbn_cd_stats(mdbn_ctx* ctx, void* stream, const float* V2, const float* P2,
     CHECK(check_mat(P2, ldh, H, "P2"));
     REQUIRE(stats != nullptr && aligned16(stats), "stats must be 16-byte aligned");
     Workspace ws;
-    CHECK(carve(workspace, workspace_bytes, B, V, H, ws, true));
+    CHECK(carve(workspace, workspace_bytes, B, V, H, ws, true, ldv, ldh));
     hipStream_t s = (hipStream_t)stream;
     const StatsView st(stats, V, ldv, ldh);
 
@@ -1840,6 +1893,7 @@ static int dense_statistics(mdbn_ctx* ctx, hipStream_t s, const mdbn_cd_args* a,
         g.C = st.S;
         HIP_OK(timed_gemm(LAY_MN, LAY_MN, g, s));
     } else {
+        REQUIRE(p.slab_floats(V, ldh) <= ws.slab_floats, "internal: statistic slabs exceed workspace");
         g.C = ws.slabs;
         HIP_OK(timed_gemm(LAY_MN, LAY_MN, g, s));
         if (upd && !overlap && g_opt_fused_update) {
@@ -1890,7 +1944,7 @@ static int cd_step_impl(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a, cons
     REQUIRE(a->persistent == nullptr || aligned16(a->persistent), "persistent not aligned");
     REQUIRE(a->indexes != nullptr || B <= a->n_data, "identity minibatch longer than data");
     Workspace ws;
-    CHECK(carve(a->workspace, a->workspace_bytes, B, V, H, ws, true));
+    CHECK(carve(a->workspace, a->workspace_bytes, B, V, H, ws, true, ldv, ldh));
     hipStream_t s = (hipStream_t)stream;
     if (a->ahead_done) *a->ahead_done = 0;
     if (upd) {

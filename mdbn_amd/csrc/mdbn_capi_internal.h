@@ -157,7 +157,8 @@ struct Workspace {
 // bytes of the whole carve-up for a (B, V, H) step under the options of the running call (mdbn_workspace_bytes)
 int64_t dense_workspace_bytes(int64_t B, int64_t V, int64_t H);
 // need_stats: the carve-up of a CD step; else propagation only (a fixed cost region at the end, everything else is slabs)
-int carve(void* ws, int64_t bytes, int64_t B, int64_t V, int64_t H, Workspace& out, bool need_stats);
+// ldv / ldh: the leading dimensions of a need_stats call (0: the policy's) -- the column-sum regions lie on them
+int carve(void* ws, int64_t bytes, int64_t B, int64_t V, int64_t H, Workspace& out, bool need_stats, int64_t ldv = 0, int64_t ldh = 0);
 
 // One affine map + activation over `rows` rows, chunked so the split-K slabs fit.
 //   up   (dir 0): x[rows, V] * W        -> [rows, H]   (bias = hbias)

@@ -154,7 +154,7 @@ int mdbn_cd_step_grouped(mdbn_ctx* ctx, void* stream, const mdbn_cd_args* a, con
     int lo, hi;
     CHECK(check_groups(group_start, group_start_host, n_groups, V, lo, hi));
     Workspace probe;                                   // the statistics' carve-up is the largest: refused here, before any launch
-    CHECK(carve(a->workspace, a->workspace_bytes, B, V, H, probe, true));
+    CHECK(carve(a->workspace, a->workspace_bytes, B, V, H, probe, true, ldv, ldh));
     REQUIRE(a->workspace_bytes >= group_partial_floats(B, V) * (int64_t)sizeof(float), "workspace too small for the cost partials");
     Workspace ws;
     CHECK(carve(a->workspace, a->workspace_bytes, B, V, H, ws, false));

@@ -196,6 +196,7 @@ class HipEngine(object):
         _lib.check(self.lib.mdbn_ctx_create(C.byref(ctx), self.device.index), "mdbn_ctx_create")
         self.ctx = ctx
         self._workspace = None
+        self._workspace_need = 0        # bytes the shared workspace was allocated for
         self._options_epoch = 0         # bumped by set_option: argument structs cached by step functions are then stale
         self._w_serial = 0              # bumped by every library call that writes parameters (what a positive phase computed
                                         # ahead of its step was computed FROM: _ahead_valid)
@@ -287,17 +288,31 @@ class HipEngine(object):
         # (torch.cuda.current_stream() builds a Stream object: 5 us per call -- a sixth of a small layer's step)
         return C.c_void_p(torch._C._cuda_getCurrentRawStream(self.device.index))
 
-    def workspace(self, B, V, H):
+    def workspace(self, B, V, H, ldv=None, ldh=None):
         """One shared workspace, grown to the largest requirement seen.  The requirement is NOT monotone in (B, V, H) (a
-        smaller minibatch takes more split-K slabs), so every shape asks the library (cached per shape)."""
-        need = self._ws_need.get((B, V, H))
+        smaller minibatch takes more split-K slabs), so every shape asks the library (cached per shape).  ``ldv`` / ``ldh``:
+        the leading dimensions of a CD step (its column-sum regions lie on them: mdbn_workspace_bytes_ld)."""
+        key = (B, V, H) if ldv is None else (B, V, H, ldv, ldh)
+        need = self._ws_need.get(key)
         if need is None:
             n = C.c_int64()
-            _lib.check(self.lib.mdbn_workspace_bytes_ctx(self.ctx, B, V, H, C.byref(n)), "mdbn_workspace_bytes_ctx")
-            need = self._ws_need[(B, V, H)] = max(n.value, 8 << 20)
-        if self._workspace is None or self._workspace.numel() * 4 < need + 256:
-            self._workspace = torch.empty(need // 4 + 64, dtype=torch.float32, device=self.device)
+            if ldv is None:
+                _lib.check(self.lib.mdbn_workspace_bytes_ctx(self.ctx, B, V, H, C.byref(n)), "mdbn_workspace_bytes_ctx")
+            else:
+                _lib.check(self.lib.mdbn_workspace_bytes_ld_ctx(self.ctx, B, V, H, ldv, ldh, C.byref(n)), "mdbn_workspace_bytes_ld_ctx")
+            need = self._ws_need[key] = max(n.value, self.WS_FLOOR)
+        if self._workspace is None or self._workspace_need < need:
+            self._workspace = self._alloc_scratch(need, "workspace")
+            self._workspace_need = need
         return self._workspace
+
+    WS_FLOOR = 8 << 20          # the shared workspace is never smaller: one allocation serves nearly every shape of a run
+    WS_PAD = 64                 # floats behind every scratch buffer (keeps a regrown buffer off the allocator's size classes)
+
+    def _alloc_scratch(self, nbytes, what):
+        """Every caller-owned workspace of a library call comes from here: an uninitialised float32 tensor that holds at
+        least ``nbytes`` bytes; ``what`` names its use.  The library is told ``numel() * 4`` bytes."""
+        return torch.empty(int(nbytes) // 4 + self.WS_PAD, dtype=torch.float32, device=self.device)
 
     def new_stats_buffer(self, V, H, ldv=None, ldh=None):
         """A packed [S | s_h | s_v | cost] buffer owned by the caller (a step function whose statistics
@@ -492,7 +507,7 @@ class HipEngine(object):
             need = max(need, n.value)
         ws = getattr(self, cache_attr, None) if cache_attr else None
         if ws is None or ws.numel() * 4 < need:
-            ws = torch.empty(need // 4 + 64, dtype=torch.float32, device=self.device)
+            ws = self._alloc_scratch(need, name)
             if cache_attr:
                 setattr(self, cache_attr, ws)
         return ws
@@ -608,7 +623,7 @@ class HipEngine(object):
         _lib.check(getattr(self.lib, sizer)(self.ctx, R, V, H, C.byref(n)), sizer)
         ws = getattr(self, cache_attr, None)
         if ws is None or ws.numel() * 4 < n.value:
-            ws = torch.empty(n.value // 4 + 64, dtype=torch.float32, device=self.device)
+            ws = self._alloc_scratch(n.value, sizer)
             setattr(self, cache_attr, ws)
         _lib.check(getattr(self.lib, name)(
             self.ctx, self._stream(), self._p(h), R, h.stride(0), self._p(W), V, H, self._p(vbias), self._p(target),
@@ -887,7 +902,7 @@ class HipEngine(object):
             stats = self.stats_buffer(V, H, stats_slot, ldv, ldh)
         if persistent is not None and persistent.stride(0) != ldh:
             raise _lib.MdbnError("persistent chain must share W's leading dimension")
-        ws = self.workspace(B, V, H)
+        ws = self.workspace(B, V, H, ldv, ldh)
         a = _lib.CdArgs()
         a.data, a.n_data = data.data_ptr(), data.shape[0]
         a.indexes = idx.data_ptr() if idx is not None else None
@@ -989,7 +1004,7 @@ class HipEngine(object):
             _lib.check(self.lib.mdbn_group_softmax_workspace_bytes(self.ctx, B, V, C.byref(n)), "mdbn_group_softmax_workspace_bytes")
             ws = getattr(self, "_group_ws", None)
             if ws is None or ws.numel() * 4 < n.value:
-                ws = self._group_ws = torch.empty(n.value // 4 + 64, dtype=torch.float32, device=self.device)
+                ws = self._group_ws = self._alloc_scratch(n.value, "mdbn_group_softmax_workspace_bytes")
         r = rng.c() if rng is not None else None
         _lib.check(self.lib.mdbn_group_softmax_sample(
             self.ctx, self._stream(), self._p(pre), B, ldv, V, self._p(groups.tensor), C.c_void_p(groups.host.ctypes.data),
@@ -1023,7 +1038,7 @@ class HipEngine(object):
         out = self.alloc_vector(H)
         ws = getattr(self, "_center_rows_ws", None)
         if ws is None or ws.numel() < 2 * B + 3:
-            ws = self._center_rows_ws = torch.empty(2 * int(B) + 64, dtype=torch.float32, device=self.device)
+            ws = self._center_rows_ws = self._alloc_scratch(4 * (2 * int(B) + 3), "mdbn_center_hidden_rows")
         _lib.check(self.lib.mdbn_center_hidden_rows(self.ctx, self._stream(), self._p(V2), V2.stride(0), self._p(P2), P2.stride(0),
                                                     int(B), int(V), int(H), self._p(stats), self._p(mu), self._p(lam),
                                                     float(row_scale), self._p(q), self._p(v_mean), float(target), float(w_scale),
@@ -1207,7 +1222,7 @@ class HipEngine(object):
         _lib.check(self.lib.mdbn_center_workspace_bytes(self.ctx, int(V), int(H), C.byref(n)), "mdbn_center_workspace_bytes")
         ws = getattr(self, "_center_ws", None)
         if ws is None or ws.numel() * 4 < n.value:
-            ws = self._center_ws = torch.empty(n.value // 4 + 64, dtype=torch.float32, device=self.device)
+            ws = self._center_ws = self._alloc_scratch(n.value, "mdbn_center_workspace_bytes")
         _lib.check(self.lib.mdbn_center_stats(self.ctx, self._stream(), self._p(stats), int(V), int(H), int(ldv), int(ldh),
                                               self._p(mu), self._p(lam), float(row_scale), self._p(ws), ws.numel() * 4),
                    "mdbn_center_stats")
@@ -1264,7 +1279,7 @@ class HipEngine(object):
         _lib.check(self.lib.mdbn_sigma_workspace_bytes(self.ctx, int(B), int(V), C.byref(n)), "mdbn_sigma_workspace_bytes")
         ws = getattr(self, "_sigma_ws", None)
         if n.value and (ws is None or ws.numel() * 4 < n.value):
-            ws = self._sigma_ws = torch.empty(n.value // 4 + 64, dtype=torch.float32, device=self.device)
+            ws = self._sigma_ws = self._alloc_scratch(n.value, "mdbn_sigma_workspace_bytes")
         _lib.check(self.lib.mdbn_sigma_update(
             self.ctx, self._stream(), self._p(U), U.stride(0), self._p(M), M.stride(0), int(B), int(V), int(n_rows), float(lr),
             float(momentum), float(lo), float(hi), self._p(log_sigma), self._p(log_sigma_speed),
@@ -1305,7 +1320,7 @@ class HipEngine(object):
                        "mdbn_updown_rec_workspace_bytes")
         ws = getattr(self, "_updown_ws", None)
         if ws is None or ws.numel() * 4 < nbytes.value:
-            ws = self._updown_ws = torch.empty(nbytes.value // 4 + 64, dtype=torch.float32, device=self.device)
+            ws = self._updown_ws = self._alloc_scratch(nbytes.value, "mdbn_updown_%s_workspace_bytes" % kind)
         return u, ws, p
 
     def updown_gen_step(self, x_lo, x_hi, G, G_speed, vbias, vbias_speed, gauss, lr, lambda_1, lambda_2, weightcost, momentum,
