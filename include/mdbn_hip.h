@@ -992,6 +992,56 @@ int  mdbn_propdown_rowll_grouped(mdbn_ctx *ctx, void *stream, const float *h, in
                                  int64_t target_div, float *out, void *workspace, int64_t workspace_bytes,
                                  const int32_t *group_start, const int32_t *group_start_host, int64_t n_groups);
 
+/* Classification RBM (added by this engine; Larochelle & Bengio 2008): a one-hot label block in columns lo .. lo + K - 1 of the
+ * visible layer (2 <= K <= MDBN_GROUP_MAX; passed as host integers, no device table is read), everything outside the block
+ * counting as input.  With x~ = the row with the block set to zero, A = hbias + x~ W (ONE propup, shared by all classes),
+ * U = rows lo .. lo + K - 1 of W and d = vbias[lo .. lo + K):
+ *   o[y][j] = A[j] + U[y][j],   a[y] = d[y] + sum_j softplus(o[y][j]),   p(y | x) = softmax_y a[y]
+ * which is softmax_y(-F(row with category y)) exactly: the terms of F that do not depend on y cancel.
+ *
+ * mdbn_class_posterior: post [B, ldk] (float32; ldk >= K, columns K.. untouched) = p(. | x) for the rows v [B, ldv] -- what v
+ * holds inside the block is ignored unless logp (nullable, [B]) is given, which receives log p(y* | x) for the category y* the
+ * block holds (a row whose block holds no 1 leaves its entry untouched).  Launches: the kernel that writes x~, the propup
+ * (pre-activations only), the class kernel -- two passes over (y, j) per row, scores then softmax; every element forms
+ * e = exp(-|z|) once and softplus(z) = max(z, 0) + log(1 + e) from it, finite for any finite z.  No random numbers.
+ *
+ * mdbn_class_stats: the exact gradient of sum_rows log p(y* | x), ascent direction like CD's, in the packed layout of
+ * mdbn_cd_args.stats, scaled by disc_weight w and added to gen_weight times the CD statistics:
+ *   r_pos = sigmoid(o[y*][.]),  r_bar = sum_y p(y | x) sigmoid(o[y][.])
+ *   S[i][.]      (i outside the block) = sum_rows x_i (r_pos - r_bar)      s_h = sum_rows (r_pos - r_bar)
+ *   S[lo + y][.]                       = sum_rows ([y = y*] - p(y | x)) sigmoid(o[y][.])
+ *   s_v[lo + y] = sum_rows ([y = y*] - p(y | x)),  s_v elsewhere = 0
+ * gen_weight > 0 (hybrid): V2 [2B, ldv] = [v0; nv] and P2 [2B, ldh] = [ph; -nh] are the scratch a finished
+ * mdbn_cd_step_grouped (or mdbn_cd_step with keep_f32) left; the cost slot of `stats` is kept.  gen_weight = 0 (pure): V2 holds
+ * the B gathered rows v0 only, P2 is not read (may be NULL), and the cost slot receives -sum_rows log p(y* | x).  Both forms
+ * run ONE statistics GEMM, the unchanged mdbn_cd_stats, on stacked operands in the workspace:
+ *   hybrid  V2' = [v0; v0 | nv; x~]   P2' = [gen ph; w r_pos | -gen nh; -w r_bar]      (4B rows)
+ *   pure    V2' = [v0 | x~]           P2' = [w r_pos | -w r_bar]                       (2B rows)
+ * With x~'s block zero the GEMM leaves gen (CD part) + w sum_rows [y = y*] r_pos in the block's rows of S; the patch kernel then
+ * subtracts w T[y][.], T[y][.] = sum_rows p(y | x) sigmoid(o[y][.]), and rebuilds s_v whole as gen (sum v0 - sum nv) + w n
+ * (s_h is the column sum of P2' and needs no patch).  T, n and the log-likelihood go through per-workgroup partials summed in
+ * ascending order; nll_sum (nullable, device scalar) receives -sum_rows log p(y* | x) at the parameters given.  Every block of
+ * every row of v0 must hold exactly one 1 (not checked).  W, hbias, vbias are read only.
+ *
+ * No atomics, every sum in a fixed order: two runs agree bit for bit.  Pad columns H..ldh-1 and V..ldv-1 of the caller's
+ * matrices are neither read nor written, except what mdbn_cd_stats itself does to `stats`.  No call synchronises.
+ * mode of the sizer: 0 = mdbn_class_posterior, 1 = mdbn_class_stats with gen_weight = 0, 2 = with gen_weight > 0.
+ * MDBN_EINVAL with a message, before any launch and with every output untouched: sizes < 1 or > 2^24, null or misaligned
+ * matrices, a leading dimension below its width or not a multiple of 4, K < 2 or K > MDBN_GROUP_MAX, lo < 0 or lo + K > V,
+ * a negative or non-finite weight, both weights 0, gen_weight > 0 without P2; a short workspace is MDBN_ENOSPC. */
+#define MDBN_CLASS_POSTERIOR 0
+#define MDBN_CLASS_PURE      1
+#define MDBN_CLASS_HYBRID    2
+int  mdbn_class_workspace_bytes(mdbn_ctx *ctx, int64_t B, int64_t V, int64_t H, int64_t ldv, int64_t ldh, int64_t K,
+                                int mode, int64_t *bytes);
+int  mdbn_class_posterior(mdbn_ctx *ctx, void *stream, const float *v, int64_t B, int64_t ldv, const float *W, int64_t V,
+                          int64_t H, int64_t ldh, const float *hbias, const float *vbias, int64_t lo, int64_t K,
+                          float *post, int64_t ldk, float *logp, void *workspace, int64_t workspace_bytes);
+int  mdbn_class_stats(mdbn_ctx *ctx, void *stream, const float *V2, const float *P2, int64_t B, const float *W, int64_t V,
+                      int64_t H, int64_t ldv, int64_t ldh, const float *hbias, const float *vbias, int64_t lo, int64_t K,
+                      float gen_weight, float disc_weight, float *stats, float *nll_sum, void *workspace,
+                      int64_t workspace_bytes);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)) (the float32 softplus terms summed in

@@ -16,17 +16,20 @@ def _fit(net, data, held_out, batch_size, graph_output, **schedule):
     return net
 
 
-def train_top(batch_size, graph_output, joint_train_set, joint_val_set, rng, visible_groups=None, sparsity_target=None,
-              sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True, centered=False, offset_rate=0.01):
+def train_top(batch_size, graph_output, joint_train_set, joint_val_set, rng, visible_groups=None, discriminative=None,
+              label_group=-1, generative=1.0, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True,
+              centered=False, offset_rate=0.01):
     """Joint DBN over the concatenated top-layer activations of the modalities (MDBN.py:31-42).  ``sparsity_*``: the sparsity
     target, ``centered`` / ``offset_rate``: the centred gradient (``RBM.get_cost_updates``).  ``visible_groups``: categorical
     units in the joint layer (``RBM.__init__``) -- a one-hot label block appended to the activations makes it a
-    classification RBM, read out by ``RBM.group_posterior``."""
+    classification RBM, read out by ``RBM.label_posterior`` / ``RBM.predict``; ``discriminative`` / ``label_group`` /
+    ``generative`` train the joint layer for that label (the hybrid objective of ``RBM.get_cost_updates``)."""
     joint = shared(joint_train_set)
     net = DBN(numpy_rng=rng, n_ins=joint.shape[1], visible_groups=visible_groups, **TOP_SHAPE)
     return _fit(net, joint, joint_val_set, batch_size, graph_output, centered=centered, offset_rate=offset_rate,
                 sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
-                sparsity_weights=sparsity_weights, **TOP_SCHEDULE)
+                sparsity_weights=sparsity_weights, **TOP_SCHEDULE,
+                **(dict(discriminative=discriminative, label_group=label_group, generative=generative) if discriminative is not None else {}))
 
 
 def build_bottom_layer(n_visible, layers_sizes, rng, visible_groups=None):

@@ -161,6 +161,10 @@ SIGNATURES = {
     "mdbn_updown_rec_step": [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(UpdateArgs), _i32, _vp, _i64],
     "mdbn_updown_gen_grouped_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
     "mdbn_updown_gen_step_grouped": [_vp, _vp, _vp, _vp, _i64, C.POINTER(UpdateArgs), _vp, _i32, _vp, _i64, _vp, _vp, _i64],
+    "mdbn_class_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, C.POINTER(_i64)],
+    "mdbn_class_posterior": [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64],
+    "mdbn_class_stats": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _f32, _f32, _vp, _vp,
+                         _vp, _i64],
     "mdbn_round_flip": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
     "mdbn_pl_cost": [_vp, _vp, _vp, _vp, _i64, _i64, _vp],
     "mdbn_recon_cost": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64],

@@ -253,12 +253,15 @@ class DBN(object):
         return provider
 
     def training_functions(self, train_set_x, batch_size, k, lambda_1=0.0, lambda_2=0.1,
-                           monitor=False, learn_sigma=None, centered=False, offset_rate=0.01, sparsity_target=None,
-                           sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
+                           monitor=False, discriminative=None, label_group=-1, generative=1.0, learn_sigma=None, centered=False,
+                           offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         '''Per-layer step functions ``fn(indexes=, momentum=, lr=)`` and free-energy functions
         ``fn(train_sample, test_sample)`` (dbn.py:238-332).  ``centered`` / ``offset_rate``: every layer trains by the
         centred gradient; ``sparsity_*``: every layer trains with the sparsity target; ``learn_sigma``: the Gaussian INPUT
-        layer (layer 0 only) learns a standard deviation per column at that rate (``RBM.get_cost_updates``).'''
+        layer (layer 0 only) learns a standard deviation per column at that rate (``RBM.get_cost_updates``).
+        ``discriminative`` / ``label_group`` / ``generative``: the INPUT layer (layer 0 only, with ``visible_groups``) trains by
+        the hybrid or purely discriminative objective of a classification RBM (a Gaussian input layer refuses).'''
+        disc = dict(discriminative=discriminative, label_group=label_group, generative=generative) if discriminative is not None else {}
         center = dict(centered=centered, offset_rate=offset_rate) if centered else {}
         if sparsity_target is not None:
             center.update(sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
@@ -270,14 +273,15 @@ class DBN(object):
         for i, rbm in enumerate(self.rbm_layers):
             if i == 0 and learn_sigma is not None:       # (a Bernoulli input layer refuses it)
                 cost, updates = rbm.get_cost_updates(learning_rate, lambda_1=lambda_1, lambda_2=lambda_2, batch_size=batch_size,
-                                                     persistent=None, k=k, learn_sigma=learn_sigma, **center)
+                                                     persistent=None, k=k, learn_sigma=learn_sigma, **center, **disc)
             elif isinstance(rbm, GRBM):
                 cost, updates = rbm.get_cost_updates(learning_rate, lambda_1=lambda_1,
                                                      lambda_2=lambda_2, batch_size=batch_size,
-                                                     persistent=None, k=k, **center)
+                                                     persistent=None, k=k, **center, **(disc if i == 0 else {}))
             else:
                 cost, updates = rbm.get_cost_updates(learning_rate, weightcost=0.0002,
-                                                     batch_size=batch_size, persistent=None, k=k, **center)
+                                                     batch_size=batch_size, persistent=None, k=k, **center,
+                                                     **(disc if i == 0 else {}))
             train_fns.append(function(updates, train_set_x, input_fn=self._layer_input_fn(i, train_set_x),
                                       data_parallel=self.data_parallel))
             free_energy_gap_fns.append(rbm.free_energies)
@@ -285,8 +289,9 @@ class DBN(object):
 
     def training(self, train_set_x, batch_size, k, pretraining_epochs, pretrain_lr,
                  lambda_1=0.0, lambda_2=0.1, validation_set_x=None, monitor=False,
-                 graph_output=False, resume=None, on_step=None, visible_groups=None, learn_sigma=None, centered=False,
-                 offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
+                 graph_output=False, resume=None, on_step=None, visible_groups=None, learn_sigma=None, discriminative=None,
+                 label_group=-1, generative=1.0, centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0,
+                 sparsity_decay=0.9, sparsity_weights=True):
         '''Greedy layer-wise pre-training (dbn.py:334-517).  Returns, per layer, the list of
         (iteration, cost, free_energy_gap) records taken at the validation points.
 
@@ -301,7 +306,8 @@ class DBN(object):
         resume state.  ``visible_groups`` (not None): the input layer's ``set_visible_groups`` first -- it trains with
         categorical visible units (a Gaussian input layer refuses).  ``learn_sigma``: the Gaussian input layer learns a
         standard deviation per column at that rate (``training_functions``); its ``log_sigma`` and speed are part of the resume
-        state.'''
+        state.  ``discriminative`` / ``label_group`` / ``generative``: the input layer trains as a classification RBM on the
+        label block among its ``visible_groups`` (``RBM.get_cost_updates``); it keeps no state of its own.'''
         if visible_groups is not None:
             self.rbm_layers[0].set_visible_groups(visible_groups)
         data = shared(train_set_x, engine=self.engine)
@@ -314,7 +320,8 @@ class DBN(object):
                                                        lambda_1=lambda_1, lambda_2=lambda_2, monitor=monitor,
                                                        learn_sigma=learn_sigma, centered=centered, offset_rate=offset_rate,
                                                        sparsity_target=sparsity_target, sparsity_cost=sparsity_cost,
-                                                       sparsity_decay=sparsity_decay, sparsity_weights=sparsity_weights)
+                                                       sparsity_decay=sparsity_decay, sparsity_weights=sparsity_weights,
+                                                       discriminative=discriminative, label_group=label_group, generative=generative)
         self._print('... pre-training the model')
         t_start = timeit.default_timer()
         if resume is None:

@@ -1026,6 +1026,53 @@ class HipEngine(object):
                                                  C.c_void_p(groups.host.ctypes.data), groups.n_groups), "mdbn_cd_step_grouped")
         return call.stats, call.scratch
 
+    # ------------------------------------------------------------------ classification RBM (mdbn_class_*)
+    def _class_workspace(self, B, V, H, ldv, ldh, K, mode):
+        key = (B, V, H, ldv, ldh, K, mode)
+        cache = self.__dict__.setdefault("_class_need", {})
+        need = cache.get(key)
+        if need is None:
+            n = C.c_int64()
+            _lib.check(self.lib.mdbn_class_workspace_bytes(self.ctx, B, V, H, ldv, ldh, K, mode, C.byref(n)), "mdbn_class_workspace_bytes")
+            need = cache[key] = n.value
+        ws = getattr(self, "_class_ws", None)
+        if ws is None or ws.numel() * 4 < need:
+            ws = self._class_ws = self._alloc_scratch(need, "mdbn_class_workspace_bytes")
+        return ws
+
+    def class_posterior(self, v, W, hbias, vbias, lo, K, want_logp=False):
+        """Exact p(label | everything else) of the one-hot label block in columns ``lo .. lo + K - 1`` for every row of ``v``
+        (mdbn_class_posterior: one propup of the rows with the block set to zero and one class kernel): ``(post, logp)`` --
+        float32 device tensors [B, K] and, with ``want_logp``, [B] = log p(y* | x) for the category the block holds (else None)."""
+        v = self.as_matrix(v)
+        B, V = v.shape
+        H, ldv, ldh = W.shape[1], v.stride(0), W.stride(0)
+        post = torch.zeros((B, K), dtype=torch.float32, device=self.device)
+        logp = torch.zeros(B, dtype=torch.float32, device=self.device) if want_logp else None
+        if B == 0:
+            return post, logp
+        ws = self._class_workspace(B, V, H, ldv, ldh, K, 0)
+        _lib.check(self.lib.mdbn_class_posterior(self.ctx, self._stream(), self._p(v), B, ldv, self._p(W), V, H, ldh, self._p(hbias),
+                                                 self._p(vbias), int(lo), int(K), self._p(post), int(K), self._p(logp), self._p(ws),
+                                                 ws.numel() * 4), "mdbn_class_posterior")
+        return post, logp
+
+    def class_stats(self, scratch, v0, B, W, hbias, vbias, lo, K, gen_weight, disc_weight, stats):
+        """``gen_weight`` x (the CD statistics of the finished ``cd_step_grouped`` that filled ``scratch``: V2 = [v0; nv],
+        P2 = [ph; -nh]) + ``disc_weight`` x (the exact gradient of sum_rows log p(y* | x) for the label block
+        ``lo .. lo + K - 1``) into the packed ``stats`` that step left (mdbn_class_stats).  ``gen_weight`` = 0: no step ran,
+        ``scratch`` is None, ``v0`` holds the gathered rows, and the cost slot of ``stats`` receives -sum log p.  Returns
+        -sum_rows log p(y* | x) as a 0-d device tensor."""
+        V2, P2 = (scratch.V2, scratch.P2) if scratch is not None else (self.as_matrix(v0), None)
+        V, H = W.shape
+        ldv, ldh = V2.stride(0), W.stride(0)
+        nll = torch.zeros(1, dtype=torch.float32, device=self.device)
+        ws = self._class_workspace(int(B), V, H, ldv, ldh, int(K), 2 if gen_weight > 0.0 else 1)
+        _lib.check(self.lib.mdbn_class_stats(self.ctx, self._stream(), self._p(V2), self._p(P2), int(B), self._p(W), V, H, ldv, ldh,
+                                             self._p(hbias), self._p(vbias), int(lo), int(K), float(gen_weight), float(disc_weight),
+                                             self._p(stats), self._p(nll), self._p(ws), ws.numel() * 4), "mdbn_class_stats")
+        return nll[0]
+
     def center_hidden_rows(self, scratch, B, stats, V, H, ldv, ldh, mu, lam, row_scale, sparsity=None):
         """The centred hidden-bias statistic s_h' = s_h - row_scale S'^T mu from the ROWS of the step's scratch
         (mdbn_center_hidden_rows) instead of from S: [H] device vector.  Call it between ``center_offsets`` and ``center_stats``

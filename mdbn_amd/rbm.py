@@ -47,7 +47,8 @@ class UpdatePlan(object):
 
     def __init__(self, rbm, lr, k, lambda_1, lambda_2, weightcost, batch_size, persistent, W0,
                  symbolic_grad=False, centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0,
-                 sparsity_decay=0.9, sparsity_weights=True, grouped=None, learn_sigma=None):
+                 sparsity_decay=0.9, sparsity_weights=True, grouped=None, learn_sigma=None, disc_weight=None, gen_weight=1.0,
+                 label_span=None):
         self.rbm, self.lr, self.k = rbm, lr, int(k)
         self.lambda_1, self.lambda_2, self.weightcost = lambda_1, lambda_2, weightcost
         self.batch_size, self.persistent, self.W0 = batch_size, persistent, W0
@@ -71,6 +72,11 @@ class UpdatePlan(object):
         # x exp(-log_sigma); ``learn_sigma``: the rate of log_sigma's own exact gradient step, None: sigma stays as it is
         self.sigma = rbm.log_sigma is not None
         self.learn_sigma = None if learn_sigma is None else float(learn_sigma)
+        # classification RBM (StepFunction._statistics_step): ``disc_weight`` w > 0 adds w x the exact gradient of
+        # sum_rows log p(label | rest) for the label block ``label_span`` = (first column, K) to ``gen_weight`` x the CD
+        # statistics; gen_weight = 0: purely discriminative, no chain is run.  None: none of it
+        self.disc_weight = None if disc_weight is None else float(disc_weight)
+        self.gen_weight, self.label_span = float(gen_weight), label_span
 
 
 class LazyCost(object):
@@ -243,6 +249,18 @@ class StepFunction(object):
             raise NotImplementedError("a layer with log_sigma (learned per-column variance) on a data-parallel group of %d "
                                       "ranks: the step of log_sigma needs the rows of the whole minibatch, which is not "
                                       "built yet" % self.group.world_size)
+        self.discriminative_nll = None      # 0-d device tensor: -sum log p(label | rest) of the last minibatch (a discriminative plan)
+        if p.disc_weight is not None:
+            if self.group is not None and self.group.world_size > 1:
+                raise NotImplementedError("discriminative= on a data-parallel group of %d ranks: the discriminative statistics "
+                                          "are not sharded yet" % self.group.world_size)
+            if not hasattr(self.rbm.engine, "class_stats"):
+                raise NotImplementedError("discriminative= needs an engine with the classification calls (class_stats); %s has "
+                                          "none" % type(self.rbm.engine).__name__)
+            if input_fn is None and train_set_x is not None:
+                # (once, on the host: a label block that is not one-hot has no category to train for)
+                lo, K = p.label_span
+                self.rbm._check_one_hot(train_set_x, spans=[(lo, lo + K)])
         self._pending = None                # Pending: the deferred half of the last overlapped step
         self._feed = None                   # HostFeed of a host-resident table, made by its first announcement or step
         self._n_calls = 0
@@ -410,6 +428,14 @@ class StepFunction(object):
             return self._single_device_step(mb, step, lr, momentum, batch_size, next_indexes)
         return self._group_step(mb, step, lr, momentum, batch_size, next_indexes, distributed)
 
+    @property
+    def discriminative_cost(self):
+        """Mean -log p(label | rest) over the last minibatch, at the parameters before its update (a plan with
+        ``discriminative=``; None before the first step).  Reading it synchronises."""
+        if self.discriminative_nll is None:
+            return None
+        return float(self.discriminative_nll) / self._disc_rows
+
     def _single_device_step(self, mb, step, lr, momentum, batch_size, next_indexes):
         """The whole step function in one library call (mdbn_cd_train_step)."""
         p, rbm, eng = self.plan, self.rbm, self.engine
@@ -504,7 +530,13 @@ class StepFunction(object):
         conditional means m = vbias + ph_mean W^T (one noise-free propdown of the scratch's ph_mean, no RNG step) and
         ``sigma_update`` follow: g = mean_r[u (u - m)] - 1, exact -- no chain state enters --, taken at the parameters of
         before ``apply_update``; log_sigma then takes the visible bias's rule at rate ``learn_sigma``, clamped to
-        ``GRBM.log_sigma_range``."""
+        ``GRBM.log_sigma_range``.
+
+        Classification RBM (a plan with ``disc_weight`` w; Larochelle & Bengio 2008): right after the grouped CD step, and
+        before the sparsity transform, ``class_stats`` replaces the statistics by gen_weight x (those of the CD step) + w x
+        (the exact gradient of sum_rows log p(label | rest)) -- one statistics GEMM on the stacked operands of both.  With
+        gen_weight = 0 no chain is run: the rows are gathered and ``class_stats`` forms the discriminative statistics alone;
+        the monitoring cost is then the mean -log p(label | rest), which ``discriminative_cost`` gives in both forms."""
         p, rbm, eng = self.plan, self.rbm, self.engine
         data = mb.data
         fed = mb                                        # the rows as they arrived (a fed buffer goes back once they are read)
@@ -525,14 +557,28 @@ class StepFunction(object):
                 raise ValueError("persistent chain has %d rows but the minibatch has %d (the reference fails the same way, "
                                  "rbm.py:416)" % (persistent.shape[0], mb.n_global))
         V, H, ldv, ldh = rbm.n_visible, rbm.n_hidden, data.stride(0), rbm.W.tensor.stride(0)
+        pure = p.disc_weight is not None and p.gen_weight == 0.0
+        if pure:                                        # no chain: the gathered rows are all the statistics need
+            v0 = eng.gather_rows(data, mb.idx) if mb.idx is not None else data
+            ldv = v0.stride(0)
         if self._stats_slots[0] is None:
             self._stats_slots[0] = eng.new_stats_buffer(V, H, ldv, ldh)
         stats = self._stats_slots[0]
         self._n_calls += 1
-        if p.grouped is not None:
+        if pure:
+            lo, K = p.label_span
+            self._disc_rows = mb.n_global
+            self.discriminative_nll = eng.class_stats(None, v0, mb.n_global, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, lo, K,
+                                                      0.0, p.disc_weight, stats)
+        elif p.grouped is not None:
             _, scratch = eng.cd_step_grouped(data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, p.k,
                                              self._rng_addr(step, mb.lo), p.grouped, persistent=persistent, stats=stats,
                                              keep_f32=True)
+            if p.disc_weight is not None:
+                lo, K = p.label_span
+                self._disc_rows = mb.n_global
+                self.discriminative_nll = eng.class_stats(scratch, None, mb.n_global, rbm.W.tensor, rbm.hbias.tensor,
+                                                          rbm.vbias.tensor, lo, K, p.gen_weight, p.disc_weight, stats)
         else:
             _, scratch = eng.cd_step(data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, rbm.gauss, p.k,
                                      self._rng_addr(step, mb.lo), persistent=persistent, stats=stats, keep_f32=True)
@@ -779,12 +825,13 @@ class RBM(object):
             raise NotImplementedError("%s on a layer with categorical visible units (visible_groups) is not built yet: it "
                                       "would sample the groups as independent sigmoid units" % what)
 
-    def _check_one_hot(self, data):
-        """ValueError unless every group of every row of ``data`` (host copy) holds exactly one 1 and zeros."""
+    def _check_one_hot(self, data, spans=None):
+        """ValueError unless every group (``spans``: only these) of every row of ``data`` (host copy) holds exactly one 1 and
+        zeros."""
         if isinstance(data, torch.Tensor):
             data = data.detach().cpu().numpy()
         x = numpy.asarray(getattr(data, "get_value", lambda: data)())
-        for lo, hi in self.visible_groups.spans():
+        for lo, hi in (self.visible_groups.spans() if spans is None else spans):
             g = x[:, lo:hi]
             bad = numpy.nonzero(~(((g == 0) | (g == 1)).all(axis=1) & (g.sum(axis=1) == 1)))[0]
             if bad.size:
@@ -1038,6 +1085,45 @@ class RBM(object):
         neg_F -= neg_F.max(axis=1, keepdims=True)
         p = numpy.exp(neg_F)
         return p / p.sum(axis=1, keepdims=True)
+
+    def _label_span(self, group, what):
+        """(first column, K) of softmax group ``group`` (negative: from the end), the label block of a classification RBM."""
+        if self.visible_groups is None:
+            raise ValueError("%s needs a layer with visible_groups: the label block is one of its groups" % what)
+        n = self.visible_groups.n_groups
+        if not -n <= int(group) < n:
+            raise ValueError("%s: label group %r of a layer with %d groups" % (what, group, n))
+        lo, hi = self.visible_groups.spans()[int(group) % n]
+        return lo, hi - lo
+
+    def _class_call(self, v, group, what, want_logp):
+        lo, K = self._label_span(group, what)
+        if not hasattr(self.engine, "class_posterior"):
+            raise NotImplementedError("%s needs an engine with the classification calls (class_posterior); %s has none"
+                                      % (what, type(self.engine).__name__))
+        if want_logp:
+            self._check_one_hot(v, spans=[(lo, lo + K)])
+        return self.engine.class_posterior(as_tensor(v, self.engine), self.W.tensor, self.hbias.tensor, self.vbias.tensor, lo, K,
+                                           want_logp=want_logp)
+
+    def label_posterior(self, v, group=-1):
+        """Exact p(category | all other visibles) of softmax group ``group`` (the label block of a classification RBM;
+        default: the last group) for every row of ``v``: float64 [N, K].  The numbers of ``group_posterior`` from one device
+        call -- one propup of the rows with the block set to zero, shared by all categories, and one kernel for the K scores
+        and their softmax -- instead of K free-energy passes.  What ``v`` holds inside the group is ignored; no random number
+        is consumed."""
+        post, _ = self._class_call(v, group, "label_posterior", False)
+        return post.detach().cpu().to(torch.float64).numpy()
+
+    def predict(self, v, group=-1):
+        """The most probable category of group ``group`` for every row of ``v`` (``label_posterior``): int64 [N]."""
+        return self.label_posterior(v, group).argmax(axis=1)
+
+    def label_log_likelihood(self, v, group=-1):
+        """log p(y* | all other visibles) for every row of ``v``, y* the category its block of group ``group`` holds (exactly
+        one 1, checked on the host): float64 [N].  No random number is consumed."""
+        _, logp = self._class_call(v, group, "label_log_likelihood", True)
+        return logp.detach().cpu().to(torch.float64).numpy()
 
     def gibbs_hvh(self, h0_sample):
         ''' One Gibbs step starting from the hidden state (rbm.py:242-248) '''
@@ -1329,8 +1415,9 @@ class RBM(object):
 
     # ------------------------------------------------------------------ CD-k / PCD-k
     def get_cost_updates(self, lr=0.1, k=1, lambda_1=0.0, lambda_2=0.0, weightcost=0.0,
-                         batch_size=None, persistent=None, symbolic_grad=False, learn_sigma=None, centered=False,
-                         offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
+                         batch_size=None, persistent=None, symbolic_grad=False, discriminative=None, label_group=-1,
+                         generative=1.0, learn_sigma=None, centered=False, offset_rate=0.01, sparsity_target=None,
+                         sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         """One step of CD-k or PCD-k (rbm.py:258-376).  Returns ``(cost, updates)``; pass
         ``updates`` to ``mdbn_amd.function`` to obtain the step function.
 
@@ -1355,7 +1442,35 @@ class RBM(object):
         GRBM, and every step moves it by its exact gradient at rate eta under the visible bias's momentum rule
         (``StepFunction._statistics_step``).  A layer whose ``log_sigma`` is set trains in units with or without it: None
         keeps sigma as it is.  The monitoring cost of such a layer is in units.  Composes with ``centered`` and the sparsity
-        target, not with ``symbolic_grad``."""
+        target, not with ``symbolic_grad``.
+        ``discriminative`` w > 0 (a layer with ``visible_groups``; Larochelle & Bengio 2008): group ``label_group`` is a
+        one-hot label block and the step follows the hybrid objective -- ``generative`` x (the CD statistics) + w x (the exact
+        gradient of sum_rows log p(label | all other visibles), no sampling) through the unchanged update rule.
+        ``generative=0`` trains the label's conditional alone and runs no chain (no ``persistent``, no sparsity target: both
+        live on the chain's rows); the monitoring cost is then the mean -log p(label | rest), which the step function's
+        ``discriminative_cost`` gives in either form.  A sparsity target composes with ``generative > 0``; ``centered`` and
+        ``symbolic_grad`` do not compose.  None: nothing changes."""
+        label_span = None
+        if discriminative is not None:
+            w, alpha = float(discriminative), float(generative)
+            if not (w > 0.0 and numpy.isfinite(w)):
+                raise ValueError("discriminative must be a positive weight, got %r" % (discriminative,))
+            if not (alpha >= 0.0 and numpy.isfinite(alpha)):
+                raise ValueError("generative must be a weight >= 0, got %r" % (generative,))
+            label_span = self._label_span(label_group, "get_cost_updates(discriminative=)")
+            if centered:
+                raise NotImplementedError("discriminative= with centered=True is not built: the offsets are defined on the rows "
+                                          "of the CD step, the discriminative statistics have none")
+            if symbolic_grad:
+                raise NotImplementedError("discriminative= with symbolic_grad=True is not supported")
+            if alpha == 0.0 and persistent is not None:
+                raise NotImplementedError("generative=0 runs no chain: a persistent chain would never move (pass persistent=None)")
+            if alpha == 0.0 and sparsity_target is not None and float(sparsity_cost) > 0.0:
+                raise NotImplementedError("generative=0 with a sparsity target: the activity estimate reads the hidden means of "
+                                          "the CD step, which is not run")
+            if not hasattr(self.engine, "class_stats"):
+                raise NotImplementedError("discriminative= needs an engine with the classification calls (class_stats); %s has "
+                                          "none" % type(self.engine).__name__)
         if learn_sigma is not None:
             if not self.gauss:
                 raise ValueError("learn_sigma: a Bernoulli visible layer has no variance to learn (a GRBM has)")
@@ -1405,7 +1520,9 @@ class RBM(object):
         updates = UpdatePlan(self, lr, k, lambda_1, lambda_2, weightcost, batch_size, persistent, W0,
                              symbolic_grad=symbolic_grad, centered=centered, offset_rate=offset_rate,
                              sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
-                             sparsity_weights=sparsity_weights, grouped=self.visible_groups, learn_sigma=learn_sigma)
+                             sparsity_weights=sparsity_weights, grouped=self.visible_groups, learn_sigma=learn_sigma,
+                             disc_weight=discriminative, gen_weight=generative if discriminative is not None else 1.0,
+                             label_span=label_span)
         cost = CostHandle('pseudo_likelihood' if (persistent is not None and self.visible_groups is None) else 'reconstruction')
         return cost, updates
 
@@ -1438,8 +1555,8 @@ class RBM(object):
     def training(self, train_set_x, validation_set_x, training_epochs, batch_size=10,
                  learning_rate=0.1, k=1, initial_momentum=0.0, final_momentum=0.0,
                  weightcost=0.0, lambda_2=0.0, persistent=True, display_fn=None, graph_output=False, tempering=None,
-                 visible_groups=None, centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9,
-                 sparsity_weights=True):
+                 visible_groups=None, discriminative=None, label_group=-1, generative=1.0, centered=False, offset_rate=0.01,
+                 sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         """rbm.py:484-520 (note: like the reference, ``lambda_2`` is accepted but not used).
 
         ``tempering=R`` (with ``persistent``): PCD whose negative chains are the beta = 1 replicas of ``batch_size``
@@ -1448,9 +1565,11 @@ class RBM(object):
         None: nothing changes.  On a layer with ``visible_groups`` the ladders are the grouped ones (``tempered_chains``) and
         the step the grouped PCD step.  ``centered`` / ``offset_rate``: the centred gradient, ``sparsity_*``: the sparsity target
         (``get_cost_updates``).  ``visible_groups`` (not None): ``set_visible_groups`` first -- the layer trains with
-        categorical visible units."""
+        categorical visible units.  ``discriminative`` / ``label_group`` / ``generative``: the hybrid or purely discriminative
+        objective of a classification RBM (``get_cost_updates``); ``generative=0`` needs ``persistent=False``."""
         if visible_groups is not None:
             self.set_visible_groups(visible_groups)
+        disc = dict(discriminative=discriminative, label_group=label_group, generative=generative) if discriminative is not None else {}
         if tempering is not None:
             if self.visible_groups is not None and not hasattr(self.engine, "temper_grouped"):
                 self._no_groups("training(tempering=) on this engine")
@@ -1464,7 +1583,7 @@ class RBM(object):
                                               batch_size=batch_size, persistent=persistent_chain,
                                               centered=centered, offset_rate=offset_rate, sparsity_target=sparsity_target,
                                               sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
-                                              sparsity_weights=sparsity_weights)
+                                              sparsity_weights=sparsity_weights, **disc)
         step_hooks = None
         if tempering is not None:
             if not persistent:
