@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--rows", type=int, default=1024)
     ap.add_argument("--epochs", type=int, default=40)
     ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--drop", type=float, default=0.0, help="share of patients that lose one modality: also train the joint layer "
+                    "on all of them (MDBN.train_joint)")
     args = ap.parse_args()
     DBN.verbose = False
     rng = numpy.random.RandomState(123)                     # AMLsm2.py:30-31: one rng threaded through
@@ -66,6 +68,19 @@ def main():
     top.training(shared(joint_t), args.batch, k=1, pretraining_epochs=[args.epochs * (len(joint_t) // args.batch)] * 2,
                  pretrain_lr=[0.1, 0.1], validation_set_x=shared(joint_v))
     nets["top"] = top
+    if args.drop > 0.0:
+        # patients who lack a modality (the ones data/AML/common_pat_id.sh drops): a row of NaN in that modality's table; the
+        # joint layer trains on all of them, a missing block being absent from that patient's RBM (MDBN.train_joint)
+        from mdbn_amd.MDBN import TOP_SCHEDULE, train_joint
+        rows = {n: preprocess_table(tables[n], holdout=0.1, repeats=1, shuffle=False)[0].copy() for n in ("ME", "GE", "SM")}
+        lost = numpy.random.RandomState(1).uniform(size=len(joint_t)) < args.drop
+        which = numpy.random.RandomState(2).randint(3, size=len(joint_t))
+        for i, n in enumerate(("ME", "GE", "SM")):
+            rows[n][lost & (which == i)] = numpy.nan
+        TOP_SCHEDULE.update(pretraining_epochs=[args.epochs * (len(joint_t) // args.batch)] * 2)
+        top_all = train_joint([nets[n] for n in ("me", "ge", "sm")], [rows[n] for n in ("ME", "GE", "SM")], args.batch, rng)
+        print("joint layer trained on all %d patients, %d of them lacking one modality" % (len(joint_t), int(lost.sum())))
+        del top_all
     classes, D = find_unique_classes((top.get_output(joint_t) > 0.5) * numpy.ones(1))  # AMLsm2.py:103-105
     print("joint layer %s -> %d classes; trained in %.1f s" % (top.number_of_nodes(), len(numpy.unique(classes)), time.time() - t0))
     with tempfile.TemporaryDirectory() as d:

@@ -1042,6 +1042,63 @@ int  mdbn_class_stats(mdbn_ctx *ctx, void *stream, const float *V2, const float 
                       float gen_weight, float disc_weight, float *stats, float *nll_sum, void *workspace,
                       int64_t workspace_bytes);
 
+/* Absent visible units (added by this engine; Salakhutdinov, Mnih & Hinton 2007): training on tables with missing entries.
+ * NaN in a row means "this row did not observe this unit"; such a unit is absent from that row's RBM, every row has its own
+ * RBM over the set O_r it observed, and all rows share W, hbias, vbias.  With m_ri = [i in O_r] and v~ = m o v (0 where absent):
+ *   h | v:  sigmoid(hbias + v~ W);   v_i | h, i in O_r: as mdbn_cd_step draws it;  i not in O_r: 0
+ *   S = sum_r v~0_r' ph_r - n~v_r' nh_r,   s_h = sum_r ph_r - nh_r,   s_v[i] = sum_r m_ri (v0_ri - nv_ri)
+ * -- CD with a per-row mask, the CD approximation of the gradient of sum_rows log p_{O_r}(v_{r, O_r}).  A row that observed
+ * nothing has ph = nh bit for bit and contributes nothing.  The divisors of the update stay the batch size: the step is the
+ * gradient of the MEAN log-likelihood per row, not renormalised per column.
+ *
+ * mdbn_absent_split: x [B, ldx] may hold NaN in columns < V (only NaN marks a missing entry; +-inf are values).  filled
+ * [B, ld_filled] receives x with 0 where missing (filled may be x: in place); observed [B, words], words = (V + 31) / 32,
+ * bit (i & 31) of word (i >> 5) set when entry i is observed, bits of columns >= V zero; row_count [B] (nullable) the number
+ * of observed entries of each row.  Pad columns are neither read nor written.
+ *
+ * mdbn_absent_visible: p(v | h) of such rows from the linear pre-activations pre [B, ldv] = h W^T + vbias, with the geometry
+ * and Philox addressing of mdbn_group_softmax_sample without groups (one uniform per column and 4-row block at rng->draw; the
+ * normal of a noisy Gaussian layer at rng->draw | the normal bit).  gauss = 0: mean = sigmoid(pre), sample = (u < mean) --
+ * with every bit set bit for bit mdbn_propdown_sample's --; gauss = 1: mean = pre, sample = mean [+ N(0, 1) if add_noise].
+ * Absent entries of mean / sample / tap (each nullable, mean may be pre) are exactly 0.  With v0 (zero-filled) cost_sum[0]
+ * receives the sum over OBSERVED entries of the cross-entropy (gauss = 0) or of (sigmoid(pre) - v0)^2 (gauss = 1), through
+ * per-workgroup partials in `workspace` (mdbn_absent_visible_workspace_bytes).  Pad columns are neither read nor written.
+ *
+ * mdbn_cd_step_absent: mdbn_cd_step_grouped's composition on a->data rows that may hold NaN: gather, mdbn_absent_split in
+ * place on rows 0..B-1 of V2, propup; k x [linear propdown, the masked visible kernel, propup from the masked 0/1 sample --
+ * gauss: from the masked mean --]; mdbn_cd_stats.  It leaves V2 = [v~0; n~v], P2 = [ph; -nh], hs, vs (required, for Gaussian
+ * layers too: the masked sample), the packed statistics with the cost above of the last step in the cost slot, and trace_h /
+ * trace_v when given.  Draw numbering of mdbn_cd_step_grouped.  The plane, keep_f32 and gather-ahead fields are ignored.  The
+ * mask words and the cost partials live in a->workspace behind the step's own: mdbn_cd_step_absent_workspace_bytes is exact.
+ *
+ * mdbn_absent_mark_rows: rows of y [N, ld] whose row_count is 0 become NaN in columns < cols.
+ *
+ * mdbn_free_energy_absent: F_O(x_r) over the observed units of every row of x [N, ldv] (NaN = missing):
+ *   gauss = 0:  -sum_{i in O} b_i v_i - sum_j softplus(c_j + (v~ W)_j)
+ *   gauss = 1:  1/2 sum_{i in O} (v_i - b_i)^2 - sum_j softplus(c_j + (v~ W)_j)
+ * = mdbn_free_energy of the zero-filled rows, minus 1/2 sum_{i not in O} b_i^2 for a Gaussian layer (summed per row in a
+ * fixed order).  x is not written; the zero-filled copy lives in the workspace.
+ *
+ * No atomics, every sum in a fixed order: two runs agree bit for bit.  No call synchronises.  MDBN_EINVAL with a message,
+ * before any launch and with every output untouched: sizes < 1 or > 2^24, null or misaligned pointers, a leading dimension
+ * below its width or not a multiple of 4, sampling without rng, v0 without cost_sum, and for the step a->persistent,
+ * a->sample_stats and what mdbn_cd_step refuses; a short workspace is MDBN_ENOSPC, likewise before any launch. */
+int  mdbn_absent_split(mdbn_ctx *ctx, void *stream, const float *x, int64_t B, int64_t ldx, int64_t V, float *filled,
+                       int64_t ld_filled, uint32_t *observed, int32_t *row_count);
+int  mdbn_absent_visible_workspace_bytes(mdbn_ctx *ctx, int64_t B, int64_t V, int64_t *bytes);
+int  mdbn_absent_visible(mdbn_ctx *ctx, void *stream, const float *pre, int64_t B, int64_t ldv, int64_t V,
+                         const uint32_t *observed, int gauss, int add_noise, float *mean, float *sample, float *tap,
+                         const mdbn_rng *rng, const float *v0, float *cost_sum, void *workspace, int64_t workspace_bytes);
+int  mdbn_cd_step_absent_workspace_bytes(mdbn_ctx *ctx, int64_t B, int64_t V, int64_t H, int64_t ldv, int64_t ldh,
+                                         int64_t *bytes);
+int  mdbn_cd_step_absent(mdbn_ctx *ctx, void *stream, const mdbn_cd_args *a);
+int  mdbn_absent_mark_rows(mdbn_ctx *ctx, void *stream, float *y, int64_t N, int64_t ld, int64_t cols,
+                           const int32_t *row_count);
+int  mdbn_free_energy_absent_workspace_bytes(mdbn_ctx *ctx, int64_t N, int64_t V, int64_t H, int64_t ldv, int64_t *bytes);
+int  mdbn_free_energy_absent(mdbn_ctx *ctx, void *stream, const float *x, int64_t N, int64_t ldv, const float *W, int64_t V,
+                             int64_t H, int64_t ldh, const float *hbias, const float *vbias, int gauss, float *out,
+                             void *workspace, int64_t workspace_bytes);
+
 /* Pieces of get_pseudo_likelihood_cost (src/rbm.py:421-447): out = round(x) (tensor.round: half away from
  * zero) with column flip_col replaced by 1 - round(x) (flip_col < 0: no flip); then, from the free energies of
  * the two matrices, cost_out[0] = -mean(n_visible * softplus(fe - fe_flip)) (the float32 softplus terms summed in

@@ -17,18 +17,20 @@ def _fit(net, data, held_out, batch_size, graph_output, **schedule):
 
 
 def train_top(batch_size, graph_output, joint_train_set, joint_val_set, rng, visible_groups=None, discriminative=None,
-              label_group=-1, generative=1.0, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True,
-              centered=False, offset_rate=0.01):
+              label_group=-1, generative=1.0, missing=False, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9,
+              sparsity_weights=True, centered=False, offset_rate=0.01):
     """Joint DBN over the concatenated top-layer activations of the modalities (MDBN.py:31-42).  ``sparsity_*``: the sparsity
     target, ``centered`` / ``offset_rate``: the centred gradient (``RBM.get_cost_updates``).  ``visible_groups``: categorical
     units in the joint layer (``RBM.__init__``) -- a one-hot label block appended to the activations makes it a
     classification RBM, read out by ``RBM.label_posterior`` / ``RBM.predict``; ``discriminative`` / ``label_group`` /
-    ``generative`` train the joint layer for that label (the hybrid objective of ``RBM.get_cost_updates``)."""
+    ``generative`` train the joint layer for that label (the hybrid objective of ``RBM.get_cost_updates``).  ``missing=True``:
+    the joint table may hold NaN where a patient lacks a modality (``train_joint`` builds such a table) -- every layer trains
+    by the absent-unit step (``DBN.training``)."""
     joint = shared(joint_train_set)
     net = DBN(numpy_rng=rng, n_ins=joint.shape[1], visible_groups=visible_groups, **TOP_SHAPE)
     return _fit(net, joint, joint_val_set, batch_size, graph_output, centered=centered, offset_rate=offset_rate,
                 sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
-                sparsity_weights=sparsity_weights, **TOP_SCHEDULE,
+                sparsity_weights=sparsity_weights, **TOP_SCHEDULE, **({"missing": True} if missing else {}),
                 **(dict(discriminative=discriminative, label_group=label_group, generative=generative) if discriminative is not None else {}))
 
 
@@ -99,13 +101,15 @@ def train_modalities(modalities, rng, group="auto", shuffle_seed=None, graph_out
 
 def train_bottom_layer(train_set, validation_set, batch_size=20, k=1, layers_sizes=[40],
                        pretraining_epochs=[800], pretrain_lr=[0.005], lambda_1=0.0, lambda_2=0.1,
-                       rng=None, graph_output=False, visible_groups=None, learn_sigma=None, sparsity_target=None,
+                       rng=None, graph_output=False, visible_groups=None, learn_sigma=None, missing=False, sparsity_target=None,
                        sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True, centered=False, offset_rate=0.01):
     """DBN of one modality, Gaussian first layer (MDBN.py:45-76).  Returns the network and its
     outputs for the training and the validation rows (None without validation rows).  ``sparsity_*``: the sparsity target,
     ``centered`` / ``offset_rate``: the centred gradient (``RBM.get_cost_updates``).  ``visible_groups``: a categorical
     modality, on a Bernoulli first layer with those softmax groups (``build_bottom_layer``).  ``learn_sigma``: the Gaussian
-    first layer learns a standard deviation per column at that rate (``DBN.training``)."""
+    first layer learns a standard deviation per column at that rate (``DBN.training``).  ``missing=True``: the tables may hold
+    NaN for entries that were not measured (a sparse mutation or methylation table with holes; a row of NaN: a patient without
+    this modality) -- every layer trains by the absent-unit step, and the outputs are those of ``get_output(missing=True)``."""
     rows = shared(train_set)
     held_out = None if validation_set is None else shared(validation_set)
     n_visible, n_top = rows.shape[1], layers_sizes[-1]
@@ -116,8 +120,49 @@ def train_bottom_layer(train_set, validation_set, batch_size=20, k=1, layers_siz
                rows, held_out, batch_size, graph_output, k=k, pretraining_epochs=pretraining_epochs,
                pretrain_lr=pretrain_lr, lambda_1=lambda_1, lambda_2=lambda_2, centered=centered, offset_rate=offset_rate,
                sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
-               sparsity_weights=sparsity_weights, **({} if learn_sigma is None else dict(learn_sigma=learn_sigma)))
+               sparsity_weights=sparsity_weights, **({} if learn_sigma is None else dict(learn_sigma=learn_sigma)),
+               **({"missing": True} if missing else {}))
+    if missing:
+        return net, net.get_output(rows, missing=True), net.get_output(held_out, missing=True)
     return net, net.get_output(rows), net.get_output(held_out)
+
+
+def joint_table(nets, inputs):
+    """The joint layer's table for patients who may lack modalities: ``inputs[i]`` is the data matrix of modality i, or None
+    when nobody has it, with the NaN-row convention of ``impute_modalities`` -- a row of NaN: this patient lacks modality i.
+    Every modality goes up by ``get_output(missing=True)`` (a row that is only partly NaN is allowed: the modality network
+    takes it zero-filled), and a patient without the modality gets a block of NaN.  A patient with no modality at all is
+    refused (ValueError).  Returns a float32 host array [N, sum of the modality tops]."""
+    import numpy
+    widths = [net.stacked_layers_sizes[-1] for net in nets]
+    if len(inputs) != len(nets):
+        raise ValueError("one input (or None) per modality")
+    rows = [len(x) for x in inputs if x is not None]
+    if not rows or len(set(rows)) != 1:
+        raise ValueError("at least one modality must be given, and all given ones need the same number of rows")
+    table = numpy.full((rows[0], sum(widths)), numpy.nan, dtype=numpy.float32)
+    lo = 0
+    for net, x, w in zip(nets, inputs, widths):
+        if x is not None:
+            x = numpy.asarray(getattr(x, "get_value", lambda: x)(), dtype=numpy.float32)
+            table[:, lo:lo + w] = net.get_output(x, missing=True)       # (rows of NaN come out as rows of NaN)
+        lo += w
+    nobody = numpy.flatnonzero(numpy.isnan(table).all(axis=1))
+    if nobody.size:
+        raise ValueError("%d patient(s) have no modality at all (first: row %d): nothing to train on" % (nobody.size, nobody[0]))
+    return table
+
+
+def train_joint(nets, inputs, batch_size, rng, graph_output=False, validation_inputs=None, **top):
+    """The joint DBN trained on ALL patients, whichever modalities each one has -- what replaces keeping only the patients
+    present in every table (data/AML/common_pat_id.sh).  ``nets``: the trained modality DBNs in the joint layer's column
+    order; ``inputs``: as ``joint_table``; ``validation_inputs``: the same for held-out patients, or None.  The joint table
+    holds a block of NaN where a patient lacks a modality, and ``train_top(..., missing=True)`` trains on it: such a block is
+    absent from that patient's RBM (Salakhutdinov, Mnih & Hinton 2007).  ``top``: further keywords of ``train_top`` (what
+    ``missing=True`` does not compose with is refused there).  Returns the joint DBN."""
+    table = joint_table(nets, inputs)
+    held_out = None if validation_inputs is None else joint_table(nets, validation_inputs)
+    return train_top(batch_size, graph_output, table, held_out, rng, missing=True, **top)
 
 
 def impute_modalities(nets, joint, inputs, n_steps=1000, burn_in=200, n_chains=8):

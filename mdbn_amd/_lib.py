@@ -165,6 +165,14 @@ SIGNATURES = {
     "mdbn_class_posterior": [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64],
     "mdbn_class_stats": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _f32, _f32, _vp, _vp,
                          _vp, _i64],
+    "mdbn_absent_split": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp],
+    "mdbn_absent_visible_workspace_bytes": [_vp, _i64, _i64, C.POINTER(_i64)],
+    "mdbn_absent_visible": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _rngp, _vp, _vp, _vp, _i64],
+    "mdbn_cd_step_absent_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, _i64, C.POINTER(_i64)],
+    "mdbn_cd_step_absent": [_vp, _vp, C.POINTER(CdArgs)],
+    "mdbn_absent_mark_rows": [_vp, _vp, _vp, _i64, _i64, _i64, _vp],
+    "mdbn_free_energy_absent_workspace_bytes": [_vp, _i64, _i64, _i64, _i64, C.POINTER(_i64)],
+    "mdbn_free_energy_absent": [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _i64],
     "mdbn_round_flip": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
     "mdbn_pl_cost": [_vp, _vp, _vp, _vp, _i64, _i64, _vp],
     "mdbn_recon_cost": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64],

@@ -10,7 +10,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmdbn_hip.so")
-SOURCES = ["mdbn_kernels.hip", "mdbn_planes.hip", "mdbn_small.hip", "mdbn_thin.hip", "mdbn_gchain.hip", "mdbn_stream.hip", "mdbn_ais.hip", "mdbn_clamp.hip", "mdbn_temper.hip", "mdbn_bound.hip", "mdbn_center.hip", "mdbn_sparsity.hip", "mdbn_updown.hip", "mdbn_groups.hip", "mdbn_class.hip", "mdbn_sigma.hip", "mdbn_capi.hip", "mdbn_drv_samplers.hip", "mdbn_drv_train.hip", "mdbn_drv_groups.hip", "mdbn_drv_class.hip", "mdbn_drv_sigma.hip", "mdbn_feeder.hip", "mdbn_comm.hip"]
+SOURCES = ["mdbn_kernels.hip", "mdbn_planes.hip", "mdbn_small.hip", "mdbn_thin.hip", "mdbn_gchain.hip", "mdbn_stream.hip", "mdbn_ais.hip", "mdbn_clamp.hip", "mdbn_temper.hip", "mdbn_bound.hip", "mdbn_center.hip", "mdbn_sparsity.hip", "mdbn_updown.hip", "mdbn_groups.hip", "mdbn_class.hip", "mdbn_absent.hip", "mdbn_sigma.hip", "mdbn_capi.hip", "mdbn_drv_samplers.hip", "mdbn_drv_train.hip", "mdbn_drv_groups.hip", "mdbn_drv_class.hip", "mdbn_drv_absent.hip", "mdbn_drv_sigma.hip", "mdbn_feeder.hip", "mdbn_comm.hip"]
 # every header of csrc/ (an #include the list missed would change the kernels without changing source_hash(): a stale
 # library kept and tested) plus the public header; tests/test_knob_registry.py checks the list against the #include graph
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "mdbn_hip.h")]

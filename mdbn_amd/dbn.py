@@ -10,6 +10,7 @@ Not kept: matplotlib output (``graph_output`` is accepted and ignored) and Thean
 """
 from __future__ import print_function
 
+import functools
 import sys
 import timeit
 
@@ -129,10 +130,28 @@ class DBN(object):
 
     host_chunk_rows = 16384     # rows of a host-resident table forwarded per chunk (dbn.py:146's activations)
 
-    def _forward(self, input, layer):
+    def _forward_missing(self, x, layer):
+        """``_forward`` for rows with missing entries (NaN: an absent unit, ``RBM.get_cost_updates(missing=True)``): every
+        layer takes its input zero-filled, and a row that observed nothing at a layer's input -- an unmeasured patient --
+        leaves that layer as a row of NaN (``engine.absent_mark_rows``), so it stays absent for the layers above instead of
+        being fed sigmoid(b)."""
+        eng = self.engine
+        self.rbm_layers[0]._no_sigma("get_output(missing=True)")
+        x = eng.as_matrix(x)
+        for j in range(range(self.n_layers)[layer] + 1):
+            filled, _, count = eng.absent_split(x)
+            x = eng.absent_mark_rows(self.sigmoid_layers[j].forward(filled), count)
+        return x
+
+    def _forward(self, input, layer, missing=False):
         """Device activations of ``sigmoid_layers[layer]`` for a data matrix.  A host-resident table (HostTable) is
         streamed through in row chunks -- the pinned rows are gathered over PCIe, forwarded, and only the (narrower)
-        activations stay on the device -- so the table itself is never uploaded whole."""
+        activations stay on the device -- so the table itself is never uploaded whole.  ``missing``: ``_forward_missing``
+        (a host-resident table goes up in one piece)."""
+        if missing:
+            if isinstance(input, HostTable) and input._mirror is None:
+                return self._forward_missing(input.rows(slice(0, len(input))), layer)
+            return self._forward_missing(getattr(input, "tensor", input), layer)
         if isinstance(input, HostTable) and input._mirror is None and len(input) > self.host_chunk_rows:
             import torch
             out = None
@@ -147,12 +166,13 @@ class DBN(object):
             return self.sigmoid_layers[layer].output.eval(input.rows(slice(0, len(input))))
         return self.sigmoid_layers[layer].output.eval(getattr(input, "tensor", input))
 
-    def get_output(self, input, layer=-1):
+    def get_output(self, input, layer=-1, missing=False):
         '''Output of MLP layer ``layer`` for the samples ``input`` (dbn.py:214-236): host array,
-        or None if the input is None.'''
+        or None if the input is None.  ``missing=True``: NaN entries of ``input`` are units the row did not observe; rows go
+        up zero-filled, and a row that observed nothing comes out as a row of NaN at every layer (``_forward_missing``).'''
         if input is None:
             return None
-        return self.engine.to_numpy(self._forward(input, layer))
+        return self.engine.to_numpy(self._forward(input, layer, missing))
 
     def hidden_activity(self, data):
         """``RBM.hidden_activity`` of every layer, each fed the means of the layer below for the rows ``data``: a list of
@@ -229,7 +249,7 @@ class DBN(object):
                                 weightcost=weightcost, lambda_1=lambda_1, lambda_2=lambda_2, top_lr=top_lr, on_epoch=on_epoch,
                                 path=path)
 
-    def _layer_input_fn(self, i, train_set_x):
+    def _layer_input_fn(self, i, train_set_x, missing=False):
         """Input matrix of RBM i: the data for i == 0, else the activations of layer i-1
         (dbn.py:146).  Lower layers are frozen while layer i trains (dbn.py:426-458), so
         the activations are cached until a lower layer is updated again."""
@@ -243,29 +263,36 @@ class DBN(object):
             # (... and a log_sigma given to, or taken from, the input layer: set_sigma makes a new array)
             version = tuple((r._n_updates, r.W.version, r.hbias.version, id(r.log_sigma), getattr(r.log_sigma, "version", 0))
                             for r in self.rbm_layers[:i]) + \
-                (train_set_x.version, 0 if isinstance(train_set_x, HostTable) else getattr(train_set_x.tensor, "_version", 0))
+                (train_set_x.version, 0 if isinstance(train_set_x, HostTable) else getattr(train_set_x.tensor, "_version", 0)) + \
+                ((True,) if missing else ())
             hit = self._lower_cache.get(i)
             if self.cache_lower and hit is not None and hit[0] == version and hit[1] is train_set_x:
                 return hit[2]
-            out = self._forward(train_set_x, i - 1)
+            out = self._forward(train_set_x, i - 1, missing)
             self._lower_cache[i] = (version, train_set_x, out)
             return out
         return provider
 
     def training_functions(self, train_set_x, batch_size, k, lambda_1=0.0, lambda_2=0.1,
-                           monitor=False, discriminative=None, label_group=-1, generative=1.0, learn_sigma=None, centered=False,
-                           offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
+                           monitor=False, discriminative=None, label_group=-1, generative=1.0, missing=False, learn_sigma=None,
+                           centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9,
+                           sparsity_weights=True):
         '''Per-layer step functions ``fn(indexes=, momentum=, lr=)`` and free-energy functions
         ``fn(train_sample, test_sample)`` (dbn.py:238-332).  ``centered`` / ``offset_rate``: every layer trains by the
         centred gradient; ``sparsity_*``: every layer trains with the sparsity target; ``learn_sigma``: the Gaussian INPUT
         layer (layer 0 only) learns a standard deviation per column at that rate (``RBM.get_cost_updates``).
         ``discriminative`` / ``label_group`` / ``generative``: the INPUT layer (layer 0 only, with ``visible_groups``) trains by
-        the hybrid or purely discriminative objective of a classification RBM (a Gaussian input layer refuses).'''
+        the hybrid or purely discriminative objective of a classification RBM (a Gaussian input layer refuses).
+        ``missing=True``: the table may hold NaN for entries that were not measured; EVERY layer trains by the absent-unit
+        step (``RBM.get_cost_updates``) on the activations of ``get_output(missing=True)``, in which a row that observed
+        nothing stays a row of NaN, and the free-energy functions take F over the observed units.'''
         disc = dict(discriminative=discriminative, label_group=label_group, generative=generative) if discriminative is not None else {}
         center = dict(centered=centered, offset_rate=offset_rate) if centered else {}
         if sparsity_target is not None:
             center.update(sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
                           sparsity_weights=sparsity_weights)
+        if missing:
+            center.update(missing=True)
         learning_rate = Scalar('lr')
         assert batch_size > 1                                          # dbn.py:276
         train_set_x = shared(train_set_x, engine=self.engine)
@@ -282,16 +309,16 @@ class DBN(object):
                 cost, updates = rbm.get_cost_updates(learning_rate, weightcost=0.0002,
                                                      batch_size=batch_size, persistent=None, k=k, **center,
                                                      **(disc if i == 0 else {}))
-            train_fns.append(function(updates, train_set_x, input_fn=self._layer_input_fn(i, train_set_x),
+            train_fns.append(function(updates, train_set_x, input_fn=self._layer_input_fn(i, train_set_x, missing),
                                       data_parallel=self.data_parallel))
-            free_energy_gap_fns.append(rbm.free_energies)
+            free_energy_gap_fns.append(functools.partial(rbm.free_energies, missing=True) if missing else rbm.free_energies)
         return train_fns, free_energy_gap_fns
 
     def training(self, train_set_x, batch_size, k, pretraining_epochs, pretrain_lr,
                  lambda_1=0.0, lambda_2=0.1, validation_set_x=None, monitor=False,
                  graph_output=False, resume=None, on_step=None, visible_groups=None, learn_sigma=None, discriminative=None,
-                 label_group=-1, generative=1.0, centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0,
-                 sparsity_decay=0.9, sparsity_weights=True):
+                 label_group=-1, generative=1.0, missing=False, centered=False, offset_rate=0.01, sparsity_target=None,
+                 sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         '''Greedy layer-wise pre-training (dbn.py:334-517).  Returns, per layer, the list of
         (iteration, cost, free_energy_gap) records taken at the validation points.
 
@@ -307,7 +334,9 @@ class DBN(object):
         categorical visible units (a Gaussian input layer refuses).  ``learn_sigma``: the Gaussian input layer learns a
         standard deviation per column at that rate (``training_functions``); its ``log_sigma`` and speed are part of the resume
         state.  ``discriminative`` / ``label_group`` / ``generative``: the input layer trains as a classification RBM on the
-        label block among its ``visible_groups`` (``RBM.get_cost_updates``); it keeps no state of its own.'''
+        label block among its ``visible_groups`` (``RBM.get_cost_updates``); it keeps no state of its own.
+        ``missing=True``: the tables may hold NaN for entries that were not measured -- every layer trains by the
+        absent-unit step (``training_functions``); it keeps no state of its own.'''
         if visible_groups is not None:
             self.rbm_layers[0].set_visible_groups(visible_groups)
         data = shared(train_set_x, engine=self.engine)
@@ -321,7 +350,8 @@ class DBN(object):
                                                        learn_sigma=learn_sigma, centered=centered, offset_rate=offset_rate,
                                                        sparsity_target=sparsity_target, sparsity_cost=sparsity_cost,
                                                        sparsity_decay=sparsity_decay, sparsity_weights=sparsity_weights,
-                                                       discriminative=discriminative, label_group=label_group, generative=generative)
+                                                       discriminative=discriminative, label_group=label_group, generative=generative,
+                                                       **({"missing": True} if missing else {}))
         self._print('... pre-training the model')
         t_start = timeit.default_timer()
         if resume is None:
@@ -336,7 +366,7 @@ class DBN(object):
         for i in range(first, self.n_layers):
             at = resume if (resume is not None and i == first and resume.get('epoch') is not None) else None
             history.append(self._pretrain_layer(i, step_fns[i], energy_fns[i], data, held_out, batch_size, n_batches,
-                                                pretraining_epochs[i], pretrain_lr[i], history, at, on_step))
+                                                pretraining_epochs[i], pretrain_lr[i], history, at, on_step, missing))
         self.trainer_state = None
         if self.verbose:
             print('The pretraining ran for %.2fm' % ((timeit.default_timer() - t_start) / 60.), file=sys.stderr)
@@ -352,7 +382,7 @@ class DBN(object):
             numpy.random.set_state(state)
 
     def _pretrain_layer(self, i, step_fn, energy_fn, data, held_out, batch_size, n_batches, epoch_budget, lr,
-                        history=(), at=None, on_step=None):
+                        history=(), at=None, on_step=None, missing=False):
         """One layer of dbn.py:426-508: epochs of reshuffled minibatches under the layer's momentum
         schedule until the epoch budget or the early-stopping state (``_Patience``) ends it.  ``at``: the trainer
         state of an interrupted run of THIS layer (epoch, next minibatch, patience, records, shuffle state)."""
@@ -396,7 +426,7 @@ class DBN(object):
                     self._print(cost)
                     gap = None
                     if stop.observe(it, cost) and held_out is not None:
-                        gap = self._free_energy_gap(i, energy_fn, data, held_out)
+                        gap = self._free_energy_gap(i, energy_fn, data, held_out, **({"missing": True} if missing else {}))
                         self._print('Free energy gap (layer %i, epoch %i): ' % (i, epoch), end=' ')
                         self._print(gap)
                     records.append((it, cost, gap))
@@ -420,7 +450,7 @@ class DBN(object):
         step_fn.flush()
         return records
 
-    def _free_energy_gap(self, i, energy_fn, data, held_out):
+    def _free_energy_gap(self, i, energy_fn, data, held_out, missing=False):
         """mean F(validation) - mean F(training rows) (dbn.py:476-501).  The reference's two cases differ in the
         training rows they use: at layer 0 the WHOLE training set (``input_t_set = t_set``, dbn.py:478), at the
         layers above only its first ``n_val`` rows, seen through the layers below
@@ -432,7 +462,8 @@ class DBN(object):
                 f_val = energy_fn(held_out, held_out)[1]
                 rbm = self.rbm_layers[0]
                 f_train = numpy.concatenate([
-                    rbm.free_energy(data.rows(slice(lo, min(len(data), lo + self.host_chunk_rows)))).get_value()
+                    rbm.free_energy(data.rows(slice(lo, min(len(data), lo + self.host_chunk_rows))),
+                                    **({"missing": True} if missing else {})).get_value()
                     for lo in range(0, len(data), self.host_chunk_rows)])
                 return float(f_val.mean() - f_train.mean())
             below_train = data.rows(slice(0, len(data))) if isinstance(data, HostTable) and data._mirror is None \
@@ -441,8 +472,8 @@ class DBN(object):
         else:
             n_val = held_out.shape[0]
             first = data.rows(slice(0, n_val)) if isinstance(data, HostTable) else data.tensor[:n_val]
-            below_train = self._forward(first, i - 1)
-            below_val = self._forward(held_out, i - 1)
+            below_train = self._forward(first, i - 1, missing)
+            below_val = self._forward(held_out, i - 1, missing)
         f_train, f_val = energy_fn(below_train, below_val)
         return float(f_val.mean() - f_train.mean())
 

@@ -1026,6 +1026,107 @@ class HipEngine(object):
                                                  C.c_void_p(groups.host.ctypes.data), groups.n_groups), "mdbn_cd_step_grouped")
         return call.stats, call.scratch
 
+    # ------------------------------------------------------------------ absent visible units (mdbn_absent_*)
+    def _sized_scratch(self, attr, need):
+        """The engine's scratch buffer ``attr``, regrown to hold ``need`` bytes."""
+        ws = getattr(self, attr, None)
+        if ws is None or ws.numel() * 4 < need:
+            ws = self._alloc_scratch(need, attr)
+            setattr(self, attr, ws)
+        return ws
+
+    def absent_split(self, x, out=None, want_count=True):
+        """A table with missing entries (NaN: "this row did not observe this unit") -> ``(filled, observed, row_count)``
+        (mdbn_absent_split): the rows with 0 where missing (``out``: a matrix of x's shape to receive them, may be ``x``
+        itself), the observed bits as int32 words [B, (V + 31) // 32] (bit i & 31 of word i >> 5) and the number of
+        observed entries of every row (int32 [B]; None without ``want_count``)."""
+        x = self.as_matrix(x)
+        B, V = x.shape
+        filled = self.alloc_matrix(B, V, x.stride(0)) if out is None else out
+        observed = torch.zeros((B, (V + 31) // 32), dtype=torch.int32, device=self.device)
+        count = torch.zeros(B, dtype=torch.int32, device=self.device) if want_count else None
+        if B:
+            _lib.check(self.lib.mdbn_absent_split(self.ctx, self._stream(), self._p(x), B, x.stride(0), V, self._p(filled),
+                                                  filled.stride(0), self._p(observed), self._p(count)), "mdbn_absent_split")
+        return filled, observed, count
+
+    def absent_visible(self, pre, observed, gauss=False, add_noise=False, rng=None, v0=None, out=None):
+        """p(v | h) of rows with absent units from the linear pre-activations ``pre`` [B, V] = h W^T + vbias
+        (mdbn_absent_visible): ``(mean, sample)``, both exactly 0 where ``observed`` (the words of ``absent_split``) has no
+        bit; ``rng`` None: no sample.  ``out``: the matrix that receives the means (may be ``pre``).  With ``v0`` (zero-filled)
+        also the un-normalised cost sum over the observed entries (device scalar)."""
+        pre = self.as_matrix(pre)
+        B, V = pre.shape
+        ldv = pre.stride(0)
+        mean = self.alloc_matrix(B, V, ldv) if out is None else out
+        sample = self.alloc_matrix(B, V, ldv) if rng is not None else None
+        cost = ws = None
+        n = C.c_int64(0)
+        if v0 is not None:
+            v0 = self.as_matrix(v0)
+            if v0.stride(0) != ldv:                     # the target is read with the output's ld
+                t = self.alloc_matrix(B, V, ldv)
+                t.copy_(v0)
+                v0 = t
+            cost = torch.zeros(4, dtype=torch.float32, device=self.device)
+            _lib.check(self.lib.mdbn_absent_visible_workspace_bytes(self.ctx, B, V, C.byref(n)), "mdbn_absent_visible_workspace_bytes")
+            ws = self._sized_scratch("_absent_ws", n.value)
+        r = rng.c() if rng is not None else None
+        _lib.check(self.lib.mdbn_absent_visible(
+            self.ctx, self._stream(), self._p(pre), B, ldv, V, self._p(observed), int(bool(gauss)), int(bool(add_noise)),
+            self._p(mean), self._p(sample), None, C.byref(r) if r is not None else None, self._p(v0), self._p(cost), self._p(ws),
+            n.value), "mdbn_absent_visible")           # (the sizers of these calls are exact: the library is told their figure)
+        return (mean, sample) if v0 is None else (mean, sample, cost[0])
+
+    def cd_step_absent(self, data, indexes, W, hbias, vbias, gauss, k, rng, add_noise=False, stats_slot=0, stats=None):
+        """``cd_step`` on rows with missing entries (mdbn_cd_step_absent; NaN in ``data``: the unit is absent from that row's
+        RBM): the same ``(stats, scratch)``, the float32 copies in the scratch always written -- V2 = [v0; nv] zero at the
+        absent entries, ``vs`` the masked visible sample for Gaussian layers too --, the cost slot holding the monitoring cost
+        summed over the observed entries only."""
+        call = self._cd_args(data, indexes, W, hbias, vbias, gauss, k, rng, None, add_noise, stats_slot, False, stats, keep_f32=True)
+        a, sc = call.args, call.scratch
+        a.W_planes, a.W_planes_valid, a.planes, a.planes_bytes = None, 0, None, 0      # (the composed step reads f32 operands only)
+        a.planes_alt, a.next_indexes, a.v0_ready, a.ahead_done = None, None, 0, None
+        B, V, H, ldv, ldh = a.B, a.V, a.H, a.ldv, a.ldh
+        if sc.vs is None:                               # (a Gaussian layer's scratch: the absent step writes the sample)
+            sc.vs = self.alloc_matrix(B, V, ldv)
+        a.vs = sc.vs.data_ptr()
+        if self.trace_chain and sc.trace_v is None:
+            sc.trace_v = torch.zeros((int(k), B, ldv), dtype=torch.float32, device=self.device)
+            a.trace_v = sc.trace_v.data_ptr()
+        n = C.c_int64()
+        _lib.check(self.lib.mdbn_cd_step_absent_workspace_bytes(self.ctx, B, V, H, ldv, ldh, C.byref(n)),
+                   "mdbn_cd_step_absent_workspace_bytes")
+        ws = self._sized_scratch("_absent_step_ws", n.value)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), n.value
+        _lib.check(self.lib.mdbn_cd_step_absent(self.ctx, self._stream(), C.byref(a)), "mdbn_cd_step_absent")
+        return call.stats, sc
+
+    def absent_mark_rows(self, y, row_count):
+        """Rows of ``y`` whose ``row_count`` (int32 [N], of ``absent_split``) is 0 become rows of NaN, in place."""
+        N, cols = y.shape
+        if N:
+            _lib.check(self.lib.mdbn_absent_mark_rows(self.ctx, self._stream(), self._p(y), N, y.stride(0), cols, self._p(row_count)),
+                       "mdbn_absent_mark_rows")
+        return y
+
+    def free_energy_absent(self, x, W, hbias, vbias, gauss):
+        """``free_energy`` over the observed units of every row (NaN in ``x``: absent; mdbn_free_energy_absent)."""
+        x = self.as_matrix(x)
+        N, V = x.shape
+        H = W.shape[1]
+        out = self.alloc_vector(N)
+        if N == 0:
+            return out
+        n = C.c_int64()
+        _lib.check(self.lib.mdbn_free_energy_absent_workspace_bytes(self.ctx, N, V, H, x.stride(0), C.byref(n)),
+                   "mdbn_free_energy_absent_workspace_bytes")
+        ws = self._sized_scratch("_absent_fe_ws", n.value)
+        _lib.check(self.lib.mdbn_free_energy_absent(
+            self.ctx, self._stream(), self._p(x), N, x.stride(0), self._p(W), V, H, W.stride(0), self._p(hbias), self._p(vbias),
+            int(bool(gauss)), self._p(out), self._p(ws), n.value), "mdbn_free_energy_absent")
+        return out
+
     # ------------------------------------------------------------------ classification RBM (mdbn_class_*)
     def _class_workspace(self, B, V, H, ldv, ldh, K, mode):
         key = (B, V, H, ldv, ldh, K, mode)

@@ -48,7 +48,7 @@ class UpdatePlan(object):
     def __init__(self, rbm, lr, k, lambda_1, lambda_2, weightcost, batch_size, persistent, W0,
                  symbolic_grad=False, centered=False, offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0,
                  sparsity_decay=0.9, sparsity_weights=True, grouped=None, learn_sigma=None, disc_weight=None, gen_weight=1.0,
-                 label_span=None):
+                 label_span=None, absent=False):
         self.rbm, self.lr, self.k = rbm, lr, int(k)
         self.lambda_1, self.lambda_2, self.weightcost = lambda_1, lambda_2, weightcost
         self.batch_size, self.persistent, self.W0 = batch_size, persistent, W0
@@ -77,6 +77,9 @@ class UpdatePlan(object):
         # statistics; gen_weight = 0: purely discriminative, no chain is run.  None: none of it
         self.disc_weight = None if disc_weight is None else float(disc_weight)
         self.gen_weight, self.label_span = float(gen_weight), label_span
+        # absent visible units (StepFunction._statistics_step): NaN in the table means "this row did not observe this unit";
+        # the step's statistics then come from engine.cd_step_absent (CD with a per-row mask).  False: none of it
+        self.absent = bool(absent)
 
 
 class LazyCost(object):
@@ -249,6 +252,13 @@ class StepFunction(object):
             raise NotImplementedError("a layer with log_sigma (learned per-column variance) on a data-parallel group of %d "
                                       "ranks: the step of log_sigma needs the rows of the whole minibatch, which is not "
                                       "built yet" % self.group.world_size)
+        if p.absent:
+            if self.group is not None and self.group.world_size > 1:
+                raise NotImplementedError("missing=True on a data-parallel group of %d ranks: the absent-unit step is not "
+                                          "sharded yet" % self.group.world_size)
+            if not hasattr(self.rbm.engine, "cd_step_absent"):
+                raise NotImplementedError("missing=True needs an engine with the absent-unit step (cd_step_absent); %s has none"
+                                          % type(self.rbm.engine).__name__)
         self.discriminative_nll = None      # 0-d device tensor: -sum log p(label | rest) of the last minibatch (a discriminative plan)
         if p.disc_weight is not None:
             if self.group is not None and self.group.world_size > 1:
@@ -422,7 +432,7 @@ class StepFunction(object):
         batch_size = p.batch_size if (p.batch_size is not None and not p.symbolic_grad) else mb.n_global
         step = self.rbm._take_step()
         distributed = self.group is not None and self.group.world_size > 1
-        if p.centered or p.sparse or p.grouped is not None or p.sigma:
+        if p.centered or p.sparse or p.grouped is not None or p.sigma or p.absent:
             return self._statistics_step(mb, step, lr, momentum, batch_size, next_indexes)
         if not distributed and p.persistent is None and mb.hi > mb.lo:
             return self._single_device_step(mb, step, lr, momentum, batch_size, next_indexes)
@@ -536,7 +546,13 @@ class StepFunction(object):
         before the sparsity transform, ``class_stats`` replaces the statistics by gen_weight x (those of the CD step) + w x
         (the exact gradient of sum_rows log p(label | rest)) -- one statistics GEMM on the stacked operands of both.  With
         gen_weight = 0 no chain is run: the rows are gathered and ``class_stats`` forms the discriminative statistics alone;
-        the monitoring cost is then the mean -log p(label | rest), which ``discriminative_cost`` gives in both forms."""
+        the monitoring cost is then the mean -log p(label | rest), which ``discriminative_cost`` gives in both forms.
+
+        Absent visible units (a plan with ``absent``: ``get_cost_updates(missing=True)``; Salakhutdinov, Mnih & Hinton 2007):
+        the statistics come from ``cd_step_absent`` -- a NaN of the table is a unit the row's RBM does not have, v0 and nv are
+        zero there --, everything after that call is unchanged.  The divisors stay the batch size: the step follows the mean
+        log-likelihood per row.  The monitoring cost is summed over the observed entries only, so the costs of tables with
+        different missingness do not compare."""
         p, rbm, eng = self.plan, self.rbm, self.engine
         data = mb.data
         fed = mb                                        # the rows as they arrived (a fed buffer goes back once they are read)
@@ -570,6 +586,10 @@ class StepFunction(object):
             self._disc_rows = mb.n_global
             self.discriminative_nll = eng.class_stats(None, v0, mb.n_global, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, lo, K,
                                                       0.0, p.disc_weight, stats)
+        elif p.absent:
+            _, scratch = eng.cd_step_absent(data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, rbm.gauss, p.k,
+                                            self._rng_addr(step, mb.lo), add_noise=rbm.gauss and not getattr(rbm, "error_free", True),
+                                            stats=stats)
         elif p.grouped is not None:
             _, scratch = eng.cd_step_grouped(data, mb.idx, rbm.W.tensor, rbm.hbias.tensor, rbm.vbias.tensor, p.k,
                                              self._rng_addr(step, mb.lo), p.grouped, persistent=persistent, stats=stats,
@@ -880,23 +900,39 @@ class RBM(object):
         return None if t is None else SharedArray(None, engine=self.engine, _tensor=t)
 
     # ------------------------------------------------------------------ energies
-    def free_energy(self, v_sample):
+    def _zero_filled(self, v, what):
+        """``v`` with 0 where it holds NaN (an absent unit), a device matrix (``engine.absent_split``)."""
+        self._no_groups(what)
+        self._no_sigma(what)
+        return self.engine.absent_split(as_tensor(v, self.engine), want_count=False)[0]
+
+    def free_energy(self, v_sample, missing=False):
         ''' Function to compute the free energy (rbm.py:166-171); with ``log_sigma`` s: of the raw rows,
-        F(x) = F_u(x exp(-s)) + sum(s) '''
+        F(x) = F_u(x exp(-s)) + sum(s).  ``missing=True``: NaN marks a unit the row did not observe, and the free energy is
+        F_O over the units it did (``engine.free_energy_absent``; likelihoods of such rows need a partition function per
+        pattern and are not offered) '''
+        if missing:
+            self._no_groups("free_energy(missing=True)")
+            self._no_sigma("free_energy(missing=True)")
+            return self._wrap(self.engine.free_energy_absent(as_tensor(v_sample, self.engine), self.W.tensor, self.hbias.tensor,
+                                                             self.vbias.tensor, self.gauss))
         if self.log_sigma is not None:
             F = self.engine.free_energy(self._units(v_sample), self.W.tensor, self.hbias.tensor, self.vbias.tensor, self.gauss)
             return self._wrap(F + self.log_sigma.tensor.sum())
         return self._wrap(self.engine.free_energy(as_tensor(v_sample, self.engine), self.W.tensor,
                                                   self.hbias.tensor, self.vbias.tensor, self.gauss))
 
-    def free_energy_gap(self, train, test):
-        """mean F(test) - mean F(train) (rbm.py:173-180); returns a Python float."""
-        ft, fs = self.free_energy(train).tensor, self.free_energy(test).tensor
+    def free_energy_gap(self, train, test, missing=False):
+        """mean F(test) - mean F(train) (rbm.py:173-180); returns a Python float.  ``missing=True``: over the observed units
+        of every row (``free_energy``)."""
+        kw = {"missing": True} if missing else {}
+        ft, fs = self.free_energy(train, **kw).tensor, self.free_energy(test, **kw).tensor
         return float(fs.mean() - ft.mean())
 
-    def free_energies(self, train, test):
-        """rbm.py:182-185, evaluated: two host vectors (as dbn.py:498-501 consumes them)."""
-        return self.free_energy(train).get_value(), self.free_energy(test).get_value()
+    def free_energies(self, train, test, missing=False):
+        """rbm.py:182-185, evaluated: two host vectors (as dbn.py:498-501 consumes them).  ``missing``: as ``free_energy``."""
+        kw = {"missing": True} if missing else {}
+        return self.free_energy(train, **kw).get_value(), self.free_energy(test, **kw).get_value()
 
     # ------------------------------------------------------------------ likelihood (annealed importance sampling)
     def base_rate_vbias(self, data):
@@ -1008,8 +1044,10 @@ class RBM(object):
         return float(neg_F.mean() - log_Z), err
 
     # ------------------------------------------------------------------ propagation
-    def propup(self, vis):
-        '''[pre_sigmoid_activation, sigmoid(pre)] (rbm.py:187-199)'''
+    def propup(self, vis, missing=False):
+        '''[pre_sigmoid_activation, sigmoid(pre)] (rbm.py:187-199); ``missing=True``: NaN entries go up as 0 (absent units)'''
+        if missing:
+            vis = self._zero_filled(vis, "propup(missing=True)")
         pre, mean, _ = self.engine.propup(as_tensor(self._units(vis), self.engine), self.W.tensor, self.hbias.tensor,
                                           want_sample=False)
         return [self._wrap(pre), self._wrap(mean)]
@@ -1032,8 +1070,10 @@ class RBM(object):
             eng.sparsity_activity(ActivityRows(mean), rows.shape[0], q, None, float(rows.shape[0]) / float(seen))
         return numpy.asarray(eng.to_numpy(q), dtype=numpy.float32)
 
-    def sample_h_given_v(self, v0_sample):
-        ''' [pre_sigmoid_h1, h1_mean, h1_sample] (rbm.py:201-213) '''
+    def sample_h_given_v(self, v0_sample, missing=False):
+        ''' [pre_sigmoid_h1, h1_mean, h1_sample] (rbm.py:201-213); ``missing=True``: NaN entries go up as 0 (absent units) '''
+        if missing:
+            v0_sample = self._zero_filled(v0_sample, "sample_h_given_v(missing=True)")
         pre, mean, sample = self.engine.propup(as_tensor(self._units(v0_sample), self.engine), self.W.tensor,
                                                self.hbias.tensor, rng=self._rng())
         return [self._wrap(pre), self._wrap(mean), self._wrap(sample)]
@@ -1414,9 +1454,39 @@ class RBM(object):
         return sample_fn
 
     # ------------------------------------------------------------------ CD-k / PCD-k
+    def _refuse_missing(self, persistent=None, symbolic_grad=False, discriminative=None, learn_sigma=None, centered=False,
+                        sparse=False, tempering=None):
+        """What ``missing=True`` does not compose with yet, each with its reason; raised before anything runs."""
+        if self.visible_groups is not None:
+            raise NotImplementedError("missing=True on a layer with visible_groups is not built: a group with some of its "
+                                      "categories absent needs a softmax over the observed ones, which the grouped kernel lacks")
+        if self.log_sigma is not None or learn_sigma is not None:
+            raise NotImplementedError("missing=True on a layer with log_sigma / learn_sigma is not built: the variance "
+                                      "statistic would have to count the rows that observed each column")
+        if centered:
+            raise NotImplementedError("missing=True with centered=True is not built: the offsets are batch means, which a "
+                                      "column with absent entries does not have over the whole minibatch")
+        if sparse:
+            raise NotImplementedError("missing=True with a sparsity target is not built: the weight term of the penalty uses "
+                                      "the batch means of the visible units, undefined for columns with absent entries")
+        if discriminative is not None:
+            raise NotImplementedError("missing=True with discriminative= is not built: the label posterior needs the grouped "
+                                      "step, which has no mask")
+        if symbolic_grad:
+            raise NotImplementedError("missing=True with symbolic_grad=True is not supported: the absent-unit step takes its "
+                                      "negative statistics from the means")
+        if persistent is not None and persistent is not False:
+            raise NotImplementedError("missing=True with a persistent chain is not built: a fantasy particle has no pattern "
+                                      "of observed units of its own (pass persistent=None / False)")
+        if tempering is not None:
+            raise NotImplementedError("missing=True with tempering= is not built: the ladders are persistent chains")
+        if not hasattr(self.engine, "cd_step_absent"):
+            raise NotImplementedError("missing=True needs an engine with the absent-unit step (cd_step_absent); %s has none"
+                                      % type(self.engine).__name__)
+
     def get_cost_updates(self, lr=0.1, k=1, lambda_1=0.0, lambda_2=0.0, weightcost=0.0,
                          batch_size=None, persistent=None, symbolic_grad=False, discriminative=None, label_group=-1,
-                         generative=1.0, learn_sigma=None, centered=False, offset_rate=0.01, sparsity_target=None,
+                         generative=1.0, missing=False, learn_sigma=None, centered=False, offset_rate=0.01, sparsity_target=None,
                          sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         """One step of CD-k or PCD-k (rbm.py:258-376).  Returns ``(cost, updates)``; pass
         ``updates`` to ``mdbn_amd.function`` to obtain the step function.
@@ -1449,7 +1519,17 @@ class RBM(object):
         ``generative=0`` trains the label's conditional alone and runs no chain (no ``persistent``, no sparsity target: both
         live on the chain's rows); the monitoring cost is then the mean -log p(label | rest), which the step function's
         ``discriminative_cost`` gives in either form.  A sparsity target composes with ``generative > 0``; ``centered`` and
-        ``symbolic_grad`` do not compose.  None: nothing changes."""
+        ``symbolic_grad`` do not compose.  None: nothing changes.
+        ``missing=True``: the table may hold NaN, "this row did not observe this unit" (Salakhutdinov, Mnih & Hinton 2007: a
+        missing unit is absent from that row's RBM, all rows share the weights) -- the step is CD with a per-row mask
+        (``StepFunction._statistics_step``), the gradient of the MEAN log-likelihood per row over the units each row observed.
+        The monitoring cost sums over observed entries only: costs of tables with different missingness do not compare.  It
+        composes with nothing else yet (``_refuse_missing`` lists what is refused and why).  False: nothing changes, and a
+        NaN in the table behaves as before."""
+        if missing:
+            self._refuse_missing(persistent=persistent, symbolic_grad=symbolic_grad, discriminative=discriminative,
+                                 learn_sigma=learn_sigma, centered=centered,
+                                 sparse=sparsity_target is not None and float(sparsity_cost) > 0.0)
         label_span = None
         if discriminative is not None:
             w, alpha = float(discriminative), float(generative)
@@ -1522,7 +1602,7 @@ class RBM(object):
                              sparsity_target=sparsity_target, sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
                              sparsity_weights=sparsity_weights, grouped=self.visible_groups, learn_sigma=learn_sigma,
                              disc_weight=discriminative, gen_weight=generative if discriminative is not None else 1.0,
-                             label_span=label_span)
+                             label_span=label_span, absent=missing)
         cost = CostHandle('pseudo_likelihood' if (persistent is not None and self.visible_groups is None) else 'reconstruction')
         return cost, updates
 
@@ -1555,8 +1635,8 @@ class RBM(object):
     def training(self, train_set_x, validation_set_x, training_epochs, batch_size=10,
                  learning_rate=0.1, k=1, initial_momentum=0.0, final_momentum=0.0,
                  weightcost=0.0, lambda_2=0.0, persistent=True, display_fn=None, graph_output=False, tempering=None,
-                 visible_groups=None, discriminative=None, label_group=-1, generative=1.0, centered=False, offset_rate=0.01,
-                 sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
+                 visible_groups=None, discriminative=None, label_group=-1, generative=1.0, missing=False, centered=False,
+                 offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         """rbm.py:484-520 (note: like the reference, ``lambda_2`` is accepted but not used).
 
         ``tempering=R`` (with ``persistent``): PCD whose negative chains are the beta = 1 replicas of ``batch_size``
@@ -1566,9 +1646,14 @@ class RBM(object):
         the step the grouped PCD step.  ``centered`` / ``offset_rate``: the centred gradient, ``sparsity_*``: the sparsity target
         (``get_cost_updates``).  ``visible_groups`` (not None): ``set_visible_groups`` first -- the layer trains with
         categorical visible units.  ``discriminative`` / ``label_group`` / ``generative``: the hybrid or purely discriminative
-        objective of a classification RBM (``get_cost_updates``); ``generative=0`` needs ``persistent=False``."""
+        objective of a classification RBM (``get_cost_updates``); ``generative=0`` needs ``persistent=False``.
+        ``missing=True`` (needs ``persistent=False``): the tables may hold NaN for entries that were not measured
+        (``get_cost_updates``); the free-energy gap is then taken over the observed units of every row."""
         if visible_groups is not None:
             self.set_visible_groups(visible_groups)
+        if missing:
+            self._refuse_missing(persistent=persistent, discriminative=discriminative, centered=centered, tempering=tempering,
+                                 sparse=sparsity_target is not None and float(sparsity_cost) > 0.0)
         disc = dict(discriminative=discriminative, label_group=label_group, generative=generative) if discriminative is not None else {}
         if tempering is not None:
             if self.visible_groups is not None and not hasattr(self.engine, "temper_grouped"):
@@ -1583,7 +1668,7 @@ class RBM(object):
                                               batch_size=batch_size, persistent=persistent_chain,
                                               centered=centered, offset_rate=offset_rate, sparsity_target=sparsity_target,
                                               sparsity_cost=sparsity_cost, sparsity_decay=sparsity_decay,
-                                              sparsity_weights=sparsity_weights, **disc)
+                                              sparsity_weights=sparsity_weights, missing=missing, **disc)
         step_hooks = None
         if tempering is not None:
             if not persistent:
@@ -1599,11 +1684,11 @@ class RBM(object):
                                 training_epochs=training_epochs, batch_size=batch_size,
                                 initial_momentum=initial_momentum, final_momentum=final_momentum,
                                 cost=cost, updates=updates, display_fn=display_fn,
-                                graph_output=graph_output, step_hooks=step_hooks)
+                                graph_output=graph_output, step_hooks=step_hooks, missing=missing)
 
     def learn_model(self, train_set_x, validation_set_x, training_epochs, batch_size,
                     initial_momentum, final_momentum, cost, updates, display_fn, graph_output,
-                    verbose=True, shuffle_rng=None, step_hooks=None):
+                    verbose=True, shuffle_rng=None, step_hooks=None, missing=False):
         """Epoch loop of rbm.py:522-629.  ``display_fn`` / ``graph_output`` are accepted and
         ignored (plotting is outside the engine).  Returns the per-epoch (cost, gap) list.
         ``step_hooks``: ``(before, after)`` callables run around every step (``training(tempering=...)``)."""
@@ -1640,7 +1725,7 @@ class RBM(object):
             feg = None
             if n_val:
                 # rbm.py:597: gap between the first n_val training rows and the validation set
-                feg = self.free_energy_gap(train_set_x[numpy.arange(n_val)], validation_set_x)
+                feg = self.free_energy_gap(train_set_x[numpy.arange(n_val)], validation_set_x, **({"missing": True} if missing else {}))
             if verbose:
                 print('Training epoch %d, cost is ' % epoch, mean_cost)
                 print('Free energy gap is ', feg)
@@ -1724,11 +1809,12 @@ class GRBM(RBM):
     def training(self, train_set_x, validation_set_x, training_epochs, batch_size=10,
                  learning_rate=0.01, k=1, initial_momentum=0.0, final_momentum=0.0,
                  weightcost=0.0, lambda_1=0.0, lambda_2=0.1, persistent=False,
-                 display_fn=None, graph_output=False, visible_groups=None, learn_sigma=None, centered=False, offset_rate=0.01,
-                 sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
+                 display_fn=None, graph_output=False, visible_groups=None, learn_sigma=None, missing=False, centered=False,
+                 offset_rate=0.01, sparsity_target=None, sparsity_cost=0.0, sparsity_decay=0.9, sparsity_weights=True):
         """rbm.py:701-728: always CD (``persistent`` is ignored, as in the reference).  ``centered`` / ``offset_rate``: the
         centred gradient, ``sparsity_*``: the sparsity target, ``learn_sigma``: the rate of the learned per-column variance
-        (``get_cost_updates``).  ``visible_groups`` is refused."""
+        (``get_cost_updates``).  ``visible_groups`` is refused.  ``missing=True``: the tables may hold NaN for entries that
+        were not measured (``get_cost_updates``)."""
         if visible_groups is not None:
             raise ValueError("visible_groups: a Gaussian visible layer (GRBM) has no categorical units")
         cost, updates = self.get_cost_updates(lr=learning_rate, k=k, lambda_1=lambda_1,
@@ -1736,9 +1822,9 @@ class GRBM(RBM):
                                               batch_size=batch_size, learn_sigma=learn_sigma, centered=centered,
                                               offset_rate=offset_rate,
                                               sparsity_target=sparsity_target, sparsity_cost=sparsity_cost,
-                                              sparsity_decay=sparsity_decay, sparsity_weights=sparsity_weights)
+                                              sparsity_decay=sparsity_decay, sparsity_weights=sparsity_weights, missing=missing)
         return self.learn_model(train_set_x=train_set_x, validation_set_x=validation_set_x,
                                 training_epochs=training_epochs, batch_size=batch_size,
                                 initial_momentum=initial_momentum, final_momentum=final_momentum,
                                 cost=cost, updates=updates, display_fn=display_fn,
-                                graph_output=graph_output)
+                                graph_output=graph_output, missing=missing)
