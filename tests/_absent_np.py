@@ -239,9 +239,12 @@ class AbsentOracle(OracleEngine):
 
 # ------------------------------------------------------------------------------------------------------------------ kernel cases
 # (V, ldv, B): one column; one short of a mask word, a whole word, one over; two words; one over two; two column blocks; the
-# input layer of the label benchmark (four column blocks, a ragged last word).  B: one row, a ragged 4-row block, whole
-# blocks, many blocks
-KERNEL_CASES = [(1, 4, 1), (31, 32, 5), (32, 32, 4), (33, 36, 33), (64, 64, 8), (65, 68, 20), (300, 300, 7), (794, 796, 20)]
+# input layer of the label benchmark (four column blocks, a ragged last word); tables wider than 2048 columns -- 65 and 130 mask
+# words, so the lanes of absent_count's one wave per row take a second trip, and lanes 0 and 1 a third.  B: one row, a ragged
+# 4-row block, whole blocks, many blocks
+KERNEL_CASES = [(1, 4, 1), (31, 32, 5), (32, 32, 4), (33, 36, 33), (64, 64, 8), (65, 68, 20), (300, 300, 7), (794, 796, 20),
+                (2049, 2052, 3), (4133, 4136, 5)]
+COUNT_TRIP = 2048           # columns one trip of absent_count's 64 lanes covers
 VARIANTS = [("bernoulli", False, False), ("gauss", True, False), ("gauss_noise", True, True)]
 ROW_OFFSET = 6              # not a multiple of 4: the 4-row Philox blocks straddle
 # Philox seed of a case: 100 + V + 7 B unless listed here -- a seed under which the twin alone has at most TIE_CAP draws near a

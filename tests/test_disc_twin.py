@@ -83,3 +83,60 @@ def test_discriminative_steps_learn_the_toy_problem():
     acc = dn.accuracy(rows, s, lo, K)
     print("toy: NLL %.4f -> %.4f, accuracy %.3f" % (nll[0], final, acc))
     assert acc >= 0.9 and final <= 0.5 * nll[0]
+
+
+# ------------------------------------------------------------------------------------------------------------------ launch geometry
+def test_the_geometry_mirror_at_256_compute_units():
+    """The mirror of class_geom() written out at cu = 256 -- an edit of the mirror shows up here --, and what every case of
+    ``geometry_cases`` is meant to reach there: (R, rows of the last batch, trips of workgroup 0)."""
+    # (B, K, ldh, training mode) -> (R, G)
+    table = {(1, 3, 40, False): (1, 1), (33, 3, 40, False): (1, 33), (256, 3, 40, False): (1, 256), (257, 3, 40, False): (2, 129),
+             (512, 3, 40, True): (2, 256), (514, 3, 40, False): (3, 172), (769, 3, 40, False): (4, 193), (770, 64, 516, False): (4, 193),
+             (771, 3, 40, False): (4, 193), (1024, 3, 40, False): (4, 256), (4096, 3, 40, True): (4, 1024), (4097, 3, 40, True): (4, 1024),
+             (4119, 3, 40, True): (4, 1024), (4119, 3, 40, False): (4, 1030), (1 << 24, 3, 40, False): (4, 1 << 22),
+             (4119, 2, 64, True): (4, 1024), (4119, 3, 64, True): (4, 1024),
+             (4119, 2, 11008, True): (4, 1024), (4119, 3, 11008, True): (4, 1016), (4119, 64, 1024, True): (4, 512),
+             (100, 64, 1 << 24, True): (1, 1)}
+    for (B, K, ldh, train), want in table.items():
+        assert dn.class_geom(256, B, K, ldh, train) == want, (B, K, ldh, train)
+    assert dn.geometry_cases(256) == {"cu+1": (257, (2, 1, 1)), "2cu+2": (514, (3, 1, 1)), "3cu+1": (769, (4, 1, 1)),
+                                      "3cu+2": (770, (4, 2, 1)), "3cu+3": (771, (4, 3, 1)), "4cu": (1024, (4, 4, 1)),
+                                      "16cu+23": (4119, (4, 3, 2))}
+    assert list(dn.geometry_cases(256)) == dn.GEOMETRY_KEYS
+    # the busiest workgroup of the capped launch: 1030 batches on 1024 workgroups, workgroups 0 .. 5 take the second trip
+    assert dn.class_reach(256, 4119, 3, 40, True) == (4, 3, 2) and dn.class_reach(256, 4119, 3, 40, False) == (4, 3, 1)
+    # other CU counts reach the same (R, tail, trips), with B the formula's or a few rows more
+    for cu in (8, 64, 255, 304):
+        for key, (B, want) in dn.geometry_cases(cu).items():
+            f = dict((k, f) for k, f, _ in dn.GEOMETRY)[key]
+            assert 0 <= B - f(cu) <= dn.CLASS_R and dn.class_reach(cu, B, 3, 40, True) == want, (cu, key)
+
+
+@pytest.mark.parametrize("name,V,H,B,bounds,g,scale", dn.MANY_ROW_POSTERIOR, ids=[c[0] for c in dn.MANY_ROW_POSTERIOR])
+def test_the_twin_alone_on_the_many_row_posterior_cases(name, V, H, B, bounds, g, scale):
+    B = dn.rows_of(256, B)
+    distinct = name.startswith("between")
+    rows, W, hb, vb, lo, K = dn.posterior_inputs(V, H, B, bounds, g, scale, distinct)
+    p, lp = dn.posterior(rows, W, hb, vb, lo, K), dn.logp(rows, W, hb, vb, lo, K)
+    assert p.shape == (B, K) and np.isfinite(p).all() and np.isfinite(lp).all() and -lp.sum() > 0
+    assert np.abs(p.sum(axis=1) - 1.0).max() <= 1e-12
+    if distinct:
+        assert dn.distinct_inputs(rows, lo, K) == B
+    else:
+        assert dn.distinct_inputs(rows, lo, K) >= min(B, 12)        # (K = 64 of V = 70 leaves 12 different inputs)
+
+
+@pytest.mark.parametrize("name,V,H,B,bounds,g,scale", dn.MANY_ROW_STATS, ids=[c[0] for c in dn.MANY_ROW_STATS])
+def test_the_twin_alone_on_the_many_row_statistics_cases(name, V, H, B, bounds, g, scale):
+    B = dn.rows_of(256, B)
+    v0, nv, ph, nh, W, hb, vb, lo, K, _ = dn.stats_inputs(V, H, B, bounds, g, scale, name.startswith("odd_small"))
+    if name.startswith("saturated"):
+        assert np.abs(dn.scores(v0, W, hb, vb, lo, K)[0]).max() > 200
+    S, s_h, s_v, nll = dn.stats(v0, W, hb, vb, lo, K)
+    assert all(np.isfinite(t).all() for t in (S, s_h, s_v)) and np.isfinite(nll)
+    assert nll > 0 and np.abs(s_v).max() > 0 and np.abs(S).max() > 0
+    hS, hh, hv = dn.hybrid_stats(v0, W, hb, vb, lo, K, 1.0, 0.5, nv.astype(np.float64), ph.astype(np.float64), nh.astype(np.float64))
+    assert all(np.isfinite(t).all() for t in (hS, hh, hv)) and np.abs(hv).max() > 0 and np.abs(hS).max() > 0
+    # the stacked operands, what the device's one product is measured on, give the same sum
+    gS = dn.stacked_stats(v0, W, hb, vb, lo, K, gen=1.0, w=0.5, nv=nv.astype(np.float64), ph=ph.astype(np.float64), nh=nh.astype(np.float64))[0]
+    assert np.abs(gS - hS).max() <= 1e-10 * np.abs(hS).max()
